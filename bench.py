@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — LiODOM hot path on MI355X: scans/sec on the BASELINE.json headline workload.
 
-    python bench.py --gpus N --steps K --warmup W [--workload hdl64|vlp16|ouster128]
+    python bench.py --gpus N --steps K --warmup W [--workload hdl64|vlp16|ouster128] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: one scan of one stream per
 GPU (edge extraction -> 2 x [correspondences + pose solve] -> window update), with the pose read back
@@ -12,7 +12,13 @@ on the previous pose and window), so N > 1 GPUs run N independent replayed strea
 no collective on the data path); torch.distributed (gloo) is used only for the barrier / max-over-ranks
 timing and for collecting each replica's parity.
 
-Output: ONE JSON line on rank 0 with metric/value/... plus
+Output: ONE JSON line on rank 0 with metric/value/unit/ms_per_step/... of the timed steps.  A plain run does
+only that: set-up, warm-up, the timed steps, the result line.
+  --dump-outputs DIR   after the timed steps, write what the last timed step returned to its caller (rank 0's stream):
+                DIR/pose.npy       float64 [7]: the pose of the last timed scan, [qx qy qz qw tx ty tz]
+                DIR/step_info.npy  float64 [16]: its liodom_step_info_t (STEP_INFO_FIELDS)
+                The synthetic stream is seeded: the same arguments give the same inputs on every run.
+  --full        also the legs below (each a run of its own after the timed steps; never `value`):
   roofline      dominant kernel of the timed workload: algorithmic bytes / HIP-event duration
   cpu_baseline  the CPU oracle ("port") on a bounded sample of the same scans, timed on this host:
                 1 thread, and the reference's own thread policy
@@ -23,7 +29,8 @@ Output: ONE JSON line on rank 0 with metric/value/... plus
                 extraction of scan k+1 overlap the odometry of scan k), and an extractor thread + an odometer thread
                 through liodom_extract_edges / liodom_odometry_step as INTEGRATION.md §2 prescribes (never `value`)
   batched       lock-step multi-stream run on one GPU (throughput mode) with its own roofline
-Exit status 3 if any replica's parity check fails.
+  strict_sync_scans_per_s / async_replay_scans_per_s / serial_scans_per_s   the same K steps in other consumer modes
+Exit status 3 if any replica's parity check (--full) fails.
 """
 import argparse
 import ctypes
@@ -31,6 +38,7 @@ import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")   # OpenMP threads (generator, CPU baseline) must not spin during GPU timing
 os.environ.setdefault("OMP_PROC_BIND", "false")
@@ -40,6 +48,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+REPEAT_BUDGET_S = 1.0   # the timed region is repeated (up to --repeats times) until the kept repeats add up to this
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md (6.29 TB/s measured copy)
 
@@ -209,6 +219,25 @@ def roofline_from_stats(stats, n_streams, N, E, M, C, evals, workload="hdl64"):
     }
 
 
+STEP_INFO_FIELDS = ("n_edges", "map_points", "matches0", "matches1",
+                    "lm0_iterations", "lm0_accepted", "lm0_termination", "lm0_initial_cost", "lm0_final_cost",
+                    "lm1_iterations", "lm1_accepted", "lm1_termination", "lm1_initial_cost", "lm1_final_cost",
+                    "status", "scan_index")
+
+
+def step_info_array(info):
+    """liodom_step_info_t as float64, in STEP_INFO_FIELDS order (every integer field is exact in a double)."""
+    lm = [v for t in info.lm for v in (t.iterations, t.accepted, t.termination, t.initial_cost, t.final_cost)]
+    return np.array([info.n_edges, info.map_points, info.matches[0], info.matches[1]] + lm + [info.status, info.scan_index],
+                    dtype=np.float64)
+
+
+def dump_outputs(out_dir, pose, info):
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pose.npy"), np.asarray(pose, dtype=np.float64))
+    np.save(os.path.join(out_dir, "step_info.npy"), step_info_array(info))
+
+
 def pose_errors(poses_a, poses_b):
     dt = np.linalg.norm(poses_a[:, 4:] - poses_b[:, 4:], axis=1)
     dots = np.abs(np.sum(poses_a[:, :4] * poses_b[:, :4], axis=1))
@@ -243,14 +272,19 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="hdl64", choices=sorted(WORKLOADS))
-    ap.add_argument("--batched-streams", type=int, default=256, help="lock-step streams of the throughput leg (0 = skip)")
-    ap.add_argument("--batched-data-streams", type=int, default=8, help="distinct synthetic streams replayed by the batched leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the pose and step info the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: roofline, other consumer modes, host-fed / two-thread, "
+                         "oracle parity, CPU baseline, lock-step batch")
+    ap.add_argument("--batched-streams", type=int, default=256, help="lock-step streams of the throughput leg (--full; 0 = skip)")
+    ap.add_argument("--batched-data-streams", type=int, default=8, help="distinct synthetic streams replayed by the batched leg (--full)")
     ap.add_argument("--repeats", type=int, default=9,
-                    help="the K-step timed region is measured this many times (each after a reset + untimed pre-fill + W warm-up steps, "
-                         "one more discarded first); `value` is the median")
+                    help="the K-step timed region is measured up to this many times (each after a reset + untimed pre-fill + W warm-up "
+                         "steps, one more discarded first; fewer once the kept regions add up to REPEAT_BUDGET_S); `value` is the median")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=100, help="timed scans of the CPU baseline sample (bounded)")
-    ap.add_argument("--parity-scans", type=int, default=0, help="scans compared with the oracle per replica (0 = prefill + warm-up + min(steps, 100))")
+    ap.add_argument("--cpu-sample", type=int, default=100, help="timed scans of the CPU baseline sample (--full; bounded)")
+    ap.add_argument("--parity-scans", type=int, default=0, help="scans compared with the oracle per replica (--full; 0 = prefill + warm-up + min(steps, 100))")
     args = ap.parse_args()
 
     # The process that drives the GPU on ONE core, from before the HIP runtime starts its own threads (they inherit the mask) — what
@@ -316,17 +350,32 @@ def main():
     total = F + Wm + K
     n_res = total + 1                        # (+ the scan whose extraction the last timed step issues)
 
-    # ---- synthetic stream (stream id = global rank), generated before anything is timed ----
-    cfg = synth.make_cfg(H, W, wl["lidar_type"])
-    scans = [synth.scan(cfg, rep.stream_id, k)[0] for k in range(n_res)]
-    if wl.get("ragged"):
-        scans = [synth.ragged(x, H, W, wl["lidar_type"], seed=1000 * rep.stream_id + k) for k, x in enumerate(scans)]
-
     params = la.make_params(lidar_type=wl["lidar_type"], scan_lines=H, scan_regions=R, edges_per_region=epr, prev_frames=P)
     g = la.Liodom(params, la.make_config(device=local_rank, n_streams=1, max_points=N, max_width=W, pose_log_capacity=total + 8))
     g.alloc_resident(n_res)
-    for k in range(n_res):
-        g.upload_scan(0, k, scans[k])
+
+    # ---- synthetic stream (stream id = global rank), generated and uploaded before anything is timed ----
+    # In chunks of 64 scans, each uploaded while a generator thread makes the next: host memory stays bounded whatever K is (only
+    # --full keeps every scan on the host: its host-fed, oracle and batched legs read them).  The generator thread and its OpenMP
+    # team run on the whole affinity mask: on the one core this thread drives the GPU from, the team would share that core.
+    cfg = synth.make_cfg(H, W, wl["lidar_type"])
+
+    def make_chunk(k0):
+        chunk = [synth.scan(cfg, rep.stream_id, k)[0] for k in range(k0, min(k0 + 64, n_res))]
+        if wl.get("ragged"):
+            chunk = [synth.ragged(x, H, W, wl["lidar_type"], seed=1000 * rep.stream_id + k0 + i) for i, x in enumerate(chunk)]
+        return chunk
+    scans = [] if args.full else None
+    with ThreadPoolExecutor(1, initializer=os.sched_setaffinity, initargs=(0, orig_affinity)) as generator:
+        pending = generator.submit(make_chunk, 0)
+        for k0 in range(0, n_res, 64):
+            chunk = pending.result()
+            if k0 + 64 < n_res:
+                pending = generator.submit(make_chunk, k0 + 64)
+            for i, x in enumerate(chunk):
+                g.upload_scan(0, k0 + i, x)
+            if scans is not None:
+                scans.extend(chunk)
     g.sync()
     time.sleep(0.5)   # let the host settle after the OpenMP-heavy generation (container CPU quota)
 
@@ -341,15 +390,15 @@ def main():
             # is read back before scan k+1's odometry is submitted; the GPU then idles for the host's turn-around.
             # ahead: the call also issues the extraction of the scan behind its last one, as every step inside it does for its
             # successor — the next call starts with that extraction already running beside the previous odometry (steady state)
-            g.replay_resident(first, count, N, H, W, depth=depth, ahead=ahead)
-            return
+            return g.replay_resident(first, count, N, H, W, depth=depth, ahead=ahead)
         for k in range(first, first + count):
             g.process_resident(k, N, H, W, readback=readback, next_slot=(k + 1 if (pipelined and k < last) else -1))
 
     # ---- timed region: untimed pre-fill + W warm-up steps, then exactly K steps, bracketed by sync + barrier.  A K-step region
     # lasts 1.6 ms at K = 20: one sample of it sits 6-7 % below the K = 200 figure on a freshly started process (clocks, first
     # launches of every kernel).  So the SAME region (reset, pre-fill, W warm-up steps, K timed steps: identical work, identical
-    # poses) is measured `repeats` + 1 times; the first is discarded, `value` is the median, the spread is reported beside it. ----
+    # poses) is measured `repeats` + 1 times; the first is discarded, `value` is the median, the spread is reported beside it.
+    # Long regions need no such help: the repeats stop once the kept ones add up to REPEAT_BUDGET_S of timed steps. ----
     samples = []
     for r in range(max(1, args.repeats) + 1):
         if r:
@@ -363,10 +412,12 @@ def main():
         g.sync()
         rep.barrier()
         t0 = time.perf_counter()
-        run(F + Wm, K, ahead=True)
+        last_step = run(F + Wm, K, ahead=True)
         g.sync()
         rep.barrier()
         samples.append(rep.max_over_ranks(time.perf_counter() - t0))
+        if sum(samples[1:]) >= REPEAT_BUDGET_S:
+            break
     kept = sorted(samples[1:]) if len(samples) > 1 else samples
     elapsed = kept[len(kept) // 2] if len(kept) % 2 else 0.5 * (kept[len(kept) // 2 - 1] + kept[len(kept) // 2])
     poses_gpu, infos = g.pose_log(0, 0, total)
@@ -377,119 +428,123 @@ def main():
         raise SystemExit("bench.py: the device raised status bits 0x%x (ring / edge / hash overflow): results invalid" % status_bits)
     value = world * K / elapsed
     timed = infos[F + Wm:]
+    if args.dump_outputs and rank == 0:
+        # (every repeat replays the same scans from the same reset state: the last repeat's last step is the last step)
+        dump_outputs(args.dump_outputs, last_step[0][-1, 0], last_step[1][-1])
 
-    # ---- roofline leg: same K steps again with HIP events around every kernel launch ----
-    g.reset()
-    run(0, F + Wm)
-    g.sync()
-    g.reset_kernel_stats()
-    g.set_profiling(True)
-    run(F + Wm, K)
-    stats = g.kernel_stats()
-    g.set_profiling(False)
     meanE = float(np.mean([i.n_edges for i in timed]))
     meanM = float(np.mean([i.map_points for i in timed]))
     meanC = float(np.mean([(i.matches[0] + i.matches[1]) / 2.0 for i in timed]))
     mean_evals = float(np.mean([(i.lm[0].iterations + i.lm[1].iterations + 2) / 2.0 for i in timed]))
-    roofline = roofline_from_stats(stats, 1, N, meanE, meanM, meanC, mean_evals, args.workload)
-    roofline8d = roofline_8d(stats, 1, N, meanE, meanM, meanC, mean_evals)
-    # Reference legs (never `value`): a K-step region lasts 1.5-3 ms at the driver's K = 20, and one sample of it swings by a
-    # third from run to run (3 500-6 200 scans/s for the serial leg on one box) — the median of three, as for the drop-in legs.
-    def ref_leg(**kw):
-        t_ = []
-        for _ in range(3):
-            g.reset()
-            run(0, F + Wm, **kw)
-            g.sync()
-            t1 = time.perf_counter()
-            run(F + Wm, K, **kw)
-            g.sync()
-            t_.append(time.perf_counter() - t1)
-        return K / sorted(t_)[1]
-    async_rate = ref_leg(readback=False)          # asynchronous replay (no per-scan readback)
-    strict_rate = ref_leg(depth=0)                # strictly synchronous consumer (pose k read back before scan k+1's odometry is submitted)
-    serial_rate = ref_leg(pipelined=False)        # strictly serial scans (no overlap between extraction and odometry)
     modes = g.modes()
-    # ---- drop-in-shaped legs (rank 0 of a 1-GPU run only; never `value`) ----
     host_fed = two_thread = None
-    if world == 1:
-        # (a) scans arrive in HOST memory: pinned ring, upload + extraction of scan k+1 overlap the odometry of scan k, every pose read back
-        host = np.zeros((total, 1, N, 4), dtype=np.float32)
-        for k in range(total):
-            host[k, 0, :scans[k].shape[0]] = scans[k]
-        # The host ring is page-locked ONCE, outside every timed region (a node assembles its clouds in a pinned ring that lives as long
-        # as the node: liodom_scan_buffer / liodom_pin_host_buffer); earlier rounds registered and unregistered the K scans inside
-        # the timed call.  Two figures: the single call over the K timed scans (cold start: the first scan's upload + extraction
-        # overlap nothing, the pipeline drains at the end) and the STEADY-STATE rate = K / (T(2K scans) - T(K scans)), both replays
-        # from the same pre-filled state — the difference removes those fixed costs, which at the driver's K = 20 are a sixth of the call.
-        pinned = g.L.liodom_pin_host_buffer(host.ctypes.data_as(ctypes.c_void_p), host.nbytes) == 0
-        # (2K scans: the K timed scans, then the same K scans walked backwards — a continuous trajectory, page-locked as one array)
-        hf_src = np.ascontiguousarray(np.concatenate([host[F + Wm:F + Wm + K], host[F + Wm:F + Wm + K][::-1]]))
-        src_pinned = g.L.liodom_pin_host_buffer(hf_src.ctypes.data_as(ctypes.c_void_p), hf_src.nbytes) == 0
-
-        def hf_call(n_scans):
-            g.reset()
-            g.replay_host(host[:F + Wm], N, H, W, depth=1, pin=not pinned)
-            t = time.perf_counter()
-            p_, _ = g.replay_host(hf_src[:n_scans], N, H, W, depth=1, pin=not src_pinned)
-            return time.perf_counter() - t, p_
-        try:
-            t_k, t_2k, hp = [], [], None
+    if args.full:
+        # ---- roofline leg: same K steps again with HIP events around every kernel launch ----
+        g.reset()
+        run(0, F + Wm)
+        g.sync()
+        g.reset_kernel_stats()
+        g.set_profiling(True)
+        run(F + Wm, K)
+        stats = g.kernel_stats()
+        g.set_profiling(False)
+        roofline = roofline_from_stats(stats, 1, N, meanE, meanM, meanC, mean_evals, args.workload)
+        roofline8d = roofline_8d(stats, 1, N, meanE, meanM, meanC, mean_evals)
+        # Reference legs (never `value`): a K-step region lasts 1.5-3 ms at the driver's K = 20, and one sample of it swings by a
+        # third from run to run (3 500-6 200 scans/s for the serial leg on one machine) — the median of three, as for the drop-in legs.
+        def ref_leg(**kw):
+            t_ = []
             for _ in range(3):
-                a_, p_ = hf_call(K)
-                t_k.append(a_)
-                hp = p_ if hp is None else hp
-                b_, _p2 = hf_call(2 * K)
-                t_2k.append(b_)
-        finally:
-            if src_pinned:
-                g.L.liodom_unpin_host_buffer(hf_src.ctypes.data_as(ctypes.c_void_p))
-            if pinned:
-                g.L.liodom_unpin_host_buffer(host.ctypes.data_as(ctypes.c_void_p))
-        th = sorted(t_k)[1]
-        th2 = sorted(t_2k)[1]
-        # (continues the same trajectory: must equal the resident replay's poses)
-        hf_ok = bool(np.array_equal(hp[:, 0].view(np.uint64), poses_gpu[F + Wm:F + Wm + K].view(np.uint64)))
-        # (scans_per_s keeps its meaning of rounds 1-4 — one call over the K timed scans —; the differential figure has a name of its own
-        #  and is only quoted when the difference of the two medians is a measurement: at least a quarter of the single call)
-        steady = K / (th2 - th) if (th2 - th) > 0.25 * th else None
-        host_fed = {"scans_per_s": round(K / th, 2), "us_per_scan": round(th / K * 1e6, 2),
-                    "steady_state_scans_per_s": round(steady, 2) if steady else None,
-                    "single_call_spread_s": [round(x, 6) for x in sorted(t_k)], "double_call_spread_s": [round(x, 6) for x in sorted(t_2k)],
-                    "mode": "liodom_replay_host, depth 1: page-locked host ring (pinned once, outside the timed region) -> hipMemcpyAsync (%.2f MB per scan), "
-                            "upload + extraction of scan k+1 beside the odometry of scan k, every pose read back in order; scans_per_s = one call over the "
-                            "K timed scans, cold start and drain included (median of 3); steady_state_scans_per_s = K / (T(2K scans) - T(K scans)), "
-                            "the second K scans being the first K walked backwards" % (N * 16 / 1e6),
-                    "poses_bit_equal_to_resident_replay": hf_ok}
-        # (b) two threads through the C-ABI, as the reference node runs its FeatureExtractor / LaserOdometer threads (liodom_node.cc:89-91):
-        # two C++ threads (liodom_host_two_thread_replay, liodom_amd/host) — the extractor thread uploads every scan from host
-        # memory, extracts and fetches the ~edges cloud, the edge cloud itself stays on the device (ticket queue), the odometer
-        # thread reads every pose back
-        g.reset()
-        if pin_core is not None:                 # two busy threads from here on: the full mask again
-            try:
-                os.sched_setaffinity(0, wide_affinity)      # (the GPU's own socket where the topology is known)
-            except Exception:
-                pass
-        nrun = F + Wm + K
-        tt_all = []
-        for _ in range(3):                         # (median of three, like every other leg)
-            if tt_all:
                 g.reset()
-            tt_all.append(g.two_thread_replay(host[:nrun, 0], N, H, W, timed_from=F + Wm, fetch_edges=True, depth=1))
-        tt_poses, tt, tt_edges = sorted(tt_all, key=lambda x: x[1])[1]
-        two_thread = {"scans_per_s": round(K / tt, 2), "us_per_scan": round(tt / K * 1e6, 2),
-                      "mode": "two C++ threads on one handle (liodom_host_two_thread_replay): extractor = liodom_extract_edges_device "
-                              "(scan uploaded from page-locked host memory, %.2f MB) + liodom_wait_edges (the ~edges cloud, host copy); "
-                              "ticket queue; odometer = liodom_odometry_submit_device / liodom_odometry_collect (depth 1, every pose read "
-                              "back in order)" % (N * 16 / 1e6),
-                      "edges_fetched": int(tt_edges),
-                      "poses_bit_equal_to_resident_replay": bool(np.array_equal(tt_poses.view(np.uint64), poses_gpu[:nrun].view(np.uint64)))}
-        g.reset()
-        tt0_poses, tt0, _ = g.two_thread_replay(host[:nrun, 0], N, H, W, timed_from=F + Wm, fetch_edges=True, depth=0)
-        two_thread["strict_sync_scans_per_s"] = round(K / tt0, 2)
-        two_thread["poses_bit_equal_to_resident_replay"] = bool(two_thread["poses_bit_equal_to_resident_replay"] and
-                                                                np.array_equal(tt0_poses.view(np.uint64), poses_gpu[:nrun].view(np.uint64)))
+                run(0, F + Wm, **kw)
+                g.sync()
+                t1 = time.perf_counter()
+                run(F + Wm, K, **kw)
+                g.sync()
+                t_.append(time.perf_counter() - t1)
+            return K / sorted(t_)[1]
+        async_rate = ref_leg(readback=False)          # asynchronous replay (no per-scan readback)
+        strict_rate = ref_leg(depth=0)                # strictly synchronous consumer (pose k read back before scan k+1's odometry is submitted)
+        serial_rate = ref_leg(pipelined=False)        # strictly serial scans (no overlap between extraction and odometry)
+        # ---- drop-in-shaped legs (rank 0 of a 1-GPU run only; never `value`) ----
+        if world == 1:
+            # (a) scans arrive in HOST memory: pinned ring, upload + extraction of scan k+1 overlap the odometry of scan k, every pose read back
+            host = np.zeros((total, 1, N, 4), dtype=np.float32)
+            for k in range(total):
+                host[k, 0, :scans[k].shape[0]] = scans[k]
+            # The host ring is page-locked ONCE, outside every timed region (a node assembles its clouds in a pinned ring that lives as long
+            # as the node: liodom_scan_buffer / liodom_pin_host_buffer); earlier rounds registered and unregistered the K scans inside
+            # the timed call.  Two figures: the single call over the K timed scans (cold start: the first scan's upload + extraction
+            # overlap nothing, the pipeline drains at the end) and the STEADY-STATE rate = K / (T(2K scans) - T(K scans)), both replays
+            # from the same pre-filled state — the difference removes those fixed costs, which at the driver's K = 20 are a sixth of the call.
+            pinned = g.L.liodom_pin_host_buffer(host.ctypes.data_as(ctypes.c_void_p), host.nbytes) == 0
+            # (2K scans: the K timed scans, then the same K scans walked backwards — a continuous trajectory, page-locked as one array)
+            hf_src = np.ascontiguousarray(np.concatenate([host[F + Wm:F + Wm + K], host[F + Wm:F + Wm + K][::-1]]))
+            src_pinned = g.L.liodom_pin_host_buffer(hf_src.ctypes.data_as(ctypes.c_void_p), hf_src.nbytes) == 0
+
+            def hf_call(n_scans):
+                g.reset()
+                g.replay_host(host[:F + Wm], N, H, W, depth=1, pin=not pinned)
+                t = time.perf_counter()
+                p_, _ = g.replay_host(hf_src[:n_scans], N, H, W, depth=1, pin=not src_pinned)
+                return time.perf_counter() - t, p_
+            try:
+                t_k, t_2k, hp = [], [], None
+                for _ in range(3):
+                    a_, p_ = hf_call(K)
+                    t_k.append(a_)
+                    hp = p_ if hp is None else hp
+                    b_, _p2 = hf_call(2 * K)
+                    t_2k.append(b_)
+            finally:
+                if src_pinned:
+                    g.L.liodom_unpin_host_buffer(hf_src.ctypes.data_as(ctypes.c_void_p))
+                if pinned:
+                    g.L.liodom_unpin_host_buffer(host.ctypes.data_as(ctypes.c_void_p))
+            th = sorted(t_k)[1]
+            th2 = sorted(t_2k)[1]
+            # (continues the same trajectory: must equal the resident replay's poses)
+            hf_ok = bool(np.array_equal(hp[:, 0].view(np.uint64), poses_gpu[F + Wm:F + Wm + K].view(np.uint64)))
+            # (scans_per_s keeps its meaning of rounds 1-4 — one call over the K timed scans —; the differential figure has a name of its own
+            #  and is only quoted when the difference of the two medians is a measurement: at least a quarter of the single call)
+            steady = K / (th2 - th) if (th2 - th) > 0.25 * th else None
+            host_fed = {"scans_per_s": round(K / th, 2), "us_per_scan": round(th / K * 1e6, 2),
+                        "steady_state_scans_per_s": round(steady, 2) if steady else None,
+                        "single_call_spread_s": [round(x, 6) for x in sorted(t_k)], "double_call_spread_s": [round(x, 6) for x in sorted(t_2k)],
+                        "mode": "liodom_replay_host, depth 1: page-locked host ring (pinned once, outside the timed region) -> hipMemcpyAsync (%.2f MB per scan), "
+                                "upload + extraction of scan k+1 beside the odometry of scan k, every pose read back in order; scans_per_s = one call over the "
+                                "K timed scans, cold start and drain included (median of 3); steady_state_scans_per_s = K / (T(2K scans) - T(K scans)), "
+                                "the second K scans being the first K walked backwards" % (N * 16 / 1e6),
+                        "poses_bit_equal_to_resident_replay": hf_ok}
+            # (b) two threads through the C-ABI, as the reference node runs its FeatureExtractor / LaserOdometer threads (liodom_node.cc:89-91):
+            # two C++ threads (liodom_host_two_thread_replay, liodom_amd/host) — the extractor thread uploads every scan from host
+            # memory, extracts and fetches the ~edges cloud, the edge cloud itself stays on the device (ticket queue), the odometer
+            # thread reads every pose back
+            g.reset()
+            if pin_core is not None:                 # two busy threads from here on: the full mask again
+                try:
+                    os.sched_setaffinity(0, wide_affinity)      # (the GPU's own socket where the topology is known)
+                except Exception:
+                    pass
+            nrun = F + Wm + K
+            tt_all = []
+            for _ in range(3):                         # (median of three, like every other leg)
+                if tt_all:
+                    g.reset()
+                tt_all.append(g.two_thread_replay(host[:nrun, 0], N, H, W, timed_from=F + Wm, fetch_edges=True, depth=1))
+            tt_poses, tt, tt_edges = sorted(tt_all, key=lambda x: x[1])[1]
+            two_thread = {"scans_per_s": round(K / tt, 2), "us_per_scan": round(tt / K * 1e6, 2),
+                          "mode": "two C++ threads on one handle (liodom_host_two_thread_replay): extractor = liodom_extract_edges_device "
+                                  "(scan uploaded from page-locked host memory, %.2f MB) + liodom_wait_edges (the ~edges cloud, host copy); "
+                                  "ticket queue; odometer = liodom_odometry_submit_device / liodom_odometry_collect (depth 1, every pose read "
+                                  "back in order)" % (N * 16 / 1e6),
+                          "edges_fetched": int(tt_edges),
+                          "poses_bit_equal_to_resident_replay": bool(np.array_equal(tt_poses.view(np.uint64), poses_gpu[:nrun].view(np.uint64)))}
+            g.reset()
+            tt0_poses, tt0, _ = g.two_thread_replay(host[:nrun, 0], N, H, W, timed_from=F + Wm, fetch_edges=True, depth=0)
+            two_thread["strict_sync_scans_per_s"] = round(K / tt0, 2)
+            two_thread["poses_bit_equal_to_resident_replay"] = bool(two_thread["poses_bit_equal_to_resident_replay"] and
+                                                                    np.array_equal(tt0_poses.view(np.uint64), poses_gpu[:nrun].view(np.uint64)))
     dev_name, cus = g.device_info()
     g.close()
 
@@ -520,12 +575,15 @@ def main():
                        "environment": {k: v for k, v in os.environ.items() if k.startswith("LIODOM_") or k in ("HIP_FORCE_DEV_KERNARG", "AMD_SERIALIZE_KERNEL", "HIP_LAUNCH_BLOCKING")}},
             "value_spread": {"min": round(world * K / max(kept), 2), "max": round(world * K / min(kept), 2),
                              "first_discarded": round(world * K / samples[0], 2) if len(samples) > 1 else None},
-            "strict_sync_scans_per_s": round(strict_rate, 2),
-            "async_replay_scans_per_s": round(async_rate, 2),
-            "serial_scans_per_s": round(serial_rate, 2),
-            "roofline": roofline,
-            "roofline_8d": roofline8d,
         }
+        if args.full:
+            out.update({
+                "strict_sync_scans_per_s": round(strict_rate, 2),
+                "async_replay_scans_per_s": round(async_rate, 2),
+                "serial_scans_per_s": round(serial_rate, 2),
+                "roofline": roofline,
+                "roofline_8d": roofline8d,
+            })
         if host_fed:
             out["host_fed_scans_per_s"] = host_fed["scans_per_s"]          # PCIe-inclusive rate (never `value`)
             out["two_thread_scans_per_s"] = two_thread["scans_per_s"]      # the C-ABI as a patched liodom_node drives it
@@ -534,125 +592,127 @@ def main():
         if args.workload not in ("hdl64",):
             out["metric"] = "scans/sec (%dx%d cloud, prev_frames=%d) at 1 GPU; pose RMSE vs CPU ref" % (H, W, P)
 
-    # ---- parity, every replica on its own stream (the oracle on the host cores of that rank) ----
-    from oracle import oracle as orc
-    n_par = args.parity_scans if args.parity_scans > 0 else F + Wm + min(K, 100)
-    n_par = min(n_par, total)
-    want_baseline = rank == 0 and world == 1 and not args.no_cpu_baseline
-    n_cpu = min(K, max(1, args.cpu_sample))
-    n_run = max(n_par, F + Wm + n_cpu) if want_baseline else n_par
-    poses_cpu, tc = run_oracle(orc, wl, scans[:n_run], (1, 1), time_from=F + Wm)
-    dt, dr = pose_errors(poses_gpu[:n_par], poses_cpu[:n_par])
-    worst_t = rep.max_over_ranks(float(dt.max()))
-    worst_r = rep.max_over_ranks(float(dr.max()))
-    if rank == 0:
-        out["parity"] = {
-            "pose_trans_rmse_m": float(np.sqrt(np.mean(dt ** 2))), "pose_trans_max_m": float(dt.max()),
-            "pose_rot_rmse_rad": float(np.sqrt(np.mean(dr ** 2))), "pose_rot_max_rad": float(dr.max()),
-            "worst_replica_trans_max_m": worst_t, "worst_replica_rot_max_rad": worst_r, "replicas_checked": world,
-            "tolerance": "1e-4 m / 1e-4 rad per scan", "scans_compared": int(n_par),
-            "pass": bool(worst_t <= 1e-4 and worst_r <= 1e-4),
-        }
+    if args.full:
+        # ---- parity, every replica on its own stream (the oracle on the host cores of that rank) ----
+        from oracle import oracle as orc
+        n_par = args.parity_scans if args.parity_scans > 0 else F + Wm + min(K, 100)
+        n_par = min(n_par, total)
+        want_baseline = rank == 0 and world == 1 and not args.no_cpu_baseline
+        n_cpu = min(K, max(1, args.cpu_sample))
+        n_run = max(n_par, F + Wm + n_cpu) if want_baseline else n_par
+        poses_cpu, tc = run_oracle(orc, wl, scans[:n_run], (1, 1), time_from=F + Wm)
+        dt, dr = pose_errors(poses_gpu[:n_par], poses_cpu[:n_par])
+        worst_t = rep.max_over_ranks(float(dt.max()))
+        worst_r = rep.max_over_ranks(float(dr.max()))
+        if rank == 0:
+            out["parity"] = {
+                "pose_trans_rmse_m": float(np.sqrt(np.mean(dt ** 2))), "pose_trans_max_m": float(dt.max()),
+                "pose_rot_rmse_rad": float(np.sqrt(np.mean(dr ** 2))), "pose_rot_max_rad": float(dr.max()),
+                "worst_replica_trans_max_m": worst_t, "worst_replica_rot_max_rad": worst_r, "replicas_checked": world,
+                "tolerance": "1e-4 m / 1e-4 rad per scan", "scans_compared": int(n_par),
+                "pass": bool(worst_t <= 1e-4 and worst_r <= 1e-4),
+            }
 
-    # ---- CPU baseline (rank 0, N = 1 only): bounded sample, 1 thread and the reference's thread policy ----
-    if want_baseline:
-        n_timed = n_run - (F + Wm)
-        nproc = os.cpu_count() or 1
-        st_threads, ev_threads = max(2, nproc - 5), nproc      # feature_extractor.cc:29-34, laser_odometry.cc:216
-        # the reference's thread counts come from the machine, not from this process's affinity mask: give the OpenMP
-        # threads the CPUs back that pin_cpus() took away for the GPU legs (nproc threads on one NUMA node's cores
-        # would time an oversubscribed run)
-        try:
-            os.sched_setaffinity(0, orig_affinity)
-        except Exception:
-            pass
-        _, tc_ref = run_oracle(orc, wl, scans[:n_run], (st_threads, ev_threads), time_from=F + Wm)
-        try:
-            cpu_model = [l.split(":", 1)[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name")][0]
-        except Exception:
-            cpu_model = "unknown"
-        out["cpu_baseline"] = {
-            "value": round(n_timed / tc, 3), "unit": "scans/s", "cores": 1, "kind": "port",
-            "sample": "scans %d..%d of the same stream (%d timed after %d untimed pre-fill + warm-up scans), CPU oracle "
-                      "(oracle/liodom_oracle.cc, kd-tree kNN rebuilt twice per scan), 1 thread of %d" % (F + Wm, n_run - 1, n_timed, F + Wm, nproc),
-            "gpu_over_cpu": round(value / (n_timed / tc), 1),
-            "reference_policy": {
-                "value": round(n_timed / tc_ref, 3), "unit": "scans/s", "cores": nproc,
-                "stencil_threads": st_threads, "residual_eval_threads": ev_threads,
-                "policy": "stencil loop omp num_threads = max(2, nproc - 5) (feature_extractor.cc:29-34,194); residual blocks "
-                          "evaluated by nproc threads (laser_odometry.cc:216); everything else serial as in the reference",
-                "OMP_WAIT_POLICY": os.environ.get("OMP_WAIT_POLICY"), "OMP_PROC_BIND": os.environ.get("OMP_PROC_BIND"),
-            },
-            "nproc": nproc, "cpu_model": cpu_model,
-        }
-
-    # ---- batched leg: lock-step streams on one GPU (throughput mode; separately labelled) ----
-    if rank == 0 and args.batched_streams > 0 and world == 1:
-        S = args.batched_streams
-        if pin_core is not None:
+        # ---- CPU baseline (rank 0, N = 1 only): bounded sample, 1 thread and the reference's thread policy ----
+        if want_baseline:
+            n_timed = n_run - (F + Wm)
+            nproc = os.cpu_count() or 1
+            st_threads, ev_threads = max(2, nproc - 5), nproc      # feature_extractor.cc:29-34, laser_odometry.cc:216
+            # the reference's thread counts come from the machine, not from this process's affinity mask: give the OpenMP
+            # threads the CPUs back that pin_cpus() took away for the GPU legs (nproc threads on one NUMA node's cores
+            # would time an oversubscribed run)
             try:
-                os.sched_setaffinity(0, {pin_core})      # (single enqueueing thread again)
+                os.sched_setaffinity(0, orig_affinity)
             except Exception:
                 pass
-        Kb, Wb = min(K, 20), F + min(Wm, 4)      # pre-fill + a few warm-up steps, then Kb timed steps
-        tb = Kb + Wb
-        n_data = max(1, min(args.batched_data_streams, S))   # distinct synthetic streams; stream s replays data stream s % n_data
-        data = [scans[:tb]] + [[synth.scan(cfg, 1000 + d, k)[0] for k in range(tb)] for d in range(1, n_data)]
-        if wl.get("ragged"):
-            data = [data[0]] + [[synth.ragged(x, H, W, wl["lidar_type"], seed=1000 * (1000 + d) + k) for k, x in enumerate(data[d])] for d in range(1, n_data)]
-        gb = la.Liodom(params, la.make_config(device=local_rank, n_streams=S, max_points=N, max_width=W, pose_log_capacity=tb + 8))
-        bmodes = gb.modes()
-        gb.alloc_resident(tb)
-        for s in range(S):
-            for k in range(tb):
-                gb.upload_scan(s, k, data[s % n_data][k])
-        gb.sync()
-        time.sleep(0.5)
-        for k in range(Wb):
-            gb.process_resident(k, N, H, W, readback=True, next_slot=(k + 1 if k + 1 < Wb else -1))
-        gb.sync()
-        t2 = time.perf_counter()
-        for k in range(Wb, tb):      # same mode as the headline: per-step synchronous, next extraction overlapped
-            gb.process_resident(k, N, H, W, readback=True, next_slot=(k + 1 if k + 1 < tb else -1))
-        gb.sync()
-        eb = time.perf_counter() - t2
-        bposes, binfos = gb.pose_log(0, 0, tb)
-        bstatus = 0
-        for s in range(0, S, max(1, S // 8)):
-            for i in gb.pose_log(s, 0, tb)[1]:
-                bstatus |= int(i.status)
-        # lock-step stream 0 replays the headline data stream: same poses as the single-stream handle
-        bdt, bdr = pose_errors(bposes[:min(tb, n_par)], poses_gpu[:min(tb, n_par)])
-        gb.reset()
-        for k in range(Wb):
-            gb.process_resident(k, N, H, W, readback=True)
-        gb.reset_kernel_stats()
-        gb.set_profiling(True)
-        for k in range(Wb, tb):
-            gb.process_resident(k, N, H, W, readback=True)
-        bstats = gb.kernel_stats()
-        gb.set_profiling(False)
-        gb.close()
-        bt = binfos[Wb:]
-        bE = float(np.mean([i.n_edges for i in bt]))
-        bM = float(np.mean([i.map_points for i in bt]))
-        bC = float(np.mean([(i.matches[0] + i.matches[1]) / 2.0 for i in bt]))
-        bev = float(np.mean([(i.lm[0].iterations + i.lm[1].iterations + 2) / 2.0 for i in bt]))
-        out["batched"] = {
-            "streams": S, "steps": Kb, "warmup": Wb, "value": round(S * Kb / eb, 1), "unit": "scans/s (aggregate, 1 GPU)",
-            "ms_per_step": round(eb / Kb * 1e3, 4), "distinct_data_streams": n_data, "status_bits": bstatus,
-            "stream0_vs_single_stream_max_m": float(bdt.max()), "stream0_vs_single_stream_max_rad": float(bdr.max()),
-            "note": "lock-step streams in one launch per kernel, per-step synchronous, extraction of step k+1 overlapped; "
-                    "%d distinct synthetic streams replayed round-robin" % n_data,
-            "roofline": roofline_from_stats(bstats, S, N, bE, bM, bC, bev, args.workload),
-            "roofline_8d": roofline_8d(bstats, S, N, bE, bM, bC, bev),
-            "modes": bmodes,
-        }
+            _, tc_ref = run_oracle(orc, wl, scans[:n_run], (st_threads, ev_threads), time_from=F + Wm)
+            try:
+                cpu_model = [l.split(":", 1)[1].strip() for l in open("/proc/cpuinfo") if l.startswith("model name")][0]
+            except Exception:
+                cpu_model = "unknown"
+            out["cpu_baseline"] = {
+                "value": round(n_timed / tc, 3), "unit": "scans/s", "cores": 1, "kind": "port",
+                "sample": "scans %d..%d of the same stream (%d timed after %d untimed pre-fill + warm-up scans), CPU oracle "
+                          "(oracle/liodom_oracle.cc, kd-tree kNN rebuilt twice per scan), 1 thread of %d" % (F + Wm, n_run - 1, n_timed, F + Wm, nproc),
+                "gpu_over_cpu": round(value / (n_timed / tc), 1),
+                "reference_policy": {
+                    "value": round(n_timed / tc_ref, 3), "unit": "scans/s", "cores": nproc,
+                    "stencil_threads": st_threads, "residual_eval_threads": ev_threads,
+                    "policy": "stencil loop omp num_threads = max(2, nproc - 5) (feature_extractor.cc:29-34,194); residual blocks "
+                              "evaluated by nproc threads (laser_odometry.cc:216); everything else serial as in the reference",
+                    "OMP_WAIT_POLICY": os.environ.get("OMP_WAIT_POLICY"), "OMP_PROC_BIND": os.environ.get("OMP_PROC_BIND"),
+                },
+                "nproc": nproc, "cpu_model": cpu_model,
+            }
+
+        # ---- batched leg: lock-step streams on one GPU (throughput mode; separately labelled) ----
+        if rank == 0 and args.batched_streams > 0 and world == 1:
+            S = args.batched_streams
+            if pin_core is not None:
+                try:
+                    os.sched_setaffinity(0, {pin_core})      # (single enqueueing thread again)
+                except Exception:
+                    pass
+            Kb, Wb = min(K, 20), F + min(Wm, 4)      # pre-fill + a few warm-up steps, then Kb timed steps
+            tb = Kb + Wb
+            n_data = max(1, min(args.batched_data_streams, S))   # distinct synthetic streams; stream s replays data stream s % n_data
+            data = [scans[:tb]] + [[synth.scan(cfg, 1000 + d, k)[0] for k in range(tb)] for d in range(1, n_data)]
+            if wl.get("ragged"):
+                data = [data[0]] + [[synth.ragged(x, H, W, wl["lidar_type"], seed=1000 * (1000 + d) + k) for k, x in enumerate(data[d])] for d in range(1, n_data)]
+            gb = la.Liodom(params, la.make_config(device=local_rank, n_streams=S, max_points=N, max_width=W, pose_log_capacity=tb + 8))
+            bmodes = gb.modes()
+            gb.alloc_resident(tb)
+            for s in range(S):
+                for k in range(tb):
+                    gb.upload_scan(s, k, data[s % n_data][k])
+            gb.sync()
+            time.sleep(0.5)
+            for k in range(Wb):
+                gb.process_resident(k, N, H, W, readback=True, next_slot=(k + 1 if k + 1 < Wb else -1))
+            gb.sync()
+            t2 = time.perf_counter()
+            for k in range(Wb, tb):      # same mode as the headline: per-step synchronous, next extraction overlapped
+                gb.process_resident(k, N, H, W, readback=True, next_slot=(k + 1 if k + 1 < tb else -1))
+            gb.sync()
+            eb = time.perf_counter() - t2
+            bposes, binfos = gb.pose_log(0, 0, tb)
+            bstatus = 0
+            for s in range(0, S, max(1, S // 8)):
+                for i in gb.pose_log(s, 0, tb)[1]:
+                    bstatus |= int(i.status)
+            # lock-step stream 0 replays the headline data stream: same poses as the single-stream handle
+            bdt, bdr = pose_errors(bposes[:min(tb, n_par)], poses_gpu[:min(tb, n_par)])
+            gb.reset()
+            for k in range(Wb):
+                gb.process_resident(k, N, H, W, readback=True)
+            gb.reset_kernel_stats()
+            gb.set_profiling(True)
+            for k in range(Wb, tb):
+                gb.process_resident(k, N, H, W, readback=True)
+            bstats = gb.kernel_stats()
+            gb.set_profiling(False)
+            gb.close()
+            bt = binfos[Wb:]
+            bE = float(np.mean([i.n_edges for i in bt]))
+            bM = float(np.mean([i.map_points for i in bt]))
+            bC = float(np.mean([(i.matches[0] + i.matches[1]) / 2.0 for i in bt]))
+            bev = float(np.mean([(i.lm[0].iterations + i.lm[1].iterations + 2) / 2.0 for i in bt]))
+            out["batched"] = {
+                "streams": S, "steps": Kb, "warmup": Wb, "value": round(S * Kb / eb, 1), "unit": "scans/s (aggregate, 1 GPU)",
+                "ms_per_step": round(eb / Kb * 1e3, 4), "distinct_data_streams": n_data, "status_bits": bstatus,
+                "stream0_vs_single_stream_max_m": float(bdt.max()), "stream0_vs_single_stream_max_rad": float(bdr.max()),
+                "note": "lock-step streams in one launch per kernel, per-step synchronous, extraction of step k+1 overlapped; "
+                        "%d distinct synthetic streams replayed round-robin" % n_data,
+                "roofline": roofline_from_stats(bstats, S, N, bE, bM, bC, bev, args.workload),
+                "roofline_8d": roofline_8d(bstats, S, N, bE, bM, bC, bev),
+                "modes": bmodes,
+            }
 
     rep.close()
     if rank == 0:
         print(json.dumps(out))
-        if not out["parity"]["pass"] or (host_fed and not (host_fed["poses_bit_equal_to_resident_replay"] and two_thread["poses_bit_equal_to_resident_replay"])):
+        if (args.full and not out["parity"]["pass"]) or (host_fed and not (host_fed["poses_bit_equal_to_resident_replay"] and
+                                                                             two_thread["poses_bit_equal_to_resident_replay"])):
             sys.exit(3)
 
 

@@ -10,16 +10,16 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd $R
 if [ "${SKIP_PYTEST:-0}" != "1" ]; then timeout 1800 python -m pytest tests -m gpu -q > $OUT/${TAG}_pytest_gpu.log 2>&1; tail -3 $OUT/${TAG}_pytest_gpu.log; fi
-timeout 900 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.stderr
+timeout 900 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.stderr
 WLS="hdl64"
 if [ "${OTHER_WORKLOADS:-1}" = "1" ]; then WLS="hdl64 vlp16 ouster128"; fi
 for WLD in $WLS; do
   SUF="_$WLD"; if [ $WLD = hdl64 ]; then SUF=""; fi
-  if [ $WLD != hdl64 ]; then timeout 600 python bench.py --workload $WLD --batched-streams 0 > $OUT/${TAG}_bench${SUF}.json 2> $OUT/${TAG}_bench${SUF}.stderr; fi
+  if [ $WLD != hdl64 ]; then timeout 600 python bench.py --workload $WLD --full --batched-streams 0 > $OUT/${TAG}_bench${SUF}.json 2> $OUT/${TAG}_bench${SUF}.stderr; fi
   ( cd /tmp; rm -rf $OUT/prof_kt
-    timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_kt -- python3 $R/bench.py --workload $WLD --steps 100 --warmup 20 --batched-streams 0 --no-cpu-baseline > /dev/null 2> $OUT/kt_$WLD.stderr
+    timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_kt -- python3 $R/bench.py --workload $WLD --steps 100 --warmup 20 --full --batched-streams 0 --no-cpu-baseline > /dev/null 2> $OUT/kt_$WLD.stderr
     DB=$(find $OUT/prof_kt -name "*.db" | head -1)
-    { echo "# $TAG: rocprofv3 --kernel-trace --stats -- python3 bench.py --workload $WLD --steps 100 --warmup 20 --batched-streams 0 --no-cpu-baseline";
+    { echo "# $TAG: rocprofv3 --kernel-trace --stats -- python3 bench.py --workload $WLD --steps 100 --warmup 20 --full --batched-streams 0 --no-cpu-baseline";
       echo "# legs: timed (pipelined) + HIP-event + async + strict + serial (+ host-fed, two-thread)";
       python3 $R/tools/rocprof_summary.py $DB; python3 $R/tools/rocprof_passes.py $DB; } > $OUT/${TAG}_bench${SUF}_kernel_trace.txt
     rm -rf $OUT/prof_kt
