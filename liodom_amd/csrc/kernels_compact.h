@@ -24,7 +24,7 @@ __device__ __forceinline__ void compact_edges_body(const DevView& v, int s0, int
     // threads >= H contribute 0, so pre[H] already equals the total
   }
   // mirror: the device-resident hand-off also leaves the edges in host-mapped memory (slot eb) for the thread that publishes
-  // ~edges; the stores cross PCIe while the kernel runs and are complete when it ends (k_publish_edges follows in stream order)
+  // ~edges; the stores cross PCIe while the kernel runs (the launch's last workgroup publishes them behind a system-scope fence)
   const bool to_host = mirror != 0 && v.host_edges != nullptr && eb < kEdgePipeBufs;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const int acc = pre[256];
@@ -53,12 +53,11 @@ __device__ __forceinline__ void compact_edges_body(const DevView& v, int s0, int
   }
 }
 
-// pub_value != 0 (round 6): the launch also PUBLISHES the extraction — what k_publish_edges / k_set_flag did in a launch of their
-// own behind this one (~5 us of the extraction stream per scan, the stream that bounds the two-thread binding): every thread
-// completes its stores (system scope: the mirror in host memory included), the workgroups count themselves on pub_counter[eb],
-// and the last one to arrive writes the sequence number for the odometry side's kernels (pub_flag, may be null) and for the host
-// thread that waits for the edges (pub_host, may be null).  A launch whose wait gave up still counts and publishes, as the
-// separate launch did.
+// pub_value != 0: the launch also PUBLISHES the extraction (a launch of its own behind this one cost ~5 us of the extraction stream
+// per scan, the stream that bounds the two-thread binding): every thread completes its stores (system scope: the mirror in host
+// memory included), the workgroups count themselves on pub_counter[eb], and the last one to arrive writes the sequence number for
+// the odometry side's kernels (pub_flag, may be null) and for the host thread that waits for the edges (pub_host, may be null).
+// A launch whose wait gave up still counts and publishes.
 __global__ __launch_bounds__(256) void k_compact_edges(DevView v, int s0, int eb, unsigned int wait_odo, int mirror,
                                                        unsigned int* pub_flag, unsigned int* pub_host, unsigned int pub_value) {
   __shared__ int pre[257];
@@ -81,15 +80,6 @@ __global__ __launch_bounds__(256) void k_compact_edges(DevView v, int s0, int eb
       }
     }
   }
-}
-// Behind k_compact_edges in stream order (that launch has ended: its stores, to HBM and to host memory, are complete):
-// the extraction's sequence number for the odometry side's kernels (dev_flag, as k_set_flag; may be null) and for the host
-// thread that waits for the edges (host_seq, system scope; may be null).
-__global__ void k_publish_edges(unsigned int* dev_flag, unsigned int* host_seq, unsigned int value) {
-  typedef __attribute__((address_space(1))) unsigned int gu32;
-  INJECT_DELAY(19);
-  if (dev_flag) __hip_atomic_store((gu32*)dev_flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (host_seq) __hip_atomic_store(host_seq, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // For liodom_odometry_step (edges supplied by the caller): set counts and reset diagnostics.

@@ -115,29 +115,16 @@ struct liodom_handle {
   int4* host_edges_meta = nullptr;
   unsigned int* host_edges_hdr = nullptr;
   float4* pin_ring = nullptr;        // page-locked scan staging ring [kEdgePipeBufs][max_points]: liodom_scan_buffer hands slots out, pageable scans are copied through it
-  float4* stage_ring = nullptr;      // device side of the hand-off's uploads [kEdgePipeBufs][max_points] when they run on the copy stream
   std::vector<double> replay_stamps;  // (debug) host time, us since the call began, at which every pose of the last liodom_replay_resident call was collected
-  bool fold_publish = true;          // k_compact_edges publishes the extraction itself (LIODOM_FOLD_PUBLISH=0: k_set_flag / k_publish_edges in a launch behind it)
-  bool tk_copy_stream = false;       // ... (LIODOM_COPY_STREAM, default on): the upload of scan k+1 runs beside the extraction of scan k
-  hipEvent_t ev_cp[kEdgePipeBufs] = {nullptr, nullptr, nullptr};      // the upload into device staging slot r has completed (copy stream)
-  hipEvent_t ev_sdone[kEdgePipeBufs] = {nullptr, nullptr, nullptr};   // the extraction that read device staging slot r has been issued (recorded on the extraction stream)
-  bool ev_sdone_valid[kEdgePipeBufs] = {false, false, false};
-  int stage_next = 0;
   hipEvent_t ev_pin[kEdgePipeBufs] = {nullptr, nullptr, nullptr};     // the upload out of staging slot r has completed
   bool ev_pin_valid[kEdgePipeBufs] = {false, false, false};
   int pin_next = 0;
-  const float4* replay_host_dev = nullptr;   // host-fed replay in progress with zero-copy input: device-visible address of the caller's buffer ...
-  const float4* replay_host_base = nullptr;  // ... whose host address is this
-  bool zero_copy = false;            // LIODOM_ZERO_COPY=1: page-locked scans are read over PCIe by the extraction's first kernel instead of being
-                                     // uploaded by a copy call.  Measured slower (shader loads reach the host as 64-byte PCIe reads: two-thread
-                                     // binding 10.3k -> 9.0k scans/s, host-fed replay 11.5k -> 8.9k): off by default
   bool safe_mode = false;            // no in-kernel waits at all: events between the streams, one workgroup per solve, three-kernel hash rebuild
   bool ring_split_lb = false;        // lock-step batches: k_ring_split_lb (one pass, rings at a fixed pitch, predecessors' counts summed as they appear); LIODOM_RING_SPLIT_LB=0: k_classify + k_ring_scatter
   unsigned int lb_tag = 0;           // launch tag its count words carry
   bool ring_split = true;            // ring split in one pass (k_ring_split) where every workgroup of the launch is resident at once; LIODOM_RING_SPLIT=0: always k_classify + k_ring_scatter
   int ring_split_max_wgs = 0;        // ... i.e. launches of at most this many workgroups (liodom_create: occupancy of k_ring_split x CUs, with headroom for the odometry chain's kernels)
   bool streams_concurrent = true;    // liodom_create's probe: kernels of two streams of this handle ran side by side
-  std::atomic<bool> ov_off_for_copies{false};  // the overlapped pass's stream carries the hand-off's uploads (LIODOM_COPY_STREAM=2)
   std::atomic<bool> pipe_active{false};        // scans went through the pipeline edge buffers by ticket since the last drain
   std::atomic<bool> replay_live{false};        // scans went through them by the pipelined replay since the last drain (their odometries may not have been collected)
   std::atomic<bool> fallback_pending{false};   // a kernel of this handle gave up an in-kernel wait (LIODOM_STATUS_PIPE_TIMEOUT): liodom_reset() switches to events
@@ -145,6 +132,7 @@ struct liodom_handle {
   int last_eb = 0;                   // edge buffer of the most recent scan that entered odometry (inspection)
   hipEvent_t pose_event = nullptr;
   int S = 1, H = 0, P = 0;
+  bool lockstep = false;             // n_streams >= 16: a lock-step batch (throughput-bound; picks the hash build, the kNN kernels, events between the streams)
   size_t ring_lds_bytes = 0;
   // staging
   float4* stage_in = nullptr;        // [S][max_points]  (host-provided scans / edges)
@@ -159,7 +147,7 @@ struct liodom_handle {
   std::vector<int> mapper_cells_xy, mapper_cells_z;
   int hb_since = -1;            // hash_incr: scans since the last k_hash_build (-1: none yet)
   int knn8_grid = 1;            // k_knn8 workgroups per stream (each walks the blocks b, b + grid, ... of 32 queries)
-  bool knn8 = false;            // handles with >= 16 streams: k_knn8 (eight lanes per query) instead of k_knn<128>; LIODOM_KNN8=0 keeps the latter
+  bool knn8 = false;            // lock-step batches: k_knn8 (eight lanes per query) instead of k_knn<128>; LIODOM_KNN8=0 keeps the latter
   bool lds_hash_build = false;  // k_hash_build (one workgroup per stream, LDS) instead of the 3 global-atomic kernels
   bool use_flags = false;       // pipelined replay: dependencies between the two streams through flags in device memory instead of events
   bool flag_gate = false;       // ... polled by a one-wave gate launch in front of the scan's first k_knn launch instead of by that launch itself
@@ -244,34 +232,29 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ---- launch sequences -----------------------------------------------------------------------
 // Feature extraction of `count` streams starting at s0; input scan for stream s0+i at in + i*stride.
-// host_in (optional, device-visible pointer to page-locked HOST memory, stride host_stride per stream): the scan is read from
-// there by the first kernel of the chain — no upload call — and `in` is the device buffer that kernel leaves a copy in.
 int launch_extract(liodom_handle* h, hipStream_t q, int eb, int s0, int count, const float4* in, size_t in_stride,
-                   int n, int height, int width, unsigned int wait_odo = 0, int mirror = 0,
-                   const float4* host_in = nullptr, size_t host_stride = 0,
-                   unsigned int* pub_flag = nullptr, unsigned int* pub_host = nullptr, unsigned int pub_value = 0u) {
+                   int n, int height, int width, unsigned int wait_odo = 0, int mirror = 0, unsigned int* pub_flag = nullptr, unsigned int* pub_host = nullptr, unsigned int pub_value = 0u) {
   const DevView& v = h->v;
   const int tiles = std::max(1, cdiv(n, kTilePts));
   if (v.lidar_type == 1 && width > 0 && (long long)h->H * width <= (long long)v.max_points) {
     // organised cloud: ring = row, the split is a per-row compaction (no classify / scatter passes): one pass over the scan
     ProfScope ps(h, KID_RING_SCATTER, q);
-    hipLaunchKernelGGL(k_row_compact, dim3(h->H, count), dim3(kRowThreads), 0, q, v, s0, host_in ? host_in : in, host_in ? host_stride : in_stride, n, height, width);
+    hipLaunchKernelGGL(k_row_compact, dim3(h->H, count), dim3(kRowThreads), 0, q, v, s0, in, in_stride, n, height, width);
   } else {
-    if (h->ring_split_lb && !host_in && !((long long)tiles * count <= h->ring_split_max_wgs && h->ring_split)) {
+    if (h->ring_split_lb && !((long long)tiles * count <= h->ring_split_max_wgs && h->ring_split)) {
       // lock-step batches: one pass, rings at a fixed pitch, tiles sum their predecessors' counts (booked as the scatter)
       ProfScope ps(h, KID_RING_SCATTER, q);
       if (++h->lb_tag == 0u) h->lb_tag = 1u;
       hipLaunchKernelGGL(k_ring_split_lb, dim3(tiles * count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles, h->lb_tag);
       hipLaunchKernelGGL(k_ring_split_fix, dim3(1, count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles);
-    } else if (h->ring_split && !host_in && (long long)tiles * count <= h->ring_split_max_wgs) {      // (every workgroup resident at once: k_ring_split waits inside the launch)
+    } else if (h->ring_split && (long long)tiles * count <= h->ring_split_max_wgs) {      // (every workgroup resident at once: k_ring_split waits inside the launch)
       // one pass: classification and scatter in one kernel (booked as the scatter)
       ProfScope ps(h, KID_RING_SCATTER, q);
       hipLaunchKernelGGL(k_ring_split, dim3(tiles, count), dim3(kTileThreads), ring_scatter_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width);
     } else {
     {
       ProfScope ps(h, KID_CLASSIFY, q);
-      if (host_in) hipLaunchKernelGGL(k_classify, dim3(tiles, count), dim3(kTileThreads), 0, q, v, s0, host_in, host_stride, n, height, width, const_cast<float4*>(in), in_stride);
-      else hipLaunchKernelGGL(k_classify, dim3(tiles, count), dim3(kTileThreads), 0, q, v, s0, in, in_stride, n, height, width, (float4*)nullptr, (size_t)0);
+      hipLaunchKernelGGL(k_classify, dim3(tiles, count), dim3(kTileThreads), 0, q, v, s0, in, in_stride, n, height, width);
     }
     {
       ProfScope ps(h, KID_RING_SCATTER, q);
@@ -318,9 +301,18 @@ int launch_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wa
   return LIODOM_OK;
 }
 
+// The handle's part of the decision to overlap the second kNN pass (ov) and to run a scan in chain mode (chain): the streamed
+// rebuild, flags between the streams, and the GPU to this handle alone — its waiting workgroups and those of a second handle of
+// the process could end up behind each other in a shared hardware queue.  enqueue_odometry adds the scan's own conditions.
+struct OverlapModes { bool ov, chain; };
+OverlapModes overlap_modes(const liodom_handle* h) {
+  const bool base = h->v.early_rebuild && h->use_flags && g_live_handles.load() <= 1;
+  return {base && h->ov_ok, base && h->chain_ok && !h->flag_gate};
+}
+
 int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges, unsigned int signal_odo) {
   const DevView& v = h->v;
-  const bool knn_small = h->S >= 16;            // many streams: 4 queries per workgroup, else 8
+  const bool knn_small = h->lockstep;           // 4 queries per workgroup, else 8
   if (v.use_imu) {
     ProfScope ps(h, KID_OTHER);
     hipLaunchKernelGGL(k_imu_override, dim3(cdiv(count, 64)), dim3(64), 0, h->stream, v, s0, count);
@@ -332,13 +324,13 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
   const int nC = cdiv(h->v.edge_cap * std::max(1, h->P - 1), kLmThreads), nP = cdiv(h->v.edge_cap, kLmThreads);
   // Overlapped second kNN pass (kernels_sync.h): the pass goes to stream_k behind the first solve's launch and waits inside
   // the kernel; it needs kernels of different streams to run side by side (as the flags of the pipelined replay do) and the
-  // GPU mostly to itself: not while a second handle lives in this process (its waiting workgroups and ours could end up
-  // behind each other in a shared hardware queue), not under per-kernel profiling.
+  // GPU mostly to itself (overlap_modes), and is not used under per-kernel profiling.
   // (chain mode — only for scans whose edges come from the extraction stream by flag, see below — also overlaps the pass on shapes
   //  where the four-launch chain cannot: Ouster-128's 704 waiting workgroups beside full-CU rebuild workgroups cost 9 %, in chain
   //  mode the overlapped pass gains 19 % there)
-  const bool chain_cand = h->chain_ok && wait_edges != 0u && !h->flag_gate;
-  const bool overlap_ok = early && (h->ov_ok || chain_cand) && h->use_flags && !h->profiling && !h->ov_suppress && !h->ov_off_for_copies.load() && count == 1 && g_live_handles.load() <= 1;
+  const OverlapModes om = overlap_modes(h);
+  const bool chain_cand = om.chain && wait_edges != 0u;
+  const bool overlap_ok = (om.ov || chain_cand) && !h->profiling && !h->ov_suppress && count == 1;
   // The first scans of a handle are not overlapped: their launches are the first of every kernel of the chain on this queue
   // (scratch set-up, code upload), which can hold the odometry stream back for longer than a waiting kernel is willing to
   // poll.  At a switch to overlapped scans stream_k waits (event) for the odometry stream to have drained, so that its
@@ -413,7 +405,7 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
         hipLaunchKernelGGL(k_line_gate, dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb);
       } else if (knn_small) {
         hipLaunchKernelGGL(k_knn<128>, dim3(kx, count), dim3(128), 0, h->stream, v, s0, it, eb, wait_edges, signal_odo, 0u, 0);
-        if (v.knn_nn) hipLaunchKernelGGL(k_line_gate, dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb);
+        hipLaunchKernelGGL(k_line_gate, dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb);
       } else if (it == 1 && seq_k) {
         hipLaunchKernelGGL(k_ov_gate, dim3(1), dim3(64), 0, h->stream_k, v, s0, seq_k);
         hipLaunchKernelGGL((k_knn<256, true>), dim3(kx, count), dim3(256), 0, h->stream_k, v, s0, it, eb, 0u, 0u, seq_k, -1);
@@ -536,6 +528,11 @@ hipStream_t extract_queue(liodom_handle* h) { return h->profiling ? h->stream : 
 
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : dflt;
+}
+
 // The plain (non-pipelined) entry points run everything on h->stream with edge buffer 0; make
 // sure no extraction issued ahead by the pipelined replay is still in flight.
 int tickets_idle(liodom_handle* h) {      // the plain entry points use pipeline edge buffer 0 themselves
@@ -582,26 +579,21 @@ int enqueue_pipeline_odometry(liodom_handle* h, int eb, unsigned int wait_seq) {
 }
 
 // Extraction of resident slot `slot` into edge buffer `eb` on the extraction stream.
-int issue_extract(liodom_handle* h, int slot, int eb, int n, int height, int width, const float4* host_dev = nullptr, size_t host_stride = 0) {
+int issue_extract(liodom_handle* h, int slot, int eb, int n, int height, int width) {
   // while per-kernel profiling is on, everything runs on one stream so that the HIP-event
   // durations are not inflated by kernels of the other stream sharing the GPU
   hipStream_t q = extract_queue(h);
   const float4* in = h->resident + (size_t)slot * h->S * (size_t)h->v.max_points;
   if (h->use_flags) {
-    // dependencies through flags in device memory (pipe_wait / k_set_flag): the buffer's last reader must have
-    // completed before k_compact_edges rewrites it; the flag of this extraction is set by a launch that follows it
+    // dependencies through flags in device memory (pipe_wait): the buffer's last reader must have
+    // completed before k_compact_edges rewrites it; the last workgroup of k_compact_edges sets the flag of this extraction
     h->eb_seq[eb] = ++h->ext_seq;
     if (h->ext_seq == 0) h->eb_seq[eb] = ++h->ext_seq;      // (0 means "nothing to wait for")
-    // (fold_publish: the last workgroup of k_compact_edges sets the flag; else a launch of its own behind it)
-    int rc = launch_extract(h, q, eb, 0, h->S, in, (size_t)h->v.max_points, n, height, width, h->eb_reader[eb], 0, host_dev, host_stride,
-                            h->fold_publish ? h->v.pipe_flags + eb : nullptr, nullptr, h->fold_publish ? h->eb_seq[eb] : 0u);
-    if (rc) return rc;
-    if (!h->fold_publish) hipLaunchKernelGGL(k_set_flag, dim3(1), dim3(1), 0, q, h->v.pipe_flags + eb, h->eb_seq[eb]);
-    HIP_TRY(hipGetLastError());
-    return LIODOM_OK;
+    return launch_extract(h, q, eb, 0, h->S, in, (size_t)h->v.max_points, n, height, width, h->eb_reader[eb], 0,
+                          h->v.pipe_flags + eb, nullptr, h->eb_seq[eb]);
   }
   if (h->ev_free_valid[eb]) HIP_TRY(hipStreamWaitEvent(q, h->ev_free[eb], 0));
-  int rc = launch_extract(h, q, eb, 0, h->S, in, (size_t)h->v.max_points, n, height, width, 0u, 0, host_dev, host_stride);
+  int rc = launch_extract(h, q, eb, 0, h->S, in, (size_t)h->v.max_points, n, height, width);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
   return LIODOM_OK;
@@ -662,7 +654,7 @@ int reset_state(liodom_handle* h) {
   // the first scans after a reset are not overlapped (as after liodom_create): the first one runs with st.initialized == 0, where
   // no first solve publishes the pose an overlapped second kNN pass would wait for
   h->ov_warm = 0; h->ov_prev = false;
-  for (int b = 0; b < kEdgePipeBufs; b++) { h->tk_seq[b] = 0u; h->ev_pin_valid[b] = false; h->ev_sdone_valid[b] = false; }      // outstanding edge tickets are void
+  for (int b = 0; b < kEdgePipeBufs; b++) { h->tk_seq[b] = 0u; h->ev_pin_valid[b] = false; }      // outstanding edge tickets are void
   if (h->stream_c && !h->stream_c_shared) HIP_TRY(hipStreamSynchronize(h->stream_c));
   h->x_next = 0; h->odo_pending = 0;
   if (h->host_edges_hdr) std::memset(h->host_edges_hdr, 0, sizeof(unsigned int) * 2 * kEdgePipeBufs);
@@ -736,13 +728,14 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   h->params = *params;
   h->config = *config;
   h->S = config->n_streams; h->H = params->scan_lines; h->P = (int)params->local_map_size;
+  h->lockstep = config->n_streams >= 16;
   int rc = LIODOM_OK;
   auto fail = [&](int code) { liodom_destroy(h); return code; };
   // The odometry chain is the critical path; the extraction of the next scan only has to finish
   // before that chain ends.  Stream priorities let the chain's kernels win the CUs when both want them.
   int prio_least = 0, prio_greatest = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  const bool use_prio = std::getenv("LIODOM_NO_STREAM_PRIORITY") == nullptr && prio_least != prio_greatest;
+  const bool use_prio = prio_least != prio_greatest;
   // (a CU split — hipExtStreamCreateWithCUMask: the extraction stream on 32 / 64 / 96 CUs, the chain's streams on the rest —
   //  was measured: -0.1 / -1.5 / -2.7 %; the wave priority of the chain's kernels, LIODOM_CHAIN_PRIO, is what helps)
   auto make_stream = [&](hipStream_t* st, int prio) {
@@ -773,7 +766,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   // Measured on MI355X (headline shape): one stream rebuilds its hash in 28 us with the three
   // global-atomic kernels (many workgroups) but needs 86 us as a single LDS workgroup; 64 lock-step
   // streams need 247 us (L2-atomic bound) against 103 us with one LDS workgroup each.
-  h->lds_hash_build = config->n_streams >= 16;
+  h->lds_hash_build = h->lockstep;
   {
     // Flags instead of events between the extraction and the odometry stream: the first kNN launch of a scan polls the
     // extraction's flag in every workgroup, so all its workgroups must fit on the GPU with ample room left for the
@@ -784,18 +777,17 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, config->device);
     const int ecap = round_up(std::max(1, params->scan_lines * params->scan_regions * (params->edges_per_region + 1)), 64);
-    h->use_flags = config->n_streams < 16;
+    h->use_flags = !h->lockstep;
     h->flag_gate = !(config->n_streams == 1 && cdiv(cdiv(ecap, 8), 2) * 4 <= cus * 12);     // (larger launches: a one-wave gate launch polls instead)
     // kernels of different streams never run side by side under these: the in-kernel waits could only time out
     for (const char* name : {"AMD_SERIALIZE_KERNEL", "HIP_LAUNCH_BLOCKING", "ROCPROFILER_PMC", "ROCPROF_COUNTERS"}) {
       const char* e = std::getenv(name);
       if (e && e[0] && std::strcmp(e, "0") != 0) h->use_flags = false;
     }
-    if (const char* e = std::getenv("LIODOM_PIPE_FLAGS")) { if (std::atoi(e) == 0) h->use_flags = false; }
+    if (env_int("LIODOM_PIPE_FLAGS", 1) == 0) h->use_flags = false;
   }
   if (const char* e = std::getenv("LIODOM_HASH_BUILD")) h->lds_hash_build = std::strcmp(e, "global") != 0;
-  v.lds_cells_max = kLdsCellsMax;
-  if (const char* e = std::getenv("LIODOM_LDS_CELLS_MAX")) v.lds_cells_max = std::max(1, std::min(kLdsCellsMax, std::atoi(e)));
+  v.lds_cells_max = std::max(1, std::min(kLdsCellsMax, env_int("LIODOM_LDS_CELLS_MAX", kLdsCellsMax)));
   // solve split over G workgroups (partial sums exchanged inside the launch, ~3 us per evaluation under load): pays once an
   // evaluation is long enough.  Measured (scans/s, G = 1 / 4 / 8): HDL-64 10.1k / 10.35k / 10.34k, Ouster-128 7.3k / 8.1k / 8.3k,
   // VLP-16 12.2k / 12.1k / -.
@@ -807,7 +799,6 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     v.lm_groups = config->lm_workgroups == 0 ? auto_g
                                              : (config->lm_workgroups >= kLmGroupsMax ? kLmGroupsMax : (config->lm_workgroups < 1 ? 1 : config->lm_workgroups));
   }
-  if (const char* e = getenv("LIODOM_LM_GROUPS")) { const int gq = atoi(e); if (gq >= 1 && gq <= kLmGroupsMax) v.lm_groups = gq; }
   v.vox_inv = 1.0f / 0.4f;                                                          // setLeafSize(0.4) :290
   v.n_streams = h->S;
   v.max_points = config->max_points;
@@ -825,22 +816,19 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   // (measured, scans/s aggregate, streamed / three-kernel rebuild: 4 streams 27.6k / 27.3k, 8 streams 40.4k / 41.1k, 12 streams
   //  47.3k / 51.3k — with many streams the waiting workgroups of one stream hold the CUs the next stream's solve needs)
   v.early_rebuild = (!h->lds_hash_build && !v.filter_local_map && !params->mapping && config->n_streams <= 4) ? 1 : 0;
-  if (const char* e = std::getenv("LIODOM_EARLY_REBUILD")) { if (std::atoi(e) == 0) v.early_rebuild = 0; }
-  if (const char* e = std::getenv("LIODOM_SAFE_MODE")) { if (std::atoi(e) != 0) enter_safe_mode(h); }
-  if (const char* e = std::getenv("LIODOM_ZERO_COPY")) h->zero_copy = std::atoi(e) != 0;
-  if (const char* e = std::getenv("LIODOM_FOLD_PUBLISH")) h->fold_publish = std::atoi(e) != 0;
+  if (env_int("LIODOM_EARLY_REBUILD", 1) == 0) v.early_rebuild = 0;
+  if (env_int("LIODOM_SAFE_MODE", 0) != 0) enter_safe_mode(h);
   v.recv_cap = v.mapping ? (config->recv_capacity > 0 ? config->recv_capacity : 262144) : 0;
   v.map_cap = v.edge_cap * h->P + v.recv_cap;
   int ts = 1024;
   while (ts < 2 * (v.map_cap + (v.early_rebuild ? 8 * v.edge_cap : 0))) ts <<= 1;    // (early rebuild: cells that only the padding touches)
-  if (const char* e = std::getenv("LIODOM_TABLE_SIZE")) { const int t = std::atoi(e); if (t >= 1024 && (t & (t - 1)) == 0) ts = t; }   // (experiments; a table that is too small raises LIODOM_STATUS_HASH_FULL)
   v.table_size = ts;
   v.pose_log_cap = std::max(1, config->pose_log_capacity);
   v.debug = config->debug_buffers & 1;
   // in-kernel phase timestamps (tools/gpu_debug.py clocks): they change no result.  The result-changing ablation bits
   // of earlier rounds (LIODOM_ABLATE) are gone from the product build.
   // instrumented builds only (-DLIODOM_INSTRUMENT, tools/variant_build.sh): 1: stamps, 65: + histograms (shared-counter atomics: they perturb the timing)
-  if (kInstrument) { if (const char* e = getenv("LIODOM_DEBUG_CLOCKS")) { if (atoi(e) != 0) v.debug |= ((atoi(e) & (128 | 256)) ? (atoi(e) & 32) : 32) | (atoi(e) & (64 | 128)) | ((atoi(e) >> 8) << 8); } }
+  if (kInstrument) { const int dc = env_int("LIODOM_DEBUG_CLOCKS", 0); if (dc != 0) v.debug |= ((dc & (128 | 256)) ? (dc & 32) : 32) | (dc & (64 | 128)) | ((dc >> 8) << 8); }
   v.ring_id_stride = (size_t)round_up(config->max_points + 512, 256);
 
   const size_t S = (size_t)h->S;
@@ -852,8 +840,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   // + padding: region_keys_load reads unconditionally up to 16 * IPL + 10 points past the start of a ring's last region,
   // i.e. up to kExLPR * kExIPLBig + 10 points past the end of the last ring of the last stream (values never used)
   // k_ring_split_lb (lock-step batches of Velodyne-type clouds): rings at a fixed pitch of 9/8 of the nominal ring length
-  h->ring_split_lb = config->n_streams >= 16 && params->lidar_type == 0 && !h->safe_mode;
-  if (const char* e = std::getenv("LIODOM_RING_SPLIT_LB")) h->ring_split_lb = h->ring_split_lb && std::atoi(e) != 0;
+  h->ring_split_lb = h->lockstep && params->lidar_type == 0 && !h->safe_mode && env_int("LIODOM_RING_SPLIT_LB", 1) != 0;
   v.ring_pitch = round_up(cdiv((long long)config->max_points * 9, (long long)std::max(1, h->H) * 8), 8);
   if (const char* e = std::getenv("LIODOM_RING_PITCH")) v.ring_pitch = std::max(8, std::atoi(e));      // (tests: a pitch that real rings outgrow)
   v.ring_stride = h->ring_split_lb ? std::max((size_t)config->max_points, (size_t)h->H * (size_t)v.ring_pitch) : (size_t)config->max_points;
@@ -874,8 +861,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   ALLOC(v.edges_pad_meta, S * h->H * v.slots_per_ring, 0);
   ALLOC(v.ring_nedges, S * h->H, 0);
   {
-    if (const char* e = std::getenv("LIODOM_RING_SPLIT")) h->ring_split = std::atoi(e) != 0;
-    h->ring_split = h->ring_split && !h->safe_mode;      // (safe mode = no in-kernel waits at all: it overrides the switch, whatever the order of the variables)
+    h->ring_split = env_int("LIODOM_RING_SPLIT", 1) != 0 && !h->safe_mode;      // (safe mode = no in-kernel waits at all: it overrides the switch, whatever the order of the variables)
     if (h->ring_split) {
       // k_ring_split's tiles wait for each other inside the launch, so EVERY workgroup of a launch must be resident at once.  How
       // many fit is a property of the device (CUs, LDS per CU: a tile holds ~50 KB), not a constant: occupancy query x CU count,
@@ -892,7 +878,6 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
       }
       long long budget = (long long)std::max(0, per_cu) * std::max(0, cus) / 2;
       if (budget > 256) budget = 256;                    // (measured: above ~4 HDL-64 streams per launch the waiting tiles lose to the two-kernel split anyway)
-      if (const char* e = std::getenv("LIODOM_RING_SPLIT_MAX_WGS")) budget = std::max(0, std::atoi(e));      // (tests)
       h->ring_split_max_wgs = (int)budget;
       const int tiles_one = std::max(1, cdiv(config->max_points, kTilePts));
       if (tiles_one > h->ring_split_max_wgs) h->ring_split = false;      // not even one stream's scan fits: never use it
@@ -925,13 +910,11 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   ALLOC(v.imu_q, S * 4, 0);
   v.ovf_base = v.early_rebuild ? v.map_cap + 8 * v.edge_cap : v.map_cap;
   v.sorted_cap = v.early_rebuild ? v.ovf_base + v.edge_cap : v.map_cap;
-  {
-    // incremental cell hash (k_hash_append; decided for good below, once the kNN instance is known): every cell keeps room for the
-    // points of the frames that arrive before the next rebuild — twice the window + 64k places per stream
-    bool want = config->n_streams >= 16 && h->lds_hash_build && !params->mapping && !params->filter_local_map;
-    if (const char* e = std::getenv("LIODOM_HASH_INCR")) { if (std::atoi(e) == 0) want = false; }
-    if (want && !v.early_rebuild) v.sorted_cap = 2 * v.map_cap + 65536 + (kHbPeriod - 1) * v.edge_cap;      // (+ the spill list)
-  }
+  // incremental cell hash (k_hash_append; decided for good below, once the kNN instance is known): every cell keeps room for the
+  // points of the frames that arrive before the next rebuild — twice the window + 64k places per stream
+  const bool hash_incr_on = env_int("LIODOM_HASH_INCR", 1) != 0;
+  if (hash_incr_on && h->lockstep && h->lds_hash_build && !params->mapping && !params->filter_local_map && !v.early_rebuild)
+    v.sorted_cap = 2 * v.map_cap + 65536 + (kHbPeriod - 1) * v.edge_cap;      // (+ the spill list)
   ALLOC(v.sorted_pts, (v.early_rebuild ? 2 : 1) * S * (size_t)v.sorted_cap, 0);
   if (v.early_rebuild) ALLOC(v.cell_pad, 2 * S * (size_t)v.table_size, 0); else v.cell_pad = nullptr;
   v.rebuild_delta = 0.25f;
@@ -990,38 +973,31 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     h->streams_concurrent = res == 1u;
     if (!h->streams_concurrent) h->use_flags = false;
   }
-  {
-    bool gate_kernel = config->n_streams >= 16;         // lock-step batches: line gates in their own launch (k_line_gate)
-    if (const char* e = std::getenv("LIODOM_GATE_KERNEL")) gate_kernel = gate_kernel && std::atoi(e) != 0;
-    if (gate_kernel) ALLOC(v.knn_nn, S * (size_t)v.edge_cap * 5, 0); else v.knn_nn = nullptr;
-  }
-  h->knn8 = config->n_streams >= 16 && v.knn_nn != nullptr;
-  if (const char* e = std::getenv("LIODOM_KNN8")) { if (std::atoi(e) == 0) h->knn8 = false; }
+  if (h->lockstep) ALLOC(v.knn_nn, S * (size_t)v.edge_cap * 5, 0); else v.knn_nn = nullptr;      // lock-step batches: line gates in their own launch (k_line_gate)
+  h->knn8 = h->lockstep && env_int("LIODOM_KNN8", 1) != 0;
   h->knn8_grid = std::max(1, cdiv(cdiv(v.edge_cap, kKnn8Queries), kKnnGridDiv));
-  if (const char* e = std::getenv("LIODOM_KNN8_GRID")) h->knn8_grid = std::max(1, std::min(65535, std::atoi(e)));      // (experiments)
   // incremental cell hash: lock-step batches that search with k_knn8 (it skips evicted points) on the LDS-built table, window only
-  v.hash_incr = (h->knn8 && h->lds_hash_build && !params->mapping && !params->filter_local_map && h->P > kHbPeriod &&
+  v.hash_incr = (hash_incr_on && h->knn8 && h->lds_hash_build && !params->mapping && !params->filter_local_map && h->P > kHbPeriod &&
                  v.sorted_cap >= 2 * v.map_cap + (kHbPeriod - 1) * v.edge_cap) ? 1 : 0;      // (windows of more frames than a period: the evicted frames are frames the rebuild knew)
   v.hb_spill_base = v.sorted_cap - (kHbPeriod - 1) * v.edge_cap;
-  if (const char* e = std::getenv("LIODOM_HASH_INCR")) { if (std::atoi(e) == 0) v.hash_incr = 0; }
   if (v.hash_incr) ALLOC(v.cell_cap, S * (size_t)v.table_size, 0); else v.cell_cap = nullptr;
   v.hb_slack_min = kHbSlackMin; v.hb_new_room = kHbNewRoom;
   if (const char* e = std::getenv("LIODOM_HB_SLACK")) v.hb_slack_min = std::max(0, std::atoi(e));            // (tests: cells that run out of room)
   if (const char* e = std::getenv("LIODOM_HB_NEW_ROOM")) v.hb_new_room = std::max(1, std::atoi(e));
   if (h->knn8) { ALLOC(v.knn8_cnt, S, 0); ALLOC(v.knn8_list, S * (size_t)v.edge_cap, 0); } else { v.knn8_cnt = nullptr; v.knn8_list = nullptr; }
-  v.knn_queries = config->n_streams >= 16 ? 4 : 8;          // must match the k_knn instance launch_odometry picks (k_knn8 leaves k_line_gate the same layout)
-  v.knn_partials = config->n_streams >= 16 ? 0 : 1;         // measured: +37 % on the VALU-bound 256-stream kNN pass, -2 us per solve on one stream
+  v.knn_queries = h->lockstep ? 4 : 8;          // must match the k_knn instance launch_odometry picks (k_knn8 leaves k_line_gate the same layout)
+  v.knn_partials = h->lockstep ? 0 : 1;         // measured: +37 % on the VALU-bound 256-stream kNN pass, -2 us per solve on one stream
   v.knn_blocks = round_up(cdiv(v.edge_cap, v.knn_queries), 4);
   v.knn_grid = std::max(1, cdiv(v.knn_blocks, kKnnGridDiv));   // sized for the usual edge count (~1/3 of the capacity): a workgroup takes a second block if there are more
   {
     // LIODOM_KNN_SAVE: 2 (default) second pass re-ranks the first pass's kept candidates and prunes with its fifth distance;
     // 1: pruning bound only; 0: the second pass searches like the first (all three give the same results)
-    const int save = std::getenv("LIODOM_KNN_SAVE") ? std::atoi(std::getenv("LIODOM_KNN_SAVE")) : 2;
+    const int save = env_int("LIODOM_KNN_SAVE", 2);
     if (save >= 1) ALLOC(v.knn_save_q, S * (size_t)v.edge_cap, 0); else v.knn_save_q = nullptr;
     if (save >= 2) { ALLOC(v.knn_save_pos, S * (size_t)v.edge_cap * kKnnGroup, 0xFF); ALLOC(v.knn_save_g, S * (size_t)v.edge_cap, 0); }
     else { v.knn_save_pos = nullptr; v.knn_save_g = nullptr; }
   }
-  if (const char* e = std::getenv("LIODOM_KNN_EXACT_ONLY")) v.knn_exact_only = std::atoi(e) != 0 ? 1 : 0;
+  v.knn_exact_only = env_int("LIODOM_KNN_EXACT_ONLY", 0) != 0 ? 1 : 0;
   ALLOC(v.knn_part, S * 2 * (size_t)v.knn_blocks * 32, 0);
   ALLOC(v.ov_flags, S, 0);
   ALLOC(v.pose_xch0, S * (size_t)kOvReplicas * 512, 0);
@@ -1079,24 +1055,22 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, config->device);
     // (measured with half of the slots allowed: Ouster-128, 704 workgroups = 2 816 waves, loses — 9.0k -> 8.4k scans/s)
-    h->ov_ok = v.early_rebuild && S == 1 && v.knn_partials && (long long)v.knn_grid * 4 * 3 <= (long long)cus * 24;
-    if (const char* e = std::getenv("LIODOM_KNN_OVERLAP")) { if (std::atoi(e) == 0) h->ov_ok = false; if (std::atoi(e) == 2) h->ov_ok = v.early_rebuild && S == 1 && v.knn_partials; }      // (2: also where the pass takes more than a third of the wave slots)
+    const int knn_overlap = env_int("LIODOM_KNN_OVERLAP", 1);      // (2: also where the pass takes more than a third of the wave slots)
+    h->ov_ok = knn_overlap != 0 && v.early_rebuild && S == 1 && v.knn_partials && (knn_overlap == 2 || (long long)v.knn_grid * 4 * 3 <= (long long)cus * 24);
     // (the stream exists only on handles that use it: HIP multiplexes its streams onto a few hardware queues, and one more
     //  stream made the host-fed replay's copy stream share a queue — 11.3k -> 7.5k scans/s on every workload)
     // chain mode (kernels_sync.h): one-stream handles with the streamed rebuild whose passes leave at least half of the wave slots
     // free; the IMU override rewrites the prediction between two scans on the odometry stream (k_imu_override), which the first
     // pass on stream_k would not be ordered behind
     h->chain_ok = v.early_rebuild && S == 1 && v.knn_partials && !v.use_imu && (long long)v.knn_grid * 4 * 2 <= (long long)cus * 24;
-    if (const char* e = std::getenv("LIODOM_KNN_OVERLAP")) { if (std::atoi(e) == 0) h->chain_ok = false; }
-    if (const char* e = std::getenv("LIODOM_CHAIN")) { if (std::atoi(e) == 0) h->chain_ok = false; }
+    if (knn_overlap == 0 || env_int("LIODOM_CHAIN", 1) == 0) h->chain_ok = false;
     // speculative hand-over of the solves' results (kernels_sync.h): LIODOM_SPECULATE=0 off, 1 by the model's predicted cost change
     // (default), 2 (tests): as early as possible, i.e. practically always wrong — every receiver is then repeated from the confirmed
     // result; 4 / 5 (debugging): only the first / only the finalising solve's hand-over.  LIODOM_SPEC_THETA: the predictor's threshold
     // (fraction of the function tolerance, default 0.8)
     v.speculate = (h->ov_ok || h->chain_ok) ? 1 : 0;
-    if (const char* e = std::getenv("LIODOM_SPECULATE")) { if (v.speculate) v.speculate = std::max(0, std::min(7, std::atoi(e))); }
+    if (v.speculate) v.speculate = std::max(0, std::min(7, env_int("LIODOM_SPECULATE", 1)));
     v.spec_backoff = 16;
-    if (const char* e = std::getenv("LIODOM_SPEC_BACKOFF")) v.spec_backoff = std::max(0, std::atoi(e));
     v.spec_theta = 0.8;
     if (const char* e = std::getenv("LIODOM_SPEC_THETA")) v.spec_theta = std::atof(e);
     if ((h->ov_ok || h->chain_ok) && make_stream(&h->stream_k, prio_greatest) != hipSuccess) { g_last_error = "hipStreamCreate failed"; return fail(LIODOM_ERR_HIP); }
@@ -1140,7 +1114,7 @@ void liodom_destroy(liodom_handle_t* h) {
   if (h->host_edges_meta) hipHostFree(h->host_edges_meta);
   if (h->host_edges_hdr) hipHostFree(h->host_edges_hdr);
   if (h->pin_ring) hipHostFree(h->pin_ring);
-  for (int b = 0; b < kEdgePipeBufs; b++) { if (h->ev_pin[b]) hipEventDestroy(h->ev_pin[b]); if (h->ev_sdone[b]) hipEventDestroy(h->ev_sdone[b]); if (h->ev_cp[b]) hipEventDestroy(h->ev_cp[b]); }
+  for (int b = 0; b < kEdgePipeBufs; b++) { if (h->ev_pin[b]) hipEventDestroy(h->ev_pin[b]); }
   for (auto& e : h->ev_pool) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   if (h->pose_event) hipEventDestroy(h->pose_event);
   for (int b = 0; b < kEdgePipeBufs; b++) { if (h->ev_edges[b]) hipEventDestroy(h->ev_edges[b]); if (h->ev_free[b]) hipEventDestroy(h->ev_free[b]); }
@@ -1275,36 +1249,6 @@ static int ensure_pin_ring(liodom_handle* h) {
   HIP_TRY(hipHostMalloc(&p, sizeof(float4) * (size_t)kEdgePipeBufs * (size_t)h->v.max_points, hipHostMallocDefault));
   h->pin_ring = static_cast<float4*>(p);
   for (int b = 0; b < kEdgePipeBufs; b++) HIP_TRY(hipEventCreateWithFlags(&h->ev_pin[b], hipEventDisableTiming));
-  // LIODOM_COPY_STREAM=1: uploads on a copy stream of their own, into a ring of device staging slots, so that the DMA of scan k+1
-  // (1.84 MB, ~37 us) runs beside the extraction kernels of scan k instead of in front of its own on the extraction stream.
-  // Measured (MI355X, HDL-64 shape, two C++ threads): 10.3k scans/s WITHOUT it, 7.5k with it, with GPU_MAX_HW_QUEUES=8 as well —
-  // the same loss the host-fed replay saw with a fourth stream per handle (the two cross-stream event edges per scan cost more
-  // than the overlap gains).  Off by default; kept for runtimes where a fourth stream is cheap.
-  // LIODOM_COPY_STREAM=2: the uploads take the stream of the overlapped second kNN pass (as the host-fed replay does), which is
-  // then not overlapped on this handle any more: three streams per handle, the upload beside the previous extraction.
-  int want = 0;
-  if (const char* e = std::getenv("LIODOM_COPY_STREAM")) want = std::atoi(e);
-  if (want != 0 && !h->profiling) {
-    void* d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(float4) * (size_t)kEdgePipeBufs * (size_t)h->v.max_points));
-    h->stage_ring = static_cast<float4*>(d);
-    h->allocs.push_back(d);
-    if (!h->stream_c) {
-      if (want == 2 && h->stream_k) {
-        // (the odometry side may be enqueueing an overlapped pass right now: from here on it does not — ov_off_for_copies is read
-        //  by enqueue_odometry — and what is already in that stream simply runs ahead of the first copy)
-        h->ov_off_for_copies.store(true);
-        h->stream_c = h->stream_k; h->stream_c_shared = true;
-      } else {
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream_c, hipStreamNonBlocking));
-      }
-    }
-    for (int b = 0; b < kEdgePipeBufs; b++) {
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_sdone[b], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&h->ev_cp[b], hipEventDisableTiming));
-    }
-    h->tk_copy_stream = true;
-  }
   return LIODOM_OK;
 }
 
@@ -1344,8 +1288,6 @@ int liodom_extract_edges_device(liodom_handle_t* h, int stream, const float* xyz
   }
   hipStream_t q = extract_queue(h);
   float4* in = h->stage_in + (size_t)stream * h->v.max_points;
-  const float4* host_dev = nullptr;                  // device-visible address of the page-locked scan (zero-copy)
-  int pin_slot_used = -1;
   if (n) {
     // The scan's upload is asynchronous when it starts from page-locked memory: a slot of the handle's own ring
     // (liodom_scan_buffer), or a buffer the caller registered (liodom_pin_host_buffer) — which must stay untouched until
@@ -1366,59 +1308,22 @@ int liodom_extract_edges_device(liodom_handle_t* h, int stream, const float* xyz
       std::memcpy(h->pin_ring + (size_t)r * h->v.max_points, xyzi, sizeof(float4) * (size_t)n);
       xyzi = reinterpret_cast<const float*>(h->pin_ring + (size_t)r * h->v.max_points);
     }
-    // Zero-copy (LIODOM_ZERO_COPY=1; default is hipMemcpyAsync): the extraction's first kernel reads the page-locked scan over
-    // PCIe itself — no copy call, no second stream, no event.  Measured slower than the DMA upload (see zero_copy).
-    if (h->zero_copy && (reinterpret_cast<uintptr_t>(xyzi) & 15u) == 0) {
-      void* dp = nullptr;
-      if (hipHostGetDevicePointer(&dp, const_cast<float*>(xyzi), 0) == hipSuccess && dp) host_dev = static_cast<const float4*>(dp);
-      else (void)hipGetLastError();
-    }
-    hipStream_t qc = q;
-    int sr = -1;
-    if (host_dev) {
-      if (own || !pinned) { pin_slot_used = r; h->pin_next = (r + 1) % kEdgePipeBufs; }
-    } else
-    if (h->tk_copy_stream && !h->profiling) {
-      // device staging slot sr: free once the extraction that last read it has run (ev_sdone, recorded on the extraction stream)
-      sr = h->stage_next;
-      h->stage_next = (sr + 1) % kEdgePipeBufs;
-      qc = h->stream_c;
-      in = h->stage_ring + (size_t)sr * h->v.max_points;
-      if (h->ev_sdone_valid[sr]) HIP_TRY(hipStreamWaitEvent(qc, h->ev_sdone[sr], 0));
-    }
-    if (!host_dev) HIP_TRY(hipMemcpyAsync(in, xyzi, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, qc));
-    if (!host_dev && (own || !pinned)) {             // the page-locked ring slot may be refilled once this upload has left it
-      HIP_TRY(hipEventRecord(h->ev_pin[r], qc));
+    HIP_TRY(hipMemcpyAsync(in, xyzi, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, q));
+    if (own || !pinned) {                            // the page-locked ring slot may be refilled once this upload has left it
+      HIP_TRY(hipEventRecord(h->ev_pin[r], q));
       h->ev_pin_valid[r] = true;
       h->pin_next = (r + 1) % kEdgePipeBufs;
     }
-    if (sr >= 0) {                                   // the extraction starts when the upload into its staging slot has completed
-      HIP_TRY(hipEventRecord(h->ev_cp[sr], qc));
-      HIP_TRY(hipStreamWaitEvent(q, h->ev_cp[sr], 0));
-    }
   }
-  const bool staged_on_ring = n > 0 && !host_dev && h->tk_copy_stream && !h->profiling;
   unsigned int seq = ++h->ext_seq;
   if (seq == 0u) seq = ++h->ext_seq;                 // (0 means "nothing to wait for")
   unsigned int* host_seq = h->v.host_edges_hdr ? h->v.host_edges_hdr + eb : nullptr;
   // (the slot is free: the odometry that last read buffer eb has been collected, i.e. has completed — no wait on the device,
   //  which would depend on when the other thread submits its next scan)
   unsigned int* const dev_flag = h->use_flags ? h->v.pipe_flags + eb : (unsigned int*)nullptr;
-  rc = launch_extract(h, q, eb, stream, 1, in, 0, (int)n, height, width, 0u, 1, host_dev, 0,
-                      h->fold_publish ? dev_flag : nullptr, h->fold_publish ? host_seq : nullptr, h->fold_publish ? seq : 0u);
+  rc = launch_extract(h, q, eb, stream, 1, in, 0, (int)n, height, width, 0u, 1, dev_flag, host_seq, seq);
   if (rc) return rc;
-  if (!h->fold_publish) hipLaunchKernelGGL(k_publish_edges, dim3(1), dim3(1), 0, q, dev_flag, host_seq, seq);
   if (!h->use_flags) HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
-  HIP_TRY(hipGetLastError());
-  if (pin_slot_used >= 0) {                          // (zero-copy) the ring slot may be refilled once the extraction's first kernel has read it
-    HIP_TRY(hipEventRecord(h->ev_pin[pin_slot_used], q));
-    h->ev_pin_valid[pin_slot_used] = true;
-  }
-  if (staged_on_ring) {
-    const int sr = (h->stage_next + kEdgePipeBufs - 1) % kEdgePipeBufs;
-    HIP_TRY(hipEventRecord(h->ev_sdone[sr], q));
-    h->ev_sdone_valid[sr] = true;
-  }
   h->eb_seq[eb] = seq;
   h->pipe_active.store(true);
   h->tk_seq[eb].store(seq);
@@ -1754,19 +1659,12 @@ static int replay_one(liodom_handle_t* h, int slot, int next_slot, int64_t n, in
   if (rc) return rc;
   h->parity = (eb + 1) % kEdgePipeBufs;
   if (next_slot >= 0) {                           // overlap the next scan's (upload and) extraction with this odometry
-    if (next_host && !h->replay_host_dev) { rc = upload_slot_async(h, next_slot, next_host, host_stride, n); if (rc) return rc; }
+    if (next_host) { rc = upload_slot_async(h, next_slot, next_host, host_stride, n); if (rc) return rc; }
     // (a gate in front of the next scan's extraction — start it when this scan's first solve starts, so that it runs beside the
     //  solves instead of beside the first kNN pass — was measured: -1.6 %; removed)
-    if (next_host && h->replay_host_dev) {
-      // zero-copy: the extraction's first kernel reads the page-locked scan itself (device-visible address of next_host) and
-      // leaves its device copy in the resident slot; no upload, no copy stream, no events
-      const float4* hd = h->replay_host_dev + (reinterpret_cast<const float4*>(next_host) - h->replay_host_base);
-      rc = issue_extract(h, next_slot, h->parity, (int)n, height, width, hd, (size_t)host_stride / 4);
-    } else {
-      rc = issue_extract(h, next_slot, h->parity, (int)n, height, width);
-    }
+    rc = issue_extract(h, next_slot, h->parity, (int)n, height, width);
     if (rc) return rc;
-    if (next_host && !h->replay_host_dev) { rc = upload_slot_consumed(h, next_slot); if (rc) return rc; }
+    if (next_host) { rc = upload_slot_consumed(h, next_slot); if (rc) return rc; }
     h->pf_slot = next_slot;
   }
   if (wait) return wait_pose(h, 0, h->S, poses_out, infos_out);
@@ -1791,39 +1689,21 @@ int liodom_replay_host(liodom_handle_t* h, const float* xyzi_base, int64_t scan_
   // Measured (MI355X, HDL-64 shape): with uploads the loop is bound by the host's enqueue work (an upload, three event
   // operations, six extraction and five odometry launches per scan: 88 us); the overlapped second kNN pass adds a gate and an
   // ALLOC launch on a third stream and made it 133 us.  So not here.
-  struct Suppress { liodom_handle* h; ~Suppress() { h->ov_suppress = false; h->replay_host_dev = nullptr; h->replay_host_base = nullptr; } } suppress{h};
+  struct Suppress { liodom_handle* h; ~Suppress() { h->ov_suppress = false; } } suppress{h};
   h->ov_suppress = true;
-  if (h->zero_copy && count > 0 && n > 0 && scan_stride_floats % 4 == 0 && (reinterpret_cast<uintptr_t>(xyzi_base) & 15u) == 0) {
-    // page-locked AND mapped (liodom_pin_host_buffer, hipHostMalloc): the extraction reads the scans in place — the loop then
-    // enqueues no upload and no event, and the overlapped second kNN pass stays on (its stream is not needed for copies)
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, const_cast<float*>(xyzi_base), 0) == hipSuccess && dp) {
-      h->replay_host_dev = static_cast<const float4*>(dp);
-      h->replay_host_base = reinterpret_cast<const float4*>(xyzi_base);
-      h->ov_suppress = false;
-    } else {
-      (void)hipGetLastError();
-    }
-  }
   auto out_p = [&](int i) { return poses_out ? poses_out + (size_t)i * h->S * 7 : nullptr; };
   auto out_i = [&](int i) { return infos_out ? infos_out + (size_t)i * h->S : nullptr; };
   auto src = [&](int i) { return xyzi_base + (size_t)i * (size_t)h->S * (size_t)scan_stride_floats; };
   for (int i = 0; i < count; i++) {
     const int slot = i % kRing, next = (i + 1 < count) ? (i + 1) % kRing : -1;
     if (i == 0) {                                 // first scan: upload + extraction now
-      if (h->replay_host_dev) {
-        rc = issue_extract(h, slot, h->parity, (int)n, height, width, h->replay_host_dev, (size_t)scan_stride_floats / 4);
-        if (rc) return rc;
-        h->pf_slot = slot;
-      } else {
-        rc = upload_slot_async(h, slot, src(0), scan_stride_floats, n);
-        if (rc) return rc;
-        rc = issue_extract(h, slot, h->parity, (int)n, height, width);
-        if (rc) return rc;
-        h->pf_slot = slot;
-        rc = upload_slot_consumed(h, slot);
-        if (rc) return rc;
-      }
+      rc = upload_slot_async(h, slot, src(0), scan_stride_floats, n);
+      if (rc) return rc;
+      rc = issue_extract(h, slot, h->parity, (int)n, height, width);
+      if (rc) return rc;
+      h->pf_slot = slot;
+      rc = upload_slot_consumed(h, slot);
+      if (rc) return rc;
     }
     const float* nh = next >= 0 ? src(i + 1) : nullptr;
     if (depth == 0) {
@@ -2093,6 +1973,7 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   if (int rc = enter(h)) return rc;
   SideLocks lk(h, true, true);
   const DevView& v = h->v;
+  const OverlapModes om = overlap_modes(h);
   // (speculative hand-overs of stream 0 since the last reset: the launches enqueued so far have to have run for the figures to mean
   //  anything — a caller that wants them synchronises first; this call does not)
   int spec[4] = {0, 0, 0, 0}, hbs[4] = {0, 0, 0, 0};
@@ -2103,13 +1984,13 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   snprintf(buf, (size_t)cap,
            "n_streams=%d early_rebuild=%d hash_build=%s pipe_flags=%d flag_gate=%d lm_groups=%d knn_instance=%d knn_queries=%d "
            "knn_grid=%d/%d knn8=%d hash_incr=%d hash_rebuilds=%d hash_appends=%d hash_appends_spilled=%d hash_points_spilled=%d knn_partials=%d knn_saved_bound=%d knn_exact_only=%d line_gate_kernel=%d filter_local_map=%d mapping=%d "
-           "rotation_mode=%d table_size=%d rebuild_delta=%.3f knn_overlap=%d streams_concurrent=%d safe_mode=%d ring_split=%d ring_split_max_wgs=%d ring_split_lb=%d fold_publish=%d chain=%d speculate=%d spec_early=%d/%d spec_unconfirmed=%d/%d chain_done=%u/%u/%u replay_enqueue_us=%.2f replay_wait_us=%.2f debug=%d",
+           "rotation_mode=%d table_size=%d rebuild_delta=%.3f knn_overlap=%d streams_concurrent=%d safe_mode=%d ring_split=%d ring_split_max_wgs=%d ring_split_lb=%d chain=%d speculate=%d spec_early=%d/%d spec_unconfirmed=%d/%d chain_done=%u/%u/%u replay_enqueue_us=%.2f replay_wait_us=%.2f debug=%d",
            h->S, v.early_rebuild, v.early_rebuild ? "streamed" : (h->lds_hash_build ? "lds" : "global"), h->use_flags ? 1 : 0,
-           (h->use_flags && h->flag_gate) ? 1 : 0, v.lm_groups, h->S >= 16 ? 128 : 256, v.knn_queries, v.knn_grid,
+           (h->use_flags && h->flag_gate) ? 1 : 0, v.lm_groups, h->lockstep ? 128 : 256, v.knn_queries, v.knn_grid,
            v.knn_blocks, h->knn8 ? 1 : 0, v.hash_incr, hbs[0], hbs[1], hbs[2], hbs[3], v.knn_partials, v.knn_save_pos ? 2 : (v.knn_save_q ? 1 : 0), v.knn_exact_only, v.knn_nn ? 1 : 0, v.filter_local_map, v.mapping,
            v.rotation_mode, v.table_size, (double)v.rebuild_delta,
-           (v.early_rebuild && (h->ov_ok || (h->chain_ok && !h->flag_gate)) && h->use_flags && g_live_handles.load() <= 1) ? 1 : 0, h->streams_concurrent ? 1 : 0, h->safe_mode ? 1 : 0, h->ring_split ? 1 : 0, h->ring_split ? h->ring_split_max_wgs : 0, h->ring_split_lb ? 1 : 0, h->fold_publish ? 1 : 0,
-           (v.early_rebuild && h->chain_ok && h->use_flags && !h->flag_gate && g_live_handles.load() <= 1) ? 1 : 0, v.speculate, spec[0], spec[2], spec[1], spec[3], h->chain_count, done_cnt[0], done_cnt[32],
+           (om.ov || om.chain) ? 1 : 0, h->streams_concurrent ? 1 : 0, h->safe_mode ? 1 : 0, h->ring_split ? 1 : 0, h->ring_split ? h->ring_split_max_wgs : 0, h->ring_split_lb ? 1 : 0,
+           om.chain ? 1 : 0, v.speculate, spec[0], spec[2], spec[1], spec[3], h->chain_count, done_cnt[0], done_cnt[32],
            h->replay_timed ? h->replay_enq_ns / (1e3 * (double)h->replay_timed) : 0.0, h->replay_timed ? h->replay_wait_ns / (1e3 * (double)h->replay_timed) : 0.0, v.debug);
   return LIODOM_OK;
 }

@@ -275,7 +275,7 @@ struct DevView {
   float4* host_edges;           // [kEdgePipeBufs][edge_cap] host-mapped
   int4* host_edges_meta;        // [kEdgePipeBufs][edge_cap] (ring, idx_in_ring, src, 0)
   unsigned int* host_edges_hdr; // [2][kEdgePipeBufs]: sequence number of the extraction whose edges are complete in slot b (written by
-                                // k_publish_edges, system scope); number of edges in slot b
+                                // k_compact_edges' last workgroup, system scope); number of edges in slot b
   unsigned long long* dbg_clk;  // [16][32] phase timestamps (100 MHz) and counters, debug bit 5 only
   unsigned int* dbg_q;          // [2][edge_cap][8] per-query phase times of stream 0's latest scan (10 ns ticks since the workgroup's start), debug bit 5 only
 };
