@@ -746,7 +746,9 @@ __device__ __forceinline__ void hash_build_global(const DevView& v, int s, Strea
   int* prank = v.pt_rank + (size_t)s * v.map_cap;
   const float4* recv = v.recv_pts + (size_t)s * v.recv_cap;
   CellSlot empty; empty.key = kEmptyKey; empty.start = 0; empty.cnt = 0;
-  if (st.table_mask != (unsigned int)v.table_size - 1u) {
+  // slots [0, kLdsSlots) hold an LDS-built table that no used_cells list names: its mask is the LDS one, or — a table of exactly
+  // kLdsSlots slots, where the masks agree — an LDS rebuild is recorded (hb_main_fc)
+  if (st.table_mask != (unsigned int)v.table_size - 1u || st.hb_main_fc != 0) {
     for (int i = tid; i < kLdsSlots; i += kBuildThreads) { cells[i] = empty; }
     for (int i = tid; i < kLdsSlots / 32; i += kBuildThreads) bits[i] = 0u;
   }
@@ -836,12 +838,15 @@ __global__ __launch_bounds__(kBuildThreads) void k_hash_append(DevView v, int s0
   const int tid = threadIdx.x, lane = tid & 63;
   const int nf = st.n_frames, fc = st.frame_count, Mw = st.n_map;
   const unsigned int tmask = st.table_mask;
-  int d = (fc - nf) - st.hb_main_old;                  // frames evicted since the rebuild (< kHbPeriod <= frames of the window then: hb_base knows them)
+  int d = (fc - nf) - st.hb_main_old;                  // frames evicted since the rebuild (<= frames appended since, < kHbPeriod below: hb_base knows them)
   d = d < 0 ? 0 : (d > 7 ? 7 : d);
   if (nf < 1) return;
   win_index_load(v, s, nf, w, tid, kBuildThreads);
   if (tid == 0) sh_flag = 0;
-  if (tmask != (unsigned int)kLdsSlots - 1u) {            // (uniform) the window outgrew the LDS table: a global table has no room to append to
+  // (uniform) the window outgrew the LDS table — a global table has no room to append to —, or this stream has no LDS rebuild to
+  // append to: none yet, or kHbPeriod or more frames ago (the host counts periods per stream, so this is a guard: the spill list holds
+  // kHbPeriod - 1 frames and hb_base the evictions of fewer than 8)
+  if (tmask != (unsigned int)kLdsSlots - 1u || st.hb_main_fc == 0 || fc - st.hb_main_fc >= kHbPeriod) {
     __syncthreads();
     hash_build_global(v, s, st, w, nf, Mw, Mw, eb, tid);
     return;
@@ -922,7 +927,12 @@ __global__ __launch_bounds__(kBuildThreads) void k_hash_append(DevView v, int s0
         const unsigned int pos = pos0 + (unsigned int)run.rank;
         const float4 rec = make_float4(pt[u].x, pt[u].y, pt[u].z, __int_as_float(first_new + i + shift));
         if (ok && pos < cap0) sp[pos] = rec;
-        else { const int k = atomicAdd(&st.hb_spill, 1); if (k < v.sorted_cap - v.hb_spill_base) sp[v.hb_spill_base + k] = rec; sh_flag = 1; atomicAdd(&st.hb_stats[3], 1); }
+        else {
+          const int k = atomicAdd(&st.hb_spill, 1);
+          if (k < v.sorted_cap - v.hb_spill_base) sp[v.hb_spill_base + k] = rec;
+          else atomicOr(&st.status, LIODOM_STATUS_HASH_FULL);     // (the spill list is full: the scan fails rather than lose the point)
+          sh_flag = 1; atomicAdd(&st.hb_stats[3], 1);
+        }
       }
     }
     __syncthreads();
@@ -1009,8 +1019,8 @@ __global__ __launch_bounds__(kBuildThreads) void k_hash_build(DevView v, int s0,
   OV_STAMP(v, tid == 0 && s == 0, 21);
   // ---- exclusive prefix of the counts over the slots (8 consecutive slots per thread) ----
   // hash_incr: every cell gets ROOM for the points k_hash_append will add until the next rebuild (hash_cell_slack) — if the point
-  // array holds that much
-  const bool slack = v.hash_incr && !v.mapping && 2ll * M + (long long)v.hb_slack_min * sh_used <= (long long)v.sorted_cap;
+  // array holds that much in front of the spill list (2M + slack * cells bounds M + sum of max(cnt, slack))
+  const bool slack = v.hash_incr && !v.mapping && 2ll * M + (long long)v.hb_slack_min * sh_used <= (long long)v.hb_spill_base;
   {
     constexpr int PER = kLdsSlots / kBuildThreads;   // 8
     unsigned int c[PER];

@@ -145,7 +145,7 @@ struct liodom_handle {
   std::atomic<bool> profiling{false};   // read without a lock by SideLocks / extract_queue, written under both mutexes
   std::vector<liodom_map*> mappers;   // per stream: attached device map (mapping replay) or null
   std::vector<int> mapper_cells_xy, mapper_cells_z;
-  int hb_since = -1;            // hash_incr: scans since the last k_hash_build (-1: none yet)
+  std::vector<int> hb_since;    // hash_incr, per stream: scans since the stream's last k_hash_build (-1: none yet)
   int knn8_grid = 1;            // k_knn8 workgroups per stream (each walks the blocks b, b + grid, ... of 32 queries)
   bool knn8 = false;            // lock-step batches: k_knn8 (eight lanes per query) instead of k_knn<128>; LIODOM_KNN8=0 keeps the latter
   bool lds_hash_build = false;  // k_hash_build (one workgroup per stream, LDS) instead of the 3 global-atomic kernels
@@ -446,8 +446,11 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
     ProfScope ps(h, KID_HASH_BUILD);        // window append + LDS-built cell hash, one workgroup per stream
     // (hash_incr: the new frame is appended to the table of the last rebuild; k_hash_build only works when that says so)
     // (hash_incr: k_hash_build every kHbPeriod-th scan, k_hash_append — the new frame into the cells of the last rebuild — in between)
-    const bool rebuild = !v.hash_incr || h->hb_since < 0 || h->hb_since >= kHbPeriod - 1;
-    h->hb_since = rebuild ? 0 : h->hb_since + 1;
+    // (per stream: a single-stream call of a lock-step handle steps one stream only.  A launch over several streams rebuilds them all
+    //  if any one is due — a rebuild is always exact — so that lock-step batches keep every counter in step.)
+    bool rebuild = !v.hash_incr;
+    for (int s = s0; s < s0 + count; s++) rebuild = rebuild || h->hb_since[s] < 0 || h->hb_since[s] >= kHbPeriod - 1;
+    for (int s = s0; s < s0 + count; s++) h->hb_since[s] = rebuild ? 0 : h->hb_since[s] + 1;
     if (!rebuild) hipLaunchKernelGGL(k_hash_append, dim3(count), dim3(kBuildThreads), 0, h->stream, v, s0, eb);
     else hipLaunchKernelGGL(k_hash_build, dim3(count), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, s0, eb);
   } else {
@@ -649,7 +652,7 @@ int reset_state(liodom_handle* h) {
   }
   h->pf_slot = -1; h->parity = 0; h->last_eb = 0; h->ev_free_valid[0] = h->ev_free_valid[1] = h->ev_free_valid[2] = false;
   h->replay_live.store(false);
-  h->hb_since = -1;
+  h->hb_since.assign((size_t)h->S, -1);
   h->ext_seq = h->odo_seq = 0;
   // the first scans after a reset are not overlapped (as after liodom_create): the first one runs with st.initialized == 0, where
   // no first solve publishes the pose an overlapped second kNN pass would wait for
@@ -1984,11 +1987,11 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   snprintf(buf, (size_t)cap,
            "n_streams=%d early_rebuild=%d hash_build=%s pipe_flags=%d flag_gate=%d lm_groups=%d knn_instance=%d knn_queries=%d "
            "knn_grid=%d/%d knn8=%d hash_incr=%d hash_rebuilds=%d hash_appends=%d hash_appends_spilled=%d hash_points_spilled=%d knn_partials=%d knn_saved_bound=%d knn_exact_only=%d line_gate_kernel=%d filter_local_map=%d mapping=%d "
-           "rotation_mode=%d table_size=%d rebuild_delta=%.3f knn_overlap=%d streams_concurrent=%d safe_mode=%d ring_split=%d ring_split_max_wgs=%d ring_split_lb=%d chain=%d speculate=%d spec_early=%d/%d spec_unconfirmed=%d/%d chain_done=%u/%u/%u replay_enqueue_us=%.2f replay_wait_us=%.2f debug=%d",
+           "rotation_mode=%d table_size=%d sorted_cap=%d hb_spill_base=%d rebuild_delta=%.3f knn_overlap=%d streams_concurrent=%d safe_mode=%d ring_split=%d ring_split_max_wgs=%d ring_split_lb=%d chain=%d speculate=%d spec_early=%d/%d spec_unconfirmed=%d/%d chain_done=%u/%u/%u replay_enqueue_us=%.2f replay_wait_us=%.2f debug=%d",
            h->S, v.early_rebuild, v.early_rebuild ? "streamed" : (h->lds_hash_build ? "lds" : "global"), h->use_flags ? 1 : 0,
            (h->use_flags && h->flag_gate) ? 1 : 0, v.lm_groups, h->lockstep ? 128 : 256, v.knn_queries, v.knn_grid,
            v.knn_blocks, h->knn8 ? 1 : 0, v.hash_incr, hbs[0], hbs[1], hbs[2], hbs[3], v.knn_partials, v.knn_save_pos ? 2 : (v.knn_save_q ? 1 : 0), v.knn_exact_only, v.knn_nn ? 1 : 0, v.filter_local_map, v.mapping,
-           v.rotation_mode, v.table_size, (double)v.rebuild_delta,
+           v.rotation_mode, v.table_size, v.sorted_cap, v.hb_spill_base, (double)v.rebuild_delta,
            (om.ov || om.chain) ? 1 : 0, h->streams_concurrent ? 1 : 0, h->safe_mode ? 1 : 0, h->ring_split ? 1 : 0, h->ring_split ? h->ring_split_max_wgs : 0, h->ring_split_lb ? 1 : 0,
            om.chain ? 1 : 0, v.speculate, spec[0], spec[2], spec[1], spec[3], h->chain_count, done_cnt[0], done_cnt[32],
            h->replay_timed ? h->replay_enq_ns / (1e3 * (double)h->replay_timed) : 0.0, h->replay_timed ? h->replay_wait_ns / (1e3 * (double)h->replay_timed) : 0.0, v.debug);
