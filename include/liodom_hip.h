@@ -104,7 +104,8 @@ typedef struct liodom_config_t {
                                  1 (default) = Eigen 3.3.x, the README's platform: orthonormal polar factor of linear()
                                  (computeRotationScaling, JacobiSVD) for every Mode; 0 = Eigen >= 3.4: alias of linear()
                                  for an Isometry.  See DESIGN.md §4. */
-  int32_t reserved0;
+  int32_t pose_covariance;   /* 1 = per-scan pose covariance records (liodom_pose_cov_t below); 0 (default) = none: the handle launches
+                                exactly what it launches without the feature and allocates nothing for it */
 } liodom_config_t;
 
 typedef struct liodom_lm_trace_t {
@@ -126,6 +127,40 @@ typedef struct liodom_step_info_t {
   uint32_t status;
   int32_t scan_index;
 } liodom_step_info_t;
+
+/* ---- per-scan pose covariance (config.pose_covariance = 1) ----
+ * One record per scan per stream, written for every scan that gets a pose-log entry.  It describes the pose the finalising solve
+ * returned, in the solver's own tangent space — the one ceres::Covariance::GetCovarianceMatrixInTangentSpace would use for this
+ * problem: (d0 d1 d2 dtx dty dtz).  The rotation part is the EigenQuaternionParameterization increment
+ * q <- [sin|d| d/|d|, cos|d|] (x) q (left multiplication, world frame): the ROTATION ANGLE IS 2|d| — a half-angle tangent (for
+ * rotation variances in radians^2 multiply the rotation block by 4; pose_cov_to_ros in liodom_math.h converts the whole matrix
+ * to nav_msgs/Odometry order for the pose published with laser_to_base).  The translation part is additive, world coordinates.
+ *   information   H = sum rho' J^T J over the valid residual blocks at the returned pose: the loss-corrected Gauss-Newton matrix the
+ *                 LM controller holds there (Huber a = 0.2).
+ *   sigma2        2 final_cost / (3 C - 6), the a-posteriori variance factor.  The residuals are weighted point-to-line distances
+ *                 (factors.hpp: distance x (1.01 - normalised range)), not whitened measurements: sigma2 scales H^-1 to the
+ *                 observed residual level, it does not make the covariance a calibrated measurement covariance.
+ *   covariance    sigma2 H^-1.
+ *   eigenvalues / eigenvectors of H: the small eigenvalues and their vectors name the directions the scan leaves unconstrained
+ *                 (a corridor, vertical edges only, the mapping-mode degeneracy of DESIGN.md).
+ * Undefined values are NaN. */
+typedef struct liodom_pose_cov_t {
+  int32_t scan_index;        /* = liodom_step_info_t.scan_index of the same scan */
+  uint32_t flags;            /* LIODOM_COV_* below */
+  int32_t n_residuals;       /* C: valid residual blocks of the finalising solve */
+  int32_t termination;       /* = info.lm[1].termination */
+  double final_cost;         /* 0.5 * sum rho at the returned pose (bit-equal to info.lm[1].final_cost) */
+  double sigma2;             /* 2 * final_cost / (3 C - 6); NaN if 3 C <= 6 */
+  double information[36];    /* H = sum rho' J^T J at the returned pose, full symmetric, row-major */
+  double covariance[36];     /* sigma2 * H^-1; NaN-filled unless flags has LIODOM_COV_VALID and not SINGULAR */
+  double eigenvalues[6];     /* of H, ascending */
+  double eigenvectors[36];   /* row-major; column j belongs to eigenvalues[j]; unit length; sign: largest-|.| component > 0 */
+} liodom_pose_cov_t;
+#define LIODOM_COV_VALID 1u          /* a solve ran and its evaluation at the returned pose was finite (and had residual blocks) */
+#define LIODOM_COV_SINGULAR 2u       /* Cholesky of H failed: covariance is NaN; eigen-decomposition still valid */
+#define LIODOM_COV_NO_SOLVE 4u       /* first scan of a stream (or first after liodom_reset): no H, everything NaN */
+#define LIODOM_COV_EVAL_FAILURE 8u   /* termination 5 (non-finite blocks): H is meaningless, everything NaN */
+#define LIODOM_COV_FEW_RESIDUALS 16u /* 3 C <= 6: sigma2 and covariance NaN */
 
 typedef struct liodom_handle liodom_handle_t;
 typedef struct liodom_map liodom_map_t;
@@ -258,6 +293,16 @@ int liodom_unpin_host_buffer(void* p);
 int liodom_sync(liodom_handle_t* h);
 int liodom_get_pose_log(liodom_handle_t* h, int stream, int first, int count, double* poses_out,
                         liodom_step_info_t* infos_out);
+/* Pose covariance records (handles created with pose_covariance = 1; else LIODOM_ERR_UNSUPPORTED).
+ * liodom_get_pose_covariance_log: entries first .. first + count - 1 of a stream's device-side log, indexed like the pose log
+ * (scan k at entry k, scans k >= pose_log_capacity are not logged); same range rules and synchronisation as liodom_get_pose_log.
+ * liodom_wait_pose_covariance: the record of scan `scan_index` from host-mapped memory the device writes after every scan (two
+ * records per stream: the latest two scans), waited for with a bounded spin — the call for the per-scan paths
+ * (liodom_process_scan, liodom_odometry_step, liodom_odometry_collect), after the pose of that scan has been returned.  A scan
+ * older than the two kept records, or one not enqueued yet, returns LIODOM_ERR_INVALID_ARG; a wait that runs out returns
+ * LIODOM_ERR_HIP, never stale data.  liodom_reset clears the records. */
+int liodom_get_pose_covariance_log(liodom_handle_t* h, int stream, int first, int count, liodom_pose_cov_t* out);
+int liodom_wait_pose_covariance(liodom_handle_t* h, int stream, int scan_index, liodom_pose_cov_t* out);
 /* Resets the odometry state (pose, window, map) of every stream; capacities are kept. */
 int liodom_reset(liodom_handle_t* h);
 

@@ -12,7 +12,7 @@ _HASH = _LIB + ".srchash"
 _BUILD_INFO = {"rebuilt": None, "source_hash": None}
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kernels.h", "kernels_extract.h", "kernels_sync.h",
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
-                                                  "kernels_filter.h", "liodom_math.h", "wave_ops.h",
+                                                  "kernels_filter.h", "kernels_cov.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -104,7 +104,7 @@ class Config(C.Structure):
         ("device", C.c_int32), ("n_streams", C.c_int32), ("max_points", C.c_int32), ("max_width", C.c_int32),
         ("reserved1", C.c_int32), ("lm_apply_step_on_ftol", C.c_int32), ("pose_log_capacity", C.c_int32),
         ("debug_buffers", C.c_int32), ("lm_workgroups", C.c_int32), ("recv_capacity", C.c_int32),
-        ("pose_rotation_mode", C.c_int32), ("reserved0", C.c_int32),
+        ("pose_rotation_mode", C.c_int32), ("pose_covariance", C.c_int32),
     ]
 
 
@@ -119,6 +119,26 @@ class StepInfo(C.Structure):
 
 
 NUM_KERNELS = 12
+
+
+class PoseCov(C.Structure):
+    """liodom_pose_cov_t: the pose covariance record of one scan (include/liodom_hip.h)."""
+    _fields_ = [("scan_index", C.c_int32), ("flags", C.c_uint32), ("n_residuals", C.c_int32), ("termination", C.c_int32),
+                ("final_cost", C.c_double), ("sigma2", C.c_double), ("information", C.c_double * 36), ("covariance", C.c_double * 36),
+                ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36)]
+
+
+COV_VALID, COV_SINGULAR, COV_NO_SOLVE, COV_EVAL_FAILURE, COV_FEW_RESIDUALS = 1, 2, 4, 8, 16
+
+
+def pose_cov_dict(r):
+    """A PoseCov record as NumPy arrays: information / covariance / eigenvectors 6 x 6, eigenvalues (6,), plus the scalars."""
+    return dict(scan_index=r.scan_index, flags=r.flags, n_residuals=r.n_residuals, termination=r.termination,
+                final_cost=r.final_cost, sigma2=r.sigma2,
+                information=np.ctypeslib.as_array(r.information).reshape(6, 6).copy(),
+                covariance=np.ctypeslib.as_array(r.covariance).reshape(6, 6).copy(),
+                eigenvalues=np.ctypeslib.as_array(r.eigenvalues).copy(),
+                eigenvectors=np.ctypeslib.as_array(r.eigenvectors).reshape(6, 6).copy())
 
 
 class MapConfig(C.Structure):
@@ -190,6 +210,10 @@ def load():
     L.liodom_sync.argtypes = [vp]
     L.liodom_get_pose_log.restype = C.c_int
     L.liodom_get_pose_log.argtypes = [vp, C.c_int, C.c_int, C.c_int, dp, C.POINTER(StepInfo)]
+    L.liodom_get_pose_covariance_log.restype = C.c_int
+    L.liodom_get_pose_covariance_log.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(PoseCov)]
+    L.liodom_wait_pose_covariance.restype = C.c_int
+    L.liodom_wait_pose_covariance.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PoseCov)]
     L.liodom_reset.restype = C.c_int
     L.liodom_reset.argtypes = [vp]
     L.liodom_get_edges.restype = C.c_int
@@ -291,6 +315,7 @@ EXPORTED_SYMBOLS = [
     "liodom_set_imu_orientation", "liodom_set_laser_to_base",
     "liodom_scan_buffer", "liodom_extract_edges_device", "liodom_wait_edges", "liodom_odometry_step_device",
     "liodom_odometry_submit_device", "liodom_odometry_collect",
+    "liodom_get_pose_covariance_log", "liodom_wait_pose_covariance",
 ]
 
 
@@ -546,6 +571,19 @@ class Liodom:
         infos = (StepInfo * count)()
         self._check(self.L.liodom_get_pose_log(self.h, stream, first, count, _dp(poses), infos))
         return poses, infos
+
+    def pose_covariance_log(self, stream, first, count):
+        """Covariance records of scans first .. first + count - 1 (handles created with pose_covariance = 1): a list of dicts of
+        NumPy arrays (pose_cov_dict); the flags are in each dict."""
+        recs = (PoseCov * max(count, 1))()
+        self._check(self.L.liodom_get_pose_covariance_log(self.h, stream, first, count, recs))
+        return [pose_cov_dict(recs[i]) for i in range(count)]
+
+    def wait_pose_covariance(self, stream, scan_index):
+        """The covariance record of scan `scan_index` (one of the two latest of the stream), as a dict of NumPy arrays."""
+        r = PoseCov()
+        self._check(self.L.liodom_wait_pose_covariance(self.h, stream, scan_index, C.byref(r)))
+        return pose_cov_dict(r)
 
     # --- inspection ---
     def window(self, stream=0):

@@ -413,6 +413,27 @@ __global__ void k_imu_override(DevView v, int s0, int count) {
   st.param_t[0] = out[3]; st.param_t[1] = out[7]; st.param_t[2] = out[11];         // :192-195
 }
 
+// Pose covariance (config.pose_covariance = 1, kernels_cov.h): the finalising solve's workgroup 0 leaves H at the returned pose, the
+// cost, the residual blocks and the termination for k_pose_cov, which runs behind this launch on the same HIP stream.  Called after
+// finalize_scan, so that nothing another kernel waits for is delayed; 22 threads of the second wave, one stored value each (thread
+// 64 — the one that wrote st.info.scan_index in finalize_scan — also the header).  H is the controller's lm.H, except when
+// lm_apply_step_on_ftol applied the last candidate without accepting it (lm_update, LM_TERM_FUNC_TOL): lm.H still belongs to the
+// previous iterate then, and the last evaluation's accumulator — at that candidate, the returned pose — holds the matrix.
+// (No re-evaluation in a kernel of its own: the ticket API frees the edge slot as soon as the pose has been collected.)
+__device__ __forceinline__ void pose_cov_store(const DevView& v, int s, const StreamState& st, const LmState& lm, const double* acc, int nblocks, int tid) {
+  const int j = tid - 64;
+  if (j < 0 || j >= 21) return;
+  PoseCovRaw* r = v.cov_raw + s;
+  bool applied = lm.termination == LM_TERM_FUNC_TOL && lm.apply_on_ftol != 0;
+  for (int k = 0; k < 4; k++) applied = applied && lm.q[k] == lm.cand_q[k];
+  for (int k = 0; k < 3; k++) applied = applied && lm.t[k] == lm.cand_t[k];
+  r->H[j] = applied ? acc[7 + j] : lm.H[j];
+  if (j == 0) {
+    r->scan_index = st.info.scan_index; r->n_res = nblocks; r->termination = lm.termination; r->has_solve = 1;
+    r->cost = lm.cost;
+  }
+}
+
 __device__ __forceinline__ void rebuild_beside_solve(const DevView& v, int s, StreamState& st, int eb, int outer_it, int block, int nblocks, unsigned int seq, int* sbase, int* sslot);
 
 // chain != 0 (chain mode, kernels_sync.h; done_target: the first pass's done count to wait for): the launch holds the solving workgroups only (the rebuild rides on the other stream as
@@ -533,6 +554,10 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
       __syncthreads();                       // (also: the prefetched sh_prev / sh_fc)
       finalize_scan(v, s, st, sh_cnt, eb, true, 0, 0, sh_T0, 1, true, sh_prev, sh_fc);
       if (tid == 0) st.initialized = 1;
+      if (v.cov_raw && tid == 64) {          // (pose covariance: no solve, no H)
+        PoseCovRaw* r = v.cov_raw + s;
+        r->scan_index = st.info.scan_index; r->n_res = 0; r->termination = st.info.lm[1].termination; r->has_solve = 0; r->cost = st.info.lm[1].final_cost;
+      }
     }
     return;
   }
@@ -751,6 +776,7 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
   DBG_STAMP(v, dbgb, 2, 21);
   if (outer_it == 1) {
     finalize_scan(v, s, st, sh_cnt, eb, false, kLmCtl, chain, sh_ov, 0, false, sh_prev, sh_fc, spec_done ? 2 : 3, (!spec_done || sh_nmoved == spec_moves) ? 1u : 2u, &sh_trace);
+    if (v.cov_raw) pose_cov_store(v, s, st, lm, sh_acc, nblocks, tid);
     DBG_STAMP(v, dbgb, 2, 22);
   }
   DBG_STAMP(v, dbgb, 2, 28);

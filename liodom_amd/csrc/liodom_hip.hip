@@ -139,6 +139,7 @@ struct liodom_handle {
   float4* resident = nullptr;        // [S][n_slots][max_points]
   int n_slots = 0;
   HostOut* host_out = nullptr;       // host-mapped pinned result records, one per stream
+  HostCov* cov_host = nullptr;       // pose_covariance = 1: host-mapped covariance records, two per stream (DevView::cov_host)
   std::vector<int> scans_enqueued;   // per stream: scans launched so far (expected HostOut.seq)
   std::vector<void*> allocs;
   // profiling
@@ -386,6 +387,9 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
     // (speculative hand-over not confirmed — rare —: the pass's workgroups once more; the launch's first workgroups are ALLOC)
     if (v.speculate) hipLaunchKernelGGL(k_knn_redo<256>, dim3(kRebuildAllocBlocks + v.knn_grid, 1), dim3(256), 0, h->stream_k, v, s0, eb, seq_k, scan_no, kRebuildAllocBlocks);
     hipLaunchKernelGGL((k_lm_solve<1, true>), dim3(gx, 1), dim3(kLmThreads), lds, h->stream, v, s0, eb, seq_k, done_target);
+    // (pose covariance: behind the finalising solve on its stream; the next scan's first solve follows it there, and the next second
+    //  pass — hence the next finalising solve, the next writer of cov_raw — waits for that solve: kernels_cov.h)
+    if (v.cov_raw) hipLaunchKernelGGL(k_pose_cov, dim3(count), dim3(64), 0, h->stream, v, s0);
     if (!v.speculate) hipLaunchKernelGGL(k_rebuild_alloc, dim3(kRebuildAllocBlocks, 1), dim3(256), 0, h->stream_k, v, s0);
     const int nCf = cdiv(h->v.edge_cap * std::max(1, h->P - 1), kRebFinThreads), nPf = cdiv(h->v.edge_cap, kRebFinThreads);
     hipLaunchKernelGGL(k_rebuild_fin, dim3(nPf + kRebuildAuxBlocks + nCf, 1), dim3(kRebFinThreads), 0, h->stream_k, v, s0, eb);
@@ -423,6 +427,10 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
       const int gx = std::max(h->v.lm_groups + extra, (h->v.lm_groups - 1) * 8 + 1);      // solvers on blocks 0, 8, 16, ... (one XCD)
       if (it == 0) hipLaunchKernelGGL((k_lm_solve<0, false>), dim3(gx, count), dim3(kLmThreads), lm_lds_bytes(h->v.edge_cap), h->stream, v, s0, eb, seq_k, 0u);
       else hipLaunchKernelGGL((k_lm_solve<1, false>), dim3(gx, count), dim3(kLmThreads), lm_lds_bytes(h->v.edge_cap), h->stream, v, s0, eb, seq_k, 0u);
+    }
+    if (it == 1 && v.cov_raw) {             // pose covariance of the scan, straight behind its finalising solve (kernels_cov.h)
+      ProfScope ps(h, KID_OTHER);
+      hipLaunchKernelGGL(k_pose_cov, dim3(count), dim3(64), 0, h->stream, v, s0);
     }
   }
   if (v.mapping) {
@@ -670,6 +678,10 @@ int reset_state(liodom_handle* h) {
   HIP_TRY(hipMemsetAsync(h->v.knn_done0, 0, sizeof(unsigned int) * ((size_t)h->S + 64), h->stream));
   h->chain_prev = false; h->chain_count = 0; h->chain_fix_pending = false; h->verdict_scan = -1; h->replay_enq_ns = 0.0; h->replay_wait_ns = 0.0; h->replay_timed = 0;
   std::memset(h->host_out, 0, sizeof(HostOut) * 2 * (size_t)h->S);
+  if (h->cov_host) {
+    std::memset(h->cov_host, 0, sizeof(HostCov) * 2 * (size_t)h->S);
+    HIP_TRY(hipMemsetAsync(h->v.cov_raw, 0, sizeof(PoseCovRaw) * (size_t)h->S, h->stream));
+  }
   std::fill(h->scans_enqueued.begin(), h->scans_enqueued.end(), 0);
   HIP_TRY(hipMemsetAsync(h->v.win_n, 0, sizeof(int) * (size_t)h->S * h->P, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1025,6 +1037,20 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     h->scans_enqueued.assign(S, 0);
     h->mappers.assign(S, nullptr); h->mapper_cells_xy.assign(S, 2); h->mapper_cells_z.assign(S, 1);
   }
+  if (config->pose_covariance) {
+    // per-scan pose covariance (kernels_cov.h): nothing of it exists on handles created without it
+    ALLOC(v.cov_raw, S, 0);
+    ALLOC(v.cov_log, S * (size_t)v.pose_log_cap, 0);
+    void* hp = nullptr;
+    if (hipHostMalloc(&hp, sizeof(HostCov) * 2 * S, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { g_last_error = "hipHostMalloc failed"; return fail(LIODOM_ERR_HIP); }
+    h->cov_host = static_cast<HostCov*>(hp);
+    std::memset(hp, 0, sizeof(HostCov) * 2 * S);
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
+    v.cov_host = static_cast<HostCov*>(dp);
+  } else {
+    v.cov_raw = nullptr; v.cov_log = nullptr; v.cov_host = nullptr;
+  }
   if (ring_scatter_lds_bytes(h->H) > 48 * 1024) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_scatter), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)ring_scatter_lds_bytes(h->H)) != hipSuccess) {
@@ -1113,6 +1139,7 @@ void liodom_destroy(liodom_handle_t* h) {
   for (void* p : h->allocs) hipFree(p);
   if (h->resident) hipFree(h->resident);
   if (h->host_out) hipHostFree(h->host_out);
+  if (h->cov_host) hipHostFree(h->cov_host);
   if (h->host_edges) hipHostFree(h->host_edges);
   if (h->host_edges_meta) hipHostFree(h->host_edges_meta);
   if (h->host_edges_hdr) hipHostFree(h->host_edges_hdr);
@@ -1762,6 +1789,44 @@ int liodom_get_pose_log(liodom_handle_t* h, int stream, int first, int count, do
   return LIODOM_OK;
 }
 
+int liodom_get_pose_covariance_log(liodom_handle_t* h, int stream, int first, int count, liodom_pose_cov_t* out) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if (!h->v.cov_log) { g_last_error = "liodom_get_pose_covariance_log: the handle was created with pose_covariance = 0"; return LIODOM_ERR_UNSUPPORTED; }
+  if (first < 0 || count < 0 || first + count > h->v.pose_log_cap) { g_last_error = "pose log range"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, true, false);
+  HIP_TRY(sync_odometry(h));
+  if (out && count)
+    HIP_TRY(hipMemcpy(out, h->v.cov_log + (size_t)stream * h->v.pose_log_cap + first, sizeof(liodom_pose_cov_t) * (size_t)count, hipMemcpyDeviceToHost));
+  return LIODOM_OK;
+}
+
+int liodom_wait_pose_covariance(liodom_handle_t* h, int stream, int scan_index, liodom_pose_cov_t* out) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if (!h->cov_host) { g_last_error = "liodom_wait_pose_covariance: the handle was created with pose_covariance = 0"; return LIODOM_ERR_UNSUPPORTED; }
+  if (!out) return LIODOM_ERR_INVALID_ARG;
+  SideLocks lk(h, true, false);      // (no scan can be enqueued meanwhile: record scan_index & 1 is not rewritten while this waits)
+  const int enq = h->scans_enqueued[stream];
+  if (scan_index < 0 || scan_index >= enq || scan_index < enq - 2) {
+    g_last_error = "liodom_wait_pose_covariance: the scan is not among the two latest enqueued scans of the stream";
+    return LIODOM_ERR_INVALID_ARG;
+  }
+  volatile HostCov* hc = h->cov_host + (size_t)stream * 2 + (scan_index & 1);
+  const auto t0 = std::chrono::steady_clock::now();
+  unsigned long long spins = 0;
+  while (__atomic_load_n(&hc->seq, __ATOMIC_ACQUIRE) != scan_index + 1) {
+    if ((++spins & 0xFFFFull) == 0) {
+      const hipError_t q = hipStreamQuery(h->stream);
+      if (q != hipErrorNotReady && q != hipSuccess) { g_last_error = std::string("stream error while waiting: ") + hipGetErrorString(q); return LIODOM_ERR_HIP; }
+      if (q == hipSuccess && __atomic_load_n(&hc->seq, __ATOMIC_ACQUIRE) != scan_index + 1) { g_last_error = "stream drained without publishing the scan's covariance record"; return LIODOM_ERR_HIP; }
+      if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) { g_last_error = "liodom_wait_pose_covariance: timed out"; return LIODOM_ERR_HIP; }
+    }
+  }
+  std::memcpy(out, const_cast<const liodom_pose_cov_t*>(&h->cov_host[(size_t)stream * 2 + (scan_index & 1)].rec), sizeof(liodom_pose_cov_t));
+  return LIODOM_OK;
+}
+
 static int get_window_impl(liodom_handle_t* h, int stream, float* xyzi, int64_t cap, int64_t* n_points, int* n_frames) {
   HIP_TRY(sync_odometry(h));
   StreamState st;
@@ -1995,6 +2060,10 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
            (om.ov || om.chain) ? 1 : 0, h->streams_concurrent ? 1 : 0, h->safe_mode ? 1 : 0, h->ring_split ? 1 : 0, h->ring_split ? h->ring_split_max_wgs : 0, h->ring_split_lb ? 1 : 0,
            om.chain ? 1 : 0, v.speculate, spec[0], spec[2], spec[1], spec[3], h->chain_count, done_cnt[0], done_cnt[32],
            h->replay_timed ? h->replay_enq_ns / (1e3 * (double)h->replay_timed) : 0.0, h->replay_timed ? h->replay_wait_ns / (1e3 * (double)h->replay_timed) : 0.0, v.debug);
+  if (v.cov_raw) {
+    const size_t len = std::strlen(buf);
+    snprintf(buf + len, (size_t)cap - len, " pose_cov=1");
+  }
   return LIODOM_OK;
 }
 

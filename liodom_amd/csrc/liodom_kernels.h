@@ -21,6 +21,7 @@
 //                            >= 16 streams)
 //   k_voxel_* / k_filt_*  A7 filter_local_map: VoxelGrid(0.4) of the full window (:286-292)
 //   k_imu_override    A8     use_imu: roll / pitch of the prediction from the IMU (:152-183)
+//   k_pose_cov               (pose_covariance = 1) covariance + eigen-decomposition of the finalising solve's H, one wave per stream
 //   (liodom_map.h)    A12-A14 the mapping node's Map: updateMap / getLocalMap / getMap
 //
 // All FP on the parity-critical paths is compiled with -ffp-contract=off.
@@ -139,6 +140,20 @@ struct __attribute__((aligned(16))) CellSlot {
 struct HostOut {
   double pose[7];
   liodom_step_info_t info;
+  int seq;
+  int pad;
+};
+
+// Pose covariance (config.pose_covariance = 1; kernels_cov.h): what the finalising solve's controller leaves for k_pose_cov —
+// the 21 upper-triangle entries of H at the returned pose, the cost, the residual blocks and the termination.  One per stream.
+struct PoseCovRaw {
+  int scan_index, n_res, termination, has_solve;      // has_solve 0: first scan of the stream (no solve ran)
+  double cost;
+  double H[21];
+};
+// Host-mapped record of a scan (two per stream, scan k in slot k & 1): payload first, then seq = k + 1 with a system-scope release.
+struct HostCov {
+  liodom_pose_cov_t rec;
   int seq;
   int pad;
 };
@@ -278,6 +293,10 @@ struct DevView {
                                 // k_compact_edges' last workgroup, system scope); number of edges in slot b
   unsigned long long* dbg_clk;  // [16][32] phase timestamps (100 MHz) and counters, debug bit 5 only
   unsigned int* dbg_q;          // [2][edge_cap][8] per-query phase times of stream 0's latest scan (10 ns ticks since the workgroup's start), debug bit 5 only
+  // pose covariance (config.pose_covariance = 1; all three null otherwise: k_lm_solve then stores nothing and k_pose_cov is not launched)
+  PoseCovRaw* cov_raw;          // [S] written by the finalising solve (workgroup 0), read by k_pose_cov right behind it on the same HIP stream
+  liodom_pose_cov_t* cov_log;   // [S][pose_log_cap] device-side log, indexed like pose_log
+  HostCov* cov_host;            // [S][2] host-mapped, polled by liodom_wait_pose_covariance
 };
 
 // computeLocalMap's condition (laser_odometry.cc:286): filter && window full && !mapping
@@ -374,5 +393,6 @@ __device__ __forceinline__ void inject_delay(unsigned int site) {
 #include "kernels_lm.h"
 #include "kernels_rebuild.h"
 #include "kernels_filter.h"
+#include "kernels_cov.h"
 
 }  // namespace liodom_dev

@@ -658,6 +658,219 @@ LD_HD bool chol_solve6_packed(double* A /*21, overwritten by L*/, const double* 
   return true;
 }
 
+// ---------------------------------------------------------------------------------------
+// Pose covariance of a finished solve (k_pose_cov, kernels_cov.h; record layout: liodom_pose_cov_t in include/liodom_hip.h).
+// H is the loss-corrected J^T J the LM controller holds at the returned pose, tangent (d0 d1 d2 dtx dty dtz) of
+// EigenQuaternionParameterization x additive translation.  Strict FP64, no contraction (these run once per scan).
+// ---------------------------------------------------------------------------------------
+constexpr unsigned int kCovValid = 1u, kCovSingular = 2u, kCovNoSolve = 4u, kCovEvalFailure = 8u, kCovFewResiduals = 16u;
+constexpr int kCovJacobiSweeps = 12;
+
+// Inverse of the symmetric 6 x 6 matrix H (21 upper-triangle entries, h_idx) by Cholesky: H = L L^T, L^-1 by forward
+// substitution, H^-1 = L^-T L^-1 (symmetric by construction: entry (i, j) and (j, i) are the same sum).  Returns false — and
+// leaves inv36 untouched — when a pivot is not > 0 or not finite.  (Every loop unrolls to constant indices: on the device the
+// work arrays stay in registers.)
+LD_HD bool spd_inverse6(const double* H21, double* inv36) {
+  double L[21];              // packed lower triangle, lt_idx
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) {
+    LD_UNROLL
+    for (int j = 0; j <= i; j++) L[lt_idx(i, j)] = H21[h_idx(j, i)];
+  }
+  bool ok = true;
+  LD_UNROLL
+  for (int j = 0; j < 6; j++) {
+    double d = L[lt_idx(j, j)];
+    LD_UNROLL
+    for (int k = 0; k < j; k++) d -= L[lt_idx(j, k)] * L[lt_idx(j, k)];
+    ok = ok && d > 0.0 && ld_isfinite(d);
+    const double ljj = sqrt(d);
+    L[lt_idx(j, j)] = ljj;
+    LD_UNROLL
+    for (int i = j + 1; i < 6; i++) {
+      double s = L[lt_idx(i, j)];
+      LD_UNROLL
+      for (int k = 0; k < j; k++) s -= L[lt_idx(i, k)] * L[lt_idx(j, k)];
+      L[lt_idx(i, j)] = s / ljj;
+    }
+  }
+  if (!ok) return false;
+  double Li[21];             // L^-1, lower triangular
+  LD_UNROLL
+  for (int j = 0; j < 6; j++) {
+    Li[lt_idx(j, j)] = 1.0 / L[lt_idx(j, j)];
+    LD_UNROLL
+    for (int i = j + 1; i < 6; i++) {
+      double s = 0.0;
+      LD_UNROLL
+      for (int k = j; k < i; k++) s -= L[lt_idx(i, k)] * Li[lt_idx(k, j)];
+      Li[lt_idx(i, j)] = s / L[lt_idx(i, i)];
+    }
+  }
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) {
+    LD_UNROLL
+    for (int j = i; j < 6; j++) {
+      double s = 0.0;
+      LD_UNROLL
+      for (int k = j; k < 6; k++) s += Li[lt_idx(k, i)] * Li[lt_idx(k, j)];
+      inv36[i * 6 + j] = s;
+      inv36[j * 6 + i] = s;
+    }
+  }
+  return true;
+}
+
+// Eigen-decomposition of the symmetric 6 x 6 matrix A36 (row-major, full) by cyclic Jacobi until the off-diagonal Frobenius
+// norm is <= 1e-15 ||A||_F, at most kCovJacobiSweeps sweeps.  evals ascending; evecs row-major, column j belongs to evals[j],
+// unit length, sign: the component of largest magnitude (the first of equal ones) is positive.  Returns the sweeps used.
+LD_HD int sym_eig6(const double* A36, double* evals, double* evecs) {
+  double a[36], V[36];
+  double fro2 = 0.0;
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) { a[i] = A36[i]; V[i] = (i % 7 == 0) ? 1.0 : 0.0; fro2 += a[i] * a[i]; }
+  const double tol2 = 1e-30 * fro2;
+  int sweep = 0;
+  for (; sweep < kCovJacobiSweeps; sweep++) {
+    double off2 = 0.0;
+    LD_UNROLL
+    for (int p = 0; p < 6; p++) {
+      LD_UNROLL
+      for (int q = p + 1; q < 6; q++) off2 += 2.0 * a[p * 6 + q] * a[p * 6 + q];
+    }
+    if (off2 <= tol2) break;
+    LD_UNROLL
+    for (int p = 0; p < 5; p++) {
+      LD_UNROLL
+      for (int q = p + 1; q < 6; q++) {
+        const double apq = a[p * 6 + q];
+        if (apq != 0.0) {
+          // Golub & Van Loan, sym.schur2: the rotation (c, s) that zeroes a_pq, the smaller of the two angles
+          const double tau = (a[q * 6 + q] - a[p * 6 + p]) / (2.0 * apq);
+          const double at = fabs(tau);
+          double t = at > 1e150 ? 0.5 / at : 1.0 / (at + sqrt(1.0 + tau * tau));
+          if (tau < 0.0) t = -t;
+          const double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
+          LD_UNROLL
+          for (int k = 0; k < 6; k++) {          // A <- A J (columns p, q)
+            const double akp = a[k * 6 + p], akq = a[k * 6 + q];
+            a[k * 6 + p] = c * akp - s * akq;
+            a[k * 6 + q] = s * akp + c * akq;
+          }
+          LD_UNROLL
+          for (int k = 0; k < 6; k++) {          // A <- J^T A (rows p, q)
+            const double apk = a[p * 6 + k], aqk = a[q * 6 + k];
+            a[p * 6 + k] = c * apk - s * aqk;
+            a[q * 6 + k] = s * apk + c * aqk;
+          }
+          a[p * 6 + q] = 0.0; a[q * 6 + p] = 0.0;
+          LD_UNROLL
+          for (int k = 0; k < 6; k++) {          // V <- V J
+            const double vkp = V[k * 6 + p], vkq = V[k * 6 + q];
+            V[k * 6 + p] = c * vkp - s * vkq;
+            V[k * 6 + q] = s * vkp + c * vkq;
+          }
+        }
+      }
+    }
+  }
+  LD_UNROLL
+  for (int o = 0; o < 6; o++) {
+    int r = 0;                                   // rank of eigenvalue o (ties: column order)
+    LD_UNROLL
+    for (int j = 0; j < 6; j++) r += (a[j * 7] < a[o * 7] || (a[j * 7] == a[o * 7] && j < o)) ? 1 : 0;
+    evals[r] = a[o * 7];
+    double n2 = 0.0, big = 0.0;
+    LD_UNROLL
+    for (int k = 0; k < 6; k++) {
+      const double x = V[k * 6 + o];
+      n2 += x * x;
+      if (fabs(x) > fabs(big)) big = x;
+    }
+    const double sc = (big < 0.0 ? -1.0 : 1.0) / sqrt(n2);
+    LD_UNROLL
+    for (int k = 0; k < 6; k++) evecs[k * 6 + r] = V[k * 6 + o] * sc;
+  }
+  return sweep;
+}
+
+// The whole record from what the finalising solve left: information (full), sigma^2, covariance, eigen-decomposition and the
+// flags.  has_solve = 0: the first scan of a stream (no solve ran).  Everything that is not defined is NaN.
+LD_HD unsigned int pose_cov_compute(const double* H21, double final_cost, int n_res, int termination, int has_solve,
+                                    double* sigma2, double* info36, double* cov36, double* evals6, double* evecs36) {
+  const double nan = __builtin_nan("");
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) { info36[i] = nan; cov36[i] = nan; evecs36[i] = nan; }
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) evals6[i] = nan;
+  *sigma2 = nan;
+  if (!has_solve) return kCovNoSolve;
+  if (termination == LM_TERM_EVAL_FAILURE) return kCovEvalFailure;
+  unsigned int flags = 0u;
+  bool finite = true;
+  LD_UNROLL
+  for (int i = 0; i < 21; i++) finite = finite && ld_isfinite(H21[i]);
+  if (n_res > 0 && finite && ld_isfinite(final_cost)) flags |= kCovValid;
+  if (3 * n_res <= 6) flags |= kCovFewResiduals;
+  else *sigma2 = 2.0 * final_cost / (double)(3 * n_res - 6);
+  if (!finite) return flags | kCovSingular;
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) {
+    LD_UNROLL
+    for (int j = 0; j < 6; j++) info36[i * 6 + j] = h_at(H21, i, j);
+  }
+  sym_eig6(info36, evals6, evecs36);
+  double inv[36];
+  if (!spd_inverse6(H21, inv)) return flags | kCovSingular;
+  if ((flags & kCovValid) && !(flags & kCovFewResiduals)) {
+    LD_UNROLL
+    for (int i = 0; i < 36; i++) cov36[i] = *sigma2 * inv[i];
+  }
+  return flags;
+}
+
+// Covariance of the pose solved in the tangent above -> covariance of the published pose P = T L (L = laser_to_base) in
+// nav_msgs/Odometry order (x y z rotX rotY rotZ).  Derivation, to first order: the solver moves the rotation by left
+// multiplication, q' = [sin|d| d/|d|, cos|d|] (x) q, i.e. R' = Exp(2 d) R — a rotation vector theta = 2 d in the world frame (the
+// quaternion half-angle); the translation moves additively, t' = t + dt.  P's rotation R_P = R R_L then moves by the same
+// world-frame theta, and P's position p = R t_L + t by dp = theta x (R t_L) + dt = dt - [R t_L]x theta.  With
+// A = [[-2 [R t_L]x, I], [2 I, 0]] acting on (d, dt): out = A cov A^T.  T12, L12: 3 x 4 row-major (world <- laser, laser <- base).
+LD_HD void pose_cov_to_ros(const double* cov36_tangent, const double* T12, const double* L12, double* out36) {
+  double u[3];               // R t_L
+  LD_UNROLL
+  for (int i = 0; i < 3; i++) u[i] = T12[4 * i] * L12[3] + T12[4 * i + 1] * L12[7] + T12[4 * i + 2] * L12[11];
+  double A[36];
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) A[i] = 0.0;
+  // rows 0..2 (position): -2 [u]x on d, I on dt;  [u]x = [[0, -u2, u1], [u2, 0, -u0], [-u1, u0, 0]]
+  A[0 * 6 + 1] = 2.0 * u[2];  A[0 * 6 + 2] = -2.0 * u[1];
+  A[1 * 6 + 0] = -2.0 * u[2]; A[1 * 6 + 2] = 2.0 * u[0];
+  A[2 * 6 + 0] = 2.0 * u[1];  A[2 * 6 + 1] = -2.0 * u[0];
+  LD_UNROLL
+  for (int i = 0; i < 3; i++) { A[i * 6 + 3 + i] = 1.0; A[(3 + i) * 6 + i] = 2.0; }
+  double AS[36];
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) {
+    LD_UNROLL
+    for (int j = 0; j < 6; j++) {
+      double s = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 6; k++) s += A[i * 6 + k] * cov36_tangent[k * 6 + j];
+      AS[i * 6 + j] = s;
+    }
+  }
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) {
+    LD_UNROLL
+    for (int j = 0; j < 6; j++) {
+      double s = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 6; k++) s += AS[i * 6 + k] * A[j * 6 + k];
+      out36[i * 6 + j] = s;
+    }
+  }
+}
+
 LD_HD double norm7(const double* q, const double* t) {
   LD_FP_CONTRACT_FAST
   return sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] + t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);

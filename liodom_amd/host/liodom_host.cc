@@ -156,12 +156,13 @@ void SharedData::clear() {
   pc_buf_ = {}; feat_buf_ = {};
 }
 
-Engine::Engine(const Params& p, int device, int max_points, int max_width, int pose_rotation_mode) {
+Engine::Engine(const Params& p, int device, int max_points, int max_width, int pose_rotation_mode, int pose_covariance) {
   liodom_params_t cp = p.toC();
   liodom_config_t cfg;
   liodom_config_default(&cfg);
   cfg.device = device; cfg.n_streams = 1; cfg.max_points = max_points; cfg.max_width = max_width;
   cfg.pose_rotation_mode = pose_rotation_mode; rotation_mode_ = pose_rotation_mode != 0 ? 1 : 0;
+  cfg.pose_covariance = pose_covariance != 0 ? 1 : 0; covariance_ = pose_covariance != 0;
   check(liodom_create(&cp, &cfg, &h_), "liodom_create");
   edge_cap_ = p.scan_lines_ * p.scan_regions_ * (p.edges_per_region_ + 1) + 64;
 }
@@ -308,6 +309,13 @@ OdometryMsg LaserOdometer::publishOdom(double stamp, const Pose& pose) {
   std::memcpy(msg.position, out + 4, sizeof(double) * 3);
   std::memcpy(msg.linear, out + 7, sizeof(double) * 3);
   std::memcpy(msg.angular, out + 10, sizeof(double) * 3);
+  if (eng_->covariance() && last_scan_ >= 0) {
+    liodom_pose_cov_t rec;
+    check(liodom_wait_pose_covariance(eng_->handle(), 0, last_scan_, &rec), "liodom_wait_pose_covariance");
+    liodom_dev::pose_cov_to_ros(rec.covariance, cur.data(), laser_to_base_.data(), msg.pose_covariance);
+    msg.has_covariance = true;
+    msg.covariance_flags = rec.flags;
+  }
   prev_odom_ = cur;                                // the reference's prev_odom_ (:149) is the pose of the previous scan here
   prev_stamp_ = stamp;                             // :266
   return msg;
@@ -348,8 +356,11 @@ void LaserOdometer::updateFrequencies(double in_stamp_secs, double now_secs) {
 Pose LaserOdometer::process(const PointCloud& feats, double stamp, liodom_step_info_t* info) {
   const auto start_t = Clock::now();
   double p[7];
+  liodom_step_info_t local;
   check(liodom_odometry_step(eng_->handle(), 0, reinterpret_cast<const float*>(feats.points.data()),
-                             (int)feats.size(), stamp, p, info), "liodom_odometry_step");
+                             (int)feats.size(), stamp, p, &local), "liodom_odometry_step");
+  if (info) *info = local;
+  last_scan_ = local.scan_index;
   Pose out;
   std::memcpy(out.q, p, sizeof(double) * 4); std::memcpy(out.t, p + 4, sizeof(double) * 3);
   const auto end_t = Clock::now();                                    // laser_odometry.cc:237
@@ -367,7 +378,10 @@ Pose LaserOdometer::process(const Features& feats, liodom_step_info_t* info) {
   if (feats.ticket.seq == 0u) return process(feats.edges, feats.stamp, info);
   const auto start_t = Clock::now();
   double p[7];
-  check(liodom_odometry_step_device(eng_->handle(), &feats.ticket, feats.stamp, p, info), "liodom_odometry_step_device");
+  liodom_step_info_t local;
+  check(liodom_odometry_step_device(eng_->handle(), &feats.ticket, feats.stamp, p, &local), "liodom_odometry_step_device");
+  if (info) *info = local;
+  last_scan_ = local.scan_index;
   Pose out;
   std::memcpy(out.q, p, sizeof(double) * 4); std::memcpy(out.t, p + 4, sizeof(double) * 3);
   const auto end_t = Clock::now();                                    // laser_odometry.cc:237
@@ -478,6 +492,7 @@ Pose LaserOdometer::processScan(const PointCloud& pc_in, double stamp, liodom_st
                             (int64_t)pc_in.size(), (int)pc_in.height, (int)pc_in.width, stamp, p, &local),
         "liodom_process_scan");
   if (info) *info = local;
+  last_scan_ = local.scan_index;
   Pose out;
   std::memcpy(out.q, p, sizeof(double) * 4); std::memcpy(out.t, p + 4, sizeof(double) * 3);
   if (init_) updateFrequencies(stamp, wall_secs());                   // laser_odometry.cc:239-256

@@ -122,13 +122,16 @@ class SharedData {
 class Engine {
  public:
   // pose_rotation_mode: see liodom_config_t (1 = Eigen 3.3.x Transform::rotation(), the default)
-  Engine(const Params& p, int device, int max_points, int max_width, int pose_rotation_mode = 1);
+  // pose_covariance: see liodom_config_t (1 = per-scan covariance records, OdometryMsg::pose_covariance)
+  Engine(const Params& p, int device, int max_points, int max_width, int pose_rotation_mode = 1, int pose_covariance = 0);
   ~Engine();
   liodom_handle_t* handle() const { return h_; }
   int edge_capacity() const { return edge_cap_; }
   int rotation_mode() const { return rotation_mode_; }
+  bool covariance() const { return covariance_; }
  private:
   liodom_handle_t* h_ = nullptr;
+  bool covariance_ = false;
   int edge_cap_ = 0;
   int rotation_mode_ = 1;
 };
@@ -190,6 +193,12 @@ struct OdometryMsg {
   double position[3] = {0, 0, 0};
   double linear[3] = {0, 0, 0};           // delta translation / delta stamp
   double angular[3] = {0, 0, 0};          // tf RPY of the delta rotation / delta stamp
+  // pose.covariance in nav_msgs/Odometry order (x y z rotX rotY rotZ): zeros, as the reference publishes, unless the engine was
+  // created with pose covariance; then the scan's record (liodom_pose_cov_t) converted by pose_cov_to_ros for the published
+  // pose (pose * laser_to_base_) — NaN where the record has none (covariance_flags other than LIODOM_COV_VALID alone)
+  double pose_covariance[36] = {0};
+  bool has_covariance = false;
+  uint32_t covariance_flags = 0;
 };
 
 class LaserOdometer {
@@ -223,6 +232,7 @@ class LaserOdometer {
   std::array<double, 12> laser_to_base_{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};  // laser_odometry.h:104
   double prev_stamp_ = 0.0;                                                     // laser_odometry.h:97
   bool published_ = false;
+  int last_scan_ = -1;                     // scan_index of the pose returned last (its covariance record goes into publishOdom's message)
   // output-rate watchdog (laser_odometry.cc:239-256; state laser_odometry.h:105-111, initial values laser_odometry.cc:83-90)
   void updateFrequencies(double in_stamp_secs, double now_secs);
   double in_freqs_[5], out_freqs_[5];

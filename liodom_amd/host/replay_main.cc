@@ -56,7 +56,9 @@ int main(int argc, char** argv) {
     max_pts = std::max(max_pts, clouds[i].points.size());
   }
   try {
-    auto eng = std::make_shared<liodom::Engine>(*params, 0, (int)max_pts, (int)(max_pts / (size_t)params->scan_lines_ + 1));
+    bool covariance = false;      // covariance=1: per-scan pose covariance, written to covariances.txt
+    for (const std::string& a : kv) if (a == "covariance=1" || a == "covariance=true") covariance = true;
+    auto eng = std::make_shared<liodom::Engine>(*params, 0, (int)max_pts, (int)(max_pts / (size_t)params->scan_lines_ + 1), 1, covariance ? 1 : 0);
     liodom::LaserOdometer odometer(eng);
     std::unique_ptr<liodom::Map> mapper;
     if (params->mapping_) {
@@ -74,6 +76,15 @@ int main(int argc, char** argv) {
     }
     std::ofstream odom_log(out + "odom.txt");      // stamp, orientation xyzw, position, twist linear, twist angular
     odom_log.precision(17);
+    std::ofstream cov_log;                          // covariance=1: scan index, flags, the 36 values of OdometryMsg::pose_covariance
+    if (covariance) { cov_log.open(out + "covariances.txt"); cov_log.precision(17); }
+    size_t cov_rows = 0;
+    auto write_cov = [&](const liodom::OdometryMsg& msg) {
+      if (!covariance) return;
+      cov_log << cov_rows++ << ' ' << msg.covariance_flags;
+      for (double v : msg.pose_covariance) cov_log << ' ' << v;
+      cov_log << '\n';
+    };
     bool threads = false, host_handoff = false;
     int poll_us = 2000;
     for (const std::string& a : kv) {
@@ -111,6 +122,7 @@ int main(int argc, char** argv) {
         for (double v : msg.linear) odom_log << ' ' << v;
         for (double v : msg.angular) odom_log << ' ' << v;
         odom_log << '\n';
+        write_cov(msg);
       }
       std::printf("threads: %zu scans through the extractor / odometer threads in %.3f s = %.1f scans/s (handoff=%s, poll_us=%d)\n",
                   msgs.size(), secs, (double)msgs.size() / secs, host_handoff ? "host" : "device", poll_us);
@@ -126,6 +138,7 @@ int main(int argc, char** argv) {
       for (double v : msg.linear) odom_log << ' ' << v;
       for (double v : msg.angular) odom_log << ' ' << v;
       odom_log << '\n';
+      write_cov(msg);
       if (i % 50 == 0) std::printf("scan %zu: %d edges, %d matches, t = %.3f %.3f %.3f\n", i, info.n_edges, info.matches[1], p.t[0], p.t[1], p.t[2]);
     }
     liodom::Stats::getInstance()->writeResults(out);

@@ -100,6 +100,10 @@ struct Node {
     odom.pose.pose.position.x = m.position[0]; odom.pose.pose.position.y = m.position[1]; odom.pose.pose.position.z = m.position[2];
     odom.twist.twist.linear.x = m.linear[0]; odom.twist.twist.linear.y = m.linear[1]; odom.twist.twist.linear.z = m.linear[2];
     odom.twist.twist.angular.x = m.angular[0]; odom.twist.twist.angular.y = m.angular[1]; odom.twist.twist.angular.z = m.angular[2];
+    // engine created with pose covariance: the scan's covariance where it is defined (flags == LIODOM_COV_VALID), else the
+    // reference's all-zero covariance
+    if (m.has_covariance && m.covariance_flags == LIODOM_COV_VALID)
+      for (int i = 0; i < 36; i++) odom.pose.covariance[i] = m.pose_covariance[i];
     odom_pub.publish(odom);
     geometry_msgs::TwistStamped tw;
     tw.header.frame_id = m.child_frame_id; tw.header.stamp = header.stamp; tw.twist = odom.twist.twist;
