@@ -6,9 +6,10 @@
 //   so that the G workgroups share an XCD; every other block of the launch is a workgroup of the streamed rebuild, kernels_rebuild.h).
 //   first evaluation: the reduction of the per-workgroup partial normal equations k_knn left (handles with knn_partials);
 //   eval: every workgroup takes a contiguous share of the accepted correspondences; every thread accumulates the 29-entry
-//   normal-equation accumulator over its blocks (fused residual + analytic Jacobian + Huber), transposed LDS reduction in a fixed
-//   order (deterministic, no atomics, no MFMA: this is a 6x6 reduction); with G > 1 the 29 partial sums are exchanged inside the
-//   launch as tagged 8-byte granules (lm_exchange) and every workgroup continues with bit-identical totals.
+//   normal-equation accumulator over its blocks (fused residual + analytic Jacobian + Huber), each wave reduces it in registers
+//   (reduce-scatter, wave_ops.h), one barrier, the controller's wave sums the wave partials in a fixed order (deterministic, no
+//   atomics, no MFMA: this is a 6x6 reduction); with G > 1 that wave exchanges the 29 partial sums inside the launch as tagged
+//   8-byte granules (lm_exchange) and every workgroup continues with bit-identical totals.  Two workgroup barriers per step.
 //   controller: lane 0 of the last wave (tid kLmCtl) runs lm_begin / lm_update (liodom_math.h) between evaluations, redundantly in
 //   every workgroup; beside its first step the other waves compact the accepted correspondences and cache their triples in registers.
 //   finalize (second outer iteration, or the very first frame; workgroup 0): pose log + host-mapped record, constant-velocity
@@ -25,14 +26,10 @@
 // =============================================================================================
 // Indices of the edges with an accepted correspondence, in edge order (deterministic), built once
 // per solve in LDS so that every evaluation runs over C dense items instead of E sparse ones.
-// dynamic LDS of k_lm_solve: index list + reduction scratch (full transposed matrix if it fits the
-// 160 KB of a CU next to ~3 KB of static LDS, else one partial per 16-lane row)
-__host__ __device__ __forceinline__ bool lm_lds_reduce_fits(int edge_cap) {
-  return (size_t)((edge_cap + 3) & ~3) * sizeof(int) + (size_t)kAccN * kLmEvalThreads * sizeof(double) + 8192 <= 160 * 1024;
-}
+// dynamic LDS of k_lm_solve: the index list (the reduction's per-wave sums, sh_wsum, are static: 1 KiB)
+constexpr int kLmWaves = kLmThreads / 64;
 __host__ __device__ __forceinline__ size_t lm_lds_bytes(int edge_cap) {
-  return (size_t)((edge_cap + 3) & ~3) * sizeof(int) +
-         (lm_lds_reduce_fits(edge_cap) ? (size_t)kAccN * kLmEvalThreads : (size_t)(kLmThreads / 16) * kAccN) * sizeof(double);
+  return (size_t)((edge_cap + 3) & ~3) * sizeof(int);
 }
 
 
@@ -84,19 +81,21 @@ __device__ __forceinline__ void lm_cache_load(const DevView& v, int s, int outer
   }
 }
 
-// Evaluation of the blocks c_lo .. c_hi of the compacted list by the evaluator waves, then the reduction by
-// everybody.  part: [kAccN][kLmEvalThreads] or [kLmThreads/16][kAccN].
+// Evaluation of the blocks c_lo .. c_hi of the compacted list by every thread, then the first half of the reduction: every wave
+// that holds blocks reduces its 29 partial sums in registers (wave_reduce_scatter32_f64, entries padded to 32) and stores them as
+// row `wave` of wsum (lane 2e: entry e), one store per lane; waves without blocks skip it (wave-uniform: c_hi - c_lo).  Ends with
+// the workgroup barrier behind which the controller's wave sums the rows (lm_wave_total).  Fixed order -> deterministic, no atomics.
 __device__ __forceinline__ void lm_eval(const DevView& v, int s, int outer_it, int eb, int c_lo, int c_hi, const int* idx, const double* Rm_sh,
-                                        double* part, double* acc_out /*[kAccN]*/, const LmCache& k) {
+                                        double* wsum /*LDS [kLmWaves][32]*/, const LmCache& k) {
   const int et = (int)threadIdx.x;
 #ifdef LIODOM_LM_NOCACHE      // (debugging: every evaluation reads its triples from memory)
   const bool cached = false;
 #else
   const bool cached = et < kLmCtl;
 #endif
-  double acc[kAccN];
+  double acc[32];
 #pragma unroll
-  for (int i = 0; i < kAccN; i++) acc[i] = 0.0;
+  for (int i = 0; i < 32; i++) acc[i] = 0.0;
   {
     double Rm[12];
 #pragma unroll
@@ -127,52 +126,20 @@ __device__ __forceinline__ void lm_eval(const DevView& v, int s, int outer_it, i
       residual_accumulate(Rm, p, a, b, v.min_range, v.max_range, acc);
     }
   }
-  if (v.lm_lds_reduce) {
-    // Reduction through LDS, transposed: every evaluator stores its 29 partial sums as column et of
-    // red[29][kLmEvalThreads] (conflict-free 8-byte stores); then thread (v, r) = (t / 16, t % 16) sums
-    // the elements r, r + 16, r + 32, ... of row v (conflict-free loads, 28 adds), a 4-step DPP row
-    // sum finishes row v.  Fixed order -> deterministic, no atomics.
-    // (only the columns of threads that hold a block — with several workgroups per solve about half of them — rounded up
-    //  to whole 16-lane rows: the other threads' partial sums are zero and neither written nor read)
-    const int nb_here = c_hi - c_lo;
-    const int ncol = ((nb_here < kLmEvalThreads ? nb_here : kLmEvalThreads) + 15) & ~15;
-    if (et < ncol) {
-#pragma unroll
-      for (int i = 0; i < kAccN; i++) part[i * kLmEvalThreads + et] = acc[i];
-    }
-    __syncthreads();
-    const int r = threadIdx.x & 15;
-#pragma unroll
-    for (int vrow = threadIdx.x >> 4; vrow < ((kAccN + kLmThreads / 16 - 1) / (kLmThreads / 16)) * (kLmThreads / 16); vrow += kLmThreads / 16) {
-      double x = 0.0;
-      if (vrow < kAccN) {
-        const double* rowp = part + vrow * kLmEvalThreads + r;
-        const int nk = ncol >> 4;
-#pragma unroll 8
-        for (int kk = 0; kk < nk; kk++) x += rowp[kk * 16];
-      }
-      x = row_sum_f64(x);
-      if (vrow < kAccN && r == 0) acc_out[vrow] = x;
-    }
-    __syncthreads();
-    return;
-  }
-  // Large edge capacities (the matrix no longer fits beside the index list): DPP butterfly
-  // inside each 16-lane row, one partial per row into LDS, then a fixed-order sum of the partials.
-#pragma unroll
-  for (int i = 0; i < kAccN; i++) acc[i] = row_sum_f64(acc[i]);
-  const int row = threadIdx.x >> 4;
-  if ((threadIdx.x & 15) == 0) {
-#pragma unroll
-    for (int i = 0; i < kAccN; i++) part[row * kAccN + i] = acc[i];
+  const int wave = et >> 6;
+  if (c_hi - c_lo > wave * 64) {
+    const double x = wave_reduce_scatter32_f64(acc);
+    if ((et & 1) == 0) wsum[wave * 32 + ((et & 63) >> 1)] = x;
   }
   __syncthreads();
-  if (threadIdx.x < kAccN) {
-    double x = 0.0;
-    for (int w = 0; w < kLmThreads / 16; w++) x += part[w * kAccN + threadIdx.x];
-    acc_out[threadIdx.x] = x;
-  }
-  __syncthreads();
+}
+
+// Second half (any lane, behind lm_eval's barrier): the workgroup's sum of entry e (0..31) over the waves that held blocks, in wave order.
+__device__ __forceinline__ double lm_wave_total(const double* wsum, int nb_here, int e) {
+  const int nw = nb_here <= 0 ? 0 : ((nb_here + 63) >> 6 < kLmWaves ? (nb_here + 63) >> 6 : kLmWaves);
+  double x = 0.0;
+  for (int w = 0; w < nw; w++) x += wsum[w * 32 + e];
+  return x;
 }
 
 // Resets the hash slots occupied by the build that this scan searched (list used_cells[0 .. nup));
@@ -321,60 +288,59 @@ __device__ __forceinline__ void finalize_scan(const DevView& v, int s, StreamSta
 // that XCD's L2, where the L1-bypassing loads of the others find them.  The first exchange of a launch always takes the
 // memory-side transport and tells whether the later ones may go local.
 __device__ __forceinline__ unsigned int xcc_id() { return (unsigned int)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 0xFu; }   // HW_REG_XCC_ID[3:0]
-__device__ void lm_exchange(const DevView& v, int s, int g, int G, unsigned int epoch,
-                            const double* acc_local, double* acc_total, unsigned int* status, bool local, int* same_xcc /*LDS*/) {
+// Run by the controller's wave alone (lane 0 .. 63), behind lm_eval's barrier; x: this workgroup's total of entry lane >> 1 (lanes
+// 0 .. 57).  Leaves the totals in acc_total (lanes 0 .. 28; visible to the wave once it has passed a wave barrier) and returns
+// whether every workgroup ran on the same XCC (wave-uniform).
+__device__ bool lm_exchange(const DevView& v, int s, int g, int G, unsigned int epoch,
+                            double x, double* acc_total, unsigned int* status, bool local, int lane) {
   typedef __attribute__((address_space(1))) unsigned long long gu64;
   unsigned long long* base = v.lm_xch + ((size_t)s * 2 + (epoch & 1u)) * kLmGroupsMax * 64;
-  const int tid = threadIdx.x;
   INJECT_DELAY(16);
-  if (tid <= 2 * kAccN) {
+  if (lane <= 2 * kAccN) {
     unsigned long long half;
-    if (tid < 2 * kAccN) {
-      const unsigned long long bits = (unsigned long long)__double_as_longlong(acc_local[tid >> 1]);
-      half = (tid & 1) ? (bits >> 32) : (bits & 0xFFFFFFFFull);
+    if (lane < 2 * kAccN) {
+      const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
+      half = (lane & 1) ? (bits >> 32) : (bits & 0xFFFFFFFFull);
     } else {
       half = xcc_id();                                   // granule 58: where this workgroup runs
     }
     const unsigned long long word = ((unsigned long long)epoch << 32) | half;
-    if (local) __hip_atomic_store((gu64*)(base + g * 64 + tid), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // plain store: stays in the XCD's L2
-    else __hip_atomic_store((gu64*)(base + g * 64 + tid), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (local) __hip_atomic_store((gu64*)(base + g * 64 + lane), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // plain store: stays in the XCD's L2
+    else __hip_atomic_store((gu64*)(base + g * 64 + lane), word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (tid < 64) {
-    double tot = 0.0;
-    unsigned int spins = 0;
-    unsigned long long t0w = 0;
-    bool same = true;
-    while (true) {
-      bool ok = true;
-      tot = 0.0;
-      same = true;
-      if (tid <= kAccN) {
-        // all 2 G loads in flight at once (a loop over the runtime G waits for every pair: G round trips per poll)
-        unsigned long long lo[kLmGroupsMax], hi[kLmGroupsMax];
-        const int i0 = tid < kAccN ? 2 * tid : 2 * kAccN, i1 = tid < kAccN ? 2 * tid + 1 : 2 * kAccN;   // lane 29: the XCC ids
+  double tot = 0.0;
+  unsigned int spins = 0;
+  unsigned long long t0w = 0;
+  bool same = true;
+  while (true) {
+    bool ok = true;
+    tot = 0.0;
+    same = true;
+    if (lane <= kAccN) {
+      // all 2 G loads in flight at once (a loop over the runtime G waits for every pair: G round trips per poll)
+      unsigned long long lo[kLmGroupsMax], hi[kLmGroupsMax];
+      const int i0 = lane < kAccN ? 2 * lane : 2 * kAccN, i1 = lane < kAccN ? 2 * lane + 1 : 2 * kAccN;   // lane 29: the XCC ids
 #pragma unroll
-        for (int gg = 0; gg < kLmGroupsMax; gg++) {
-          const int gq = gg < G ? gg : 0;
-          lo[gg] = __hip_atomic_load((gu64*)(base + gq * 64 + i0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          hi[gg] = __hip_atomic_load((gu64*)(base + gq * 64 + i1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+      for (int gg = 0; gg < kLmGroupsMax; gg++) {
+        const int gq = gg < G ? gg : 0;
+        lo[gg] = __hip_atomic_load((gu64*)(base + gq * 64 + i0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        hi[gg] = __hip_atomic_load((gu64*)(base + gq * 64 + i1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
 #pragma unroll
-        for (int gg = 0; gg < kLmGroupsMax; gg++) {
-          if (gg < G) {
-            ok = ok && ((unsigned int)(lo[gg] >> 32) == epoch) && ((unsigned int)(hi[gg] >> 32) == epoch);
-            tot += __longlong_as_double((long long)((hi[gg] << 32) | (lo[gg] & 0xFFFFFFFFull)));
-            same = same && ((unsigned int)lo[gg] == (unsigned int)lo[0]);
-          }
+      for (int gg = 0; gg < kLmGroupsMax; gg++) {
+        if (gg < G) {
+          ok = ok && ((unsigned int)(lo[gg] >> 32) == epoch) && ((unsigned int)(hi[gg] >> 32) == epoch);
+          tot += __longlong_as_double((long long)((hi[gg] << 32) | (lo[gg] & 0xFFFFFFFFull)));
+          same = same && ((unsigned int)lo[gg] == (unsigned int)lo[0]);
         }
       }
-      if (__all(ok)) break;
-      if (++spins > 4000000u || __any(wait_expired(spins, t0w))) { if (tid == 0) atomicOr(status, LIODOM_STATUS_LM_SYNC_TIMEOUT); same = false; break; }
-      __builtin_amdgcn_s_sleep(1);
     }
-    if (tid < kAccN) acc_total[tid] = tot;
-    if (tid == kAccN) *same_xcc = same ? 1 : 0;
+    if (__all(ok)) break;
+    if (++spins > 4000000u || __any(wait_expired(spins, t0w))) { if (lane == 0) atomicOr(status, LIODOM_STATUS_LM_SYNC_TIMEOUT); same = false; break; }
+    __builtin_amdgcn_s_sleep(1);
   }
-  __syncthreads();
+  if (lane < kAccN) acc_total[lane] = tot;
+  return __builtin_amdgcn_readlane((int)same, kAccN) != 0;
 }
 
 // early_rebuild: the solved pose travels from the solving workgroup to the workgroups that append the new frame inside
@@ -475,7 +441,6 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
   const int g = is_solver ? bxl / gstride : G + (bxl < G * gstride ? bxl - (bxl / gstride + 1) : bxl - G);
   StreamState& st = v.state[s];
   __shared__ int sh_cnt[kMaxFrames + 1];
-  __shared__ int sh_same_xcc;
   // seq != 0: the scan's second kNN pass runs beside this launch ("Overlapped second kNN pass"): the first solve's launch says
   // that it has started (= the first pass has completed), the finalising one waits for the second pass where it needs it
   OV_STAMP(v, bxl == 0 && threadIdx.x == 0, outer_it == 0 ? 0 : 3);
@@ -490,7 +455,7 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
     rebuild_beside_solve(v, s, st, eb, outer_it, g - G, (int)gridDim.x - G, seq, sh_cnt, sh_slot);
     return;
   }
-  __shared__ double sh_loc[kAccN];
+  __shared__ double sh_wsum[kLmWaves][32];     // lm_eval: the per-wave sums of an evaluation
   __shared__ double sh_red[16][32];
   // State that earlier launches on THIS stream wrote (the start point: the previous scan's finalising solve, or this scan's first
   // solve; the previous pose and the frame count: the previous scan's finalising solve) is fetched now — in chain mode and beside an
@@ -514,8 +479,7 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
   // or correspondences — poses off by 1e-8; with 384 / 512 threads the first edition had always finished before this launch began.)
   __shared__ int sh_redo;
   if (threadIdx.x == 78) sh_redo = st.spec_redo[outer_it == 0 ? 1 : 0];
-  extern __shared__ __attribute__((aligned(16))) int sh_idx[];   // [edge_cap] compacted correspondence indices, then the reduction matrix
-  double* sh_part = reinterpret_cast<double*>(sh_idx + ((v.edge_cap + 3) & ~3));   // [kAccN][kLmEvalThreads]
+  extern __shared__ __attribute__((aligned(16))) int sh_idx[];   // [edge_cap] compacted correspondence indices
   const int tid = threadIdx.x;
   const bool prep = tid < kLmCtl;               // the other waves: compaction + register cache while the controller lane works
   // chain mode, first solve: nothing of the stream's state that the extraction writes (n_edges_buf) and nothing of the first pass's
@@ -577,10 +541,30 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
   __shared__ int sh_nmatch;
   __shared__ double sh_scale[8];
   const unsigned int epoch0 = ((unsigned int)(st.scan_counter + 1) << 6) | ((unsigned int)outer_it << 5);
-  unsigned int n_eval = 0;
-  bool xch_local = false;       // the G workgroups were seen on one XCD: exchanges through its L2 (lm_exchange)
+  unsigned int n_eval = 0;       // (counted by the controller's wave)
+  bool xch_local = false;       // the G workgroups were seen on one XCD: exchanges through its L2 (lm_exchange; the controller's wave)
   LmCache cache;
   int c_lo = 0, c_hi = 0;
+  int dbg_it = 0;
+  // One evaluation at `pose`: lm_eval by everybody (ends with a workgroup barrier), then the controller's wave alone forms the totals
+  // in sh_acc — with G > 1 through lm_exchange — and passes a wave barrier into the controller step.  The other waves go straight on to
+  // the barrier behind that step, the only one they need before they read its results: two workgroup barriers per trust-region step.
+  auto evaluate = [&](const double* pose) {
+    lm_eval(v, s, outer_it, eb, c_lo, c_hi, sh_idx, pose, &sh_wsum[0][0], cache);
+    if (tid >= kLmCtl) {
+      const int lane = tid - kLmCtl;
+      if (G > 1) {
+        const double x = lm_wave_total(&sh_wsum[0][0], c_hi - c_lo, lane >> 1);
+        DBG_STAMP(v, dbgb && dbg_it < 4, 2, 12 + dbg_it);
+        xch_local = lm_exchange(v, s, g, G, epoch0 | ++n_eval, x, sh_acc, &st.status, xch_local, lane);
+      } else {
+        if (lane < kAccN) sh_acc[lane] = lm_wave_total(&sh_wsum[0][0], c_hi - c_lo, lane);
+        ++n_eval;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+    }
+  };
   auto my_share = [&](int C) {                           // this workgroup's contiguous share of the compacted blocks
     const int chunk = (C + G - 1) / G;
     c_lo = g * chunk < C ? g * chunk : C;
@@ -638,14 +622,12 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
     __syncthreads();
     my_share(sh_C);
     lm_cache_load(v, s, outer_it, eb, c_lo, c_hi, sh_idx, cache);
-    if (G > 1) { lm_eval(v, s, outer_it, eb, c_lo, c_hi, sh_idx, sh_pose2[0], sh_part, sh_loc, cache); lm_exchange(v, s, g, G, epoch0 | ++n_eval, sh_loc, sh_acc, &st.status, xch_local, &sh_same_xcc); xch_local = sh_same_xcc != 0; }
-    else { lm_eval(v, s, outer_it, eb, c_lo, c_hi, sh_idx, sh_pose2[0], sh_part, sh_acc, cache); ++n_eval; }
+    evaluate(sh_pose2[0]);
   }
   DBG_STAMP(v, dbgb, 2, 2);
   // ---- trust-region loop.  Controller step on lane 0 of the last wave; beside it the other waves prepare the
   // evaluations (step 0: validity bytes -> index list, triples into registers) or reset the hash slots of the
   // build this scan searched (step 1 of the finalising solve) ----
-  int dbg_it = 0;
   int pi = 0, ci = -1, nmoved = 0;     // (controller lane) candidate / iterate buffer, moves of the iterate
   const unsigned int n_eval0 = n_eval;       // evaluations of this launch before the loop (lock-step batches: the one at the start point)
   const bool spec_ok = v.speculate != 0 && v.speculate != 5 && v.speculate != 7 && g == 0 && seq != 0u && outer_it == 0;      // (debugging: 4 / 5 only the first / only the finalising solve; 6 / 7 the same with the predictor forced wrong, as 2 forces both)
@@ -718,8 +700,7 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
       spec_moves = sh_nmoved;
     }
     const double* pose_c = sh_pose2[sh_pi];
-    if (G > 1) { lm_eval(v, s, outer_it, eb, c_lo, c_hi, sh_idx, pose_c, sh_part, sh_loc, cache); DBG_STAMP(v, dbgb && dbg_it < 4, 2, 12 + dbg_it); lm_exchange(v, s, g, G, epoch0 | ++n_eval, sh_loc, sh_acc, &st.status, xch_local, &sh_same_xcc); xch_local = sh_same_xcc != 0; }
-    else { lm_eval(v, s, outer_it, eb, c_lo, c_hi, sh_idx, pose_c, sh_part, sh_acc, cache); ++n_eval; }
+    evaluate(pose_c);
     DBG_STAMP(v, dbgb && dbg_it < 5, 2, 4 + 2 * dbg_it);
   }
   if (clr_pending) clear_hash_slots();                   // (the solve ended at its first step)

@@ -1061,8 +1061,8 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
                           (int)hash_build_lds_bytes()) != hipSuccess) {
     g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP);
   }
-  v.lm_lds_reduce = lm_lds_reduce_fits(v.edge_cap) ? 1 : 0;
-  if (lm_lds_bytes(v.edge_cap) + 8192 > 160 * 1024) { g_last_error = "liodom_create: edge capacity too large for the solve's LDS tile"; return fail(LIODOM_ERR_INVALID_ARG); }
+  // (the solve's dynamic LDS is its index list, up to ~36 800 edges; 16 KiB are left for its static LDS, 8.7 KiB at most today)
+  if (lm_lds_bytes(v.edge_cap) + 16384 > 160 * 1024) { g_last_error = "liodom_create: edge capacity too large for the solve's LDS tile"; return fail(LIODOM_ERR_INVALID_ARG); }
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lm_solve<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds_bytes(h->v.edge_cap)) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lm_solve<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds_bytes(h->v.edge_cap)) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lm_solve<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds_bytes(h->v.edge_cap)) != hipSuccess ||

@@ -209,7 +209,6 @@ struct DevView {
   int* win_base;            // [S][P+1] logical prefix (oldest first)
   int* win_slot;            // [S][P]  logical frame -> slot
   CellSlot* cells;          // [S][table_size]  {key, start, cnt}: one 16-B load per probe
-  int lm_lds_reduce;        // k_lm_solve reduces through the transposed LDS matrix (fits for edge_cap <= ~10 000)
   int use_imu;              // params.use_imu_ (laser_odometry.cc:152)
   double laser_to_base[12]; // laser_to_base_ (laser_odometry.cc:110-119), identity unless liodom_set_laser_to_base
   double* imu_q;            // [S][4] last IMU orientation [x y z w] (SharedData::last_IMU_ori_)

@@ -120,6 +120,49 @@ __device__ __forceinline__ double row_sum_f64(double x) {
   return x;
 }
 
+// Reduce-scatter of a per-lane accumulator of 32 doubles over the 64 lanes of a wave (every lane active).  Halving butterfly: at
+// each step a lane keeps half of its remaining entries and adds its partner's copy of that half.  Partners and the lane bit that
+// picks the kept half: lane ^ 32 (v_permlane32_swap, bit 5 keeps entries 16..31), lane ^ 16 (v_permlane16_swap, bit 4), then within
+// the 16-lane row r <-> 15 - r (row mirror, bit 3), r <-> 7 - r in each 8 lanes (half mirror, bit 2), r ^ 2 (bit 1); a last step
+// adds the two copies of lanes r and r ^ 1.  Lane-to-entry map: lanes 2e and 2e + 1 both return the wave sum of entry e = lane >> 1
+// (bit for bit: a + b == b + a).  31 + 1 FP64 adds; the pairing is fixed, so the result is deterministic.  a[] is consumed.
+// v_permlane32_swap(x, y) leaves (x of lanes 0-31, y of lanes 0-31) in its first result and (x of lanes 32-63, y of lanes 32-63)
+// in its second: their sum is a halving step with no select.  v_permlane16_swap does the same for odd / even 16-lane rows.
+__device__ __forceinline__ double fold_xor32_f64(double x, double y) {
+  const unsigned long long xb = (unsigned long long)__double_as_longlong(x), yb = (unsigned long long)__double_as_longlong(y);
+  const auto lo = __builtin_amdgcn_permlane32_swap((unsigned int)xb, (unsigned int)yb, false, false);
+  const auto hi = __builtin_amdgcn_permlane32_swap((unsigned int)(xb >> 32), (unsigned int)(yb >> 32), false, false);
+  const double a = __longlong_as_double((long long)(((unsigned long long)hi[0] << 32) | lo[0]));
+  const double b = __longlong_as_double((long long)(((unsigned long long)hi[1] << 32) | lo[1]));
+  return a + b;     // lanes 0-31: x + x of lane + 32; lanes 32-63: y of lane - 32 + y
+}
+__device__ __forceinline__ double fold_xor16_f64(double x, double y) {
+  const unsigned long long xb = (unsigned long long)__double_as_longlong(x), yb = (unsigned long long)__double_as_longlong(y);
+  const auto lo = __builtin_amdgcn_permlane16_swap((unsigned int)xb, (unsigned int)yb, false, false);
+  const auto hi = __builtin_amdgcn_permlane16_swap((unsigned int)(xb >> 32), (unsigned int)(yb >> 32), false, false);
+  const double a = __longlong_as_double((long long)(((unsigned long long)hi[0] << 32) | lo[0]));
+  const double b = __longlong_as_double((long long)(((unsigned long long)hi[1] << 32) | lo[1]));
+  return a + b;     // even rows: x + x of the next row; odd rows: y of the previous row + y
+}
+template <int CTRL>
+__device__ __forceinline__ double fold_dpp_f64(double x, double y, bool upper) {
+  // (the partner, which has the other `upper`, keeps what this lane gives)
+  return (upper ? y : x) + dpp_f64<CTRL>(upper ? x : y);
+}
+__device__ __forceinline__ double wave_reduce_scatter32_f64(double (&a)[32]) {
+  const int lane = (int)(threadIdx.x & 63);
+#pragma unroll
+  for (int j = 0; j < 16; j++) a[j] = fold_xor32_f64(a[j], a[j + 16]);
+#pragma unroll
+  for (int j = 0; j < 8; j++) a[j] = fold_xor16_f64(a[j], a[j + 8]);
+#pragma unroll
+  for (int j = 0; j < 4; j++) a[j] = fold_dpp_f64<DPP_MIRROR>(a[j], a[j + 4], (lane & 8) != 0);
+#pragma unroll
+  for (int j = 0; j < 2; j++) a[j] = fold_dpp_f64<DPP_HALF_MIRROR>(a[j], a[j + 2], (lane & 4) != 0);
+  a[0] = fold_dpp_f64<DPP_XOR2>(a[0], a[1], (lane & 2) != 0);
+  return a[0] + dpp_f64<DPP_XOR1>(a[0]);
+}
+
 // ---- scans ------------------------------------------------------------------------------
 // Inclusive prefix sum over the wave (64 lanes).
 __device__ __forceinline__ int wave_incl_scan_i32(int v) {
