@@ -924,8 +924,9 @@ def test_sixteen_lockstep_streams_match_single_stream(orc, synth):
 
 
 def test_sixteen_streams_headline_size_against_the_oracle(orc, synth):
-    """The code that produces the batched number — k_knn<128> + k_line_gate, the one-workgroup lock-step k_lm_solve,
-    k_hash_build — on a 16-stream handle at the headline size (64 x 1800, P = 20, 26 scans: the window fills and evicts),
+    """The code that produces the batched number — k_ring_split_lb, k_knn8 + k_line_gate, the one-workgroup lock-step k_lm_solve,
+    the incremental cell hash (k_hash_build every kHbPeriod-th scan, k_hash_append in between) — on a 16-stream handle at the
+    headline size (64 x 1800, P = 20, 26 scans: the window fills and evicts),
     checked against the oracle DIRECTLY, per stream: correspondences of both passes exactly equal to the oracle's loop
     (laser_odometry.cc:320-361) on that stream's own queries and local map, LM iteration counts and terminations equal to
     the oracle's run (laser_odometry.cc:201-218), pose within 1e-4 m / 1e-4 rad.  Stream 3 replays ragged scans."""
@@ -938,6 +939,10 @@ def test_sixteen_streams_headline_size_against_the_oracle(orc, synth):
     po, gb = mk(orc, H, W, 0, R, epr, P, S=S, debug=1, pose_log_capacity=K + 8)
     modes = gb.modes()
     assert modes["knn_instance"] == "128" and modes["line_gate_kernel"] == "1" and modes["hash_build"] == "lds"
+    assert modes["knn8"] == "1" and modes["hash_incr"] == "1" and modes["ring_split_lb"] == "1", modes
+    # (launch_extract takes k_ring_split_lb over the all-resident k_ring_split when the launch's 57 tiles x 16 streams exceed what
+    #  the latter may hold resident)
+    assert -(-N // 2048) * S > int(modes["ring_split_max_wgs"]) or modes["ring_split"] == "0", modes
     gb.alloc_resident(K)
     for s in range(S):
         for k in range(K):
