@@ -14,6 +14,8 @@ These shapes reach code that the 16 x 900 and 64 x 1800 batches never run:
   * scans of more than edge_cap / 2 edges: k_knn8's workgroups walk their second query block (the grid is half the blocks).
 Every test proves from the handle's modes, the GPU's own local maps, edge counts and counters that its path ran.  Run with -m gpu
 on an MI355X."""
+import collections
+import hashlib
 import os
 
 import numpy as np
@@ -102,77 +104,126 @@ def set_env(monkeypatch, env):
         monkeypatch.setenv(name, val)
 
 
-def lockstep_replay(orc, shape, data, env, want_modes, monkeypatch, check_oracle):
-    """Replays `data` (per data stream d: data[d][k]) on a handle of STREAMS[shape] streams under `env`, handle stream s replaying
-    data stream s % D, every step one process_resident launch over all streams, whose ring split must be SPLIT[shape] (split_kernel
-    on the handle's modes).  Per step: every stream's status is 0, streams with equal
-    data have bit-equal poses and equal match counts; with check_oracle, streams 0 .. D-1 against the oracle: edges bit-equal to
-    orc.extract, n_edges and map_points equal, both passes' valid flags and line-point indices exactly equal to the oracle's loop
-    (laser_odometry.cc:320-361) on the GPU's own queries and the local map the step searched, match counts, LM iterations and
-    terminations equal to orc.Odometer's, pose within 1e-4 m / 1e-4 rad.
-    Returns the records (_assert_batch_runs_equal's layout), cells[k, d] (cells of stream d's window after step k: what a rebuild
-    on step k bins), n_edges[k, d], the modes after the run (stream 0's hash_* counters) and the worst pose errors."""
-    H, W, lt, R, epr, P = SHAPES[shape]
-    N, S = H * W, STREAMS[shape]
-    D, K = len(data), len(data[0])
+Record = collections.namedtuple("Record", "pose n_edges map_points matches lm edges corr")
+Replay = collections.namedtuple("Replay", "out cells n_edges modes worst records")
+
+
+def digest(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def assert_records_equal(a, b, what):
+    """Two per-stream step records (Record) bit-identical field by field."""
+    for field in Record._fields:
+        assert getattr(a, field) == getattr(b, field), (what, field)
+
+
+def lockstep_replay(orc, dims, data, env, want_modes, want_split, monkeypatch, oracle=(), track=(), next_slot=False):
+    """Replays data[s] (scan k of handle stream s: data[s][k]) on a handle of len(data) streams of shape dims = (H, W, lidar_type,
+    R, epr, P) under `env`, every step one process_resident launch over all streams; with next_slot that launch also issues the
+    next step's extraction, as bench.py's batched leg does.  The handle's modes must hold want_modes and its ring split must be
+    want_split (split_kernel on the handle's modes).
+    Per step and stream: status 0, and a Record — pose bits, n_edges, map_points, match counts, LM iterations and terminations of
+    both passes, digests of get_edges and of both passes' correspondences; streams that replay the same sequence object have
+    equal records.  After the run every stream's pose log equals its steps' readbacks, scan_index k on step k.
+    Streams in `oracle` against the oracle: edges bit-equal to orc.extract, n_edges and map_points equal, both passes' valid flags
+    and line-point indices exactly equal to the oracle's loop (laser_odometry.cc:320-361) on the GPU's own queries and the local
+    map the step searched, match counts, LM iterations and terminations equal to orc.Odometer's, pose within 1e-4 m / 1e-4 rad.
+    Returns a Replay: out (per step: poses, match counts of every stream, both passes' correspondences of the streams in
+    `track` — _assert_batch_runs_equal's layout), cells[k, j] (cells of the window of stream track[j] after step k: what a
+    rebuild on step k bins), n_edges[k, j], the modes after the run (stream 0's hash_* counters), the worst pose errors against
+    the oracle and records[k][s]."""
+    H, W, lt, R, epr, P = dims
+    N, S, K = H * W, len(data), len(data[0])
+    track, oracle = list(track), list(oracle)
+    seen = sorted(set(track) | set(oracle))
     set_env(monkeypatch, env)
     po = orc.make_params(lidar_type=lt, scan_lines=H, scan_regions=R, edges_per_region=epr, prev_frames=P, knn_mode=1)
     g = la.Liodom(la.make_params(lidar_type=lt, scan_lines=H, scan_regions=R, edges_per_region=epr, prev_frames=P),
                   la.make_config(n_streams=S, max_points=N, max_width=W, debug_buffers=1, pose_log_capacity=K + 8))
     modes = g.modes()
     for key, val in want_modes.items():
-        assert modes[key] == val, (shape, env, key, modes)
-    assert split_kernel(modes, H, W, lt, S) == SPLIT[shape], (shape, env, modes)
+        assert modes[key] == val, (dims, S, env, key, modes)
+    assert split_kernel(modes, H, W, lt, S) == want_split, (dims, S, env, modes)
     g.alloc_resident(K)
     for s in range(S):
         for k in range(K):
-            g.upload_scan(s, k, data[s % D][k])
-    ods = [orc.Odometer(po) for _ in range(D)]
-    out = []
-    cells = np.zeros((K, D), np.int64)
-    n_edges = np.zeros((K, D), np.int64)
+            g.upload_scan(s, k, data[s][k])
+    first = {}                                          # streams replaying one sequence object: their first stream
+    for s in range(S):
+        first.setdefault(id(data[s]), s)
+    ods = {s: orc.Odometer(po) for s in oracle}
+    out, records, readback = [], [], []
+    cells = np.zeros((K, len(track)), np.int64)
+    n_edges = np.zeros((K, len(track)), np.int64)
     worst_t = worst_r = 0.0
-    maps = [g.local_map(d)[0] for d in range(D)]         # what the next step's kNN passes search, per checked stream
+    maps = {s: g.local_map(s)[0] for s in seen}         # what the next step's kNN passes search, per checked stream
     for k in range(K):
-        poses, infos = g.process_resident(k, N, H, W, readback=True)
+        poses, infos = g.process_resident(k, N, H, W, readback=True, next_slot=(k + 1 if next_slot and k + 1 < K else -1))
+        readback.append((poses.copy(), [bytes(i) for i in infos]))
+        recs, corr, edges = [], {}, {}
         for s in range(S):
-            what = (shape, env, "step", k, "stream", s)
-            assert infos[s].status == 0, (what, infos[s].status)
-            assert np.array_equal(poses[s].view(np.uint64), poses[s % D].view(np.uint64)), what      # equal data, equal bits
-            assert tuple(infos[s].matches) == tuple(infos[s % D].matches), what
-        corr = [[tuple(a.copy() for a in g.correspondences(it, stream=d)) for it in (0, 1)] for d in range(D)]
-        for d in range(D if check_oracle else 0):
-            what = (shape, env, "step", k, "stream", d)
-            ig = infos[d]
-            o = orc.extract(po, data[d][k], H, W)
-            assert_edges_equal(g.get_edges(d), o)
-            pose_o, info_o = ods[d].step(o["edges"])
+            what = (dims, S, env, "step", k, "stream", s)
+            ig = infos[s]
+            assert ig.status == 0, (what, ig.status)
+            c = [tuple(a.copy() for a in g.correspondences(it, stream=s)) for it in (0, 1)]
+            e = g.get_edges(s)
+            recs.append(Record(poses[s].view(np.uint64).tobytes(), ig.n_edges, ig.map_points, tuple(ig.matches),
+                               tuple((t.iterations, t.termination) for t in ig.lm),
+                               digest(e["edges"].view(np.uint32), e["ring"], e["idx_in_ring"], e["src"]),
+                               tuple(digest(*ci) for ci in c)))
+            assert_records_equal(recs[s], recs[first[id(data[s])]], what)      # equal data, equal bits
+            if s in seen:
+                corr[s], edges[s] = c, e
+        for s in oracle:
+            what = (dims, S, env, "step", k, "stream", s)
+            ig = infos[s]
+            o = orc.extract(po, data[s][k], H, W)
+            assert_edges_equal(edges[s], o)
+            pose_o, info_o = ods[s].step(o["edges"])
             assert ig.n_edges == info_o.n_edges, what
-            dt = np.linalg.norm(poses[d][4:] - pose_o[4:])
-            dr = rot_angle(poses[d][:4], pose_o[:4])
+            dt = np.linalg.norm(poses[s][4:] - pose_o[4:])
+            dr = rot_angle(poses[s][:4], pose_o[:4])
             worst_t, worst_r = max(worst_t, dt), max(worst_r, dr)
             assert dt <= POSE_TOL_T and dr <= POSE_TOL_R, (what, dt, dr)
             if k == 0:
                 continue
             assert ig.map_points == info_o.map_points, what
             for it in (0, 1):
-                vg, ag, bg = corr[d][it]
-                vk, ak, bk = orc.match_edges(po, maps[d], g.knn_queries(it, stream=d))
+                vg, ag, bg = corr[s][it]
+                vk, ak, bk = orc.match_edges(po, maps[s], g.knn_queries(it, stream=s))
                 assert np.array_equal(vk, vg) and np.array_equal(ak, ag) and np.array_equal(bk, bg), \
                     "%s pass %d: kNN / line gate differ from the oracle on identical inputs at edges %s" % (
                         what, it, np.nonzero((vk != vg) | (ak != ag) | (bk != bg))[0][:10])
                 assert ig.matches[it] == int(vk.sum()), (what, it)
                 assert ig.lm[it].iterations == info_o.lm[it].iterations, (what, it)
                 assert ig.lm[it].termination == info_o.lm[it].termination, (what, it)
-        maps = [g.local_map(d)[0] for d in range(D)]
-        for d in range(D):
-            cells[k, d] = cell_count(maps[d])
-            n_edges[k, d] = infos[d].n_edges
-        out.append((poses.copy(), [tuple(i.matches) for i in infos], corr))
+        maps = {s: g.local_map(s)[0] for s in seen}
+        for j, s in enumerate(track):
+            cells[k, j] = cell_count(maps[s])
+            n_edges[k, j] = infos[s].n_edges
+        out.append((poses.copy(), [tuple(i.matches) for i in infos], [corr[s] for s in track]))
+        records.append(recs)
     g.sync()
+    for s in range(S):
+        lp, li = g.pose_log(s, 0, K)
+        for k in range(K):
+            assert np.array_equal(lp[k].view(np.uint64), readback[k][0][s].view(np.uint64)), (dims, S, env, "pose log", k, s)
+            assert bytes(li[k]) == readback[k][1][s] and li[k].scan_index == k, (dims, S, env, "info log", k, s, li[k].scan_index)
     modes = g.modes()
     g.close()
-    return out, cells, n_edges, modes, (worst_t, worst_r)
+    return Replay(out, cells, n_edges, modes, (worst_t, worst_r), records)
+
+
+def replay_shape(orc, shape, data, env, want_modes, monkeypatch, check_oracle):
+    """lockstep_replay of `data` (per data stream d: data[d][k]) at SHAPES[shape] on STREAMS[shape] streams, handle stream s
+    replaying data stream s % D; streams 0 .. D-1 tracked and, with check_oracle, checked against the oracle."""
+    S, D = STREAMS[shape], len(data)
+    return lockstep_replay(orc, SHAPES[shape], [data[s % D] for s in range(S)], env, want_modes, SPLIT[shape], monkeypatch,
+                           oracle=range(D) if check_oracle else (), track=range(D))
 
 
 def report(name, cells, n_edges, cap):
@@ -200,7 +251,7 @@ def test_lockstep_batch_against_the_oracle(orc, synth, monkeypatch, shape):
             scans_of(synth, shape, 1002, K, noise_sigma=0.03 if shape == "vlp16" else 0.01)]
     want = {"knn8": "1", "hash_incr": "1", "hash_build": "lds", "line_gate_kernel": "1", "lm_groups": "1",
             "ring_split_lb": "1" if lt == 0 else "0", "table_size": str(device_table_size(H, R, epr, P))}
-    _, cells, n_edges, modes, (wt, wr) = lockstep_replay(orc, shape, data, {}, want, monkeypatch, check_oracle=True)
+    _, cells, n_edges, modes, (wt, wr), _ = replay_shape(orc, shape, data, {}, want, monkeypatch, check_oracle=True)
     report(shape, cells, n_edges, cap)
     assert wt < 1e-6 and wr < 1e-6, (wt, wr)
     # the paths ran: k_knn8's second query block; stream 0's table kinds as its counters tell; at Ouster one launch on both tables
@@ -234,7 +285,7 @@ def test_lockstep_cell_hash_table_kind_transitions(orc, synth, monkeypatch):
             scans_of(synth, shape, 1003, K, noise_sigma=0.03)]
     env = {"LIODOM_LDS_CELLS_MAX": str(limit)}
     want = {"knn8": "1", "hash_incr": "1", "hash_build": "lds", "table_size": str(device_table_size(H, R, epr, P))}
-    base, cells, n_edges, modes, (wt, wr) = lockstep_replay(orc, shape, data, env, want, monkeypatch, check_oracle=True)
+    base, cells, n_edges, modes, (wt, wr), _ = replay_shape(orc, shape, data, env, want, monkeypatch, check_oracle=True)
     report("vlp16, limit %d" % limit, cells, n_edges, cap)
     assert wt < 1e-6 and wr < 1e-6, (wt, wr)
     assert n_edges.max() > cap // 2, (n_edges.max(axis=0), cap)
@@ -255,7 +306,7 @@ def test_lockstep_cell_hash_table_kind_transitions(orc, synth, monkeypatch):
     for extra, want2 in (({"LIODOM_HASH_INCR": "0"}, {"knn8": "1", "hash_incr": "0", "hash_build": "lds"}),
                          ({"LIODOM_HASH_BUILD": "global"}, {"knn8": "1", "hash_incr": "0", "hash_build": "global"})):
         env2 = dict(env, **extra)
-        other, cells2, _, modes2, _ = lockstep_replay(orc, shape, data, env2, want2, monkeypatch, check_oracle=False)
+        other, cells2, _, modes2, _, _ = replay_shape(orc, shape, data, env2, want2, monkeypatch, check_oracle=False)
         _assert_batch_runs_equal(base, other, env2)
         assert np.array_equal(cells, cells2), env2
         # (a rebuild on every step: one LDS rebuild per step whose window fits the limit; the global build counts nothing)

@@ -923,63 +923,26 @@ def test_sixteen_lockstep_streams_match_single_stream(orc, synth):
         g1.close()
 
 
-def test_sixteen_streams_headline_size_against_the_oracle(orc, synth):
+def test_sixteen_streams_headline_size_against_the_oracle(orc, synth, monkeypatch):
     """The code that produces the batched number — k_ring_split_lb, k_knn8 + k_line_gate, the one-workgroup lock-step k_lm_solve,
     the incremental cell hash (k_hash_build every kHbPeriod-th scan, k_hash_append in between) — on a 16-stream handle at the
-    headline size (64 x 1800, P = 20, 26 scans: the window fills and evicts),
-    checked against the oracle DIRECTLY, per stream: correspondences of both passes exactly equal to the oracle's loop
-    (laser_odometry.cc:320-361) on that stream's own queries and local map, LM iteration counts and terminations equal to
-    the oracle's run (laser_odometry.cc:201-218), pose within 1e-4 m / 1e-4 rad.  Stream 3 replays ragged scans."""
+    headline size (64 x 1800, P = 20, 26 scans: the window fills and evicts), the next step's extraction overlapped,
+    checked against the oracle DIRECTLY, per stream (test_gpu_lockstep_shapes.lockstep_replay): correspondences of both passes
+    exactly equal to the oracle's loop (laser_odometry.cc:320-361) on that stream's own queries and local map, LM iteration counts
+    and terminations equal to the oracle's run (laser_odometry.cc:201-218), pose within 1e-4 m / 1e-4 rad.  Stream 3 replays
+    ragged scans."""
+    from test_gpu_lockstep_shapes import lockstep_replay
     H, W, R, epr, P, S, K = 64, 1800, 8, 10, 20, 16, 26
-    N = H * W
     D = 4                                     # distinct data streams; handle stream s replays data stream s % D
     cfg = synth.make_cfg(H, W, 0)
     data = [[synth.scan(cfg, 20 + d, k)[0] for k in range(K)] for d in range(D)]
     data[3] = [synth.ragged(x, H, W, 0, seed=100 + k) for k, x in enumerate(data[3])]
-    po, gb = mk(orc, H, W, 0, R, epr, P, S=S, debug=1, pose_log_capacity=K + 8)
-    modes = gb.modes()
-    assert modes["knn_instance"] == "128" and modes["line_gate_kernel"] == "1" and modes["hash_build"] == "lds"
-    assert modes["knn8"] == "1" and modes["hash_incr"] == "1" and modes["ring_split_lb"] == "1", modes
+    want = {"knn_instance": "128", "line_gate_kernel": "1", "hash_build": "lds", "knn8": "1", "hash_incr": "1", "ring_split_lb": "1"}
     # (launch_extract takes k_ring_split_lb over the all-resident k_ring_split when the launch's 57 tiles x 16 streams exceed what
     #  the latter may hold resident)
-    assert -(-N // 2048) * S > int(modes["ring_split_max_wgs"]) or modes["ring_split"] == "0", modes
-    gb.alloc_resident(K)
-    for s in range(S):
-        for k in range(K):
-            gb.upload_scan(s, k, data[s % D][k])
-    ods = [orc.Odometer(po) for _ in range(D)]
-    worst_t = worst_r = 0.0
-    for k in range(K):
-        maps = [gb.local_map(d)[0] for d in range(D)]          # what this step's kNN passes search, per checked stream
-        poses, infos = gb.process_resident(k, N, H, W, readback=True, next_slot=(k + 1 if k + 1 < K else -1))
-        for s in range(S):
-            assert infos[s].status == 0, (k, s)
-            assert np.array_equal(poses[s].view(np.uint64), poses[s % D].view(np.uint64)), (k, s)      # equal data, equal bits
-            assert tuple(infos[s].matches) == tuple(infos[s % D].matches), (k, s)
-        for d in range(D):
-            o = orc.extract(po, data[d][k], H, W)
-            pose_o, info_o = ods[d].step(o["edges"])
-            ig = infos[d]
-            assert ig.n_edges == info_o.n_edges, (k, d)
-            dt = np.linalg.norm(poses[d][4:] - pose_o[4:])
-            dr = rot_angle(poses[d][:4], pose_o[:4])
-            worst_t, worst_r = max(worst_t, dt), max(worst_r, dr)
-            assert dt <= POSE_TOL_T and dr <= POSE_TOL_R, "scan %d stream %d: dt=%g dr=%g" % (k, d, dt, dr)
-            if k == 0:
-                continue
-            assert ig.map_points == info_o.map_points, (k, d)
-            for it in (0, 1):
-                vg, ag, bg = gb.correspondences(it, stream=d)
-                qg = gb.knn_queries(it, stream=d)
-                vk, ak, bk = orc.match_edges(po, maps[d], qg)
-                assert np.array_equal(vk, vg) and np.array_equal(ak, ag) and np.array_equal(bk, bg), \
-                    "scan %d stream %d pass %d: kNN / line gate differ from the oracle on identical inputs at edges %s" % (
-                        k, d, it, np.nonzero((vk != vg) | (ak != ag) | (bk != bg))[0][:10])
-                assert ig.matches[it] == int(vk.sum()), (k, d, it)
-                assert ig.lm[it].iterations == info_o.lm[it].iterations, (k, d, it)
-                assert ig.lm[it].termination == info_o.lm[it].termination, (k, d, it)
-    gb.close()
-    assert worst_t < 1e-6 and worst_r < 1e-6
+    r = lockstep_replay(orc, (H, W, 0, R, epr, P), [data[s % D] for s in range(S)], {}, want, "k_ring_split_lb", monkeypatch,
+                        oracle=range(D), next_slot=True)
+    assert r.worst[0] < 1e-6 and r.worst[1] < 1e-6, r.worst
 
 
 @pytest.mark.parametrize("shape,scans", [("hdl64", 1200), ("vlp16", 1200), ("ouster128", 300)])
