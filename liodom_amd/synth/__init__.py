@@ -17,6 +17,7 @@ class SynthCfg(C.Structure):
         ("height", C.c_int32), ("width", C.c_int32), ("lidar_type", C.c_int32), ("world_seed", C.c_uint32),
         ("noise_sigma", C.c_double), ("max_cast_range", C.c_double),
         ("yaw_rate_deg", C.c_double), ("speed", C.c_double),
+        ("sweep", C.c_int32), ("pad_", C.c_int32),
     ]
 
 
@@ -45,11 +46,13 @@ def lib():
 
 
 def make_cfg(height, width, lidar_type=0, world_seed=7, noise_sigma=0.01, max_cast_range=120.0,
-             yaw_rate_deg=0.5, speed=0.1):
+             yaw_rate_deg=0.5, speed=0.1, sweep=0):
+    """sweep=1: each column is fired from the pose the sensor has at that point of the sweep (see synth.cc, synth_scan)."""
     c = SynthCfg()
     c.height, c.width, c.lidar_type, c.world_seed = height, width, lidar_type, world_seed
     c.noise_sigma, c.max_cast_range = noise_sigma, max_cast_range
     c.yaw_rate_deg, c.speed = yaw_rate_deg, speed
+    c.sweep = int(sweep)
     return c
 
 

@@ -161,6 +161,38 @@ inline double ray_box(const double o[3], const double d[3], const Box& b) {
   return tmin > 0.0 ? tmin : -1.0;
 }
 
+// Sweep interpolation of the deskew model ("Finding: deskewing by the predicted motion ..."; tests/deskewref.py): the
+// motion D = T_{k-1}^-1 T_k split into a rotation by theta in [0, pi] about a unit axis and a translation; D^s = (R(s theta), s t).
+struct SweepMotion { double axis[3]; double theta; double t[3]; };
+
+void sweep_motion(const Pose& A, const Pose& B, SweepMotion& m) {
+  double R[9];   // A.R^T B.R
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) R[r * 3 + c] = A.R[0 * 3 + r] * B.R[0 * 3 + c] + A.R[1 * 3 + r] * B.R[1 * 3 + c] + A.R[2 * 3 + r] * B.R[2 * 3 + c];
+  const double d[3] = {B.t[0] - A.t[0], B.t[1] - A.t[1], B.t[2] - A.t[2]};
+  for (int r = 0; r < 3; ++r) m.t[r] = A.R[0 * 3 + r] * d[0] + A.R[1 * 3 + r] * d[1] + A.R[2 * 3 + r] * d[2];
+  // rotation vector of R: axis * theta, from the skew part and the trace (theta < pi on any trajectory used here)
+  const double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+  const double sn = 0.5 * std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+  const double cs = 0.5 * (R[0] + R[4] + R[8] - 1.0);
+  m.theta = std::atan2(sn, cs);
+  if (sn > 0.0) { for (int i = 0; i < 3; ++i) m.axis[i] = v[i] / (2.0 * sn); }
+  else { m.axis[0] = 0.0; m.axis[1] = 0.0; m.axis[2] = 1.0; m.theta = 0.0; }
+}
+
+// A * D^s (Rodrigues)
+void sweep_pose(const Pose& A, const SweepMotion& m, double s, Pose& out) {
+  const double phi = s * m.theta, sp = std::sin(phi), cp1 = 1.0 - std::cos(phi);
+  const double x = m.axis[0], y = m.axis[1], z = m.axis[2];
+  const double Rs[9] = {1.0 - cp1 * (y * y + z * z), -sp * z + cp1 * x * y, sp * y + cp1 * x * z,
+                        sp * z + cp1 * x * y, 1.0 - cp1 * (x * x + z * z), -sp * x + cp1 * y * z,
+                        -sp * y + cp1 * x * z, sp * x + cp1 * y * z, 1.0 - cp1 * (x * x + y * y)};
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) out.R[r * 3 + c] = A.R[r * 3 + 0] * Rs[0 * 3 + c] + A.R[r * 3 + 1] * Rs[1 * 3 + c] + A.R[r * 3 + 2] * Rs[2 * 3 + c];
+    out.t[r] = A.t[r] + s * (A.R[r * 3 + 0] * m.t[0] + A.R[r * 3 + 1] * m.t[1] + A.R[r * 3 + 2] * m.t[2]);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -174,10 +206,16 @@ struct synth_cfg_t {
   double max_cast_range; // rays longer than this return NaN
   double yaw_rate_deg;   // yaw per scan (deg); default 0.5 (see header)
   double speed;          // forward motion per scan (m); SURVEY.md §8(d): 0.1
+  int32_t sweep;         // 0 (default): every column is cast from the scan's pose; 1: rolling sweep (see synth_scan)
+  int32_t pad_;
 };
 
 // Fills xyzi (height*width*4 floats) for scan `scan` of stream `stream`, and the ground-truth
 // pose gt_pose = [qx qy qz qw tx ty tz] (world <- sensor).  Returns 0.
+// sweep = 1: column c is fired at s_c = c / W of the sweep from the pose T_{k-1} D^{s_c}, D = T_{k-1}^-1 T_k (the generator's own
+// trajectory, interpolated as the deskew model does), and its points are expressed in that firing frame; the azimuth of column c
+// in its own frame is 2 pi c / W, so the deskew start azimuth is 0 and the spin direction +1.  gt_pose stays T_k, the end of the
+// sweep.
 int synth_scan(const synth_cfg_t* cfg, int stream, int scan, float* xyzi, double* gt_pose) {
   if (!cfg || !xyzi || cfg->height <= 0 || cfg->width <= 0) return -1;
   const double radius = cfg->yaw_rate_deg != 0.0 ? cfg->speed / (cfg->yaw_rate_deg * M_PI / 180.0) : -1.0;
@@ -187,12 +225,23 @@ int synth_scan(const synth_cfg_t* cfg, int stream, int scan, float* xyzi, double
   ring_elevations(H, el);
   Pose P; double q[4];
   trajectory(stream, scan, cfg->yaw_rate_deg, cfg->speed, P, q);
+  const bool sweep = cfg->sweep != 0;
+  Pose P0;               // sweep: T_{k-1}, the pose at the start of the sweep
+  SweepMotion mo{};
+  double reach = 0.0;    // sweep: how far the sensor moves inside the sweep
+  if (sweep) {
+    double q0[4];
+    trajectory(stream, scan - 1, cfg->yaw_rate_deg, cfg->speed, P0, q0);
+    sweep_motion(P0, P, mo);
+    reach = std::sqrt(mo.t[0] * mo.t[0] + mo.t[1] * mo.t[1] + mo.t[2] * mo.t[2]);
+  }
   if (gt_pose) {
     gt_pose[0] = q[0]; gt_pose[1] = q[1]; gt_pose[2] = q[2]; gt_pose[3] = q[3];
     gt_pose[4] = P.t[0]; gt_pose[5] = P.t[1]; gt_pose[6] = P.t[2];
   }
   // Azimuth buckets (1 deg, world frame) of candidate boxes, widened by the box's angular
-  // radius plus 3 deg to absorb roll/pitch.
+  // radius plus 3 deg to absorb roll/pitch; with sweep, the box is also widened by how far the ray origins move in the sweep
+  // (the ray directions are exact per column).
   const int NB = 360;
   std::vector<std::vector<int>> bucket(NB);
   const double maxr = cfg->max_cast_range;
@@ -201,6 +250,7 @@ int synth_scan(const synth_cfg_t* cfg, int stream, int scan, float* xyzi, double
     double cx = 0.5 * (b.lo[0] + b.hi[0]) - P.t[0], cy = 0.5 * (b.lo[1] + b.hi[1]) - P.t[1];
     double rad = 0.5 * std::sqrt((b.hi[0] - b.lo[0]) * (b.hi[0] - b.lo[0]) +
                                  (b.hi[1] - b.lo[1]) * (b.hi[1] - b.lo[1]));
+    if (sweep) rad += reach;
     double dist = std::sqrt(cx * cx + cy * cy);
     if (dist - rad > maxr) continue;
     if (dist <= rad + 0.5) { for (int k = 0; k < NB; ++k) bucket[k].push_back((int)bi); continue; }
@@ -223,22 +273,25 @@ int synth_scan(const synth_cfg_t* cfg, int stream, int scan, float* xyzi, double
   for (int c = 0; c < W; ++c) {
     double phi = 2.0 * M_PI * c / W;
     double cphi = std::cos(phi), sphi = std::sin(phi);
+    Pose Pc;
+    if (sweep) sweep_pose(P0, mo, (double)c / W, Pc);
+    const Pose& F = sweep ? Pc : P;   // the firing pose of this column
     for (int r = 0; r < H; ++r) {
       double th = el[r] * M_PI / 180.0;
       double ds[3] = {std::cos(th) * cphi, std::cos(th) * sphi, std::sin(th)};
-      double dw[3] = {P.R[0] * ds[0] + P.R[1] * ds[1] + P.R[2] * ds[2],
-                      P.R[3] * ds[0] + P.R[4] * ds[1] + P.R[5] * ds[2],
-                      P.R[6] * ds[0] + P.R[7] * ds[1] + P.R[8] * ds[2]};
+      double dw[3] = {F.R[0] * ds[0] + F.R[1] * ds[1] + F.R[2] * ds[2],
+                      F.R[3] * ds[0] + F.R[4] * ds[1] + F.R[5] * ds[2],
+                      F.R[6] * ds[0] + F.R[7] * ds[1] + F.R[8] * ds[2]};
       double best = std::numeric_limits<double>::infinity();
       if (dw[2] < -1e-9) {  // ground plane z = -1.7
-        double tg = (-1.7 - P.t[2]) / dw[2];
+        double tg = (-1.7 - F.t[2]) / dw[2];
         if (tg > 0) best = tg;
       }
       double azw = std::atan2(dw[1], dw[0]) * 180.0 / M_PI;
       int bk = (((int)std::floor(azw)) % NB + NB) % NB;
       const std::vector<int>& cand = bucket[bk];
       for (size_t i = 0; i < cand.size(); ++i) {
-        double t = ray_box(P.t, dw, g_world.boxes[cand[i]]);
+        double t = ray_box(F.t, dw, g_world.boxes[cand[i]]);
         if (t > 0 && t < best) best = t;
       }
       size_t idx = (cfg->lidar_type == 0) ? ((size_t)c * H + r) : ((size_t)r * W + c);
