@@ -306,6 +306,37 @@ int liodom_wait_pose_covariance(liodom_handle_t* h, int stream, int scan_index, 
 /* Resets the odometry state (pose, window, map) of every stream; capacities are kept. */
 int liodom_reset(liodom_handle_t* h);
 
+/* ---- streams with a life of their own (no counterpart in the reference: one LaserOdometer object is one stream there) ----
+ * The streams of a handle step in lock-step, but each one's odometry state is its own.  The four calls below reset one stream,
+ * take its state out of a handle and put a state in, while the other streams keep theirs.  None of them is on the per-scan path:
+ * each takes both sides of the handle, waits for all its HIP streams (the other streams stall for the duration of the call) and
+ * returns LIODOM_ERR_BUSY while edge tickets of liodom_extract_edges_device are outstanding.  An extraction already issued ahead
+ * by the pipelined replay (next_slot) stays valid for every stream.
+ *
+ *   liodom_reset_stream          what liodom_reset does, for one stream (no counterpart in the reference): the stream's next
+ *       scan is its first — window initialisation, no solve, scan_index 0, LIODOM_COV_NO_SOLVE on its covariance record; its
+ *       sticky status bits are cleared.  The handle's pipeline (edge buffers, slots, sequence numbers) is left alone, and the
+ *       call never switches the handle to safe mode: after LIODOM_STATUS_PIPE_TIMEOUT the recovery remains liodom_reset.
+ *   liodom_stream_state_size     upper bound, in bytes, of a state blob of this handle (no counterpart in the reference).
+ *   liodom_export_stream_state   the stream's logical state as one blob (no counterpart in the reference): header (magic
+ *       "LIODOMST", version, size, and the parameters that must match on import: local_map_size, mapping, filter_local_map,
+ *       use_imu, pose_rotation_mode, lm_apply_step_on_ftol), poses, counters and flags, the window frames oldest first as
+ *       liodom_get_window orders them, with mapping the received map, with use_imu the last IMU orientation; layout in
+ *       DESIGN.md §3.  Derived structures (cell hash, filtered local map) and tuning state do not travel, so a blob fits any
+ *       handle with the same parameters, whatever its n_streams and code paths.  An attached liodom_map_t is not part of it.
+ *       cap too small: LIODOM_ERR_CAPACITY with *bytes = the size needed.
+ *   liodom_import_stream_state   puts a blob's state into a stream (no counterpart in the reference) and rebuilds what the
+ *       stream's next scan searches.  The stream's scan_index, pose log and covariance log carry on from the blob's scan count.
+ *       Bad magic / version / size or other parameters: LIODOM_ERR_INVALID_ARG; a frame larger than the handle's edge capacity
+ *       or a map larger than recv_capacity: LIODOM_ERR_CAPACITY; the handle is untouched in both cases.  Importing the state of
+ *       a stream that never ran equals liodom_reset_stream.
+ * A continuation after export / import is bit-identical to the uninterrupted run on a handle of the same shape
+ * (tests/test_gpu_stream_state.py). */
+int liodom_reset_stream(liodom_handle_t* h, int stream);
+int liodom_stream_state_size(liodom_handle_t* h, int64_t* max_bytes);
+int liodom_export_stream_state(liodom_handle_t* h, int stream, void* blob, int64_t cap, int64_t* bytes);
+int liodom_import_stream_state(liodom_handle_t* h, int stream, const void* blob, int64_t bytes);
+
 /* ---- inspection (tests, parity checks) ---- */
 /* Edges of the last scan of a stream as left on the device by process_scan / process_resident. */
 int liodom_get_edges(liodom_handle_t* h, int stream, float* edges_xyzi, int32_t* edge_ring,

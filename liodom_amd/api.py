@@ -12,7 +12,7 @@ _HASH = _LIB + ".srchash"
 _BUILD_INFO = {"rebuilt": None, "source_hash": None}
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kernels.h", "kernels_extract.h", "kernels_sync.h",
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
-                                                  "kernels_filter.h", "kernels_cov.h", "liodom_math.h", "wave_ops.h",
+                                                  "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -154,8 +154,63 @@ class EdgeTicket(C.Structure):
     _fields_ = [("seq", C.c_uint32), ("slot", C.c_int32), ("stream", C.c_int32), ("reserved", C.c_int32)]
 
 
+ERR_INVALID_ARG = -1
+ERR_CAPACITY = -3
 ERR_BUSY = -6
 ERR_NEEDS_SYNC = -7
+
+
+# ---- stream-state blob (liodom_export_stream_state; layout in csrc/kernels_state.h and DESIGN.md §3) ----
+STATE_MAGIC = b"LIODOMST"
+STATE_VERSION = 1
+STATE_HEADER_BYTES = 64
+STATE_RECORD_BYTES = 416
+_STATE_FINGERPRINT = ("local_map_size", "mapping", "filter_local_map", "use_imu", "pose_rotation_mode", "lm_apply_step_on_ftol")
+
+
+def parse_stream_state(blob):
+    """A stream-state blob as a dict of NumPy arrays and scalars (pure Python: no library, no GPU).  Keys: version, total_bytes,
+    the six fingerprint parameters, odom / prev_odom / final_odom (3 x 4), param_q, param_t, initialized, append_raw, frame_count,
+    n_frames, scan_counter, status, has_imu, imu_q, frame_counts (n_frames,), frames (list of [count, 4] float32 arrays, oldest
+    first), window (the frames back to back: what liodom_get_window returns), received_map ([n_recv, 4]).  Raises ValueError on a
+    bad magic, version or size."""
+    b = bytes(blob)
+    if len(b) < STATE_HEADER_BYTES + STATE_RECORD_BYTES:
+        raise ValueError("stream-state blob truncated (%d bytes)" % len(b))
+    if b[:8] != STATE_MAGIC:
+        raise ValueError("not a stream-state blob (bad magic)")
+    version, header_bytes = np.frombuffer(b, "<u4", 2, 8)
+    total = int(np.frombuffer(b, "<u8", 1, 16)[0])
+    if version != STATE_VERSION or header_bytes != STATE_HEADER_BYTES:
+        raise ValueError("stream-state blob of version %d (this code reads %d)" % (version, STATE_VERSION))
+    if total != len(b):
+        raise ValueError("stream-state blob says %d bytes, has %d" % (total, len(b)))
+    out = dict(version=int(version), total_bytes=total)
+    out.update(zip(_STATE_FINGERPRINT, (int(x) for x in np.frombuffer(b, "<u4", 6, 24))))
+    d = np.frombuffer(b, "<f8", 43, STATE_HEADER_BYTES)
+    out.update(odom=d[0:12].reshape(3, 4).copy(), prev_odom=d[12:24].reshape(3, 4).copy(), final_odom=d[24:36].reshape(3, 4).copy(),
+               param_q=d[36:40].copy(), param_t=d[40:43].copy())
+    i = np.frombuffer(b, "<i4", 10, STATE_HEADER_BYTES + 344)
+    out.update(initialized=int(i[0]), append_raw=int(i[1]), frame_count=int(i[2]), n_frames=int(i[3]), scan_counter=int(i[4]),
+               status=int(np.uint32(i[5])), has_imu=int(i[8]))
+    n_points, n_recv = int(i[6]), int(i[7])
+    out["imu_q"] = np.frombuffer(b, "<f8", 4, STATE_HEADER_BYTES + 384).copy()
+    P = out["local_map_size"]
+    off = STATE_HEADER_BYTES + STATE_RECORD_BYTES
+    n_counts = (P + 3) // 4 * 4
+    pts_off = off + 4 * n_counts
+    if out["n_frames"] < 0 or out["n_frames"] > P or n_points < 0 or n_recv < 0 or total != pts_off + 16 * (n_points + n_recv):
+        raise ValueError("stream-state blob: sizes do not add up")
+    counts = np.frombuffer(b, "<i4", n_counts, off)[:out["n_frames"]].copy()
+    if (counts < 0).any() or int(counts.sum()) != n_points:
+        raise ValueError("stream-state blob: frame counts do not add up")
+    pts = np.frombuffer(b, "<f4", 4 * (n_points + n_recv), pts_off).reshape(-1, 4)
+    out["frame_counts"] = counts
+    out["window"] = pts[:n_points].copy()
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(int)
+    out["frames"] = [out["window"][starts[j]:starts[j + 1]] for j in range(out["n_frames"])]
+    out["received_map"] = pts[n_points:].copy()
+    return out
 
 
 class KernelStat(C.Structure):
@@ -216,6 +271,14 @@ def load():
     L.liodom_wait_pose_covariance.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PoseCov)]
     L.liodom_reset.restype = C.c_int
     L.liodom_reset.argtypes = [vp]
+    L.liodom_reset_stream.restype = C.c_int
+    L.liodom_reset_stream.argtypes = [vp, C.c_int]
+    L.liodom_stream_state_size.restype = C.c_int
+    L.liodom_stream_state_size.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.liodom_export_stream_state.restype = C.c_int
+    L.liodom_export_stream_state.argtypes = [vp, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.liodom_import_stream_state.restype = C.c_int
+    L.liodom_import_stream_state.argtypes = [vp, C.c_int, C.c_void_p, C.c_int64]
     L.liodom_get_edges.restype = C.c_int
     L.liodom_get_edges.argtypes = [vp, C.c_int, fp, ip, ip, ip, C.c_int, ip]
     L.liodom_get_window.restype = C.c_int
@@ -316,6 +379,7 @@ EXPORTED_SYMBOLS = [
     "liodom_scan_buffer", "liodom_extract_edges_device", "liodom_wait_edges", "liodom_odometry_step_device",
     "liodom_odometry_submit_device", "liodom_odometry_collect",
     "liodom_get_pose_covariance_log", "liodom_wait_pose_covariance",
+    "liodom_reset_stream", "liodom_stream_state_size", "liodom_export_stream_state", "liodom_import_stream_state",
 ]
 
 
@@ -565,6 +629,30 @@ class Liodom:
 
     def reset(self):
         self._check(self.L.liodom_reset(self.h))
+
+    # --- streams with a life of their own ---
+    def reset_stream(self, stream):
+        """liodom_reset for one stream: its next scan is its first; the other streams and the pipeline keep what they have."""
+        self._check(self.L.liodom_reset_stream(self.h, int(stream)))
+
+    def stream_state_size(self):
+        n = C.c_int64()
+        self._check(self.L.liodom_stream_state_size(self.h, C.byref(n)))
+        return n.value
+
+    def export_stream_state(self, stream):
+        """The stream's odometry state as bytes (liodom_export_stream_state); parse_stream_state reads it."""
+        cap = self.stream_state_size()
+        buf = (C.c_ubyte * cap)()
+        n = C.c_int64()
+        self._check(self.L.liodom_export_stream_state(self.h, int(stream), buf, cap, C.byref(n)))
+        return bytes(memoryview(buf)[:n.value])
+
+    def import_stream_state(self, stream, blob):
+        """Puts an exported state into `stream` (liodom_import_stream_state): any handle with the same local_map_size, mapping,
+        filter_local_map, use_imu, pose_rotation_mode and lm_apply_step_on_ftol will do, whatever its n_streams."""
+        b = bytes(blob)
+        self._check(self.L.liodom_import_stream_state(self.h, int(stream), b, len(b)))
 
     def pose_log(self, stream, first, count):
         poses = np.zeros((count, 7))

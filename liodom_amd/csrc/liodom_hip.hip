@@ -141,6 +141,8 @@ struct liodom_handle {
   HostOut* host_out = nullptr;       // host-mapped pinned result records, one per stream
   HostCov* cov_host = nullptr;       // pose_covariance = 1: host-mapped covariance records, two per stream (DevView::cov_host)
   std::vector<int> scans_enqueued;   // per stream: scans launched so far (expected HostOut.seq)
+  unsigned char* state_stage = nullptr;       // stream-state blob staging (liodom_export_stream_state / liodom_import_stream_state): device side,
+  unsigned char* state_stage_host = nullptr;  // page-locked host side; both allocated by the first export or import
   std::vector<void*> allocs;
   // profiling
   std::atomic<bool> profiling{false};   // read without a lock by SideLocks / extract_queue, written under both mutexes
@@ -1144,6 +1146,7 @@ void liodom_destroy(liodom_handle_t* h) {
   if (h->host_edges_meta) hipHostFree(h->host_edges_meta);
   if (h->host_edges_hdr) hipHostFree(h->host_edges_hdr);
   if (h->pin_ring) hipHostFree(h->pin_ring);
+  if (h->state_stage_host) hipHostFree(h->state_stage_host);
   for (int b = 0; b < kEdgePipeBufs; b++) { if (h->ev_pin[b]) hipEventDestroy(h->ev_pin[b]); }
   for (auto& e : h->ev_pool) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   if (h->pose_event) hipEventDestroy(h->pose_event);
@@ -1160,6 +1163,191 @@ int liodom_reset(liodom_handle_t* h) {
   if (rc) return rc;
   SideLocks lk(h, true, true);
   return reset_state(h);
+}
+
+// ---- streams with a life of their own: per-stream reset, export and import of the odometry state (kernels_state.h) ----
+// None of these calls is on the per-scan path; each takes both sides, refuses while edge tickets are outstanding, and waits for
+// every HIP stream of the handle (a pending chain-mode repair included) before it touches anything.
+static size_t state_max_bytes(const liodom_handle* h) {
+  return state_blob_bytes(h->P, (long long)h->P * h->v.edge_cap, h->v.recv_cap);
+}
+static int state_quiesce(liodom_handle* h) {
+  int rc = tickets_idle(h);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream_x));
+  HIP_TRY(sync_odometry(h));
+  if (h->stream_k) HIP_TRY(hipStreamSynchronize(h->stream_k));
+  if (h->stream_c && !h->stream_c_shared) HIP_TRY(hipStreamSynchronize(h->stream_c));
+  return LIODOM_OK;
+}
+static int ensure_state_stage(liodom_handle* h) {
+  if (h->state_stage) return LIODOM_OK;
+  void* hp = nullptr;
+  HIP_TRY(hipHostMalloc(&hp, state_max_bytes(h), hipHostMallocDefault));
+  h->state_stage_host = static_cast<unsigned char*>(hp);
+  void* dp = nullptr;
+  HIP_TRY(hipMalloc(&dp, state_max_bytes(h)));
+  h->allocs.push_back(dp);
+  h->state_stage = static_cast<unsigned char*>(dp);
+  return LIODOM_OK;
+}
+static void state_fingerprint(const liodom_handle* h, StateBlobHeader* hd) {
+  hd->local_map_size = (uint32_t)h->P; hd->mapping = h->params.mapping ? 1u : 0u; hd->filter_local_map = h->params.filter_local_map ? 1u : 0u;
+  hd->use_imu = h->params.use_imu ? 1u : 0u; hd->pose_rotation_mode = (uint32_t)h->v.rotation_mode; hd->lm_apply_step_on_ftol = h->v.apply_on_ftol ? 1u : 0u;
+}
+// Everything of stream `stream` but its edge buffers becomes what `blob` (device staging; null: a stream that never ran) says, and
+// the structure its next scan searches is rebuilt from the window for the variant this handle runs.  Streams are idle (state_quiesce).
+// Left alone: the handle-wide pipeline state (pf_slot, parity, edge buffers, eb_seq / eb_reader, ext_seq / odo_seq, pipe_flags):
+// an extraction issued ahead stays valid for every stream.
+static int install_stream_state(liodom_handle* h, int stream, const unsigned char* blob, int n_frames, int scan_counter) {
+  const DevView& v = h->v;
+  const size_t S = (size_t)h->S, s = (size_t)stream;
+  const int map_blocks = cdiv(v.map_cap, 256);
+  hipLaunchKernelGGL(k_stream_clear, dim3(64), dim3(kStateThreads), 0, h->stream, v, stream);
+  hipLaunchKernelGGL(k_state_unpack, dim3(std::max(1, cdiv(v.map_cap, kStateThreads))), dim3(kStateThreads), 0, h->stream, v, stream, blob);
+  // the stream's exchange granules carry tags derived from its frame and scan counts, which start over or jump here
+  HIP_TRY(hipMemsetAsync(v.lm_xch + s * 2 * kLmGroupsMax * 64, 0, sizeof(unsigned long long) * 2 * kLmGroupsMax * 64, h->stream));
+  HIP_TRY(hipMemsetAsync(v.pose_xch + s * 64, 0, sizeof(unsigned long long) * 64, h->stream));
+  if (v.pred_xch) HIP_TRY(hipMemsetAsync(v.pred_xch + s * kOvReplicas * 512, 0, sizeof(unsigned long long) * kOvReplicas * 512, h->stream));
+  if (v.cov_raw) HIP_TRY(hipMemsetAsync(v.cov_raw + s, 0, sizeof(PoseCovRaw), h->stream));
+  if (S == 1) {
+    // one-stream handles: the overlapped pass and chain mode start as after liodom_create — the first scans run every launch on the
+    // odometry stream (an uninitialised stream publishes no pose an overlapped pass could wait for; the prediction granules of an
+    // imported stream are written by its first scan here); their counters start over with the device's
+    HIP_TRY(hipMemsetAsync(v.knn_done0, 0, sizeof(unsigned int) * (S + 64), h->stream));
+    h->ov_warm = 0; h->ov_prev = false; h->chain_prev = false; h->chain_count = 0; h->chain_fix_pending = false; h->verdict_scan = -1;
+  }
+  if (n_frames > 0) {
+    if (h->lds_hash_build) {
+      hipLaunchKernelGGL(k_hash_build, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
+    } else {
+      // (early_rebuild: the three kernels fill the table of parity frame_count & 1, the one the next scan searches; the other one
+      //  and both overflow lists are empty)
+      hipLaunchKernelGGL(k_window_insert, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream, -1);
+      hipLaunchKernelGGL(k_hash_alloc, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_hash_scatter, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+    }
+    if (v.filter_local_map) {     // VoxelGrid(0.4) of a full window (every kernel exits otherwise)
+      hipLaunchKernelGGL(k_voxel_bbox, dim3(1), dim3(1024), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_insert, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_alloc, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_scatter, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_centroid, dim3(cdiv(v.map_cap, 8), 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_filt_insert, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_filt_alloc, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_filt_scatter, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  std::memset(h->host_out + 2 * s, 0, sizeof(HostOut) * 2);
+  if (h->cov_host) std::memset(h->cov_host + 2 * s, 0, sizeof(HostCov) * 2);
+  h->scans_enqueued[s] = scan_counter;
+  h->hb_since[s] = -1;      // (hash_incr: the stream's next step rebuilds from the whole window)
+  return LIODOM_OK;
+}
+
+int liodom_reset_stream(liodom_handle_t* h, int stream) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if ((rc = check_usable(h))) return rc;
+  SideLocks lk(h, true, true);
+  if ((rc = state_quiesce(h))) return rc;
+  return install_stream_state(h, stream, nullptr, 0, 0);
+}
+
+int liodom_stream_state_size(liodom_handle_t* h, int64_t* max_bytes) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if (!max_bytes) return LIODOM_ERR_INVALID_ARG;
+  *max_bytes = (int64_t)state_max_bytes(h);
+  return LIODOM_OK;
+}
+
+int liodom_export_stream_state(liodom_handle_t* h, int stream, void* blob, int64_t cap, int64_t* bytes) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if (!bytes || cap < 0 || (cap > 0 && !blob)) return LIODOM_ERR_INVALID_ARG;
+  SideLocks lk(h, true, true);
+  if ((rc = state_quiesce(h))) return rc;
+  if ((rc = ensure_state_stage(h))) return rc;
+  const DevView& v = h->v;
+  // one kernel gathers record, frame counts, frames (oldest first) and the received map into the staging buffer; the record and the
+  // counts come over first (they say how large the blob is), then the points in ONE copy of the blob's real size — not of the
+  // buffer's upper bound, and not one copy per frame
+  hipLaunchKernelGGL(k_state_pack, dim3(std::max(1, cdiv(v.map_cap, kStateThreads))), dim3(kStateThreads), 0, h->stream, v, stream, h->state_stage);
+  HIP_TRY(hipGetLastError());
+  const size_t prefix = state_points_offset(h->P);
+  HIP_TRY(hipMemcpyAsync(h->state_stage_host, h->state_stage, prefix, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  StateBlobRecord rec;
+  std::memcpy(&rec, h->state_stage_host + kStateHeaderBytes, sizeof(rec));
+  if (rec.n_points < 0 || rec.n_points > (long long)h->P * v.edge_cap || rec.n_recv < 0 || rec.n_recv > v.recv_cap) {
+    g_last_error = "liodom_export_stream_state: inconsistent stream state"; return LIODOM_ERR_HIP;
+  }
+  const size_t need = state_blob_bytes(h->P, rec.n_points, rec.n_recv);
+  *bytes = (int64_t)need;
+  if ((int64_t)need > cap) { g_last_error = "liodom_export_stream_state: blob buffer too small"; return LIODOM_ERR_CAPACITY; }
+  if (need > prefix) {
+    HIP_TRY(hipMemcpyAsync(h->state_stage_host + prefix, h->state_stage + prefix, need - prefix, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  StateBlobHeader hd;
+  std::memset(&hd, 0, sizeof(hd));
+  std::memcpy(hd.magic, "LIODOMST", 8);
+  hd.version = kStateBlobVersion; hd.header_bytes = (uint32_t)kStateHeaderBytes; hd.total_bytes = (uint64_t)need;
+  state_fingerprint(h, &hd);
+  std::memcpy(blob, &hd, sizeof(hd));
+  std::memcpy(static_cast<unsigned char*>(blob) + kStateHeaderBytes, h->state_stage_host + kStateHeaderBytes, need - (size_t)kStateHeaderBytes);
+  return LIODOM_OK;
+}
+
+int liodom_import_stream_state(liodom_handle_t* h, int stream, const void* blob, int64_t bytes) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if ((rc = check_usable(h))) return rc;
+  if (!blob) return LIODOM_ERR_INVALID_ARG;
+  SideLocks lk(h, true, true);
+  if ((rc = state_quiesce(h))) return rc;
+  // every rejection comes before the handle is touched
+  const int P = h->P;
+  const unsigned char* b = static_cast<const unsigned char*>(blob);
+  if (bytes < (int64_t)state_points_offset(P)) { g_last_error = "liodom_import_stream_state: blob truncated"; return LIODOM_ERR_INVALID_ARG; }
+  StateBlobHeader hd, mine;
+  std::memcpy(&hd, b, sizeof(hd));
+  if (std::memcmp(hd.magic, "LIODOMST", 8) != 0 || hd.version != kStateBlobVersion || hd.header_bytes != (uint32_t)kStateHeaderBytes ||
+      hd.total_bytes != (uint64_t)bytes) {
+    g_last_error = "liodom_import_stream_state: not a stream-state blob of this version and size"; return LIODOM_ERR_INVALID_ARG;
+  }
+  std::memset(&mine, 0, sizeof(mine));
+  state_fingerprint(h, &mine);
+  if (hd.local_map_size != mine.local_map_size || hd.mapping != mine.mapping || hd.filter_local_map != mine.filter_local_map ||
+      hd.use_imu != mine.use_imu || hd.pose_rotation_mode != mine.pose_rotation_mode || hd.lm_apply_step_on_ftol != mine.lm_apply_step_on_ftol) {
+    g_last_error = "liodom_import_stream_state: the blob comes from a handle with other parameters (local_map_size, mapping, filter_local_map, "
+                   "use_imu, pose_rotation_mode, lm_apply_step_on_ftol must match)";
+    return LIODOM_ERR_INVALID_ARG;
+  }
+  StateBlobRecord rec;
+  std::memcpy(&rec, b + kStateHeaderBytes, sizeof(rec));
+  const int nf_want = rec.frame_count < P ? rec.frame_count : P;
+  if (rec.frame_count < 0 || rec.n_frames != nf_want || rec.scan_counter != rec.frame_count || rec.n_points < 0 || rec.n_recv < 0 ||
+      (rec.n_recv > 0 && !h->v.mapping) || (rec.initialized != 0 && rec.initialized != 1) || (rec.append_raw != 0 && rec.append_raw != 1) ||
+      (uint64_t)state_blob_bytes(P, rec.n_points, rec.n_recv) != hd.total_bytes) {
+    g_last_error = "liodom_import_stream_state: inconsistent state record"; return LIODOM_ERR_INVALID_ARG;
+  }
+  const int32_t* cnt = reinterpret_cast<const int32_t*>(b + kStateCountsOffset);
+  long long sum = 0;
+  for (int j = 0; j < state_counts_bytes(P) / 4; j++) {
+    if (cnt[j] < 0 || (j >= rec.n_frames && cnt[j] != 0)) { g_last_error = "liodom_import_stream_state: bad frame count"; return LIODOM_ERR_INVALID_ARG; }
+    if (cnt[j] > h->v.edge_cap) { g_last_error = "liodom_import_stream_state: a frame is larger than the handle's edge capacity"; return LIODOM_ERR_CAPACITY; }
+    sum += cnt[j];
+  }
+  if (sum != rec.n_points) { g_last_error = "liodom_import_stream_state: frame counts do not add up"; return LIODOM_ERR_INVALID_ARG; }
+  if (rec.n_recv > h->v.recv_cap) { g_last_error = "liodom_import_stream_state: received map larger than recv_capacity"; return LIODOM_ERR_CAPACITY; }
+  if ((rc = ensure_state_stage(h))) return rc;
+  std::memcpy(h->state_stage_host, b, (size_t)bytes);
+  HIP_TRY(hipMemcpyAsync(h->state_stage, h->state_stage_host, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
+  return install_stream_state(h, stream, h->state_stage, rec.n_frames, rec.scan_counter);
 }
 
 static int copy_edges_out(liodom_handle_t* h, int stream, int eb, hipStream_t q, float* edges_xyzi, int32_t* edge_ring,

@@ -22,6 +22,8 @@
 //   k_voxel_* / k_filt_*  A7 filter_local_map: VoxelGrid(0.4) of the full window (:286-292)
 //   k_imu_override    A8     use_imu: roll / pitch of the prediction from the IMU (:152-183)
 //   k_pose_cov               (pose_covariance = 1) covariance + eigen-decomposition of the finalising solve's H, one wave per stream
+//   k_state_pack / k_state_unpack / k_stream_clear   a stream's odometry state as one blob (liodom_export_stream_state /
+//                            liodom_import_stream_state / liodom_reset_stream; kernels_state.h): never on the per-scan path
 //   (liodom_map.h)    A12-A14 the mapping node's Map: updateMap / getLocalMap / getMap
 //
 // All FP on the parity-critical paths is compiled with -ffp-contract=off.
@@ -393,5 +395,6 @@ __device__ __forceinline__ void inject_delay(unsigned int site) {
 #include "kernels_rebuild.h"
 #include "kernels_filter.h"
 #include "kernels_cov.h"
+#include "kernels_state.h"
 
 }  // namespace liodom_dev

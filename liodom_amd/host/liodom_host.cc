@@ -167,6 +167,18 @@ Engine::Engine(const Params& p, int device, int max_points, int max_width, int p
   edge_cap_ = p.scan_lines_ * p.scan_regions_ * (p.edges_per_region_ + 1) + 64;
 }
 Engine::~Engine() { liodom_destroy(h_); }
+void Engine::resetStream(int stream) { check(liodom_reset_stream(h_, stream), "liodom_reset_stream"); }
+std::vector<uint8_t> Engine::saveState(int stream) {
+  int64_t cap = 0, n = 0;
+  check(liodom_stream_state_size(h_, &cap), "liodom_stream_state_size");
+  std::vector<uint8_t> blob((size_t)cap);
+  check(liodom_export_stream_state(h_, stream, blob.data(), cap, &n), "liodom_export_stream_state");
+  blob.resize((size_t)n);
+  return blob;
+}
+void Engine::loadState(const std::vector<uint8_t>& blob, int stream) {
+  check(liodom_import_stream_state(h_, stream, blob.data(), (int64_t)blob.size()), "liodom_import_stream_state");
+}
 
 FeatureExtractor::FeatureExtractor(std::shared_ptr<Engine> e)
     : eng_(std::move(e)), params(Params::getInstance()), stats(Stats::getInstance()) {}
@@ -319,6 +331,36 @@ OdometryMsg LaserOdometer::publishOdom(double stamp, const Pose& pose) {
   prev_odom_ = cur;                                // the reference's prev_odom_ (:149) is the pose of the previous scan here
   prev_stamp_ = stamp;                             // :266
   return msg;
+}
+// Host trailer behind the engine's blob: magic, prev_odom_ [12], prev_stamp_, published_ / init_ / last_scan_.
+namespace {
+struct HostTrailer { char magic[8]; double prev_odom[12]; double prev_stamp; int32_t published, init, last_scan, pad; };
+}
+std::vector<uint8_t> LaserOdometer::saveState() {
+  std::vector<uint8_t> out = eng_->saveState(0);
+  HostTrailer t;
+  std::memset(&t, 0, sizeof(t));
+  std::memcpy(t.magic, "LIODOMHS", 8);
+  for (int i = 0; i < 12; i++) t.prev_odom[i] = prev_odom_[(size_t)i];
+  t.prev_stamp = prev_stamp_; t.published = published_ ? 1 : 0; t.init = init_ ? 1 : 0; t.last_scan = last_scan_;
+  const uint8_t* p = reinterpret_cast<const uint8_t*>(&t);
+  out.insert(out.end(), p, p + sizeof(t));
+  return out;
+}
+void LaserOdometer::loadState(const std::vector<uint8_t>& state) {
+  HostTrailer t;
+  if (state.size() < sizeof(t)) throw std::runtime_error("LaserOdometer::loadState: state too short");
+  std::memcpy(&t, state.data() + state.size() - sizeof(t), sizeof(t));
+  if (std::memcmp(t.magic, "LIODOMHS", 8) != 0) throw std::runtime_error("LaserOdometer::loadState: not a state written by LaserOdometer::saveState");
+  eng_->loadState(std::vector<uint8_t>(state.begin(), state.end() - (std::ptrdiff_t)sizeof(t)), 0);
+  for (int i = 0; i < 12; i++) prev_odom_[(size_t)i] = t.prev_odom[i];
+  prev_stamp_ = t.prev_stamp; published_ = t.published != 0; init_ = t.init != 0;
+  last_scan_ = -1;      // (the covariance record of the scan before the checkpoint stayed with the engine that solved it)
+}
+void LaserOdometer::reset() {
+  eng_->resetStream(0);
+  prev_odom_ = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
+  prev_stamp_ = 0.0; published_ = false; init_ = false; last_scan_ = -1;
 }
 void LaserOdometer::attachMapper(Map* map, int cells_xy, int cells_z) {
   check(liodom_attach_mapper(eng_->handle(), 0, map ? map->handle() : nullptr, cells_xy, cells_z), "liodom_attach_mapper");

@@ -129,6 +129,12 @@ class Engine {
   int edge_capacity() const { return edge_cap_; }
   int rotation_mode() const { return rotation_mode_; }
   bool covariance() const { return covariance_; }
+  // Streams with a life of their own (liodom_reset_stream / liodom_export_stream_state / liodom_import_stream_state; no
+  // counterpart in the reference).  resetStream: the stream's next scan is its first.  saveState: the stream's odometry state as
+  // one blob (layout: DESIGN.md §3).  loadState: puts such a blob — of any engine with the same parameters — into the stream.
+  void resetStream(int stream = 0);
+  std::vector<uint8_t> saveState(int stream = 0);
+  void loadState(const std::vector<uint8_t>& blob, int stream = 0);
  private:
   liodom_handle_t* h_ = nullptr;
   bool covariance_ = false;
@@ -223,6 +229,11 @@ class LaserOdometer {
   // The worker loop of the odometer thread (laser_odometry.cc:100-272): pop features, process, publish.
   // `published` (optional) receives every message in order.
   void operator()(std::atomic<bool>& running, std::vector<OdometryMsg>* published = nullptr, std::vector<Pose>* poses = nullptr);
+  // Checkpoint of this odometer: Engine::saveState's blob followed by what publishOdom keeps on the host (previous published pose
+  // and stamp), so that the ~odom / ~twist numbers of a resumed run carry on exactly.  loadState takes it back; reset starts over.
+  std::vector<uint8_t> saveState();
+  void loadState(const std::vector<uint8_t>& state);
+  void reset();
   LocalMapManager lmap_manager;
  private:
   std::shared_ptr<Engine> eng_;

@@ -11,6 +11,9 @@
 // side on the same handle (src/liodom_node.cc:89-91) and hand edge clouds over through the queue — the clouds stay on the
 // device (tickets; handoff=host restores host clouds).  poll_us= sets the worker loops' sleep (2000 as the reference; 0 = yield);
 // the run prints its scans/s.
+// save_state=FILE save_at=K writes the odometer's state (LaserOdometer::saveState) after scan K and goes on; load_state=FILE
+// first=K+1 starts from such a file at scan K+1: the result files of the two runs, one behind the other, are those of one run
+// (last=K stops after scan K).  Fused per-scan path only (not with threads=true).
 #include <algorithm>
 #include <cstdio>
 #include <dirent.h>
@@ -87,6 +90,43 @@ int main(int argc, char** argv) {
     };
     bool threads = false, host_handoff = false;
     int poll_us = 2000;
+    std::string save_state, load_state;
+    long save_at = -1, first = 0, last = (long)clouds.size() - 1;
+    for (const std::string& a : kv) {
+      if (a.rfind("save_state=", 0) == 0) save_state = a.substr(11);
+      if (a.rfind("load_state=", 0) == 0) load_state = a.substr(11);
+      if (a.rfind("save_at=", 0) == 0) save_at = std::stol(a.substr(8));
+      if (a.rfind("first=", 0) == 0) first = std::stol(a.substr(6));
+      if (a.rfind("last=", 0) == 0) last = std::min(last, std::stol(a.substr(5)));
+    }
+    if ((!save_state.empty() || !load_state.empty()) && mapper) { std::fprintf(stderr, "liodom_replay: save_state / load_state do not carry an attached map\n"); return 2; }
+    {
+      // option combinations that would silently do something else than asked
+      bool want_threads = false, has_first = false, has_last = false;
+      for (const std::string& a : kv) {
+        if (a == "threads=true" || a == "threads=1") want_threads = true;
+        if (a.rfind("first=", 0) == 0) has_first = true;
+        if (a.rfind("last=", 0) == 0) has_last = true;
+      }
+      const char* bad = nullptr;
+      if (want_threads && (!save_state.empty() || !load_state.empty() || save_at >= 0 || has_first || has_last))
+        bad = "save_state / load_state / save_at / first / last work on the fused per-scan path only, not with threads=true";
+      else if (save_state.empty() != (save_at < 0)) bad = "save_state=FILE and save_at=K go together";
+      else if (save_at >= (long)clouds.size()) bad = "save_at names a scan behind the last one";
+      else if (has_first && load_state.empty()) bad = "first=K needs load_state=FILE (the state after scan K - 1)";
+      else if (!load_state.empty() && !has_first) bad = "load_state=FILE needs first=K, the scan the state continues with";
+      else if (first < 0 || first > last + 1) bad = "first / last out of range";
+      else if (save_at >= 0 && (save_at < first || save_at > last)) bad = "save_at lies outside first .. last: the state would never be written";
+      if (bad) { std::fprintf(stderr, "liodom_replay: %s\n", bad); return 2; }
+    }
+    if (!load_state.empty()) {
+      std::ifstream f(load_state, std::ios::binary | std::ios::ate);
+      if (!f) { std::fprintf(stderr, "liodom_replay: cannot read %s\n", load_state.c_str()); return 1; }
+      std::vector<uint8_t> st((size_t)f.tellg());
+      f.seekg(0);
+      f.read(reinterpret_cast<char*>(st.data()), (std::streamsize)st.size());
+      odometer.loadState(st);
+    }
     for (const std::string& a : kv) {
       if (a == "threads=true" || a == "threads=1") threads = true;
       if (a == "handoff=host") host_handoff = true;
@@ -128,7 +168,7 @@ int main(int argc, char** argv) {
                   msgs.size(), secs, (double)msgs.size() / secs, host_handoff ? "host" : "device", poll_us);
       if (msgs.size() != clouds.size()) { std::fprintf(stderr, "liodom_replay: %zu of %zu scans processed\n", msgs.size(), clouds.size()); return 1; }
     }
-    for (size_t i = 0; i < clouds.size() && !threads; i++) {
+    for (size_t i = (size_t)std::max(0l, first); (long)i <= last && !threads; i++) {
       liodom_step_info_t info;
       liodom::Pose p = odometer.processScan(clouds[i], 0.1 * (double)i, &info);
       const liodom::OdometryMsg msg = odometer.publishOdom(0.1 * (double)i, p);      // ~odom / ~twist numbers
@@ -140,6 +180,12 @@ int main(int argc, char** argv) {
       odom_log << '\n';
       write_cov(msg);
       if (i % 50 == 0) std::printf("scan %zu: %d edges, %d matches, t = %.3f %.3f %.3f\n", i, info.n_edges, info.matches[1], p.t[0], p.t[1], p.t[2]);
+      if ((long)i == save_at && !save_state.empty()) {
+        const std::vector<uint8_t> st = odometer.saveState();
+        std::ofstream f(save_state, std::ios::binary);
+        f.write(reinterpret_cast<const char*>(st.data()), (std::streamsize)st.size());
+        std::printf("state after scan %zu: %zu bytes -> %s\n", i, st.size(), save_state.c_str());
+      }
     }
     liodom::Stats::getInstance()->writeResults(out);
     if (mapper) {
