@@ -839,6 +839,9 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   v.map_cap = v.edge_cap * h->P + v.recv_cap;
   int ts = 1024;
   while (ts < 2 * (v.map_cap + (v.early_rebuild ? 8 * v.edge_cap : 0))) ts <<= 1;    // (early rebuild: cells that only the padding touches)
+  // k_hash_build publishes its LDS table into slots [0, kLdsSlots) of the stream's table (keys, occupancy bits, cell_cap), however
+  // small the window: a lock-step handle with fewer than 2048 window points wrote into the next stream's table and past the last one
+  if (h->lds_hash_build && ts < kLdsSlots) ts = kLdsSlots;
   v.table_size = ts;
   v.pose_log_cap = std::max(1, config->pose_log_capacity);
   v.debug = config->debug_buffers & 1;
