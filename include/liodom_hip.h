@@ -264,6 +264,24 @@ int liodom_process_resident(liodom_handle_t* h, int slot, int64_t n, int height,
  * then name that slot. */
 int liodom_process_resident_pipelined(liodom_handle_t* h, int slot, int next_slot, int64_t n, int height,
                                       int width, double* poses_out, liodom_step_info_t* infos_out);
+/* liodom_process_resident_pipelined for some of the streams: the streams in streams[0 .. n_active) — strictly ascending indices
+ * in [0, n_streams) — advance by one scan, every other stream sits the step out and keeps its state to the bit.  Stream s reads
+ * its scan from resident slot `slot` at its own place (as liodom_upload_scan(h, s, slot, ...) wrote it); n, height and width are
+ * per step, not per stream.  The step is ONE launch sequence over n_active rows, whatever the list looks like, and each listed
+ * stream's result is bit-identical to the same stream fed the same scans by full steps.  poses_out (n_active * 7 doubles) and
+ * infos_out (n_active records) are in list order; both NULL: the step is enqueued only (pose log).  The per-stream getters
+ * (liodom_get_edges, liodom_get_correspondences, ...) return a stream's own latest scan, however many steps it has sat out.
+ * next_slot >= 0 issues the extraction of that slot ahead for next_streams[0 .. n_next) (NULL: the same list as this step); the
+ * next call should name that slot and that list — if it names anything else the extraction is issued again for what it names,
+ * results never depend on the hint.  (A hint that names a stream which then sits out overwrites that stream's scratch edges in
+ * the pipeline buffer, i.e. what liodom_get_edges shows for it, nothing else.)
+ * A list that is not strictly ascending or leaves [0, n_streams), n_active < 0 or n_active > n_streams: LIODOM_ERR_INVALID_ARG,
+ * nothing enqueued.  n_active == 0: LIODOM_OK, no stream advances (the extraction ahead is still issued).  The full list
+ * 0 .. n_streams-1 (with a full or no list ahead) IS liodom_process_resident_pipelined.  liodom_get_modes: subset_steps counts
+ * the steps that ran over a list. */
+int liodom_process_resident_subset(liodom_handle_t* h, int slot, const int32_t* streams, int n_active,
+                                   int next_slot, const int32_t* next_streams, int n_next,
+                                   int64_t n, int height, int width, double* poses_out, liodom_step_info_t* infos_out);
 /* The consumer loop of the pipelined replay, in C: resident slots first_slot .. first_slot + count - 1 in order, every
  * scan exactly as liodom_process_resident_pipelined (the extraction of scan k+1 is issued beside the odometry of scan k)
  * and every pose read back, in order — like the LaserOdometer thread that publishes ~odom per scan

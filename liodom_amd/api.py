@@ -261,6 +261,8 @@ def load():
     L.liodom_replay_resident.restype = C.c_int
     L.liodom_replay_resident.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, dp, C.POINTER(StepInfo)]
     L.liodom_process_resident_pipelined.argtypes = [vp, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, dp, C.POINTER(StepInfo)]
+    L.liodom_process_resident_subset.restype = C.c_int
+    L.liodom_process_resident_subset.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, ip, C.c_int, C.c_int64, C.c_int, C.c_int, dp, C.POINTER(StepInfo)]
     L.liodom_sync.restype = C.c_int
     L.liodom_sync.argtypes = [vp]
     L.liodom_get_pose_log.restype = C.c_int
@@ -369,7 +371,7 @@ def host_lib():
 EXPORTED_SYMBOLS = [
     "liodom_params_default", "liodom_config_default", "liodom_create", "liodom_destroy", "liodom_last_error",
     "liodom_extract_edges", "liodom_odometry_step", "liodom_process_scan", "liodom_set_received_map",
-    "liodom_alloc_resident", "liodom_upload_scan", "liodom_process_resident", "liodom_process_resident_pipelined", "liodom_replay_resident", "liodom_sync", "liodom_get_pose_log",
+    "liodom_alloc_resident", "liodom_upload_scan", "liodom_process_resident", "liodom_process_resident_pipelined", "liodom_process_resident_subset", "liodom_replay_resident", "liodom_sync", "liodom_get_pose_log",
     "liodom_reset", "liodom_get_edges", "liodom_get_window", "liodom_get_local_map", "liodom_get_correspondences", "liodom_get_curvature", "liodom_get_knn_queries",
     "liodom_set_profiling", "liodom_get_kernel_stats", "liodom_reset_kernel_stats", "liodom_device_info",
     "liodom_device_count", "liodom_device_pci_bus_id", "liodom_get_modes", "liodom_replay_host", "liodom_pin_host_buffer", "liodom_unpin_host_buffer",
@@ -587,6 +589,23 @@ class Liodom:
         self._check(self.L.liodom_process_resident_pipelined(self.h, slot, next_slot, n, height, width, None, None))
         return None, None
 
+    def process_resident_subset(self, slot, streams, n, height, width, readback=True, next_slot=-1, next_streams=None):
+        """One lock-step step for the streams in `streams` only (strictly ascending stream indices; liodom_process_resident_subset):
+        every other stream sits the step out, untouched.  Stream s reads resident slot `slot` at its own place (upload_scan(s, slot, ...)).
+        Returns (poses[len(streams), 7], infos) in list order, or (None, None) without readback or for an empty list.
+        next_slot >= 0: also issue that slot's extraction ahead for next_streams (None: the same list)."""
+        ls = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        m = int(ls.shape[0])
+        nx = None if next_streams is None else np.ascontiguousarray(next_streams, dtype=np.int32).reshape(-1)
+        nxp, nxn = (None, 0) if nx is None else (_ip(nx), int(nx.shape[0]))
+        if readback and m > 0:
+            poses = np.zeros((m, 7))
+            infos = (StepInfo * m)()
+            self._check(self.L.liodom_process_resident_subset(self.h, slot, _ip(ls), m, next_slot, nxp, nxn, n, height, width, _dp(poses), infos))
+            return poses, infos
+        self._check(self.L.liodom_process_resident_subset(self.h, slot, _ip(ls), m, next_slot, nxp, nxn, n, height, width, None, None))
+        return None, None
+
     def replay_resident(self, first_slot, count, n, height, width, ahead=False, depth=0):
         """The pipelined consumer loop over resident slots first_slot .. first_slot + count - 1, in C
         (liodom_replay_resident): every pose read back in order; depth 0 = strictly synchronous, 1 = the odometry of
@@ -619,9 +638,9 @@ class Liodom:
 
     def modes(self):
         """The code paths this handle runs ("key=value ..." from liodom_get_modes) as a dict of strings."""
-        buf = C.create_string_buffer(1024)
+        buf = C.create_string_buffer(2048)
         self.L.liodom_get_modes.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-        self._check(self.L.liodom_get_modes(self.h, buf, 1024))
+        self._check(self.L.liodom_get_modes(self.h, buf, 2048))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split())
 
     def sync(self):

@@ -6,8 +6,9 @@
 // grid (kCompactBlocks, streams): every workgroup scans the <= 256 ring counts itself (cheaper than a
 // second launch) and copies its interleaved share of the edges.
 constexpr int kCompactBlocks = 8;
+template <bool kList>
 __device__ __forceinline__ void compact_edges_body(const DevView& v, int s0, int eb, int mirror, int* pre, int* cntr) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   const int H = v.scan_lines;
   const int* rn = v.ring_nedges + (size_t)s * H;
   {
@@ -58,13 +59,14 @@ __device__ __forceinline__ void compact_edges_body(const DevView& v, int s0, int
 // memory included), the workgroups count themselves on pub_counter[eb], and the last one to arrive writes the sequence number for
 // the odometry side's kernels (pub_flag, may be null) and for the host thread that waits for the edges (pub_host, may be null).
 // A launch whose wait gave up still counts and publishes.
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_compact_edges(DevView v, int s0, int eb, unsigned int wait_odo, int mirror,
                                                        unsigned int* pub_flag, unsigned int* pub_host, unsigned int pub_value) {
   __shared__ int pre[257];
   __shared__ int cntr[256];
   // (pipelined replay) the odometry that last read edge buffer eb must have completed before it is rewritten
-  const bool go = !(wait_odo && !pipe_wait(v.pipe_flags + kEdgePipeBufs, wait_odo, &v.state[s0 + blockIdx.y].status));      // (uniform over the workgroup)
-  if (go) compact_edges_body(v, s0, eb, mirror, pre, cntr);
+  const bool go = !(wait_odo && !pipe_wait(v.pipe_flags + kEdgePipeBufs, wait_odo, &v.state[stream_of<kList>(v, s0, (int)blockIdx.y)].status));      // (uniform over the workgroup)
+  if (go) compact_edges_body<kList>(v, s0, eb, mirror, pre, cntr);
   if (pub_value) {
     typedef __attribute__((address_space(1))) unsigned int gu32;
     __threadfence_system();

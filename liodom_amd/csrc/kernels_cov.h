@@ -12,8 +12,9 @@
 //   it follows this launch in stream order, and the next second kNN pass (and so the next finalising solve) waits for that solve.
 //   The host-mapped slot k & 1 is rewritten by scan k + 2 only, whose launches follow this one on the same stream.
 // =============================================================================================
+template <bool kList = false>
 __global__ __launch_bounds__(64) void k_pose_cov(DevView v, int s0) {
-  const int s = s0 + (int)blockIdx.x;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.x);
   const int lane = (int)threadIdx.x;
   __shared__ liodom_pose_cov_t rec;
   __shared__ double sh_H[21];

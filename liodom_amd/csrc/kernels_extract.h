@@ -62,10 +62,11 @@ __device__ __forceinline__ unsigned char classify_point(const DevView& v, const 
   return r >= 0 ? (unsigned char)r : (unsigned char)0xFF;
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(kTileThreads) void k_classify(DevView v, int s0, const float4* __restrict__ in,
                                                            size_t in_stride, int n, int height, int width) {
   __shared__ int hist[256];
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y), sy = scan_row_of<kList>(s0, (int)blockIdx.y, s);
   const int tile = blockIdx.x;
   const int H = v.scan_lines;
   if (threadIdx.x < 256) hist[threadIdx.x] = 0;
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(kTileThreads) void k_classify(DevView v, int s0, co
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const int i = tile * kTilePts + j * kTileThreads + threadIdx.x;
-    if (i < n) p[j] = in[(size_t)blockIdx.y * in_stride + i];
+    if (i < n) p[j] = in[(size_t)sy * in_stride + i];
   }
 #pragma unroll
   for (int j = 0; j < 4; j++) {
@@ -113,10 +114,11 @@ __host__ __device__ __forceinline__ size_t ring_split_lb_lds_bytes(int H) {     
 __device__ __forceinline__ int stage_swz16(int e) { return e ^ ((e >> 5) & 15); }
 __device__ __forceinline__ int stage_swz4(int e) { return e ^ ((e >> 6) & 63); }
 
+template <bool kList = false>
 __global__ __launch_bounds__(kTileThreads) void k_ring_scatter(DevView v, int s0, const float4* __restrict__ in,
                                                                size_t in_stride, int n) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y), sy = scan_row_of<kList>(s0, (int)blockIdx.y, s);
   const int tile = blockIdx.x, ntiles = gridDim.x;
   const int H = v.scan_lines;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -200,7 +202,7 @@ __global__ __launch_bounds__(kTileThreads) void k_ring_scatter(DevView v, int s0
   for (int j = 0; j < 4; j++) {
     if (slot[j] >= 0) {
       const int i = tile * kTilePts + j * kTileThreads + tid;
-      spts[stage_swz16(slot[j])] = in[(size_t)blockIdx.y * in_stride + i];       // coalesced read
+      spts[stage_swz16(slot[j])] = in[(size_t)sy * in_stride + i];       // coalesced read
       sdst[stage_swz4(slot[j])] = dst[j];
       ssrc[stage_swz4(slot[j])] = i;
     }
@@ -232,6 +234,7 @@ __global__ __launch_bounds__(kTileThreads) void k_ring_scatter(DevView v, int s0
 // 135 + 305 us per 256-stream step: a waiting workgroup holds its 50 KB of LDS, three per CU, and the tiles of a stream are
 // spread over eight XCDs that advance at their own pace — so batches keep k_classify + k_ring_scatter.
 // =============================================================================================
+template <bool kList = false>
 __global__ __launch_bounds__(kTileThreads) void k_ring_split(DevView v, int s0, const float4* __restrict__ in,
                                                              size_t in_stride, int n, int height, int width) {
   typedef __attribute__((address_space(1))) unsigned int gu32;
@@ -244,8 +247,8 @@ __global__ __launch_bounds__(kTileThreads) void k_ring_split(DevView v, int s0, 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid < 256) hist[tid] = 0;
   __syncthreads();
-  const int sy = blockIdx.y, tile = blockIdx.x;
-  const int s = s0 + sy;
+  const int tile = blockIdx.x;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y), sy = scan_row_of<kList>(s0, (int)blockIdx.y, s);
   const int Hp = ring_scatter_stride(H);
   unsigned long long* wmask = reinterpret_cast<unsigned long long*>(smem);          // [32][Hp]   (phase A)
   unsigned short* cbase = reinterpret_cast<unsigned short*>(wmask + kTileChunks * Hp);  // [32][Hp]   (phase A)
@@ -419,6 +422,7 @@ __device__ __forceinline__ void ring_tile_masks_prefix(unsigned long long* wmask
   }
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(kTileThreads) void k_ring_split_lb(DevView v, int s0, const float4* __restrict__ in, size_t in_stride, int n,
                                                                 int height, int width, int ntiles, unsigned int tag) {
   typedef __attribute__((address_space(1))) unsigned long long gu64;
@@ -431,8 +435,8 @@ __global__ __launch_bounds__(kTileThreads) void k_ring_split_lb(DevView v, int s
   if (tid < 256) { hist[tid] = 0; sh_pre[tid] = 0; }
   if (tid == 0) { sh_ticket = (int)atomicAdd(v.lb_ticket, 1u); sh_ok = 1; }
   __syncthreads();
-  const int sy = sh_ticket / ntiles, tile = sh_ticket - sy * ntiles;      // stream-major: the tiles before this one have started
-  const int s = s0 + sy;
+  const int row = sh_ticket / ntiles, tile = sh_ticket - row * ntiles;      // row-major (a row is a stream of the launch): the tiles before this one have started
+  const int s = stream_of<kList>(v, s0, row), sy = scan_row_of<kList>(s0, row, s);
   const int Hp = ring_scatter_stride(H);
   unsigned long long* wmask = reinterpret_cast<unsigned long long*>(smem);          // [32][Hp]   (phase A)
   unsigned short* cbase = reinterpret_cast<unsigned short*>(wmask + kTileChunks * Hp);  // [32][Hp]   (phase A)
@@ -564,12 +568,13 @@ __global__ __launch_bounds__(kTileThreads) void k_ring_split_lb(DevView v, int s
 // scan itself fits), tile by tile: a first sweep counts, a second places every point at ring start + points of the ring in earlier
 // tiles + rank inside the tile (stable: feature_extractor.cc:115-175 appends in input order).  Slow — one workgroup walks the
 // whole scan twice — and only ever run for clouds no spinning LiDAR produces.
+template <bool kList = false>
 __global__ __launch_bounds__(kTileThreads) void k_ring_split_fix(DevView v, int s0, const float4* __restrict__ in, size_t in_stride, int n,
                                                                  int height, int width, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int tot[256];          // points of every ring (first sweep), then its running position (second sweep)
   __shared__ int wtot[16];
-  const int sy = blockIdx.y, s = s0 + sy;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y), sy = scan_row_of<kList>(s0, (int)blockIdx.y, s);
   if (!v.lb_ovf[s]) return;         // (uniform)
   const int H = v.scan_lines;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -655,13 +660,14 @@ __global__ __launch_bounds__(kTileThreads) void k_ring_split_fix(DevView v, int 
 // =============================================================================================
 constexpr int kRowThreads = 512;
 constexpr int kRowRounds = 4;              // columns per thread in flight (rows of up to 2048 points in one sweep)
+template <bool kList = false>
 __global__ __launch_bounds__(kRowThreads) void k_row_compact(DevView v, int s0, const float4* __restrict__ in, size_t in_stride,
                                                              int n, int height, int width) {
   __shared__ int s_cnt[kRowRounds][kRowThreads / 64];  // [round of the sweep][wave] valid points
   __shared__ int s_base;
-  const int s = s0 + blockIdx.y, row = blockIdx.x, H = v.scan_lines;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y), row = blockIdx.x, H = v.scan_lines;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float4* src = in + (size_t)blockIdx.y * in_stride;
+  const float4* src = in + (size_t)scan_row_of<kList>(s0, (int)blockIdx.y, s) * in_stride;
   float4* out = v.ring_pts + (size_t)s * v.ring_stride + (size_t)row * width;
   int* osrc = v.ring_src + (size_t)s * v.ring_stride + (size_t)row * width;
   if (tid == 0) { s_base = 0; v.ring_start[(size_t)s * (H + 1) + row] = row * width; if (row == H - 1) v.ring_start[(size_t)s * (H + 1) + H] = H * width; }
@@ -1146,12 +1152,12 @@ __device__ __forceinline__ void ring_extract_ring(const DevView& v, int s, int r
   if ((kInstrument && (v.debug & 32)) && s == 0 && tid == 0 && ring < 64) { v.dbg_clk[128 + ring] = wall_clock64() - t_begin; v.dbg_clk[96 + (ring & 31)] = (unsigned long long)dbg_rounds | ((unsigned long long)*nedges_out << 8); }
 }
 
-template <int kMaxThreads, int IPL>
+template <int kMaxThreads, int IPL, bool kList = false>
 __global__ __launch_bounds__(kMaxThreads) void k_ring_extract(DevView v, int s0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (v.split_ctr && blockIdx.x == 0 && threadIdx.x == 0) {      // (k_ring_split's counters, for the next scan)
-    v.split_ctr[2 * (s0 + (int)blockIdx.y) + 1] = 0u;
+    v.split_ctr[2 * stream_of<kList>(v, s0, (int)blockIdx.y) + 1] = 0u;
   }
   if (v.lb_ticket && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *v.lb_ticket = 0u;      // (k_ring_split_lb's ticket counter)
-  ring_extract_ring<IPL>(v, s0 + (int)blockIdx.y, (int)blockIdx.x, smem);
+  ring_extract_ring<IPL>(v, stream_of<kList>(v, s0, (int)blockIdx.y), (int)blockIdx.x, smem);
 }

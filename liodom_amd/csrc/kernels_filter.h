@@ -17,10 +17,11 @@
 //                     of the filtered cloud)
 // Every kernel exits immediately unless filter_active().
 // =============================================================================================
+template <bool kList = false>
 __global__ __launch_bounds__(1024) void k_voxel_bbox(DevView v, int s0) {
   __shared__ WinIndex w;
   __shared__ float red[6][16];
-  const int s = s0 + blockIdx.x;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.x);
   StreamState& st = v.state[s];
   const int tid = threadIdx.x;
   // clear the voxel table of the previous build (also when the filter just became inactive)
@@ -67,9 +68,10 @@ __global__ __launch_bounds__(1024) void k_voxel_bbox(DevView v, int s0) {
   }
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_voxel_insert(DevView v, int s0) {
   __shared__ WinIndex w;
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   if (!filter_active(v, st)) return;
   const int M = st.n_map, nf = st.n_frames;
@@ -106,8 +108,9 @@ __global__ __launch_bounds__(256) void k_voxel_insert(DevView v, int s0) {
   *pv = found;
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_voxel_alloc(DevView v, int s0) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   if (!filter_active(v, st)) return;
   const int u = blockIdx.x * 256 + threadIdx.x;
@@ -116,8 +119,9 @@ __global__ __launch_bounds__(256) void k_voxel_alloc(DevView v, int s0) {
   slot->start = (unsigned int)atomicAdd(&st.vox_cursor, (int)slot->cnt);
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_voxel_scatter(DevView v, int s0) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   const StreamState& st = v.state[s];
   if (!filter_active(v, st)) return;
   const int m = blockIdx.x * 256 + threadIdx.x;
@@ -130,11 +134,12 @@ __global__ __launch_bounds__(256) void k_voxel_scatter(DevView v, int s0) {
 }
 
 // 32 lanes per leaf, 8 leaves per workgroup.
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_voxel_centroid(DevView v, int s0) {
   __shared__ WinIndex w;
   constexpr int CAP = 512;
   __shared__ int ord[8][CAP];
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   if (!filter_active(v, st)) return;
   const int nvox = st.vox_used;
@@ -194,8 +199,9 @@ __global__ __launch_bounds__(256) void k_voxel_centroid(DevView v, int s0) {
 }
 
 // 1 m cell hash over the filtered cloud (same slot protocol as k_window_insert).
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_filt_insert(DevView v, int s0) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   if (!filter_active(v, st)) return;
   const int u = blockIdx.x * 256 + threadIdx.x;
@@ -225,8 +231,9 @@ __global__ __launch_bounds__(256) void k_filt_insert(DevView v, int s0) {
   *pc = found;
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_filt_alloc(DevView v, int s0) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   if (!filter_active(v, st)) return;
   const int u = blockIdx.x * 256 + threadIdx.x;
@@ -235,8 +242,9 @@ __global__ __launch_bounds__(256) void k_filt_alloc(DevView v, int s0) {
   slot->start = (unsigned int)atomicAdd(&st.cursor, (int)slot->cnt);
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_filt_scatter(DevView v, int s0) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   const StreamState& st = v.state[s];
   if (!filter_active(v, st)) return;
   const int u = blockIdx.x * 256 + threadIdx.x;

@@ -1064,7 +1064,7 @@ __device__ __forceinline__ bool knn_pass(const DevView& v, int s, int bxi, int b
   return true;
 }
 
-template <int kKnnThreads, bool kOv = false, bool kChain = false>
+template <int kKnnThreads, bool kOv = false, bool kChain = false, bool kList = false>
 __global__ __launch_bounds__(kKnnThreads, (kKnnThreads >= 256 ? 1 : LIODOM_TUNE_B_WAVES)) void k_knn(DevView v, int s0, int outer_it, int eb, unsigned int wait_edges, unsigned int signal_odo, unsigned int seq, int scan_no) {
   constexpr int kKnnQueries = kKnnThreads / kKnnGroup;
 #if defined(LIODOM_CHAIN_PRIO)
@@ -1078,7 +1078,7 @@ __global__ __launch_bounds__(kKnnThreads, (kKnnThreads >= 256 ? 1 : LIODOM_TUNE_
   __shared__ double sh_ov[(kOv || kChain) ? 20 : 1];       // overlapped pass: the first solve's odom[12], q[4], t[3]; chain mode: the prediction
   int bxi = (int)blockIdx.x, byi = (int)blockIdx.y;
   xcd_remap(bxi, byi);
-  const int s = s0 + byi;
+  const int s = stream_of<kList>(v, s0, byi);
   if constexpr (kOv) {
     // chain mode: COUNT + PAD of the streamed rebuild as extra workgroups of the second pass's launch (light ones: 256 threads at
     // this kernel's register budget), beside the pass's search and its wait for the first solve.  (As a launch of their own in
@@ -1212,8 +1212,9 @@ __global__ void k_ov_gate(DevView v, int s, unsigned int seq) {
 // k_line_gate (lock-step batches): the line gate of laser_odometry.cc:325-344 for the queries of one kNN pass, one query
 // per lane; writes the correspondences (:351-357), counts the matches (:346) and leaves the validity bytes the solve's
 // compaction reads (bit q of byte b = query q of k_knn workgroup b).
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_line_gate(DevView v, int s0, int outer_it, int eb) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   if (v.knn8_cnt && blockIdx.x == 0 && threadIdx.x == 0) v.knn8_cnt[s] = 0;      // (k_knn8's list for k_knn8_exact, the launch before this one: consumed)
   if (!st.initialized) return;

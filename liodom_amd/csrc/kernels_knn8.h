@@ -232,11 +232,11 @@ constexpr bool kKnn8Sort = LIODOM_KNN8_SORT != 0;      // first pass: queries de
 #ifndef LIODOM_KNN8_WAVES
 #define LIODOM_KNN8_WAVES 7
 #endif
-template <int outer_it>      // the scan's first (0) or second (1) pass: two instances, each without the other's code and registers
+template <int outer_it, bool kList = false>      // the scan's first (0) or second (1) pass: two instances, each without the other's code and registers
 __global__ __launch_bounds__(kKnn8Threads, LIODOM_KNN8_WAVES) void k_knn8(DevView v, int s0, int eb) {
   int bxi = (int)blockIdx.x, byi = (int)blockIdx.y;
   xcd_remap(bxi, byi);
-  const int s = s0 + byi;
+  const int s = stream_of<kList>(v, s0, byi);
   StreamState& st = v.state[s];
   if (!st.initialized) return;                           // (uniform) first scan: no map yet
   if (st.status & LIODOM_STATUS_PIPE_TIMEOUT) return;
@@ -436,8 +436,9 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
   const unsigned long long o = xor32_u64(v);
   return o < v ? o : v;
 }
+template <bool kList = false>
 __global__ __launch_bounds__(kKnn8Threads) void k_knn8_exact(DevView v, int s0, int outer_it, int eb) {
-  const int s = s0 + (int)blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   const int n = v.knn8_cnt[s];
   if (n <= 0 || !st.initialized) return;

@@ -362,16 +362,18 @@ __device__ __forceinline__ void publish_final_pose(const DevView& v, int s, cons
 
 // use_imu (laser_odometry.cc:152-183): the prediction (made when the previous scan finished) gets
 // the roll and pitch of the latest IMU orientation before the first kNN pass; one thread per stream.
+template <bool kList = false>
 __global__ void k_imu_override(DevView v, int s0, int count) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  StreamState& st = v.state[s0 + i];
+  const int s = stream_of_lane<kList>(v, s0, i);
+  StreamState& st = v.state[s];
   if (!st.initialized) return;
   double odom[12], out[12], l2b[12], q[4];
 #pragma unroll
   for (int k = 0; k < 12; k++) { odom[k] = st.odom[k]; l2b[k] = v.laser_to_base[k]; }
 #pragma unroll
-  for (int k = 0; k < 4; k++) q[k] = v.imu_q[(size_t)(s0 + i) * 4 + k];
+  for (int k = 0; k < 4; k++) q[k] = v.imu_q[(size_t)s * 4 + k];
   imu_override(odom, q, l2b, v.rotation_mode, out);
 #pragma unroll
   for (int k = 0; k < 12; k++) st.odom[k] = out[k];
@@ -411,7 +413,7 @@ __device__ __forceinline__ void rebuild_beside_solve(const DevView& v, int s, St
 // (round 6: and one instance per MODE — the four-launch chain of the host-fed replay, the strict / serial legs, the lock-step batches
 //  and per-kernel profiling never waits for a pass's done count and never hands a result over early: as a run-time `chain` that code
 //  cost its finalising solve 200 B of scratch per lane)
-template <int kOuterIt, bool kChainMode>
+template <int kOuterIt, bool kChainMode, bool kList = false>
 #ifndef LIODOM_LM_WAVES_PER_SIMD
 #define LIODOM_LM_WAVES_PER_SIMD 1      // (experiments: 256-thread workgroups at 2 -> 256 registers per lane, half of the CU's register file)
 #endif
@@ -430,7 +432,7 @@ __global__ __launch_bounds__(kLmThreads, LIODOM_LM_WAVES_PER_SIMD) void k_lm_sol
   __shared__ LmState lm;
   __shared__ int sh_flag;
   __shared__ int sh_C;
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
 #if defined(LIODOM_CHAIN_PRIO)
   if (v.n_streams <= 4) __builtin_amdgcn_s_setprio(LIODOM_CHAIN_PRIO);      // (see k_knn)
 #endif

@@ -67,10 +67,11 @@ __device__ __forceinline__ void hash_count_point(const DevView& v, int s, int pa
 // The new frame's edges (dense edge buffer eb, sensor frame) are transformed with the solved pose
 // (laser_odometry.cc:231-232), then stored in the window slot (:235).  Every point of the window is counted
 // into its 1 m cell (hash_count_point).  (Not launched by handles with early_rebuild: see "streamed rebuild".)
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_window_insert(DevView v, int s0, int eb) {
   __shared__ int sbase[kMaxFrames + 1];
   __shared__ int sslot[kMaxFrames];
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   const int M = st.n_map;
   const int MT = M + (v.mapping ? st.n_recv : 0);      // window ++ received map (:310-314)
@@ -275,8 +276,9 @@ __device__ __forceinline__ void rebuild_alloc(const DevView& v, int s, StreamSta
   }
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_rebuild_alloc(DevView v, int s0) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   rebuild_alloc(v, s, st, (int)blockIdx.x, (int)gridDim.x);
 }
@@ -574,8 +576,9 @@ __global__ __launch_bounds__(kKnnThreads, 1) void k_chain_redo0(DevView v, int s
 // Start offsets of the occupied cells (any order: only contiguity per cell matters).  One atomic
 // per wave: the 64 counts are scanned in the wave and lane 0 reserves the wave's total — 3 500
 // same-address atomics serialise in L2 (measured 7.5 us for this launch), 55 do not.
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_hash_alloc(DevView v, int s0) {
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   StreamState& st = v.state[s];
   const int par = LD_TAB_PARITY(v, st.frame_count), sp = s + par * v.n_streams;
   const int nu = st.n_used_tab[par];
@@ -595,10 +598,11 @@ __global__ __launch_bounds__(256) void k_hash_alloc(DevView v, int s0) {
   if (slot) slot->start = (unsigned int)(base + incl - cnt);
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(256) void k_hash_scatter(DevView v, int s0) {
   __shared__ int sbase[kMaxFrames + 1];
   __shared__ int sslot[kMaxFrames];
-  const int s = s0 + blockIdx.y;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.y);
   const StreamState& st = v.state[s];
   const int M = st.n_map;
   const int MT = M + (v.mapping ? st.n_recv : 0);
@@ -830,10 +834,11 @@ constexpr int kHbSlackMin = 32;
 // Candidates are a set to k_knn8 (ties go by window index): results are bit-identical to a rebuild every scan (LIODOM_HASH_INCR=0).
 // One workgroup per stream: a barrier separates "every cell exists" from "points take their places".
 // =============================================================================================
+template <bool kList = false>
 __global__ __launch_bounds__(kBuildThreads) void k_hash_append(DevView v, int s0, int eb) {
   __shared__ WinIndex w;
   __shared__ int sh_flag;
-  const int s = s0 + blockIdx.x;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.x);
   StreamState& st = v.state[s];
   const int tid = threadIdx.x, lane = tid & 63;
   const int nf = st.n_frames, fc = st.frame_count, Mw = st.n_map;
@@ -940,6 +945,7 @@ __global__ __launch_bounds__(kBuildThreads) void k_hash_append(DevView v, int s0
   if (tid == 0) { st.hb_shift = shift; st.n_search = Mw; st.n_filt = 0; st.hb_stats[1] += 1; st.hb_stats[2] += sh_flag; }
 }
 
+template <bool kList = false>
 __global__ __launch_bounds__(kBuildThreads) void k_hash_build(DevView v, int s0, int eb) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ WinIndex w;
@@ -947,7 +953,7 @@ __global__ __launch_bounds__(kBuildThreads) void k_hash_build(DevView v, int s0,
   unsigned long long* lkey = reinterpret_cast<unsigned long long*>(smem);           // [kLdsSlots]
   unsigned int* lcnt = reinterpret_cast<unsigned int*>(lkey + kLdsSlots);           // [kLdsSlots]
   unsigned int* lstart = lcnt + kLdsSlots;                                          // [kLdsSlots]
-  const int s = s0 + blockIdx.x;
+  const int s = stream_of<kList>(v, s0, (int)blockIdx.x);
   StreamState& st = v.state[s];
   const int tid = threadIdx.x;
   const int Mw = st.n_map, nf = st.n_frames;

@@ -40,11 +40,12 @@ __device__ __forceinline__ bool pipe_wait(const unsigned int* flag, unsigned int
 // Gate in front of a scan's first k_knn launch for handles whose launch is too large to poll the flag itself (its polling
 // workgroups would fill the GPU and starve the extraction they wait for): one wave waits for the extraction's flag and
 // publishes that the previous odometry has completed; the launches behind it start when it retires.
+template <bool kList = false>
 __global__ void k_pipe_gate(DevView v, int s0, int eb, unsigned int wait_edges, unsigned int signal_odo) {
   typedef __attribute__((address_space(1))) unsigned int gu32;
   INJECT_DELAY(2);
   if (signal_odo && threadIdx.x == 0) __hip_atomic_store((gu32*)(v.pipe_flags + kEdgePipeBufs), signal_odo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (wait_edges && !pipe_wait(v.pipe_flags + eb, wait_edges, &v.state[s0].status)) {
+  if (wait_edges && !pipe_wait(v.pipe_flags + eb, wait_edges, &v.state[stream_of<kList>(v, s0, 0)].status)) {
     // the launches behind the gate check the status bit of their own stream (k_knn) and skip the scan
     for (int s = (int)threadIdx.x; s < v.n_streams; s += (int)blockDim.x) atomicOr(&v.state[s].status, LIODOM_STATUS_PIPE_TIMEOUT);
   }

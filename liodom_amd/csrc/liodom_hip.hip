@@ -14,6 +14,7 @@
 #include <chrono>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "liodom_kernels.h"
@@ -129,7 +130,10 @@ struct liodom_handle {
   std::atomic<bool> replay_live{false};        // scans went through them by the pipelined replay since the last drain (their odometries may not have been collected)
   std::atomic<bool> fallback_pending{false};   // a kernel of this handle gave up an in-kernel wait (LIODOM_STATUS_PIPE_TIMEOUT): liodom_reset() switches to events
   int pf_slot = -1;                  // resident slot whose extraction has been issued ahead
-  int last_eb = 0;                   // edge buffer of the most recent scan that entered odometry (inspection)
+  bool pf_subset = false;            // ... for the streams of pf_list only (liodom_process_resident_subset); false: for every stream
+  std::vector<int32_t> pf_list;
+  long long subset_steps = 0;        // steps that ran over a stream list (liodom_get_modes)
+  std::vector<int> last_eb;          // per stream: edge buffer of the stream's most recent scan that entered odometry (inspection)
   hipEvent_t pose_event = nullptr;
   int S = 1, H = 0, P = 0;
   bool lockstep = false;             // n_streams >= 16: a lock-step batch (throughput-bound; picks the hash build, the kNN kernels, events between the streams)
@@ -235,33 +239,36 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // ---- launch sequences -----------------------------------------------------------------------
 // Feature extraction of `count` streams starting at s0; input scan for stream s0+i at in + i*stride.
+// s0 < 0: of the `count` streams of device-side stream list -s0 - 1 (put_stream_list); input scan of stream s at in + s*stride.
 int launch_extract(liodom_handle* h, hipStream_t q, int eb, int s0, int count, const float4* in, size_t in_stride,
                    int n, int height, int width, unsigned int wait_odo = 0, int mirror = 0, unsigned int* pub_flag = nullptr, unsigned int* pub_host = nullptr, unsigned int pub_value = 0u) {
   const DevView& v = h->v;
+  // every kernel comes in two instances (stream_of): rows = streams s0 + row, rows = entries of a stream list
+  auto by_rows = [&](auto launch) { if (s0 < 0) launch(std::true_type{}); else launch(std::false_type{}); };
   const int tiles = std::max(1, cdiv(n, kTilePts));
   if (v.lidar_type == 1 && width > 0 && (long long)h->H * width <= (long long)v.max_points) {
     // organised cloud: ring = row, the split is a per-row compaction (no classify / scatter passes): one pass over the scan
     ProfScope ps(h, KID_RING_SCATTER, q);
-    hipLaunchKernelGGL(k_row_compact, dim3(h->H, count), dim3(kRowThreads), 0, q, v, s0, in, in_stride, n, height, width);
+    by_rows([&](auto L) { hipLaunchKernelGGL((k_row_compact<decltype(L)::value>), dim3(h->H, count), dim3(kRowThreads), 0, q, v, s0, in, in_stride, n, height, width); });
   } else {
     if (h->ring_split_lb && !((long long)tiles * count <= h->ring_split_max_wgs && h->ring_split)) {
       // lock-step batches: one pass, rings at a fixed pitch, tiles sum their predecessors' counts (booked as the scatter)
       ProfScope ps(h, KID_RING_SCATTER, q);
       if (++h->lb_tag == 0u) h->lb_tag = 1u;
-      hipLaunchKernelGGL(k_ring_split_lb, dim3(tiles * count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles, h->lb_tag);
-      hipLaunchKernelGGL(k_ring_split_fix, dim3(1, count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split_lb<decltype(L)::value>), dim3(tiles * count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles, h->lb_tag); });
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split_fix<decltype(L)::value>), dim3(1, count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles); });
     } else if (h->ring_split && (long long)tiles * count <= h->ring_split_max_wgs) {      // (every workgroup resident at once: k_ring_split waits inside the launch)
       // one pass: classification and scatter in one kernel (booked as the scatter)
       ProfScope ps(h, KID_RING_SCATTER, q);
-      hipLaunchKernelGGL(k_ring_split, dim3(tiles, count), dim3(kTileThreads), ring_scatter_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split<decltype(L)::value>), dim3(tiles, count), dim3(kTileThreads), ring_scatter_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width); });
     } else {
     {
       ProfScope ps(h, KID_CLASSIFY, q);
-      hipLaunchKernelGGL(k_classify, dim3(tiles, count), dim3(kTileThreads), 0, q, v, s0, in, in_stride, n, height, width);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_classify<decltype(L)::value>), dim3(tiles, count), dim3(kTileThreads), 0, q, v, s0, in, in_stride, n, height, width); });
     }
     {
       ProfScope ps(h, KID_RING_SCATTER, q);
-      hipLaunchKernelGGL(k_ring_scatter, dim3(tiles, count), dim3(kTileThreads), ring_scatter_lds_bytes(h->H), q, v, s0, in, in_stride, n);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_scatter<decltype(L)::value>), dim3(tiles, count), dim3(kTileThreads), ring_scatter_lds_bytes(h->H), q, v, s0, in, in_stride, n); });
     }
     }
   }
@@ -274,16 +281,16 @@ int launch_extract(liodom_handle* h, hipStream_t q, int eb, int s0, int count, c
     const bool big = total - sector * (v.scan_regions - 1) > kExLPR * kExIPL;
     const dim3 grid(h->H, count), block(ext);
     if (ext <= 256) {
-      if (big) hipLaunchKernelGGL((k_ring_extract<256, kExIPLBig>), grid, block, h->ring_lds_bytes, q, v, s0);
-      else hipLaunchKernelGGL((k_ring_extract<256, kExIPL>), grid, block, h->ring_lds_bytes, q, v, s0);
+      if (big) by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<256, kExIPLBig, decltype(L)::value>), grid, block, h->ring_lds_bytes, q, v, s0); });
+      else by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<256, kExIPL, decltype(L)::value>), grid, block, h->ring_lds_bytes, q, v, s0); });
     } else {
-      if (big) hipLaunchKernelGGL((k_ring_extract<1024, kExIPLBig>), grid, block, h->ring_lds_bytes, q, v, s0);
-      else hipLaunchKernelGGL((k_ring_extract<1024, kExIPL>), grid, block, h->ring_lds_bytes, q, v, s0);
+      if (big) by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<1024, kExIPLBig, decltype(L)::value>), grid, block, h->ring_lds_bytes, q, v, s0); });
+      else by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<1024, kExIPL, decltype(L)::value>), grid, block, h->ring_lds_bytes, q, v, s0); });
     }
   }
   {
     ProfScope ps(h, KID_COMPACT, q);
-    hipLaunchKernelGGL(k_compact_edges, dim3(kCompactBlocks, count), dim3(256), 0, q, v, s0, eb, wait_odo, mirror, pub_flag, pub_host, pub_value);
+    by_rows([&](auto L) { hipLaunchKernelGGL((k_compact_edges<decltype(L)::value>), dim3(kCompactBlocks, count), dim3(256), 0, q, v, s0, eb, wait_odo, mirror, pub_flag, pub_host, pub_value); });
   }
   HIP_TRY(hipGetLastError());
   return LIODOM_OK;
@@ -292,15 +299,16 @@ int launch_extract(liodom_handle* h, hipStream_t q, int eb, int s0, int count, c
 // Odometry on the dense edges already on the device.  If pose_dst != nullptr the poses + infos
 // of the streams are copied to pinned memory right after the solve and pose_event is recorded,
 // so the host can pick them up while the window / hash rebuild still runs.
-int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges, unsigned int signal_odo);
+// s0 < 0: the `count` streams of device-side stream list -s0 - 1, whose entries the host loops read from `list`.
+int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges, unsigned int signal_odo, const int32_t* list = nullptr);
 
-int launch_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges = 0, unsigned int signal_odo = 0) {
+int launch_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges = 0, unsigned int signal_odo = 0, const int32_t* list = nullptr) {
   // (a hipGraph replay of this launch sequence was measured slower than the eager launches in rounds 1-2 — the chain is
   //  bound by its kernels, the host enqueue is hidden behind them, hipGraphLaunch adds start latency — and removed in round 3)
-  const int rc = enqueue_odometry(h, eb, s0, count, wait_edges, signal_odo);
+  const int rc = enqueue_odometry(h, eb, s0, count, wait_edges, signal_odo, list);
   if (rc) return rc;
-  h->last_eb = eb;       // results are published by k_lm_solve into host-mapped memory (HostOut)
-  for (int i = 0; i < count; i++) h->scans_enqueued[s0 + i]++;
+  // results are published by k_lm_solve into host-mapped memory (HostOut)
+  for (int i = 0; i < count; i++) { const int s = list ? list[i] : s0 + i; h->last_eb[s] = eb; h->scans_enqueued[s]++; }
   return LIODOM_OK;
 }
 
@@ -313,12 +321,14 @@ OverlapModes overlap_modes(const liodom_handle* h) {
   return {base && h->ov_ok, base && h->chain_ok && !h->flag_gate};
 }
 
-int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges, unsigned int signal_odo) {
+int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges, unsigned int signal_odo, const int32_t* list) {
   const DevView& v = h->v;
+  auto stream_at = [&](int i) { return list ? (int)list[i] : s0 + i; };
+  auto by_rows = [&](auto launch) { if (s0 < 0) launch(std::true_type{}); else launch(std::false_type{}); };      // (as in launch_extract)
   const bool knn_small = h->lockstep;           // 4 queries per workgroup, else 8
   if (v.use_imu) {
     ProfScope ps(h, KID_OTHER);
-    hipLaunchKernelGGL(k_imu_override, dim3(cdiv(count, 64)), dim3(64), 0, h->stream, v, s0, count);
+    by_rows([&](auto L) { hipLaunchKernelGGL((k_imu_override<decltype(L)::value>), dim3(cdiv(count, 64)), dim3(64), 0, h->stream, v, s0, count); });
   }
   // early rebuild ("streamed rebuild", kernels_rebuild.h): the four launches of a scan carry extra workgroups that build
   // the next scan's cell hash in the second table; nothing follows the finalising solve
@@ -391,8 +401,8 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
     hipLaunchKernelGGL((k_lm_solve<1, true>), dim3(gx, 1), dim3(kLmThreads), lds, h->stream, v, s0, eb, seq_k, done_target);
     // (pose covariance: behind the finalising solve on its stream; the next scan's first solve follows it there, and the next second
     //  pass — hence the next finalising solve, the next writer of cov_raw — waits for that solve: kernels_cov.h)
-    if (v.cov_raw) hipLaunchKernelGGL(k_pose_cov, dim3(count), dim3(64), 0, h->stream, v, s0);
-    if (!v.speculate) hipLaunchKernelGGL(k_rebuild_alloc, dim3(kRebuildAllocBlocks, 1), dim3(256), 0, h->stream_k, v, s0);
+    if (v.cov_raw) hipLaunchKernelGGL(k_pose_cov<>, dim3(count), dim3(64), 0, h->stream, v, s0);
+    if (!v.speculate) hipLaunchKernelGGL(k_rebuild_alloc<>, dim3(kRebuildAllocBlocks, 1), dim3(256), 0, h->stream_k, v, s0);
     const int nCf = cdiv(h->v.edge_cap * std::max(1, h->P - 1), kRebFinThreads), nPf = cdiv(h->v.edge_cap, kRebFinThreads);
     hipLaunchKernelGGL(k_rebuild_fin, dim3(nPf + kRebuildAuxBlocks + nCf, 1), dim3(kRebFinThreads), 0, h->stream_k, v, s0, eb);
     HIP_TRY(hipGetLastError());
@@ -405,21 +415,21 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
       if (knn_small && h->knn8) {
         // lock-step batches: eight lanes per query (kernels_knn8.h); the workgroups of a stream walk its blocks of 32 queries
         const dim3 g8(h->knn8_grid, count);
-        if (it == 0) hipLaunchKernelGGL(k_knn8<0>, g8, dim3(kKnn8Threads), 0, h->stream, v, s0, eb);
-        else hipLaunchKernelGGL(k_knn8<1>, g8, dim3(kKnn8Threads), 0, h->stream, v, s0, eb);
-        hipLaunchKernelGGL(k_knn8_exact, dim3(kKnn8ExactBlocks, count), dim3(kKnn8Threads), 0, h->stream, v, s0, it, eb);      // (the ~1 % of the queries the fast path cannot certify)
-        hipLaunchKernelGGL(k_line_gate, dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb);
+        if (it == 0) by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8<0, decltype(L)::value>), g8, dim3(kKnn8Threads), 0, h->stream, v, s0, eb); });
+        else by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8<1, decltype(L)::value>), g8, dim3(kKnn8Threads), 0, h->stream, v, s0, eb); });
+        by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8_exact<decltype(L)::value>), dim3(kKnn8ExactBlocks, count), dim3(kKnn8Threads), 0, h->stream, v, s0, it, eb); });      // (the ~1 % of the queries the fast path cannot certify)
+        by_rows([&](auto L) { hipLaunchKernelGGL((k_line_gate<decltype(L)::value>), dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb); });
       } else if (knn_small) {
-        hipLaunchKernelGGL(k_knn<128>, dim3(kx, count), dim3(128), 0, h->stream, v, s0, it, eb, wait_edges, signal_odo, 0u, 0);
-        hipLaunchKernelGGL(k_line_gate, dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb);
+        by_rows([&](auto L) { hipLaunchKernelGGL((k_knn<128, false, false, decltype(L)::value>), dim3(kx, count), dim3(128), 0, h->stream, v, s0, it, eb, wait_edges, signal_odo, 0u, 0); });
+        by_rows([&](auto L) { hipLaunchKernelGGL((k_line_gate<decltype(L)::value>), dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb); });
       } else if (it == 1 && seq_k) {
         hipLaunchKernelGGL(k_ov_gate, dim3(1), dim3(64), 0, h->stream_k, v, s0, seq_k);
         hipLaunchKernelGGL((k_knn<256, true>), dim3(kx, count), dim3(256), 0, h->stream_k, v, s0, it, eb, 0u, 0u, seq_k, -1);
         if (v.speculate) hipLaunchKernelGGL(k_knn_redo<256>, dim3(v.knn_grid, count), dim3(256), 0, h->stream_k, v, s0, eb, seq_k, -1, 0);      // (speculative hand-over not confirmed: rare)
         // ALLOC between the two solve launches, beside the pass's tail
-        hipLaunchKernelGGL(k_rebuild_alloc, dim3(kRebuildAllocBlocks, count), dim3(256), 0, h->stream, v, s0);
+        hipLaunchKernelGGL(k_rebuild_alloc<>, dim3(kRebuildAllocBlocks, count), dim3(256), 0, h->stream, v, s0);
       } else {
-        hipLaunchKernelGGL(k_knn<256>, dim3(kx, count), dim3(256), 0, h->stream, v, s0, it, eb, wait_edges, signal_odo, 0u, 0);
+        by_rows([&](auto L) { hipLaunchKernelGGL((k_knn<256, false, false, decltype(L)::value>), dim3(kx, count), dim3(256), 0, h->stream, v, s0, it, eb, wait_edges, signal_odo, 0u, 0); });
       }
     }
     {
@@ -427,18 +437,19 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
       // it 0: + COUNT, PAD; it 1: + APPEND, CLEAR, SCATTER
       const int extra = !early ? 0 : (it == 0 ? nC + nP : nP + kRebuildAuxBlocks + nC);
       const int gx = std::max(h->v.lm_groups + extra, (h->v.lm_groups - 1) * 8 + 1);      // solvers on blocks 0, 8, 16, ... (one XCD)
-      if (it == 0) hipLaunchKernelGGL((k_lm_solve<0, false>), dim3(gx, count), dim3(kLmThreads), lm_lds_bytes(h->v.edge_cap), h->stream, v, s0, eb, seq_k, 0u);
-      else hipLaunchKernelGGL((k_lm_solve<1, false>), dim3(gx, count), dim3(kLmThreads), lm_lds_bytes(h->v.edge_cap), h->stream, v, s0, eb, seq_k, 0u);
+      if (it == 0) by_rows([&](auto L) { hipLaunchKernelGGL((k_lm_solve<0, false, decltype(L)::value>), dim3(gx, count), dim3(kLmThreads), lm_lds_bytes(h->v.edge_cap), h->stream, v, s0, eb, seq_k, 0u); });
+      else by_rows([&](auto L) { hipLaunchKernelGGL((k_lm_solve<1, false, decltype(L)::value>), dim3(gx, count), dim3(kLmThreads), lm_lds_bytes(h->v.edge_cap), h->stream, v, s0, eb, seq_k, 0u); });
     }
     if (it == 1 && v.cov_raw) {             // pose covariance of the scan, straight behind its finalising solve (kernels_cov.h)
       ProfScope ps(h, KID_OTHER);
-      hipLaunchKernelGGL(k_pose_cov, dim3(count), dim3(64), 0, h->stream, v, s0);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_pose_cov<decltype(L)::value>), dim3(count), dim3(64), 0, h->stream, v, s0); });
     }
   }
   if (v.mapping) {
     // synchronous replay of the mapping node for the streams with an attached map: updateMap(edges_k,
     // pose_k), then getLocalMap(pose_k) straight into the stream's received-map buffer
-    for (int s = s0; s < s0 + count; s++) {
+    for (int i = 0; i < count; i++) {
+      const int s = stream_at(i);
       liodom_map* mp = h->mappers[s];
       if (!mp) continue;
       ProfScope ps(h, KID_OTHER);
@@ -456,44 +467,44 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
     ProfScope ps(h, KID_HASH_BUILD);        // window append + LDS-built cell hash, one workgroup per stream
     // (hash_incr: the new frame is appended to the table of the last rebuild; k_hash_build only works when that says so)
     // (hash_incr: k_hash_build every kHbPeriod-th scan, k_hash_append — the new frame into the cells of the last rebuild — in between)
-    // (per stream: a single-stream call of a lock-step handle steps one stream only.  A launch over several streams rebuilds them all
+    // (per stream: a single-stream call or a subset step of a lock-step handle steps some of the streams only.  A launch over several streams rebuilds them all
     //  if any one is due — a rebuild is always exact — so that lock-step batches keep every counter in step.)
     bool rebuild = !v.hash_incr;
-    for (int s = s0; s < s0 + count; s++) rebuild = rebuild || h->hb_since[s] < 0 || h->hb_since[s] >= kHbPeriod - 1;
-    for (int s = s0; s < s0 + count; s++) h->hb_since[s] = rebuild ? 0 : h->hb_since[s] + 1;
-    if (!rebuild) hipLaunchKernelGGL(k_hash_append, dim3(count), dim3(kBuildThreads), 0, h->stream, v, s0, eb);
-    else hipLaunchKernelGGL(k_hash_build, dim3(count), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, s0, eb);
+    for (int i = 0; i < count; i++) rebuild = rebuild || h->hb_since[stream_at(i)] < 0 || h->hb_since[stream_at(i)] >= kHbPeriod - 1;
+    for (int i = 0; i < count; i++) h->hb_since[stream_at(i)] = rebuild ? 0 : h->hb_since[stream_at(i)] + 1;
+    if (!rebuild) by_rows([&](auto L) { hipLaunchKernelGGL((k_hash_append<decltype(L)::value>), dim3(count), dim3(kBuildThreads), 0, h->stream, v, s0, eb); });
+    else by_rows([&](auto L) { hipLaunchKernelGGL((k_hash_build<decltype(L)::value>), dim3(count), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, s0, eb); });
   } else {
     {
       ProfScope ps(h, KID_WINDOW_INSERT);   // window append + cell hash in global memory, map_blocks workgroups per stream
-      hipLaunchKernelGGL(k_window_insert, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0, eb);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_window_insert<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0, eb); });
     }
     {
       ProfScope ps(h, KID_HASH_ALLOC);
-      hipLaunchKernelGGL(k_hash_alloc, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_hash_alloc<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
     }
     {
       ProfScope ps(h, KID_HASH_SCATTER);
-      hipLaunchKernelGGL(k_hash_scatter, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_hash_scatter<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
     }
   }
   if (v.filter_local_map) {     // VoxelGrid(0.4) of the full window (every kernel exits unless the window is full)
     {
       ProfScope ps(h, KID_OTHER);
-      hipLaunchKernelGGL(k_voxel_bbox, dim3(count), dim3(1024), 0, h->stream, v, s0);
-      hipLaunchKernelGGL(k_voxel_insert, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0);
-      hipLaunchKernelGGL(k_voxel_alloc, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0);
-      hipLaunchKernelGGL(k_voxel_scatter, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0);
-      hipLaunchKernelGGL(k_voxel_centroid, dim3(cdiv(h->v.map_cap, 8), count), dim3(256), 0, h->stream, v, s0);
-      hipLaunchKernelGGL(k_filt_insert, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_bbox<decltype(L)::value>), dim3(count), dim3(1024), 0, h->stream, v, s0); });
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_insert<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_alloc<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_scatter<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_centroid<decltype(L)::value>), dim3(cdiv(h->v.map_cap, 8), count), dim3(256), 0, h->stream, v, s0); });
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_filt_insert<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
     }
     {
       ProfScope ps(h, KID_HASH_ALLOC);
-      hipLaunchKernelGGL(k_filt_alloc, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_filt_alloc<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
     }
     {
       ProfScope ps(h, KID_HASH_SCATTER);
-      hipLaunchKernelGGL(k_filt_scatter, dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_filt_scatter<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
     }
   }
   HIP_TRY(hipGetLastError());
@@ -559,7 +570,7 @@ int drain_pipeline(liodom_handle* h) {
   if (h->pf_slot >= 0 || h->parity != 0 || h->pipe_active.exchange(false) || replayed) {
     HIP_TRY(hipStreamSynchronize(h->stream_x));
     HIP_TRY(sync_odometry(h));
-    h->pf_slot = -1; h->parity = 0; h->ev_free_valid[0] = h->ev_free_valid[1] = h->ev_free_valid[2] = false;
+    h->pf_slot = -1; h->pf_subset = false; h->parity = 0; h->ev_free_valid[0] = h->ev_free_valid[1] = h->ev_free_valid[2] = false;
     for (int b = 0; b < kEdgePipeBufs; b++) h->eb_reader[b] = 0;      // (everything has completed: nothing to wait for)
   }
   return LIODOM_OK;
@@ -567,23 +578,26 @@ int drain_pipeline(liodom_handle* h) {
 
 // The odometry of the scan in pipeline edge buffer eb behind whatever produces that buffer (extraction number wait_seq with
 // flags, ev_edges[eb] with events), as the pipelined replay and the device-resident hand-off enqueue it.  Odometry side.
-int enqueue_pipeline_odometry(liodom_handle* h, int eb, unsigned int wait_seq) {
+// (s0, count, list): the step's streams as launch_odometry takes them; every stream by default.
+int enqueue_pipeline_odometry(liodom_handle* h, int eb, unsigned int wait_seq, int s0 = 0, int count = -1, const int32_t* list = nullptr) {
   int rc;
+  if (count < 0) count = h->S;
   if (h->use_flags) {
     // no cross-stream events (they cost ~11 us of idle odometry stream per scan, with the host far ahead as well): the
     // first kNN launch waits for the extraction's flag and signals that the previous odometry has completed
     const unsigned int m = ++h->odo_seq == 0 ? ++h->odo_seq : h->odo_seq;
     if (h->flag_gate) {
-      hipLaunchKernelGGL(k_pipe_gate, dim3(1), dim3(64), 0, h->stream, h->v, 0, eb, wait_seq, m - 1u);
-      rc = launch_odometry(h, eb, 0, h->S);
+      if (s0 < 0) hipLaunchKernelGGL(k_pipe_gate<true>, dim3(1), dim3(64), 0, h->stream, h->v, s0, eb, wait_seq, m - 1u);
+      else hipLaunchKernelGGL(k_pipe_gate<>, dim3(1), dim3(64), 0, h->stream, h->v, s0, eb, wait_seq, m - 1u);
+      rc = launch_odometry(h, eb, s0, count, 0u, 0u, list);
     } else {
-      rc = launch_odometry(h, eb, 0, h->S, wait_seq, m - 1u);
+      rc = launch_odometry(h, eb, s0, count, wait_seq, m - 1u, list);
     }
     if (rc) return rc;
     h->eb_reader[eb] = m;
   } else {
     HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_edges[eb], 0));
-    rc = launch_odometry(h, eb, 0, h->S);
+    rc = launch_odometry(h, eb, s0, count, 0u, 0u, list);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(h->ev_free[eb], h->stream));
     h->ev_free_valid[eb] = true;
@@ -592,7 +606,9 @@ int enqueue_pipeline_odometry(liodom_handle* h, int eb, unsigned int wait_seq) {
 }
 
 // Extraction of resident slot `slot` into edge buffer `eb` on the extraction stream.
-int issue_extract(liodom_handle* h, int slot, int eb, int n, int height, int width) {
+// (s0, count): the streams as launch_extract takes them; every stream by default.  A list launch reads the slot by stream, so `in` is the slot's base either way.
+int issue_extract(liodom_handle* h, int slot, int eb, int n, int height, int width, int s0 = 0, int count = -1) {
+  if (count < 0) count = h->S;
   // while per-kernel profiling is on, everything runs on one stream so that the HIP-event
   // durations are not inflated by kernels of the other stream sharing the GPU
   hipStream_t q = extract_queue(h);
@@ -602,11 +618,11 @@ int issue_extract(liodom_handle* h, int slot, int eb, int n, int height, int wid
     // completed before k_compact_edges rewrites it; the last workgroup of k_compact_edges sets the flag of this extraction
     h->eb_seq[eb] = ++h->ext_seq;
     if (h->ext_seq == 0) h->eb_seq[eb] = ++h->ext_seq;      // (0 means "nothing to wait for")
-    return launch_extract(h, q, eb, 0, h->S, in, (size_t)h->v.max_points, n, height, width, h->eb_reader[eb], 0,
+    return launch_extract(h, q, eb, s0, count, in, (size_t)h->v.max_points, n, height, width, h->eb_reader[eb], 0,
                           h->v.pipe_flags + eb, nullptr, h->eb_seq[eb]);
   }
   if (h->ev_free_valid[eb]) HIP_TRY(hipStreamWaitEvent(q, h->ev_free[eb], 0));
-  int rc = launch_extract(h, q, eb, 0, h->S, in, (size_t)h->v.max_points, n, height, width);
+  int rc = launch_extract(h, q, eb, s0, count, in, (size_t)h->v.max_points, n, height, width);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
   return LIODOM_OK;
@@ -660,7 +676,7 @@ int reset_state(liodom_handle* h) {
     hipLaunchKernelGGL(k_init_cells, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->v);
     HIP_TRY(hipGetLastError());
   }
-  h->pf_slot = -1; h->parity = 0; h->last_eb = 0; h->ev_free_valid[0] = h->ev_free_valid[1] = h->ev_free_valid[2] = false;
+  h->pf_slot = -1; h->pf_subset = false; h->parity = 0; h->last_eb.assign((size_t)h->S, 0); h->ev_free_valid[0] = h->ev_free_valid[1] = h->ev_free_valid[2] = false;
   h->replay_live.store(false);
   h->hb_since.assign((size_t)h->S, -1);
   h->ext_seq = h->odo_seq = 0;
@@ -868,8 +884,8 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   if (h->ring_split_lb) {
     ALLOC(v.lb_desc, S * (size_t)v.tile_cap * v.lb_hpad, 0); ALLOC(v.lb_ticket, 1, 0); ALLOC(v.lb_ovf, S, 0);
     const size_t lds = ring_split_lb_lds_bytes(h->H);
-    if (lds > 48 * 1024 && (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split_lb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-                            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split_fix), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)) {
+    if (lds > 48 * 1024 && (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split_lb<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+                            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split_fix<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)) {
       (void)hipGetLastError(); h->ring_split_lb = false;
     }
   } else { v.lb_desc = nullptr; v.lb_ticket = nullptr; v.lb_ovf = nullptr; }
@@ -891,9 +907,9 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
       (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, config->device);
       const size_t lds = ring_scatter_lds_bytes(h->H);
       if (lds > 48 * 1024 &&
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         (void)hipGetLastError(); per_cu = 0;
-      } else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_ring_split), kTileThreads, lds) != hipSuccess) {
+      } else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_ring_split<>), kTileThreads, lds) != hipSuccess) {
         (void)hipGetLastError(); per_cu = 0;
       }
       long long budget = (long long)std::max(0, per_cu) * std::max(0, cus) / 2;
@@ -956,7 +972,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   ALLOC(v.lm_xch, S * 2 * kLmGroupsMax * 64, 0);
   ALLOC(v.pose_xch, S * 64, 0);
   ALLOC(v.redo_sync, 64, 0);
-  ALLOC(v.pipe_flags, kEdgePipeBufs + 1, 0);
+  ALLOC(v.pipe_flags, (size_t)kStreamListBase + (size_t)kStreamLists * S, 0);      // (+ the stream lists of subset steps, stream_of)
   v.host_edges = nullptr; v.host_edges_meta = nullptr; v.host_edges_hdr = nullptr;
   if (S == 1) {
     // device-resident hand-off (liodom_extract_edges_device): host-mapped mirror of the dense edges of the three pipeline buffers
@@ -1040,6 +1056,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
     v.host_out = static_cast<HostOut*>(dp);
     h->scans_enqueued.assign(S, 0);
+    h->last_eb.assign(S, 0);
     h->mappers.assign(S, nullptr); h->mapper_cells_xy.assign(S, 2); h->mapper_cells_z.assign(S, 1);
   }
   if (config->pose_covariance) {
@@ -1057,12 +1074,12 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     v.cov_raw = nullptr; v.cov_log = nullptr; v.cov_host = nullptr;
   }
   if (ring_scatter_lds_bytes(h->H) > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_scatter), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_scatter<>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)ring_scatter_lds_bytes(h->H)) != hipSuccess) {
       g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP);
     }
   }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hash_build), hipFuncAttributeMaxDynamicSharedMemorySize,
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hash_build<>), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)hash_build_lds_bytes()) != hipSuccess) {
     g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP);
   }
@@ -1081,6 +1098,27 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_extract<1024, kExIPLBig>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->ring_lds_bytes) != hipSuccess) {
       g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP);
     }
+  }
+  if (S > 1) {
+    // the list instances of the kernels above (subset steps, stream_of) take the same dynamic LDS
+    bool ok = true;
+    auto allow = [&](const void* f, size_t bytes, bool always = false) {
+      if ((always || bytes > 48 * 1024) && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) ok = false;
+    };
+    if (h->ring_split_lb) {
+      allow(reinterpret_cast<const void*>(&k_ring_split_lb<true>), ring_split_lb_lds_bytes(h->H));
+      allow(reinterpret_cast<const void*>(&k_ring_split_fix<true>), ring_split_lb_lds_bytes(h->H));
+    }
+    if (h->ring_split) allow(reinterpret_cast<const void*>(&k_ring_split<true>), ring_scatter_lds_bytes(h->H));
+    allow(reinterpret_cast<const void*>(&k_ring_scatter<true>), ring_scatter_lds_bytes(h->H));
+    allow(reinterpret_cast<const void*>(&k_hash_build<true>), hash_build_lds_bytes(), true);
+    allow(reinterpret_cast<const void*>(&k_lm_solve<0, false, true>), lm_lds_bytes(v.edge_cap), true);
+    allow(reinterpret_cast<const void*>(&k_lm_solve<1, false, true>), lm_lds_bytes(v.edge_cap), true);
+    allow(reinterpret_cast<const void*>(&k_ring_extract<256, kExIPL, true>), h->ring_lds_bytes);
+    allow(reinterpret_cast<const void*>(&k_ring_extract<256, kExIPLBig, true>), h->ring_lds_bytes);
+    allow(reinterpret_cast<const void*>(&k_ring_extract<1024, kExIPL, true>), h->ring_lds_bytes);
+    allow(reinterpret_cast<const void*>(&k_ring_extract<1024, kExIPLBig, true>), h->ring_lds_bytes);
+    if (!ok) { g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP); }
   }
   {
     // Overlapped second kNN pass: its workgroups wait inside the kernel for the first solve, so they must leave most of the GPU
@@ -1222,23 +1260,23 @@ static int install_stream_state(liodom_handle* h, int stream, const unsigned cha
   }
   if (n_frames > 0) {
     if (h->lds_hash_build) {
-      hipLaunchKernelGGL(k_hash_build, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
+      hipLaunchKernelGGL(k_hash_build<>, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
     } else {
       // (early_rebuild: the three kernels fill the table of parity frame_count & 1, the one the next scan searches; the other one
       //  and both overflow lists are empty)
-      hipLaunchKernelGGL(k_window_insert, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream, -1);
-      hipLaunchKernelGGL(k_hash_alloc, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_hash_scatter, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_window_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream, -1);
+      hipLaunchKernelGGL(k_hash_alloc<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_hash_scatter<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
     }
     if (v.filter_local_map) {     // VoxelGrid(0.4) of a full window (every kernel exits otherwise)
-      hipLaunchKernelGGL(k_voxel_bbox, dim3(1), dim3(1024), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_voxel_insert, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_voxel_alloc, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_voxel_scatter, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_voxel_centroid, dim3(cdiv(v.map_cap, 8), 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_filt_insert, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_filt_alloc, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_filt_scatter, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_bbox<>, dim3(1), dim3(1024), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_alloc<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_scatter<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_voxel_centroid<>, dim3(cdiv(v.map_cap, 8), 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_filt_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_filt_alloc<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+      hipLaunchKernelGGL(k_filt_scatter<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -1401,16 +1439,17 @@ int liodom_get_edges(liodom_handle_t* h, int stream, float* edges_xyzi, int32_t*
   int rc = check_stream(h, stream);
   if (rc) return rc;
   SideLocks lk(h, true, false);
-  return copy_edges_out(h, stream, h->last_eb, h->stream, edges_xyzi, edge_ring, edge_idx, edge_src, cap, n_edges);
+  return copy_edges_out(h, stream, h->last_eb[stream], h->stream, edges_xyzi, edge_ring, edge_idx, edge_src, cap, n_edges);
 }
 
-static int wait_pose(liodom_handle_t* h, int s0, int count, double* pose_out, liodom_step_info_t* info, int lag = 0) {
+static int wait_pose(liodom_handle_t* h, int s0, int count, double* pose_out, liodom_step_info_t* info, int lag = 0, const int32_t* list = nullptr) {
   // zero-copy: k_lm_solve's finalize writes pose + diagnostics into host-mapped memory and
   // releases HostOut.seq; spin on it (an event / memcpy round trip costs ~15 us on this stack)
   bool timed_out = false;
   for (int i = 0; i < count; i++) {
-    const int expect = h->scans_enqueued[s0 + i] - lag;      // lag 1: the scan before the one enqueued last
-    volatile HostOut* ho = h->host_out + (size_t)(s0 + i) * 2 + ((expect - 1) & 1);     // (scan k = expect - 1 publishes into record k & 1)
+    const int s = list ? (int)list[i] : s0 + i;      // (list: the streams of a subset step, results in list order)
+    const int expect = h->scans_enqueued[s] - lag;      // lag 1: the scan before the one enqueued last
+    volatile HostOut* ho = h->host_out + (size_t)s * 2 + ((expect - 1) & 1);     // (scan k = expect - 1 publishes into record k & 1)
     unsigned long long spins = 0;
     while (__atomic_load_n(&ho->seq, __ATOMIC_ACQUIRE) != expect) {
       if ((++spins & 0xFFFFull) == 0) {
@@ -1419,12 +1458,12 @@ static int wait_pose(liodom_handle_t* h, int s0, int count, double* pose_out, li
         if (q == hipSuccess && __atomic_load_n(&ho->seq, __ATOMIC_ACQUIRE) != expect) { g_last_error = "stream drained without publishing the scan result"; return LIODOM_ERR_HIP; }
       }
     }
-    const HostOut* r = h->host_out + (size_t)(s0 + i) * 2 + ((expect - 1) & 1);
+    const HostOut* r = h->host_out + (size_t)s * 2 + ((expect - 1) & 1);
     if (pose_out) std::memcpy(pose_out + 7 * i, r->pose, sizeof(double) * 7);
     if (info) info[i] = r->info;
     if (r->info.status & (LIODOM_STATUS_PIPE_TIMEOUT | LIODOM_STATUS_LM_SYNC_TIMEOUT)) timed_out = true;
     // (speculative hand-over: the record carries the scan's verdict — a confirmed scan needs no repair, chain_flush)
-    if (s0 + i == 0) { h->verdict_scan = expect; h->verdict_confirmed = r->pad == 1; }
+    if (s == 0) { h->verdict_scan = expect; h->verdict_confirmed = r->pad == 1; }
   }
   if (timed_out) {
     // A kernel gave up waiting for another HIP stream of the handle (pipe_wait / ov_wait_*): its workgroups skipped the scan, the
@@ -1659,11 +1698,11 @@ static int rebuild_search_structure(liodom_handle* h, int stream) {
   hipLaunchKernelGGL(k_hash_reset, dim3(64), dim3(256), 0, h->stream, v, stream);
   hipLaunchKernelGGL(k_hash_reset_done, dim3(1), dim3(1), 0, h->stream, v, stream);
   if (h->lds_hash_build) {
-    hipLaunchKernelGGL(k_hash_build, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
+    hipLaunchKernelGGL(k_hash_build<>, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
   } else {
-    hipLaunchKernelGGL(k_window_insert, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream, -1);
-    hipLaunchKernelGGL(k_hash_alloc, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-    hipLaunchKernelGGL(k_hash_scatter, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+    hipLaunchKernelGGL(k_window_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream, -1);
+    hipLaunchKernelGGL(k_hash_alloc<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
+    hipLaunchKernelGGL(k_hash_scatter<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
   }
   HIP_TRY(hipGetLastError());
   return LIODOM_OK;
@@ -1748,7 +1787,7 @@ int liodom_alloc_resident(liodom_handle_t* h, int n_slots) {
   SideLocks lk(h, true, true);
   HIP_TRY(hipStreamSynchronize(h->stream_x));       // an extraction issued ahead may still read the old buffer
   HIP_TRY(sync_odometry(h));
-  h->pf_slot = -1;
+  h->pf_slot = -1; h->pf_subset = false;
   if (h->resident) { hipFree(h->resident); h->resident = nullptr; h->n_slots = 0; }
   const size_t bytes = sizeof(float4) * (size_t)h->S * (size_t)n_slots * (size_t)h->v.max_points;
   void* raw = nullptr;
@@ -1785,6 +1824,84 @@ int liodom_process_resident_pipelined(liodom_handle_t* h, int slot, int next_slo
   SideLocks lk(h, true, true);
   if ((rc0 = tickets_idle(h))) return rc0;        // (the replay fills the same pipeline edge buffers)
   return replay_one(h, slot, next_slot, n, height, width, poses_out != nullptr || infos_out != nullptr, poses_out, infos_out);
+}
+
+// ---- subset steps: a lock-step step over a list of streams (liodom_process_resident_subset) ----
+// A strictly ascending list of stream numbers in [0, n_streams).
+static bool stream_list_valid(const liodom_handle* h, const int32_t* streams, int n) {
+  if (n < 0 || n > h->S || (n > 0 && !streams)) return false;
+  for (int i = 0; i < n; i++)
+    if (streams[i] < 0 || streams[i] >= h->S || (i > 0 && streams[i] <= streams[i - 1])) return false;
+  return true;
+}
+// Stream list `list_id` (stream_of in liodom_kernels.h) on HIP stream q, in front of the launches that read it.  The entries
+// travel in the kernel arguments of k_put_list: the caller's array is free when this returns, however far the host runs ahead.
+// (Not booked by per-kernel profiling, like the copies of the other entry points: it is the step's argument, not a stage of it.)
+static int put_stream_list(liodom_handle* h, hipStream_t q, int list_id, const int32_t* streams, int n) {
+  for (int first = 0; first < n; first += kStreamListChunk) {
+    StreamListChunk c;
+    const int cnt = std::min(kStreamListChunk, n - first);
+    std::memcpy(c.s, streams + first, sizeof(int32_t) * (size_t)cnt);
+    hipLaunchKernelGGL(k_put_list, dim3(1), dim3(kStreamListChunk), 0, q, h->v, list_id, first, cnt, c);
+  }
+  HIP_TRY(hipGetLastError());
+  return LIODOM_OK;
+}
+// Extraction of the listed streams of resident slot `slot` into pipeline edge buffer eb (list eb, uploaded on the extraction stream:
+// the previous extraction into eb, the list's last reader there, precedes it in stream order).  The full list is the plain extraction.
+static int issue_extract_list(liodom_handle* h, int slot, int eb, int n, int height, int width, const int32_t* streams, int count) {
+  if (count == h->S) return issue_extract(h, slot, eb, n, height, width);
+  const int rc = put_stream_list(h, extract_queue(h), eb, streams, count);
+  if (rc) return rc;
+  return issue_extract(h, slot, eb, n, height, width, -eb - 1, count);
+}
+
+int liodom_process_resident_subset(liodom_handle_t* h, int slot, const int32_t* streams, int n_active,
+                                   int next_slot, const int32_t* next_streams, int n_next,
+                                   int64_t n, int height, int width, double* poses_out, liodom_step_info_t* infos_out) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if ((rc = check_usable(h))) return rc;
+  if (!stream_list_valid(h, streams, n_active)) { g_last_error = "liodom_process_resident_subset: streams must be strictly ascending stream indices"; return LIODOM_ERR_INVALID_ARG; }
+  if (next_slot >= 0 && !next_streams) { next_streams = streams; n_next = n_active; }      // (the same streams step again)
+  if (next_slot >= 0 && !stream_list_valid(h, next_streams, n_next)) { g_last_error = "liodom_process_resident_subset: next_streams must be strictly ascending stream indices"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, true, true);
+  if ((rc = tickets_idle(h))) return rc;        // (the pipeline edge buffers, as the replay)
+  const bool wait = poses_out != nullptr || infos_out != nullptr;
+  // every stream now, and every stream (or nothing) ahead: the plain step, launch for launch
+  if (n_active == h->S && (next_slot < 0 || n_next == h->S)) return replay_one(h, slot, next_slot, n, height, width, wait, poses_out, infos_out);
+  if (!h->resident || slot < 0 || slot >= h->n_slots || next_slot >= h->n_slots || n < 0 || n > h->v.max_points) {
+    g_last_error = "bad resident slot"; return LIODOM_ERR_INVALID_ARG;
+  }
+  h->replay_live.store(true);
+  const bool full = n_active == h->S;
+  if (n_active > 0) {
+    const int eb = h->parity;
+    // issued ahead for exactly these streams?  Anything else — another slot, another list, nothing — is extracted now
+    const bool ahead = h->pf_slot == slot && (full ? !h->pf_subset
+                                                   : (h->pf_subset && (int)h->pf_list.size() == n_active && std::equal(streams, streams + n_active, h->pf_list.begin())));
+    if (!ahead) { rc = issue_extract_list(h, slot, eb, (int)n, height, width, streams, n_active); if (rc) return rc; }
+    h->pf_slot = -1; h->pf_subset = false;
+    if (full) {
+      rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb]);
+    } else {
+      // (list kEdgePipeBufs + eb, uploaded on the odometry stream behind the previous odometry of buffer eb)
+      rc = put_stream_list(h, h->stream, kEdgePipeBufs + eb, streams, n_active);
+      if (rc) return rc;
+      rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb], -(kEdgePipeBufs + eb) - 1, n_active, streams);
+    }
+    if (rc) return rc;
+    h->parity = (eb + 1) % kEdgePipeBufs;
+  }
+  h->subset_steps++;
+  if (next_slot >= 0) {
+    // (an extraction issued ahead earlier and not consumed — n_active == 0 — is replaced: same buffer, same HIP stream)
+    if (n_next > 0) { rc = issue_extract_list(h, next_slot, h->parity, (int)n, height, width, next_streams, n_next); if (rc) return rc; }
+    h->pf_slot = next_slot; h->pf_subset = n_next != h->S;
+    h->pf_list.assign(next_streams, next_streams + n_next);
+  }
+  if (wait && n_active > 0) return wait_pose(h, full ? 0 : -1, n_active, poses_out, infos_out, 0, full ? nullptr : streams);
+  return LIODOM_OK;
 }
 
 int liodom_replay_resident(liodom_handle_t* h, int first_slot, int count, int ahead, int depth, int64_t n, int height, int width,
@@ -1871,7 +1988,7 @@ static int replay_one(liodom_handle_t* h, int slot, int next_slot, int64_t n, in
   h->replay_live.store(true);
   const int eb = h->parity;
   int rc;
-  if (h->pf_slot != slot) {                       // extraction not issued ahead: do it now
+  if (h->pf_slot != slot || h->pf_subset) {       // extraction not issued ahead (or for some streams only, by a subset step): do it now
     rc = issue_extract(h, slot, eb, (int)n, height, width);
     if (rc) return rc;
   }
@@ -1886,7 +2003,7 @@ static int replay_one(liodom_handle_t* h, int slot, int next_slot, int64_t n, in
     rc = issue_extract(h, next_slot, h->parity, (int)n, height, width);
     if (rc) return rc;
     if (next_host) { rc = upload_slot_consumed(h, next_slot); if (rc) return rc; }
-    h->pf_slot = next_slot;
+    h->pf_slot = next_slot; h->pf_subset = false;
   }
   if (wait) return wait_pose(h, 0, h->S, poses_out, infos_out);
   return LIODOM_OK;
@@ -1922,7 +2039,7 @@ int liodom_replay_host(liodom_handle_t* h, const float* xyzi_base, int64_t scan_
       if (rc) return rc;
       rc = issue_extract(h, slot, h->parity, (int)n, height, width);
       if (rc) return rc;
-      h->pf_slot = slot;
+      h->pf_slot = slot; h->pf_subset = false;
       rc = upload_slot_consumed(h, slot);
       if (rc) return rc;
     }
@@ -2091,7 +2208,7 @@ int liodom_get_correspondences(liodom_handle_t* h, int stream, int it, int32_t* 
   HIP_TRY(sync_odometry(h));
   StreamState st;
   HIP_TRY(hipMemcpy(&st, h->v.state + stream, sizeof(st), hipMemcpyDeviceToHost));
-  const int E = st.n_edges_buf[h->last_eb];
+  const int E = st.n_edges_buf[h->last_eb[stream]];
   if (n) *n = E;
   if (E > cap) { g_last_error = "correspondence buffer too small"; return LIODOM_ERR_CAPACITY; }
   std::vector<int2> ci((size_t)std::max(E, 1));
@@ -2112,7 +2229,7 @@ int liodom_get_knn_queries(liodom_handle_t* h, int stream, int it, float* xyz0, 
   SideLocks lk(h, true, false);
   HIP_TRY(sync_odometry(h));
   int E = 0;
-  HIP_TRY(hipMemcpy(&E, &h->v.state[stream].n_edges_buf[h->last_eb], sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&E, &h->v.state[stream].n_edges_buf[h->last_eb[stream]], sizeof(int), hipMemcpyDeviceToHost));
   if (n) *n = E;
   if (E > cap) { g_last_error = "query buffer too small"; return LIODOM_ERR_CAPACITY; }
   if (E && xyz0) HIP_TRY(hipMemcpy(xyz0, h->v.knn_q + ((size_t)stream * 2 + it) * h->v.edge_cap, sizeof(float4) * (size_t)E, hipMemcpyDeviceToHost));
@@ -2254,6 +2371,10 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   if (v.cov_raw) {
     const size_t len = std::strlen(buf);
     snprintf(buf + len, (size_t)cap - len, " pose_cov=1");
+  }
+  {
+    const size_t len = std::strlen(buf);      // (steps liodom_process_resident_subset ran over a stream list, i.e. did not hand to the plain step)
+    snprintf(buf + len, (size_t)cap - len, " subset_steps=%lld", h->subset_steps);
   }
   return LIODOM_OK;
 }

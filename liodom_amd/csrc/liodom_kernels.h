@@ -1,6 +1,7 @@
 // liodom_kernels.h — hand-written HIP kernels of the LiODOM hot path for gfx950 (CDNA4).
 //
-// Kernel map (one launch covers all streams: blockIdx.y = stream):
+// Kernel map (one launch covers all streams of a step: blockIdx.y — blockIdx.x in the one-workgroup-per-stream kernels — is the ROW of the
+// launch, stream_of() below turns it into the stream: s0 + row for a contiguous range, an entry of a stream list for a subset step):
 //   k_classify        A1/A2  isValidPoint + ring id per point, per-tile ring histogram (feature_extractor.cc:84-179)
 //   k_ring_scatter    A2     stable counting sort of the scan by ring (input order kept per ring)
 //   k_ring_extract    A3-A5  11-tap curvature stencil in registers (float sums, double squares) ->
@@ -69,6 +70,9 @@ constexpr int kEdgeBufX = 3;
 constexpr int kOvReplicas = 8;           // copies of the first solve's result, 4 KiB apart, for the polling k_knn workgroups
 constexpr int kOvGranules = 38;          // 19 doubles as {tag, 32 bits} granules
 constexpr int kPredGranules = 38;        // 19 doubles (pred_xch): the prediction's matrix [12], its quaternion [4] and translation [3] (= the next solve's start point)
+constexpr int kStreamLists = 2 * kEdgePipeBufs;   // stream lists of subset steps (stream_of): [b] the extraction into pipeline edge buffer b, [kEdgePipeBufs + b] the odometry of that buffer
+constexpr int kStreamListBase = 64;      // first word of list 0 behind DevView::pipe_flags (the flags keep their cache lines); a list holds n_streams words
+constexpr int kStreamListChunk = 256;    // entries one k_put_list launch carries in its kernel arguments
 
 // Per-stream device state.
 struct StreamState {
@@ -306,6 +310,47 @@ __device__ __forceinline__ bool filter_active(const DevView& v, const StreamStat
 }
 
 // ---------------------------------------------------------------------------------------------
+// Row of a launch -> stream.  Every launch of the per-scan path covers `count` rows (blockIdx.y, or .x where a stream is one
+// workgroup).  Instances without a list (kList = false, every launch but those of a subset step): the rows are the streams s0,
+// s0 + 1, ...  List instances (kList = true, s0 < 0; liodom_process_resident_subset): the rows are the entries of stream list
+// -s0 - 1, strictly ascending stream numbers in device memory behind the pipe flags — no kernel parameter, nothing new in DevView.
+// The list was written by a launch in front of this one on the same HIP stream (k_put_list) and is rewritten only behind it, so
+// it is constant while the kernel runs: the entry comes through the constant address space, i.e. one scalar load per wave for a
+// wave-uniform row.
+// What means "this stream" (state, window, tables, logs, the stream's place in a resident slot) goes by the stream; what means
+// "first workgroup of the launch" (resetting lb_ticket, publishing the pipe flag) stays on the row.
+typedef const __attribute__((address_space(4))) int* stream_list_ptr;
+__device__ __forceinline__ stream_list_ptr stream_list(const DevView& v, int s0) {
+  return (stream_list_ptr)(reinterpret_cast<const int*>(v.pipe_flags) + kStreamListBase + (size_t)(-s0 - 1) * (size_t)v.n_streams);
+}
+// kList is a template parameter of every kernel a subset step can reach, not a run-time test of s0: a branch on s0 in front of
+// everything makes the kernel wait for that argument before it issues its other argument loads — one more round trip per
+// workgroup and launch, measured as 0.5 - 1.4 % of bench.py's legs.  The instances without a list are the code they were.
+// (row is wave-uniform: a block index, or k_ring_split_lb's ticket out of LDS — the list instance says so to the compiler)
+template <bool kList>
+__device__ __forceinline__ int stream_of(const DevView& v, int s0, int row) {
+  if constexpr (!kList) return s0 + row;
+  else return stream_list(v, s0)[__builtin_amdgcn_readfirstlane(row)];
+}
+// (row differs between the lanes: k_imu_override, one thread per stream)
+template <bool kList>
+__device__ __forceinline__ int stream_of_lane(const DevView& v, int s0, int row) {
+  if constexpr (!kList) return s0 + row;
+  else return stream_list(v, s0)[row];
+}
+// Input scans: a range launch gets `in` offset to stream s0 and reads row after row (in_stride may be 0: one staged scan); a list
+// launch gets the base of the resident slot and every stream reads its own place.
+template <bool kList>
+__device__ __forceinline__ int scan_row_of(int s0, int row, int s) { (void)s0; return kList ? s : row; }
+// Uploads (a chunk of) a stream list: the entries travel in the kernel arguments, so the host's copy is free when the launch call
+// returns and the list is in place, in stream order, before its first reader — no staging buffer whose lifetime the host would
+// have to track while it runs steps ahead of the GPU.
+struct StreamListChunk { int s[kStreamListChunk]; };
+__global__ __launch_bounds__(kStreamListChunk) void k_put_list(DevView v, int list, int first, int count, StreamListChunk c) {
+  int* dst = reinterpret_cast<int*>(v.pipe_flags) + kStreamListBase + (size_t)list * (size_t)v.n_streams + first;
+  if ((int)threadIdx.x < count) dst[threadIdx.x] = c.s[threadIdx.x];
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (kWave - 1); }
 // In-kernel instrumentation (phase timestamps, per-query times, histograms; tools/gpu_debug.py) exists only in builds with
 // -DLIODOM_INSTRUMENT (tools/variant_build.sh): the product library carries none of it — no debug branches in the hot kernels.

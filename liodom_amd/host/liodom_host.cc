@@ -180,6 +180,17 @@ void Engine::loadState(const std::vector<uint8_t>& blob, int stream) {
   check(liodom_import_stream_state(h_, stream, blob.data(), (int64_t)blob.size()), "liodom_import_stream_state");
 }
 
+std::vector<std::array<double, 7>> Engine::stepSubset(int slot, const std::vector<int32_t>& streams, int64_t n, int height, int width,
+                                                      int next_slot, const std::vector<int32_t>* next_streams) {
+  std::vector<std::array<double, 7>> poses(streams.size());
+  std::vector<liodom_step_info_t> infos(streams.size());
+  check(liodom_process_resident_subset(h_, slot, streams.data(), (int)streams.size(), next_slot,
+                                       next_streams ? next_streams->data() : nullptr, next_streams ? (int)next_streams->size() : 0,
+                                       n, height, width, poses.empty() ? nullptr : poses[0].data(), infos.empty() ? nullptr : infos.data()),
+        "liodom_process_resident_subset");
+  return poses;
+}
+
 FeatureExtractor::FeatureExtractor(std::shared_ptr<Engine> e)
     : eng_(std::move(e)), params(Params::getInstance()), stats(Stats::getInstance()) {}
 

@@ -135,6 +135,11 @@ class Engine {
   void resetStream(int stream = 0);
   std::vector<uint8_t> saveState(int stream = 0);
   void loadState(const std::vector<uint8_t>& blob, int stream = 0);
+  // One lock-step step of resident slot `slot` for the streams in `streams` only (strictly ascending; liodom_process_resident_subset;
+  // no counterpart in the reference): the other streams sit the step out.  Returns the listed streams' poses [x y z w tx ty tz]
+  // in list order.  next_slot >= 0 issues that slot's extraction ahead for next_streams (null: the same list).
+  std::vector<std::array<double, 7>> stepSubset(int slot, const std::vector<int32_t>& streams, int64_t n, int height, int width,
+                                                int next_slot = -1, const std::vector<int32_t>* next_streams = nullptr);
  private:
   liodom_handle_t* h_ = nullptr;
   bool covariance_ = false;

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Continuous batching: N logs of unequal length through an S-stream lock-step handle with S < N.  Every slot (stream) replays one
-log; when its log ends the slot is reset (liodom_reset_stream) and takes the next log in line, while the other slots go on.  A
-stream cannot sit out a lock-step step: a slot with no log left is fed its last scan again and its result is dropped.
+log; when its log ends the slot is reset (liodom_reset_stream) and takes the next log in line, while the other slots go on.  A slot with no
+log left is fed its last scan again and its result is dropped (the default), or — with --sit-out — left out of the step
+(liodom_process_resident_subset): the step then runs over the busy slots only and the GPU processes no scan that does not count.
 
-    tools/batch_logs.py [--streams 16] [--logs 24] [--min-len 6] [--max-len 40] [--shape 16x900] [--out DIR]
+    tools/batch_logs.py [--streams 16] [--logs 24] [--min-len 6] [--max-len 40] [--shape 16x900] [--sit-out] [--out DIR]
 
 replays synthetic logs, prints aggregate scans/s and writes DIR/log_NNN.txt (one pose per line: qx qy qz qw tx ty tz).
-run(g, logs, H, W) is the loop itself, for callers with their own handle and clouds."""
+run(g, logs, H, W, sit_out=False) is the loop itself, for callers with their own handle and clouds."""
 import argparse
 import os
 import sys
@@ -17,9 +18,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(g, logs, H, W):
-    """logs[i][k]: scan k of log i (float32 [H * W, 4]).  Returns dict(poses = per log its [len, 7] poses, slot_of_log, steps,
-    scans, seconds, status_bits = OR of the status bits of every scan that counted)."""
+def run(g, logs, H, W, sit_out=False):
+    """logs[i][k]: scan k of log i (float32 [H * W, 4]).  sit_out: idle slots are left out of the step instead of being fed their
+    last scan.  Returns dict(poses = per log its [len, 7] poses, slot_of_log, steps, scans, gpu_scans = scans the GPU processed
+    (counted or dropped), seconds, status_bits = OR of the status bits of every scan that counted)."""
     S = int(g.config.n_streams)
     n = H * W
     queue = list(range(len(logs)))
@@ -29,7 +31,7 @@ def run(g, logs, H, W):
     poses = {i: [] for i in range(len(logs))}
     slot_of_log = {}
     status = 0
-    steps = scans = 0
+    steps = scans = gpu_scans = 0
     g.alloc_resident(1)
     t0 = time.perf_counter()
     while True:
@@ -43,23 +45,28 @@ def run(g, logs, H, W):
                     g.reset_stream(s)          # the slot's next scan is the first of its new log
         if all(c is None for c in cur):
             break
-        for s in range(S):
+        active = [s for s in range(S) if cur[s] is not None] if sit_out else list(range(S))
+        for s in active:
             if cur[s] is not None:
                 last[s] = logs[cur[s]][pos[s]]
             elif last[s] is None:
                 last[s] = next(logs[c][0] for c in cur if c is not None)
             g.upload_scan(s, 0, last[s])
-        out, infos = g.process_resident(0, n, H, W, readback=True)
+        if sit_out:
+            out, infos = g.process_resident_subset(0, active, n, H, W, readback=True)
+        else:
+            out, infos = g.process_resident(0, n, H, W, readback=True)
         steps += 1
-        for s in range(S):
+        gpu_scans += len(active)
+        for i, s in enumerate(active):
             if cur[s] is None:
                 continue
-            poses[cur[s]].append(out[s].copy())
-            status |= int(infos[s].status)
+            poses[cur[s]].append(out[i].copy())
+            status |= int(infos[i].status)
             pos[s] += 1
             scans += 1
     secs = time.perf_counter() - t0
-    return dict(poses={i: np.array(p).reshape(-1, 7) for i, p in poses.items()}, slot_of_log=slot_of_log, steps=steps, scans=scans,
+    return dict(poses={i: np.array(p).reshape(-1, 7) for i, p in poses.items()}, slot_of_log=slot_of_log, steps=steps, scans=scans, gpu_scans=gpu_scans,
                 seconds=secs, status_bits=status)
 
 
@@ -71,6 +78,7 @@ def main():
     ap.add_argument("--max-len", type=int, default=40)
     ap.add_argument("--shape", default="16x900")
     ap.add_argument("--prev-frames", type=int, default=5)
+    ap.add_argument("--sit-out", action="store_true", help="leave idle slots out of the step instead of feeding them their last scan")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import liodom_amd as la
@@ -83,10 +91,10 @@ def main():
     logs = [[synth.scan(cfg, i, k)[0] for k in range(int(lengths[i]))] for i in range(a.logs)]
     g = la.Liodom(la.make_params(scan_lines=H, scan_regions=6 if H <= 16 else 8, prev_frames=a.prev_frames),
                   la.make_config(n_streams=a.streams, max_points=H * W, max_width=W))
-    r = run(g, logs, H, W)
+    r = run(g, logs, H, W, sit_out=a.sit_out)
     g.close()
-    print("%d logs (%d scans) through %d streams in %d lock-step steps: %.0f scans/s aggregate (uploads included), status bits 0x%x"
-          % (a.logs, r["scans"], a.streams, r["steps"], r["scans"] / r["seconds"], r["status_bits"]))
+    print("%d logs (%d scans) through %d streams in %d lock-step steps%s, %d scans processed by the GPU: %.0f scans/s aggregate (uploads included), status bits 0x%x"
+          % (a.logs, r["scans"], a.streams, r["steps"], " (idle slots sit out)" if a.sit_out else "", r["gpu_scans"], r["scans"] / r["seconds"], r["status_bits"]))
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         for i, p in r["poses"].items():
