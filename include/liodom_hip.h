@@ -236,6 +236,81 @@ int liodom_odometry_collect(liodom_handle_t* h, int stream, double* pose_out, li
 int liodom_process_scan(liodom_handle_t* h, int stream, const float* xyzi, int64_t n, int height,
                         int width, double stamp, double* pose_out, liodom_step_info_t* info);
 
+/* ---- polar scans: upload range counts, project to XYZI on the device ----
+ * No sensor produces packed XYZI.  A Velodyne firing is a 16-bit distance and an 8-bit intensity per laser plus one encoder azimuth
+ * per column; an Ouster column is a 32- or 16-bit range and a 16-bit signal per row plus one encoder tick.  In front of the reference
+ * the sensor driver projects every return to Cartesian coordinates on a CPU core and pcl::fromROSMsg copies the result into the
+ * cloud (lidarClb, src/liodom_node.cc:40-44): 16 bytes per point reach the device.  The calls below take the sensor's own numbers —
+ * 3 to 6 bytes per point — and do that projection on the device, on the stream that carries the upload, in front of the unchanged
+ * extraction.  Opt-in: a handle that never sets a polar geometry allocates and launches exactly what it does without them.
+ *
+ * The geometry is made of tables, not angles: the library does no trigonometry and the projected cloud is defined bit for bit.
+ * For a point of row `row` with range count c, in a column with encoder tick t (float arithmetic, every product and sum rounded
+ * on its own; polar_project_point in liodom_math.h):
+ *     r = (float)c * range_unit      d = r - beam_origin      h = d * cos_alt[row]
+ *     ct = cos_enc[t] * cos_baz[row] - sin_enc[t] * sin_baz[row]        st = sin_enc[t] * cos_baz[row] + cos_enc[t] * sin_baz[row]
+ *     x = h * ct + beam_origin * cos_enc[t]      y = h * st + beam_origin * sin_enc[t]      z = d * sin_alt[row]
+ *     w = (float)intensity  (0 without an intensity section)
+ * c == 0 (no return) or t >= ticks (then for the whole column): x = y = z = the quiet NaN 0x7FC00000, w is kept; isValidPoint
+ * (src/feature_extractor.cc:84-102) drops such points as it drops a driver's NaN returns.
+ *
+ * A scan is one contiguous little-endian blob (one copy): uint32 tick[width], then the counts [height * width] of range_bits,
+ * then the intensities [height * width] of intensity_bits (nothing for 0 bits); every section starts on a 16-byte boundary
+ * (liodom_polar_layout).  Point i of the two [height * width] sections is the point i of the packed cloud the handle's lidar_type
+ * expects: lidar_type 0: i = col * height + row (firing order); lidar_type 1: i = row * width + col.  Downstream nothing changes:
+ * lidar_type 0 still finds the rings by the elevation binning of the projected points, the row is not used as the ring. */
+typedef struct liodom_polar_geometry_t {
+  int32_t height, width;         /* H rows (beams), W columns; n = H * W points per scan, at most config.max_points; H <= 2048 */
+  int32_t range_bits;            /* 16 or 32 */
+  int32_t intensity_bits;        /* 0, 8 or 16 */
+  float range_unit;              /* metres per count */
+  float beam_origin;             /* distance from the lidar origin to the beam origin (Ouster's n); 0 for a Velodyne */
+  const float* cos_alt;          /* [H] beam altitude */
+  const float* sin_alt;
+  const float* cos_baz;          /* [H] azimuth offset of the beam */
+  const float* sin_baz;
+  int32_t ticks;                 /* T: entries of the encoder table (>= 1) */
+  int32_t reserved;
+  const float* cos_enc;          /* [T] azimuth of encoder tick t */
+  const float* sin_enc;
+} liodom_polar_geometry_t;
+typedef struct liodom_polar_layout_t {
+  int64_t tick_offset;           /* 0 */
+  int64_t range_offset;
+  int64_t intensity_offset;      /* = total_bytes when intensity_bits is 0 */
+  int64_t total_bytes;           /* a multiple of 16 */
+} liodom_polar_layout_t;
+/* Offsets and size of a blob of this geometry (the tables are not looked at).  Needs no handle and no device.  No counterpart in
+ * the reference.  LIODOM_ERR_INVALID_ARG for a range_bits / intensity_bits / height / width the geometry calls refuse. */
+int liodom_polar_layout(const liodom_polar_geometry_t* geom, liodom_polar_layout_t* out);
+/* Sets (or replaces) the handle's polar geometry — the calibration a sensor driver reads once (beam_altitude_angles /
+ * beam_azimuth_angles / lidar_origin_to_beam_origin_mm of an Ouster, the laser corrections of a Velodyne); no counterpart in the
+ * reference, which sees projected clouds only.  Copies the tables to the device, allocates three compact staging slots there and
+ * a page-locked ring of three blobs on the host.  Not on the per-scan path: takes both sides of the handle and waits for its
+ * streams.  LIODOM_ERR_INVALID_ARG: a null table, range_bits not 16 / 32, intensity_bits not 0 / 8 / 16, ticks < 1, height < 1 or
+ * > 2048, width < 1; LIODOM_ERR_CAPACITY: height * width > config.max_points; LIODOM_ERR_BUSY: edge tickets are outstanding.  The
+ * handle is untouched in every error case (an earlier geometry stays).  Every other polar call returns LIODOM_ERR_UNSUPPORTED until
+ * a geometry has been set; n, height and width of a polar scan are the geometry's. */
+int liodom_set_polar_geometry(liodom_handle_t* h, const liodom_polar_geometry_t* geom);
+/* The driver's projection + pcl::fromROSMsg (src/liodom_node.cc:43-44) alone: projects one blob (host) and returns the packed cloud
+ * (host, height * width points) — for callers that publish the cloud, and for tests.  Extraction side. */
+int liodom_project_polar(liodom_handle_t* h, const void* blob, float* xyzi_out);
+/* liodom_upload_scan for a blob: uploads it and projects it into resident slot `slot` of stream `stream`.  Replaces the driver's
+ * projection + pcl::fromROSMsg in front of a resident replay.  Any n_streams; everything resident stays XYZI, so
+ * liodom_process_resident* and the subset steps read the slot as they read one written by liodom_upload_scan, and the two may be
+ * mixed on one handle. */
+int liodom_upload_scan_polar(liodom_handle_t* h, int stream, int slot, const void* blob);
+/* liodom_process_scan for a blob: the driver's projection + lidarClb -> FeatureExtractor -> LaserOdometer for one scan
+ * (src/liodom_node.cc:40-55 + the two worker loops).  Poses, edges and infos are those of liodom_process_scan on the projected cloud. */
+int liodom_process_scan_polar(liodom_handle_t* h, int stream, const void* blob, double stamp, double* pose_out, liodom_step_info_t* info);
+/* The ticket path for blobs (one-stream handles): liodom_scan_buffer_polar hands out a page-locked blob (*bytes =
+ * liodom_polar_layout's total) to assemble the next scan in — the place of the driver's output buffer and of pcl::fromROSMsg's
+ * target in lidarClb; liodom_extract_edges_device_polar is liodom_extract_edges_device (feature_extractor.cc:49-77) with the
+ * projection between the upload and the extraction, same slots, same back-pressure (LIODOM_ERR_BUSY), same rules for page-locked,
+ * registered and pageable memory.  Its tickets are consumed by liodom_wait_edges and liodom_odometry_*_device like any other. */
+int liodom_scan_buffer_polar(liodom_handle_t* h, int stream, void** blob, int64_t* bytes);
+int liodom_extract_edges_device_polar(liodom_handle_t* h, int stream, const void* blob, liodom_edge_ticket_t* ticket);
+
 /* mapClb -> SharedData::setLocalMap (src/liodom_node.cc:57-64).  Only with mapping = 1: the next
  * scan's kNN cloud is window ++ this cloud (src/laser_odometry.cc:276-278,310-314). */
 int liodom_set_received_map(liodom_handle_t* h, int stream, const float* xyzi, int64_t n);

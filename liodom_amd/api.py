@@ -12,7 +12,7 @@ _HASH = _LIB + ".srchash"
 _BUILD_INFO = {"rebuilt": None, "source_hash": None}
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kernels.h", "kernels_extract.h", "kernels_sync.h",
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
-                                                  "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "liodom_math.h", "wave_ops.h",
+                                                  "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -155,6 +155,7 @@ class EdgeTicket(C.Structure):
 
 
 ERR_INVALID_ARG = -1
+ERR_UNSUPPORTED = -2
 ERR_CAPACITY = -3
 ERR_BUSY = -6
 ERR_NEEDS_SYNC = -7
@@ -211,6 +212,73 @@ def parse_stream_state(blob):
     out["frames"] = [out["window"][starts[j]:starts[j + 1]] for j in range(out["n_frames"])]
     out["received_map"] = pts[n_points:].copy()
     return out
+
+
+class PolarGeometry(C.Structure):
+    """liodom_polar_geometry_t: a polar scan's shape, number widths and tables (include/liodom_hip.h)."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("range_bits", C.c_int32), ("intensity_bits", C.c_int32),
+                ("range_unit", C.c_float), ("beam_origin", C.c_float),
+                ("cos_alt", C.POINTER(C.c_float)), ("sin_alt", C.POINTER(C.c_float)),
+                ("cos_baz", C.POINTER(C.c_float)), ("sin_baz", C.POINTER(C.c_float)),
+                ("ticks", C.c_int32), ("reserved", C.c_int32),
+                ("cos_enc", C.POINTER(C.c_float)), ("sin_enc", C.POINTER(C.c_float))]
+
+
+class PolarLayout(C.Structure):
+    _fields_ = [("tick_offset", C.c_int64), ("range_offset", C.c_int64), ("intensity_offset", C.c_int64), ("total_bytes", C.c_int64)]
+
+
+_POLAR_TABLES = ("cos_alt", "sin_alt", "cos_baz", "sin_baz", "cos_enc", "sin_enc")
+
+
+def polar_geometry(height, width, range_bits, intensity_bits, range_unit, beam_origin, cos_alt, sin_alt, cos_baz, sin_baz,
+                   cos_enc, sin_enc):
+    """A PolarGeometry from float32 tables ([height] x 4, [ticks] x 2).  The arrays are kept alive by the returned object (.tables)."""
+    g = PolarGeometry()
+    g.height, g.width, g.range_bits, g.intensity_bits = int(height), int(width), int(range_bits), int(intensity_bits)
+    g.range_unit, g.beam_origin = float(np.float32(range_unit)), float(np.float32(beam_origin))
+    g.tables = {}
+    for name, a in zip(_POLAR_TABLES, (cos_alt, sin_alt, cos_baz, sin_baz, cos_enc, sin_enc)):
+        g.tables[name] = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+        setattr(g, name, _fp(g.tables[name]))
+    g.ticks = int(g.tables["cos_enc"].shape[0])
+    return g
+
+
+def polar_geometry_from_angles(height, width, altitude_rad, beam_azimuth_rad, encoder_rad, range_bits=16, intensity_bits=8,
+                               range_unit=0.002, beam_origin=0.0):
+    """The tables from angles in radians: altitude_rad and beam_azimuth_rad per row, encoder_rad per tick (the azimuth of the
+    column that carries that tick, counter-clockwise positive).  Sines and cosines are taken in float64 and rounded to float32
+    once; from there on everything is the library's table arithmetic."""
+    alt = np.asarray(altitude_rad, np.float64).reshape(-1)
+    baz = np.broadcast_to(np.asarray(beam_azimuth_rad, np.float64), alt.shape)
+    enc = np.asarray(encoder_rad, np.float64).reshape(-1)
+    return polar_geometry(height, width, range_bits, intensity_bits, range_unit, beam_origin, np.cos(alt), np.sin(alt),
+                          np.cos(baz), np.sin(baz), np.cos(enc), np.sin(enc))
+
+
+def polar_layout(geom):
+    """Section offsets and size of a blob of this geometry (liodom_polar_layout; no handle, no device)."""
+    lay = PolarLayout()
+    rc = load().liodom_polar_layout(C.byref(geom), C.byref(lay))
+    if rc != 0:
+        raise LiodomError("liodom_polar_layout error %d: %s" % (rc, load().liodom_last_error().decode()))
+    return lay
+
+
+def pack_polar(geom, ticks, ranges, intensities=None, out=None):
+    """One scan as a blob (uint8 array of liodom_polar_layout's total size): ticks [width], range counts and intensities
+    [height * width] in the point order of the handle's lidar_type.  out: a uint8 buffer to fill instead (scan_buffer_polar)."""
+    lay = polar_layout(geom)
+    n = geom.height * geom.width
+    blob = np.zeros(lay.total_bytes, np.uint8) if out is None else out
+    blob[lay.tick_offset:lay.tick_offset + 4 * geom.width] = np.ascontiguousarray(ticks, dtype="<u4").reshape(geom.width).view(np.uint8)
+    rt = "<u2" if geom.range_bits == 16 else "<u4"
+    blob[lay.range_offset:lay.range_offset + n * geom.range_bits // 8] = np.ascontiguousarray(ranges, dtype=rt).reshape(n).view(np.uint8)
+    if geom.intensity_bits:
+        it = "u1" if geom.intensity_bits == 8 else "<u2"
+        blob[lay.intensity_offset:lay.intensity_offset + n * geom.intensity_bits // 8] = np.ascontiguousarray(intensities, dtype=it).reshape(n).view(np.uint8)
+    return blob
 
 
 class KernelStat(C.Structure):
@@ -345,6 +413,20 @@ def load():
     L.liodom_pin_host_buffer.argtypes = [C.c_void_p, C.c_int64]
     L.liodom_unpin_host_buffer.restype = C.c_int
     L.liodom_unpin_host_buffer.argtypes = [C.c_void_p]
+    L.liodom_polar_layout.restype = C.c_int
+    L.liodom_polar_layout.argtypes = [C.POINTER(PolarGeometry), C.POINTER(PolarLayout)]
+    L.liodom_set_polar_geometry.restype = C.c_int
+    L.liodom_set_polar_geometry.argtypes = [vp, C.POINTER(PolarGeometry)]
+    L.liodom_project_polar.restype = C.c_int
+    L.liodom_project_polar.argtypes = [vp, vp, fp]
+    L.liodom_upload_scan_polar.restype = C.c_int
+    L.liodom_upload_scan_polar.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.liodom_process_scan_polar.restype = C.c_int
+    L.liodom_process_scan_polar.argtypes = [vp, C.c_int, vp, C.c_double, dp, C.POINTER(StepInfo)]
+    L.liodom_scan_buffer_polar.restype = C.c_int
+    L.liodom_scan_buffer_polar.argtypes = [vp, C.c_int, C.POINTER(vp), i64p]
+    L.liodom_extract_edges_device_polar.restype = C.c_int
+    L.liodom_extract_edges_device_polar.argtypes = [vp, C.c_int, vp, tp]
     _lib = L
     return L
 
@@ -364,6 +446,9 @@ def host_lib():
         HL.liodom_host_two_thread_replay.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int,
                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                      C.POINTER(C.c_int64)]
+        HL.liodom_host_two_thread_replay_polar.restype = C.c_int
+        HL.liodom_host_two_thread_replay_polar.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         _host_lib = HL
     return _host_lib
 
@@ -382,6 +467,8 @@ EXPORTED_SYMBOLS = [
     "liodom_odometry_submit_device", "liodom_odometry_collect",
     "liodom_get_pose_covariance_log", "liodom_wait_pose_covariance",
     "liodom_reset_stream", "liodom_stream_state_size", "liodom_export_stream_state", "liodom_import_stream_state",
+    "liodom_polar_layout", "liodom_set_polar_geometry", "liodom_project_polar", "liodom_upload_scan_polar", "liodom_process_scan_polar",
+    "liodom_scan_buffer_polar", "liodom_extract_edges_device_polar",
 ]
 
 
@@ -444,6 +531,7 @@ class Liodom:
             raise LiodomError("liodom_create failed (%d): %s" % (rc, self.L.liodom_last_error().decode()))
         self.h = h
         self.edge_cap = params.scan_lines * params.scan_regions * (params.edges_per_region + 1) + 64
+        self.polar, self.polar_bytes = None, 0
 
     def _check(self, rc):
         if rc != 0:
@@ -569,6 +657,80 @@ class Liodom:
         self._check(self.L.liodom_process_scan(self.h, stream, _fp(x), x.shape[0], height, width, stamp, _dp(pose),
                                                C.byref(info)))
         return pose, info
+
+    # --- polar scans: range counts go up, the projection to XYZI runs on the device ---
+    def set_polar_geometry(self, geom):
+        """liodom_set_polar_geometry: from here on the *_polar calls take blobs of this geometry (pack_polar)."""
+        self._check(self.L.liodom_set_polar_geometry(self.h, C.byref(geom)))
+        self.polar = geom
+        self.polar_bytes = int(polar_layout(geom).total_bytes)
+
+    def _blob(self, blob):
+        if self.polar is None:
+            raise LiodomError("error %d: no polar geometry has been set (set_polar_geometry)" % ERR_UNSUPPORTED)
+        b = blob if (isinstance(blob, np.ndarray) and blob.dtype == np.uint8 and blob.flags["C_CONTIGUOUS"]) else np.ascontiguousarray(blob, dtype=np.uint8)
+        if b.size < self.polar_bytes:
+            raise ValueError("polar blob of %d bytes, the geometry needs %d" % (b.size, self.polar_bytes))
+        return b
+
+    def project_polar(self, blob):
+        """The packed cloud [height * width, 4] of one blob (liodom_project_polar)."""
+        b = self._blob(blob)
+        out = np.zeros((self.polar.height * self.polar.width, 4), np.float32)
+        self._check(self.L.liodom_project_polar(self.h, b.ctypes.data_as(C.c_void_p), _fp(out)))
+        return out
+
+    def upload_scan_polar(self, stream, slot, blob):
+        b = self._blob(blob)
+        self._check(self.L.liodom_upload_scan_polar(self.h, stream, slot, b.ctypes.data_as(C.c_void_p)))
+
+    def process_scan_polar(self, blob, stamp=0.0, stream=0):
+        b = self._blob(blob)
+        pose = np.zeros(7)
+        info = StepInfo()
+        self._check(self.L.liodom_process_scan_polar(self.h, stream, b.ctypes.data_as(C.c_void_p), stamp, _dp(pose), C.byref(info)))
+        return pose, info
+
+    def scan_buffer_polar(self, stream=0):
+        """Page-locked uint8 buffer of one blob to assemble the next scan in (liodom_scan_buffer_polar; pack_polar(..., out=))."""
+        p = C.c_void_p()
+        n = C.c_int64()
+        self._check(self.L.liodom_scan_buffer_polar(self.h, stream, C.byref(p), C.byref(n)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n.value,))
+
+    def extract_edges_device_polar(self, blob, stream=0):
+        """extract_edges_device for a blob: the ticket, or None when every hand-off slot is taken (LIODOM_ERR_BUSY)."""
+        b = self._blob(blob)
+        t = EdgeTicket()
+        rc = self.L.liodom_extract_edges_device_polar(self.h, stream, b.ctypes.data_as(C.c_void_p), C.byref(t))
+        if rc == ERR_BUSY:
+            return None
+        self._check(rc)
+        t._keep = b          # the upload may still be reading it
+        return t
+
+    def two_thread_replay_polar(self, blobs, timed_from=0, fetch_edges=True, depth=1, pin=True):
+        """two_thread_replay fed polar blobs (liodom_host_two_thread_replay_polar): blobs = uint8 [count, total_bytes].  Returns
+        (poses [count, 7], seconds from the submission of scan timed_from to the last pose, total number of edges fetched)."""
+        HL = host_lib()
+        a = np.ascontiguousarray(blobs, dtype=np.uint8)
+        count = a.shape[0]
+        if self.polar is None:
+            raise LiodomError("error %d: no polar geometry has been set (set_polar_geometry)" % ERR_UNSUPPORTED)
+        if a.shape[1] < self.polar_bytes:
+            raise ValueError("polar blobs of %d bytes, the geometry needs %d" % (a.shape[1], self.polar_bytes))
+        poses = np.zeros((count, 7))
+        secs = C.c_double()
+        tot = C.c_int64()
+        pinned = pin and self.L.liodom_pin_host_buffer(a.ctypes.data_as(C.c_void_p), a.nbytes) == 0
+        try:
+            self._check(HL.liodom_host_two_thread_replay_polar(self.h, a.ctypes.data_as(C.c_void_p), a.shape[1], count, int(timed_from),
+                                                               1 if fetch_edges else 0, int(depth), self.edge_cap, _dp(poses),
+                                                               C.byref(secs), C.byref(tot)))
+        finally:
+            if pinned:
+                self.L.liodom_unpin_host_buffer(a.ctypes.data_as(C.c_void_p))
+        return poses, secs.value, tot.value
 
     # --- resident replay ---
     def alloc_resident(self, n_slots):

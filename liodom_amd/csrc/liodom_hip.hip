@@ -120,6 +120,18 @@ struct liodom_handle {
   hipEvent_t ev_pin[kEdgePipeBufs] = {nullptr, nullptr, nullptr};     // the upload out of staging slot r has completed
   bool ev_pin_valid[kEdgePipeBufs] = {false, false, false};
   int pin_next = 0;
+  // Polar scans (liodom_set_polar_geometry; nothing below exists on a handle that never sets one): the geometry's tables on the
+  // device, three compact staging slots the blobs are uploaded into (taken in turn), and the page-locked blob ring of the ticket
+  // path (liodom_scan_buffer_polar) with the events that tell when an upload has left a ring slot.
+  bool polar = false;
+  PolarView pol{};                   // (beam / enc point into pol_tables)
+  void* pol_tables = nullptr;        // device: float4 beam[H], float2 enc[T]
+  unsigned char* pol_stage = nullptr;     // device: [kEdgePipeBufs][blob_bytes]
+  int pol_stage_next = 0;
+  unsigned char* pol_pin = nullptr;       // host, page-locked: [kEdgePipeBufs][blob_bytes]
+  hipEvent_t ev_polpin[kEdgePipeBufs] = {nullptr, nullptr, nullptr};
+  bool ev_polpin_valid[kEdgePipeBufs] = {false, false, false};
+  int pol_pin_next = 0;
   bool safe_mode = false;            // no in-kernel waits at all: events between the streams, one workgroup per solve, three-kernel hash rebuild
   bool ring_split_lb = false;        // lock-step batches: k_ring_split_lb (one pass, rings at a fixed pitch, predecessors' counts summed as they appear); LIODOM_RING_SPLIT_LB=0: k_classify + k_ring_scatter
   unsigned int lb_tag = 0;           // launch tag its count words carry
@@ -683,7 +695,7 @@ int reset_state(liodom_handle* h) {
   // the first scans after a reset are not overlapped (as after liodom_create): the first one runs with st.initialized == 0, where
   // no first solve publishes the pose an overlapped second kNN pass would wait for
   h->ov_warm = 0; h->ov_prev = false;
-  for (int b = 0; b < kEdgePipeBufs; b++) { h->tk_seq[b] = 0u; h->ev_pin_valid[b] = false; }      // outstanding edge tickets are void
+  for (int b = 0; b < kEdgePipeBufs; b++) { h->tk_seq[b] = 0u; h->ev_pin_valid[b] = false; h->ev_polpin_valid[b] = false; }      // outstanding edge tickets are void
   if (h->stream_c && !h->stream_c_shared) HIP_TRY(hipStreamSynchronize(h->stream_c));
   h->x_next = 0; h->odo_pending = 0;
   if (h->host_edges_hdr) std::memset(h->host_edges_hdr, 0, sizeof(unsigned int) * 2 * kEdgePipeBufs);
@@ -1187,6 +1199,10 @@ void liodom_destroy(liodom_handle_t* h) {
   if (h->host_edges_meta) hipHostFree(h->host_edges_meta);
   if (h->host_edges_hdr) hipHostFree(h->host_edges_hdr);
   if (h->pin_ring) hipHostFree(h->pin_ring);
+  if (h->pol_tables) hipFree(h->pol_tables);
+  if (h->pol_stage) hipFree(h->pol_stage);
+  if (h->pol_pin) hipHostFree(h->pol_pin);
+  for (int b = 0; b < kEdgePipeBufs; b++) { if (h->ev_polpin[b]) hipEventDestroy(h->ev_polpin[b]); }
   if (h->state_stage_host) hipHostFree(h->state_stage_host);
   for (int b = 0; b < kEdgePipeBufs; b++) { if (h->ev_pin[b]) hipEventDestroy(h->ev_pin[b]); }
   for (auto& e : h->ev_pool) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
@@ -1527,6 +1543,40 @@ int liodom_scan_buffer(liodom_handle_t* h, int stream, float** xyzi, int64_t* ca
   return LIODOM_OK;
 }
 
+// The two ends of liodom_extract_edges_device that its polar form shares.  Extraction side (mx_x held).
+// Is the hand-off slot of the next extraction free?
+static int ticket_slot_free(liodom_handle* h) {
+  if (h->pf_slot >= 0) { g_last_error = "edge extraction by ticket: a pipelined replay of this handle has an extraction issued ahead: call liodom_sync() first"; return LIODOM_ERR_NEEDS_SYNC; }
+  // The pipelined replay uses the same three edge buffers (h->parity) and may have odometries in flight that nobody has collected
+  // (liodom_process_resident_pipelined without read-back): this extraction would rewrite a buffer under them (wait_odo = 0 below
+  // relies on the ticket discipline: a slot is refilled only after its pose has been collected).
+  if (h->replay_live.load()) { g_last_error = "edge extraction by ticket: scans of a pipelined replay (liodom_process_resident / liodom_replay_*) are still in the edge buffers: call liodom_sync() first"; return LIODOM_ERR_NEEDS_SYNC; }      // (not BUSY: a caller that keeps the cloud and retries would spin forever)
+  if (h->tk_seq[h->x_next].load() != 0u) {
+    g_last_error = "edge extraction by ticket: all hand-off slots hold edge clouds no liodom_odometry_step_device has taken yet";
+    return LIODOM_ERR_BUSY;
+  }
+  return LIODOM_OK;
+}
+// The extraction of the cloud at `in` (device, its upload or projection enqueued on q) into the free hand-off slot, and its ticket.
+static int ticket_extract(liodom_handle* h, hipStream_t q, int stream, const float4* in, int n, int height, int width, liodom_edge_ticket_t* ticket) {
+  const int eb = h->x_next;
+  unsigned int seq = ++h->ext_seq;
+  if (seq == 0u) seq = ++h->ext_seq;                 // (0 means "nothing to wait for")
+  unsigned int* host_seq = h->v.host_edges_hdr ? h->v.host_edges_hdr + eb : nullptr;
+  // (the slot is free: the odometry that last read buffer eb has been collected, i.e. has completed — no wait on the device,
+  //  which would depend on when the other thread submits its next scan)
+  unsigned int* const dev_flag = h->use_flags ? h->v.pipe_flags + eb : (unsigned int*)nullptr;
+  int rc = launch_extract(h, q, eb, stream, 1, in, 0, n, height, width, 0u, 1, dev_flag, host_seq, seq);
+  if (rc) return rc;
+  if (!h->use_flags) HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
+  h->eb_seq[eb] = seq;
+  h->pipe_active.store(true);
+  h->tk_seq[eb].store(seq);
+  h->x_next = (eb + 1) % kEdgePipeBufs;
+  ticket->seq = seq; ticket->slot = eb; ticket->stream = stream; ticket->reserved = 0;
+  return LIODOM_OK;
+}
+
 int liodom_extract_edges_device(liodom_handle_t* h, int stream, const float* xyzi, int64_t n, int height, int width,
                                 liodom_edge_ticket_t* ticket) {
   int rc = check_stream(h, stream);
@@ -1536,16 +1586,7 @@ int liodom_extract_edges_device(liodom_handle_t* h, int stream, const float* xyz
   if (h->S != 1) { g_last_error = "liodom_extract_edges_device: one-stream handles only (lock-step handles advance all streams together: liodom_process_resident)"; return LIODOM_ERR_UNSUPPORTED; }
   if (n < 0 || n > h->v.max_points || (n > 0 && !xyzi)) { g_last_error = "bad point count"; return LIODOM_ERR_CAPACITY; }
   SideLocks lk(h, false, true);                      // extraction side only: safe beside a concurrent liodom_odometry_step_device
-  if (h->pf_slot >= 0) { g_last_error = "liodom_extract_edges_device: a pipelined replay of this handle has an extraction issued ahead: call liodom_sync() first"; return LIODOM_ERR_NEEDS_SYNC; }
-  // The pipelined replay uses the same three edge buffers (h->parity) and may have odometries in flight that nobody has collected
-  // (liodom_process_resident_pipelined without read-back): this extraction would rewrite a buffer under them (wait_odo = 0 below
-  // relies on the ticket discipline: a slot is refilled only after its pose has been collected).
-  if (h->replay_live.load()) { g_last_error = "liodom_extract_edges_device: scans of a pipelined replay (liodom_process_resident / liodom_replay_*) are still in the edge buffers: call liodom_sync() first"; return LIODOM_ERR_NEEDS_SYNC; }      // (not BUSY: a caller that keeps the cloud and retries would spin forever)
-  const int eb = h->x_next;
-  if (h->tk_seq[eb].load() != 0u) {
-    g_last_error = "liodom_extract_edges_device: all hand-off slots hold edge clouds no liodom_odometry_step_device has taken yet";
-    return LIODOM_ERR_BUSY;
-  }
+  if ((rc = ticket_slot_free(h))) return rc;
   hipStream_t q = extract_queue(h);
   float4* in = h->stage_in + (size_t)stream * h->v.max_points;
   if (n) {
@@ -1575,21 +1616,7 @@ int liodom_extract_edges_device(liodom_handle_t* h, int stream, const float* xyz
       h->pin_next = (r + 1) % kEdgePipeBufs;
     }
   }
-  unsigned int seq = ++h->ext_seq;
-  if (seq == 0u) seq = ++h->ext_seq;                 // (0 means "nothing to wait for")
-  unsigned int* host_seq = h->v.host_edges_hdr ? h->v.host_edges_hdr + eb : nullptr;
-  // (the slot is free: the odometry that last read buffer eb has been collected, i.e. has completed — no wait on the device,
-  //  which would depend on when the other thread submits its next scan)
-  unsigned int* const dev_flag = h->use_flags ? h->v.pipe_flags + eb : (unsigned int*)nullptr;
-  rc = launch_extract(h, q, eb, stream, 1, in, 0, (int)n, height, width, 0u, 1, dev_flag, host_seq, seq);
-  if (rc) return rc;
-  if (!h->use_flags) HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
-  h->eb_seq[eb] = seq;
-  h->pipe_active.store(true);
-  h->tk_seq[eb].store(seq);
-  h->x_next = (eb + 1) % kEdgePipeBufs;
-  ticket->seq = seq; ticket->slot = eb; ticket->stream = stream; ticket->reserved = 0;
-  return LIODOM_OK;
+  return ticket_extract(h, q, stream, in, (int)n, height, width, ticket);
 }
 
 int liodom_wait_edges(liodom_handle_t* h, const liodom_edge_ticket_t* ticket, float* edges_xyzi, int32_t* edge_ring,
@@ -1689,6 +1716,193 @@ int liodom_process_scan(liodom_handle_t* h, int stream, const float* xyzi, int64
   rc = launch_odometry(h, 0, stream, 1);
   if (rc) return rc;
   return wait_pose(h, stream, 1, pose_out, info);
+}
+
+// ---- polar scans: the sensor's counts go up, the projection to XYZI runs on the device (kernels_polar.h) ----
+static int polar_sizes_valid(const liodom_polar_geometry_t* g) {
+  if (!g) return LIODOM_ERR_INVALID_ARG;
+  if ((g->range_bits != 16 && g->range_bits != 32) || (g->intensity_bits != 0 && g->intensity_bits != 8 && g->intensity_bits != 16) ||
+      g->height < 1 || g->height > kPolarMaxHeight || g->width < 1) {
+    g_last_error = "polar geometry: range_bits must be 16 or 32, intensity_bits 0, 8 or 16, 1 <= height <= 2048, width >= 1";
+    return LIODOM_ERR_INVALID_ARG;
+  }
+  return LIODOM_OK;
+}
+
+int liodom_polar_layout(const liodom_polar_geometry_t* geom, liodom_polar_layout_t* out) {
+  if (!out) return LIODOM_ERR_INVALID_ARG;
+  if (int rc = polar_sizes_valid(geom)) return rc;
+  long long r, i, t;
+  polar_sections(geom->height, geom->width, geom->range_bits, geom->intensity_bits, &r, &i, &t);
+  out->tick_offset = 0; out->range_offset = r; out->intensity_offset = i; out->total_bytes = t;
+  return LIODOM_OK;
+}
+
+int liodom_set_polar_geometry(liodom_handle_t* h, const liodom_polar_geometry_t* g) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if ((rc = polar_sizes_valid(g))) return rc;
+  if (g->ticks < 1 || !g->cos_alt || !g->sin_alt || !g->cos_baz || !g->sin_baz || !g->cos_enc || !g->sin_enc) {
+    g_last_error = "polar geometry: a table is null or ticks < 1";
+    return LIODOM_ERR_INVALID_ARG;
+  }
+  if ((long long)g->height * g->width > (long long)h->v.max_points) { g_last_error = "polar geometry: height * width exceeds max_points"; return LIODOM_ERR_CAPACITY; }
+  SideLocks lk(h, true, true);
+  if ((rc = tickets_idle(h))) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream_x));       // a projection in flight reads the tables and the staging slots replaced below
+  HIP_TRY(sync_odometry(h));
+  PolarView pv{};
+  pv.H = g->height; pv.W = g->width; pv.T = g->ticks; pv.n = g->height * g->width;
+  pv.range_bytes = g->range_bits / 8; pv.inten_bytes = g->intensity_bits / 8;
+  pv.order = h->v.lidar_type == 1 ? 1 : 0;
+  pv.range_unit = g->range_unit; pv.beam_origin = g->beam_origin;
+  polar_sections(pv.H, pv.W, g->range_bits, g->intensity_bits, &pv.range_off, &pv.inten_off, &pv.blob_bytes);
+  // the tables as the kernel reads them: one float4 per row, one float2 per tick
+  const size_t beam_bytes = sizeof(float4) * (size_t)pv.H, enc_bytes = sizeof(float2) * (size_t)pv.T;
+  std::vector<float> tab((beam_bytes + enc_bytes) / sizeof(float));
+  for (int r = 0; r < pv.H; r++) { tab[4 * r] = g->cos_alt[r]; tab[4 * r + 1] = g->sin_alt[r]; tab[4 * r + 2] = g->cos_baz[r]; tab[4 * r + 3] = g->sin_baz[r]; }
+  for (int t = 0; t < pv.T; t++) { tab[4 * (size_t)pv.H + 2 * (size_t)t] = g->cos_enc[t]; tab[4 * (size_t)pv.H + 2 * (size_t)t + 1] = g->sin_enc[t]; }
+  // everything new first: a failure leaves the handle as it was
+  void *tables = nullptr, *stage = nullptr, *pin = nullptr;
+  hipError_t e = hipMalloc(&tables, beam_bytes + enc_bytes);
+  if (e == hipSuccess) e = hipMalloc(&stage, (size_t)kEdgePipeBufs * (size_t)pv.blob_bytes);
+  if (e == hipSuccess) e = hipHostMalloc(&pin, (size_t)kEdgePipeBufs * (size_t)pv.blob_bytes, hipHostMallocDefault);
+  if (e == hipSuccess) e = hipMemcpy(tables, tab.data(), beam_bytes + enc_bytes, hipMemcpyHostToDevice);
+  for (int b = 0; b < kEdgePipeBufs && e == hipSuccess; b++) if (!h->ev_polpin[b]) e = hipEventCreateWithFlags(&h->ev_polpin[b], hipEventDisableTiming);
+  if (e != hipSuccess) {
+    if (tables) (void)hipFree(tables);
+    if (stage) (void)hipFree(stage);
+    if (pin) (void)hipHostFree(pin);
+    g_last_error = std::string("liodom_set_polar_geometry: ") + hipGetErrorString(e);
+    return LIODOM_ERR_HIP;
+  }
+  if (h->pol_tables) (void)hipFree(h->pol_tables);
+  if (h->pol_stage) (void)hipFree(h->pol_stage);
+  if (h->pol_pin) (void)hipHostFree(h->pol_pin);
+  h->pol_tables = tables; h->pol_stage = static_cast<unsigned char*>(stage); h->pol_pin = static_cast<unsigned char*>(pin);
+  pv.beam = static_cast<const float4*>(tables);
+  pv.enc = reinterpret_cast<const float2*>(static_cast<const unsigned char*>(tables) + beam_bytes);
+  h->pol = pv;
+  h->pol_stage_next = 0; h->pol_pin_next = 0;
+  for (int b = 0; b < kEdgePipeBufs; b++) h->ev_polpin_valid[b] = false;
+  h->polar = true;
+  return LIODOM_OK;
+}
+
+static int polar_ready(liodom_handle* h, const void* blob) {
+  if (!h->polar) { g_last_error = "no polar geometry has been set (liodom_set_polar_geometry)"; return LIODOM_ERR_UNSUPPORTED; }
+  if (!blob) return LIODOM_ERR_INVALID_ARG;
+  return LIODOM_OK;
+}
+// Upload of a blob into the next compact staging slot and its projection into dst (device, n points), both on q.  Extraction side.
+static int polar_upload_project(liodom_handle* h, hipStream_t q, const void* blob, float4* dst) {
+  const PolarView& pv = h->pol;
+  unsigned char* st = h->pol_stage + (size_t)h->pol_stage_next * (size_t)pv.blob_bytes;
+  h->pol_stage_next = (h->pol_stage_next + 1) % kEdgePipeBufs;
+  HIP_TRY(hipMemcpyAsync(st, blob, (size_t)pv.blob_bytes, hipMemcpyHostToDevice, q));
+  {
+    ProfScope ps(h, KID_OTHER, q);
+    hipLaunchKernelGGL(k_polar_project, dim3(cdiv(pv.n, kPolarTile)), dim3(kPolarThreads), polar_lds_bytes(pv.H), q, pv, st, dst);
+  }
+  HIP_TRY(hipGetLastError());
+  return LIODOM_OK;
+}
+
+int liodom_project_polar(liodom_handle_t* h, const void* blob, float* xyzi_out) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if ((rc = polar_ready(h, blob))) return rc;
+  if (!xyzi_out) return LIODOM_ERR_INVALID_ARG;
+  SideLocks lk(h, false, true);
+  hipStream_t q = extract_queue(h);
+  if ((rc = polar_upload_project(h, q, blob, h->stage_in))) return rc;
+  HIP_TRY(hipMemcpyAsync(xyzi_out, h->stage_in, sizeof(float4) * (size_t)h->pol.n, hipMemcpyDeviceToHost, q));
+  HIP_TRY(hipStreamSynchronize(q));
+  return LIODOM_OK;
+}
+
+int liodom_upload_scan_polar(liodom_handle_t* h, int stream, int slot, const void* blob) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if ((rc = polar_ready(h, blob))) return rc;
+  if (!h->resident || slot < 0 || slot >= h->n_slots) { g_last_error = "bad resident slot"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, false, true);
+  hipStream_t q = extract_queue(h);
+  if ((rc = polar_upload_project(h, q, blob, h->resident + ((size_t)slot * h->S + stream) * (size_t)h->v.max_points))) return rc;
+  HIP_TRY(hipStreamSynchronize(q));                  // like liodom_upload_scan: the blob is the caller's again on return
+  return LIODOM_OK;
+}
+
+int liodom_process_scan_polar(liodom_handle_t* h, int stream, const void* blob, double stamp, double* pose_out, liodom_step_info_t* info) {
+  (void)stamp;
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if ((rc = check_usable(h))) return rc;
+  if ((rc = polar_ready(h, blob))) return rc;
+  SideLocks lk(h, true, true);        // as liodom_process_scan: the extraction scratch on the odometry stream
+  if ((rc = tickets_idle(h))) return rc;
+  if ((rc = drain_pipeline(h))) return rc;
+  float4* in = h->stage_in + (size_t)stream * h->v.max_points;
+  if ((rc = polar_upload_project(h, h->stream, blob, in))) return rc;
+  rc = launch_extract(h, h->stream, 0, stream, 1, in, 0, h->pol.n, h->pol.H, h->pol.W);
+  if (rc) return rc;
+  rc = launch_odometry(h, 0, stream, 1);
+  if (rc) return rc;
+  return wait_pose(h, stream, 1, pose_out, info);
+}
+
+int liodom_scan_buffer_polar(liodom_handle_t* h, int stream, void** blob, int64_t* bytes) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if (!blob) return LIODOM_ERR_INVALID_ARG;
+  if (!h->polar) { g_last_error = "no polar geometry has been set (liodom_set_polar_geometry)"; return LIODOM_ERR_UNSUPPORTED; }
+  if (h->S != 1) { g_last_error = "liodom_scan_buffer_polar: one-stream handles only"; return LIODOM_ERR_UNSUPPORTED; }
+  SideLocks lk(h, false, true);
+  const int r = h->pol_pin_next;
+  // the upload that last read this slot (three scans ago) must have left it
+  if (h->ev_polpin_valid[r]) { HIP_TRY(hipEventSynchronize(h->ev_polpin[r])); h->ev_polpin_valid[r] = false; }
+  *blob = h->pol_pin + (size_t)r * (size_t)h->pol.blob_bytes;
+  if (bytes) *bytes = h->pol.blob_bytes;
+  return LIODOM_OK;
+}
+
+int liodom_extract_edges_device_polar(liodom_handle_t* h, int stream, const void* blob, liodom_edge_ticket_t* ticket) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if ((rc = check_usable(h))) return rc;
+  if ((rc = polar_ready(h, blob))) return rc;
+  if (!ticket) return LIODOM_ERR_INVALID_ARG;
+  if (h->S != 1) { g_last_error = "liodom_extract_edges_device_polar: one-stream handles only"; return LIODOM_ERR_UNSUPPORTED; }
+  SideLocks lk(h, false, true);
+  if ((rc = ticket_slot_free(h))) return rc;
+  hipStream_t q = extract_queue(h);
+  // The source rules of liodom_extract_edges_device: a slot of the handle's own blob ring or a registered buffer is read
+  // asynchronously where it lies (and stays untouched until the ticket's edges or pose have been returned); a pageable blob is
+  // copied through the ring.
+  const size_t bb = (size_t)h->pol.blob_bytes;
+  const unsigned char* lo = h->pol_pin;
+  const unsigned char* src = static_cast<const unsigned char*>(blob);
+  const bool own = src >= lo && src < lo + (size_t)kEdgePipeBufs * bb;
+  bool pinned = own;
+  if (!own) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, blob) == hipSuccess) pinned = attr.type == hipMemoryTypeHost;
+    else (void)hipGetLastError();                    // (unregistered pageable memory: not an error)
+  }
+  const int r = own ? (int)((size_t)(src - lo) / bb) : h->pol_pin_next;
+  if (!pinned) {
+    if (h->ev_polpin_valid[r]) { HIP_TRY(hipEventSynchronize(h->ev_polpin[r])); h->ev_polpin_valid[r] = false; }
+    std::memcpy(h->pol_pin + (size_t)r * bb, blob, bb);
+    blob = h->pol_pin + (size_t)r * bb;
+  }
+  float4* in = h->stage_in + (size_t)stream * h->v.max_points;
+  if ((rc = polar_upload_project(h, q, blob, in))) return rc;
+  if (own || !pinned) {                              // the ring slot may be refilled once this upload has left it
+    HIP_TRY(hipEventRecord(h->ev_polpin[r], q));
+    h->ev_polpin_valid[r] = true;
+    h->pol_pin_next = (r + 1) % kEdgePipeBufs;
+  }
+  return ticket_extract(h, q, stream, in, h->pol.n, h->pol.H, h->pol.W, ticket);
 }
 
 // Rebuilds the kNN structure of one stream from window ++ received map without appending a frame.

@@ -441,5 +441,6 @@ __device__ __forceinline__ void inject_delay(unsigned int site) {
 #include "kernels_filter.h"
 #include "kernels_cov.h"
 #include "kernels_state.h"
+#include "kernels_polar.h"
 
 }  // namespace liodom_dev

@@ -99,6 +99,43 @@ LD_HD int velodyne_ring(double z, double dist, int scan_lines) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Polar scans (liodom_polar_geometry_t in include/liodom_hip.h): what a sensor driver does per return before the cloud reaches
+// lidarClb — count -> range -> Cartesian point — as table-driven float arithmetic.  No trigonometry here: the caller's tables
+// carry the angles, so the result is defined bit for bit (every product and sum below is rounded on its own; build with
+// -ffp-contract=off).  tests/polarref.py restates it in NumPy.
+// ---------------------------------------------------------------------------------------
+LD_HD float polar_nan() {                    // the quiet NaN invalid points get
+  union { uint32_t u; float f; } c;
+  c.u = 0x7FC00000u;
+  return c.f;
+}
+// One return.  c: range count; w: the intensity, already a float (0 without an intensity section); tick_ok: the column's tick
+// is inside the encoder table, and (ce, se) is its entry — a caller must not index the table before it has tested the tick,
+// and passes anything for (ce, se) otherwise.  (ca, sa, cb, sb): the row's beam altitude and azimuth offset.  out: x y z w.
+LD_HD void polar_project_point(uint32_t c, float w, bool tick_ok, float ce, float se, float ca, float sa, float cb, float sb,
+                               float range_unit, float beam_origin, float* out) {
+  out[3] = w;
+  if (c == 0u || !tick_ok) { out[0] = out[1] = out[2] = polar_nan(); return; }
+  const float r = (float)c * range_unit;
+  const float d = r - beam_origin;
+  const float h = d * ca;
+  const float ct = ce * cb - se * sb;
+  const float st = se * cb + ce * sb;
+  out[0] = h * ct + beam_origin * ce;
+  out[1] = h * st + beam_origin * se;
+  out[2] = d * sa;
+}
+// Sections of a polar blob: ticks uint32[W] at 0, ranges [H W] of range_bits, intensities [H W] of intensity_bits (none for 0
+// bits: its offset is then the total), each starting on a 16-byte boundary; the total is a multiple of 16 as well.
+LD_HD long long polar_align16(long long x) { return (x + 15) & ~15LL; }
+LD_HD void polar_sections(long long height, long long width, int range_bits, int intensity_bits, long long* range_off,
+                          long long* intensity_off, long long* total) {
+  *range_off = polar_align16(4 * width);
+  *intensity_off = polar_align16(*range_off + height * width * (range_bits / 8));
+  *total = polar_align16(*intensity_off + height * width * (intensity_bits / 8));
+}
+
+// ---------------------------------------------------------------------------------------
 // Curvature stencil (src/feature_extractor.cc:196-229).  All eleven operands are
 // pcl::PointXYZI floats and `10 * x` is int * float, so the reference sums in FLOAT, left to
 // right, and only the finished sum is widened to double (`double diff_x = ...`); the three squares

@@ -167,6 +167,41 @@ Engine::Engine(const Params& p, int device, int max_points, int max_width, int p
   edge_cap_ = p.scan_lines_ * p.scan_regions_ * (p.edges_per_region_ + 1) + 64;
 }
 Engine::~Engine() { liodom_destroy(h_); }
+
+PolarGeometry PolarGeometry::fromAngles(int height, int width, const std::vector<double>& altitude, const std::vector<double>& beam_azimuth,
+                                        const std::vector<double>& encoder, int range_bits, int intensity_bits, float range_unit,
+                                        float beam_origin) {
+  if (height < 1 || altitude.size() != (size_t)height || beam_azimuth.size() != (size_t)height || encoder.empty())
+    throw std::invalid_argument("PolarGeometry::fromAngles: altitude and beam_azimuth need one angle per row, encoder at least one tick");
+  PolarGeometry g;
+  g.height = height; g.width = width; g.range_bits = range_bits; g.intensity_bits = intensity_bits;
+  g.range_unit = range_unit; g.beam_origin = beam_origin;
+  for (double a : altitude) { g.cos_alt.push_back((float)std::cos(a)); g.sin_alt.push_back((float)std::sin(a)); }
+  for (double a : beam_azimuth) { g.cos_baz.push_back((float)std::cos(a)); g.sin_baz.push_back((float)std::sin(a)); }
+  for (double a : encoder) { g.cos_enc.push_back((float)std::cos(a)); g.sin_enc.push_back((float)std::sin(a)); }
+  return g;
+}
+liodom_polar_geometry_t PolarGeometry::toC() const {
+  liodom_polar_geometry_t c;
+  std::memset(&c, 0, sizeof(c));
+  c.height = height; c.width = width; c.range_bits = range_bits; c.intensity_bits = intensity_bits;
+  c.range_unit = range_unit; c.beam_origin = beam_origin;
+  const bool rows = (int)cos_alt.size() == height && (int)sin_alt.size() == height && (int)cos_baz.size() == height && (int)sin_baz.size() == height;
+  if (rows) { c.cos_alt = cos_alt.data(); c.sin_alt = sin_alt.data(); c.cos_baz = cos_baz.data(); c.sin_baz = sin_baz.data(); }
+  if (cos_enc.size() == sin_enc.size()) { c.ticks = (int32_t)cos_enc.size(); c.cos_enc = cos_enc.data(); c.sin_enc = sin_enc.data(); }
+  return c;      // (tables of the wrong length stay null: liodom_set_polar_geometry refuses them)
+}
+liodom_polar_layout_t PolarGeometry::layout() const {
+  const liodom_polar_geometry_t c = toC();
+  liodom_polar_layout_t lay;
+  check(liodom_polar_layout(&c, &lay), "liodom_polar_layout");
+  return lay;
+}
+void Engine::setPolarGeometry(const PolarGeometry& g) {
+  const liodom_polar_geometry_t c = g.toC();
+  check(liodom_set_polar_geometry(h_, &c), "liodom_set_polar_geometry");
+  polar_n_ = g.height * g.width;
+}
 void Engine::resetStream(int stream) { check(liodom_reset_stream(h_, stream), "liodom_reset_stream"); }
 std::vector<uint8_t> Engine::saveState(int stream) {
   int64_t cap = 0, n = 0;
@@ -208,6 +243,31 @@ void FeatureExtractor::extractFeatures(const PointCloud& pc_in, PointCloud& pc_e
     stats->addFeatureExtractionTime(start_t, Clock::now());
     stats->addNumOfFeats(pc_edges.size());
   }
+}
+
+void FeatureExtractor::projectPolar(const std::vector<uint8_t>& blob, PointCloud& pc_out) {
+  pc_out.points.resize((size_t)eng_->polarPoints());
+  check(liodom_project_polar(eng_->handle(), blob.data(), reinterpret_cast<float*>(pc_out.points.data())), "liodom_project_polar");
+  pc_out.width = (uint32_t)pc_out.points.size(); pc_out.height = 1;
+}
+
+bool FeatureExtractor::extractFeaturesPolar(const std::vector<uint8_t>& blob, double stamp, Features& f) {
+  const auto start_t = Clock::now();
+  f.stamp = stamp;
+  const int rc = liodom_extract_edges_device_polar(eng_->handle(), 0, blob.data(), &f.ticket);
+  if (rc == LIODOM_ERR_BUSY) return false;
+  check(rc, "liodom_extract_edges_device_polar");
+  f.edges.points.resize((size_t)eng_->edge_capacity());
+  int n = 0;
+  check(liodom_wait_edges(eng_->handle(), &f.ticket, reinterpret_cast<float*>(f.edges.points.data()), nullptr, nullptr, nullptr,
+                          eng_->edge_capacity(), &n), "liodom_wait_edges");
+  f.edges.points.resize((size_t)n);
+  f.edges.width = (uint32_t)n; f.edges.height = 1;
+  if (params->save_results_) {                                        // feature_extractor.cc:65-68
+    stats->addFeatureExtractionTime(start_t, Clock::now());
+    stats->addNumOfFeats(f.edges.size());
+  }
+  return true;
 }
 
 static void worker_pause(SharedData* sdata) {                          // feature_extractor.cc:80 / laser_odometry.cc:270
@@ -471,10 +531,11 @@ void LaserOdometer::operator()(std::atomic<bool>& running, std::vector<OdometryM
 // submitted before the previous pose is collected; depth 0: liodom_odometry_step_device).  No sleeps: both threads spin-yield.
 // scans: count clouds of n points (packed XYZI) `stride_floats` apart in host memory — page-locked (liodom_pin_host_buffer)
 // for asynchronous uploads.  The clock runs from the submission of scan `timed_from` to the collection of the last pose.
-extern "C" int liodom_host_two_thread_replay(liodom_handle_t* h, const float* scans, int64_t stride_floats, int count, int64_t n,
-                                             int height, int width, int timed_from, int fetch_edges, int depth, int edge_cap,
-                                             double* poses_out /*count x 7*/, double* seconds_out, int64_t* edges_total_out) {
-  if (!h || !scans || count <= 0 || !poses_out) return LIODOM_ERR_INVALID_ARG;
+// extract(k, ticket): the extraction call of scan k (liodom_extract_edges_device or its polar form).
+static int two_thread_replay(liodom_handle_t* h, int count, int timed_from, int fetch_edges, int depth, int edge_cap,
+                             double* poses_out /*count x 7*/, double* seconds_out, int64_t* edges_total_out,
+                             const std::function<int(int, liodom_edge_ticket_t*)>& extract) {
+  if (!h || count <= 0 || !poses_out) return LIODOM_ERR_INVALID_ARG;
   std::mutex qm;
   std::queue<liodom_edge_ticket_t> q;
   std::atomic<int> rc_x{0}, rc_o{0};
@@ -485,7 +546,7 @@ extern "C" int liodom_host_two_thread_replay(liodom_handle_t* h, const float* sc
     for (int k = 0; k < count && !abort_all; k++) {
       liodom_edge_ticket_t t;
       int rc;
-      while ((rc = liodom_extract_edges_device(h, 0, scans + (size_t)k * (size_t)stride_floats, n, height, width, &t)) == LIODOM_ERR_BUSY) {
+      while ((rc = extract(k, &t)) == LIODOM_ERR_BUSY) {
         if (abort_all) return;
         std::this_thread::yield();
       }
@@ -533,17 +594,32 @@ extern "C" int liodom_host_two_thread_replay(liodom_handle_t* h, const float* sc
   if (rc_x) return rc_x;
   return rc_o;
 }
+extern "C" int liodom_host_two_thread_replay(liodom_handle_t* h, const float* scans, int64_t stride_floats, int count, int64_t n,
+                                             int height, int width, int timed_from, int fetch_edges, int depth, int edge_cap,
+                                             double* poses_out /*count x 7*/, double* seconds_out, int64_t* edges_total_out) {
+  if (!scans) return LIODOM_ERR_INVALID_ARG;
+  return two_thread_replay(h, count, timed_from, fetch_edges, depth, edge_cap, poses_out, seconds_out, edges_total_out,
+                           [&](int k, liodom_edge_ticket_t* t) { return liodom_extract_edges_device(h, 0, scans + (size_t)k * (size_t)stride_floats, n, height, width, t); });
+}
+// The same driver fed polar blobs (liodom_set_polar_geometry first): blob k at blobs + k * stride_bytes, page-locked for asynchronous
+// uploads; same threads, same queue, same outputs.  What the patched liodom_node does when the driver hands it the sensor's packets.
+extern "C" int liodom_host_two_thread_replay_polar(liodom_handle_t* h, const unsigned char* blobs, int64_t stride_bytes, int count,
+                                                   int timed_from, int fetch_edges, int depth, int edge_cap,
+                                                   double* poses_out /*count x 7*/, double* seconds_out, int64_t* edges_total_out) {
+  if (!blobs) return LIODOM_ERR_INVALID_ARG;
+  return two_thread_replay(h, count, timed_from, fetch_edges, depth, edge_cap, poses_out, seconds_out, edges_total_out,
+                           [&](int k, liodom_edge_ticket_t* t) { return liodom_extract_edges_device_polar(h, 0, blobs + (size_t)k * (size_t)stride_bytes, t); });
+}
 
 namespace liodom {
 
-Pose LaserOdometer::processScan(const PointCloud& pc_in, double stamp, liodom_step_info_t* info) {
+// One scan through a fused call (liodom_process_scan or its polar form) and the bookkeeping around it.
+Pose LaserOdometer::fusedScan(double stamp, liodom_step_info_t* info, const std::function<void(double*, liodom_step_info_t*)>& call) {
   const auto start_t = Clock::now();
   if (params->save_results_) stats->startFrame(start_t);              // liodom_node.cc:49-52
   double p[7];
   liodom_step_info_t local;
-  check(liodom_process_scan(eng_->handle(), 0, reinterpret_cast<const float*>(pc_in.points.data()),
-                            (int64_t)pc_in.size(), (int)pc_in.height, (int)pc_in.width, stamp, p, &local),
-        "liodom_process_scan");
+  call(p, &local);
   if (info) *info = local;
   last_scan_ = local.scan_index;
   Pose out;
@@ -558,6 +634,20 @@ Pose LaserOdometer::processScan(const PointCloud& pc_in, double stamp, liodom_st
     stats->stopFrame(end_t);
   }
   return out;
+}
+
+Pose LaserOdometer::processScan(const PointCloud& pc_in, double stamp, liodom_step_info_t* info) {
+  return fusedScan(stamp, info, [&](double* p, liodom_step_info_t* local) {
+    check(liodom_process_scan(eng_->handle(), 0, reinterpret_cast<const float*>(pc_in.points.data()),
+                              (int64_t)pc_in.size(), (int)pc_in.height, (int)pc_in.width, stamp, p, local),
+          "liodom_process_scan");
+  });
+}
+
+Pose LaserOdometer::processScanPolar(const std::vector<uint8_t>& blob, double stamp, liodom_step_info_t* info) {
+  return fusedScan(stamp, info, [&](double* p, liodom_step_info_t* local) {
+    check(liodom_process_scan_polar(eng_->handle(), 0, blob.data(), stamp, p, local), "liodom_process_scan_polar");
+  });
 }
 
 }  // namespace liodom

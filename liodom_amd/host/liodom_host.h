@@ -17,6 +17,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <queue>
@@ -118,6 +119,24 @@ class SharedData {
   std::queue<Features> feat_buf_;
 };
 
+// A polar scan's geometry (liodom_polar_geometry_t) with tables it owns: what a sensor driver keeps of the calibration.  A scan
+// of it is one blob (std::vector<uint8_t> of blobBytes(), sections at layout()'s offsets) instead of a PointCloud: the driver's
+// projection and pcl::fromROSMsg (liodom_node.cc:43-44) move onto the device.  No counterpart in the reference.
+struct PolarGeometry {
+  int height = 0, width = 0, range_bits = 16, intensity_bits = 8;
+  float range_unit = 0.002f, beam_origin = 0.f;
+  std::vector<float> cos_alt, sin_alt, cos_baz, sin_baz;     // [height]
+  std::vector<float> cos_enc, sin_enc;                       // [ticks]
+  // Tables from angles in radians (altitude and azimuth offset per row, azimuth per encoder tick): sines and cosines in double,
+  // rounded to float once.
+  static PolarGeometry fromAngles(int height, int width, const std::vector<double>& altitude, const std::vector<double>& beam_azimuth,
+                                  const std::vector<double>& encoder, int range_bits = 16, int intensity_bits = 8,
+                                  float range_unit = 0.002f, float beam_origin = 0.f);
+  liodom_polar_geometry_t toC() const;                       // (points into this object)
+  liodom_polar_layout_t layout() const;
+  size_t blobBytes() const { return (size_t)layout().total_bytes; }
+};
+
 // Owns the GPU handle shared by the extractor and the odometer of one stream.
 class Engine {
  public:
@@ -132,6 +151,9 @@ class Engine {
   // Streams with a life of their own (liodom_reset_stream / liodom_export_stream_state / liodom_import_stream_state; no
   // counterpart in the reference).  resetStream: the stream's next scan is its first.  saveState: the stream's odometry state as
   // one blob (layout: DESIGN.md §3).  loadState: puts such a blob — of any engine with the same parameters — into the stream.
+  // liodom_set_polar_geometry: from here on the polar forms of FeatureExtractor / LaserOdometer take blobs of this geometry
+  void setPolarGeometry(const PolarGeometry& g);
+  int polarPoints() const { return polar_n_; }
   void resetStream(int stream = 0);
   std::vector<uint8_t> saveState(int stream = 0);
   void loadState(const std::vector<uint8_t>& blob, int stream = 0);
@@ -145,6 +167,7 @@ class Engine {
   bool covariance_ = false;
   int edge_cap_ = 0;
   int rotation_mode_ = 1;
+  int polar_n_ = 0;
 };
 
 class FeatureExtractor {
@@ -152,6 +175,11 @@ class FeatureExtractor {
   explicit FeatureExtractor(std::shared_ptr<Engine> engine);
   // splitPointCloud + extractFeatures (feature_extractor.cc:104-254) for one cloud.
   void extractFeatures(const PointCloud& pc_in, PointCloud& pc_edges);
+  // Polar forms (Engine::setPolarGeometry first).  projectPolar: the cloud the driver would have published (liodom_project_polar).
+  // extractFeaturesPolar: one blob through liodom_extract_edges_device_polar + liodom_wait_edges — the ~edges cloud and the
+  // ticket LaserOdometer::process takes; false when every hand-off slot is taken (keep the blob and retry).
+  void projectPolar(const std::vector<uint8_t>& blob, PointCloud& pc_out);
+  bool extractFeaturesPolar(const std::vector<uint8_t>& blob, double stamp, Features& f);
   // the edges of the last scan that went through LaserOdometer::processScan (the ~edges topic, :70-75)
   void lastEdges(PointCloud& pc_edges);
   // The worker loop of the extractor thread (feature_extractor.cc:42-82): pop a cloud, extract,
@@ -231,6 +259,8 @@ class LaserOdometer {
   Pose process(const Features& feats, liodom_step_info_t* info = nullptr);
   // lidarClb -> extractor -> odometer without leaving the device (one H2D copy, one result record)
   Pose processScan(const PointCloud& pc_in, double stamp, liodom_step_info_t* info = nullptr);
+  // The same for a polar blob (liodom_process_scan_polar): the driver's projection runs on the device as well
+  Pose processScanPolar(const std::vector<uint8_t>& blob, double stamp, liodom_step_info_t* info = nullptr);
   // The worker loop of the odometer thread (laser_odometry.cc:100-272): pop features, process, publish.
   // `published` (optional) receives every message in order.
   void operator()(std::atomic<bool>& running, std::vector<OdometryMsg>* published = nullptr, std::vector<Pose>* poses = nullptr);
@@ -251,6 +281,7 @@ class LaserOdometer {
   int last_scan_ = -1;                     // scan_index of the pose returned last (its covariance record goes into publishOdom's message)
   // output-rate watchdog (laser_odometry.cc:239-256; state laser_odometry.h:105-111, initial values laser_odometry.cc:83-90)
   void updateFrequencies(double in_stamp_secs, double now_secs);
+  Pose fusedScan(double stamp, liodom_step_info_t* info, const std::function<void(double*, liodom_step_info_t*)>& call);
   double in_freqs_[5], out_freqs_[5];
   double mean_in_freq_ = 100.0, mean_out_freq_ = 100.0;
   int num_freqs_ = 0;

@@ -16,6 +16,18 @@
 #include "cloud_io.h"
 #include "liodom_host.h"
 
+// Polar path for an Ouster (-DLIODOM_WITH_OUSTER, needs ouster_ros + the ouster client library): the node subscribes to the
+// driver's lidar PACKETS instead of its projected cloud, batches them into a LidarScan and hands the scan's ranges, signals and
+// encoder ticks to the device as one blob — the projection to XYZ (the driver's cartesian() on a CPU core) and pcl::fromROSMsg
+// run on the GPU (include/liodom_hip.h, "polar scans").
+#ifdef LIODOM_WITH_OUSTER
+#include <cmath>
+#include <cstring>
+#include <ouster/lidar_scan.h>
+#include <ouster/types.h>
+#include <ouster_ros/PacketMsg.h>
+#endif
+
 namespace {
 
 struct Node {
@@ -82,15 +94,80 @@ struct Node {
       return;
     }
     ROS_DEBUG("Extracted edges: %d, correct matchings: %d", info.n_edges, info.matches[1]);
-    if (edges_pub.getNumSubscribers() > 0) {              // feature_extractor.cc:70-75
-      liodom::PointCloud edges;
-      extractor->lastEdges(edges);
-      sensor_msgs::PointCloud2 out;
-      liodom_ros::to_msg(edges, msg->header, out);
-      edges_pub.publish(out);
-    }
+    publish_edges(msg->header);
     publish(msg->header, odometer->publishOdom(msg->header.stamp.toSec(), pose));
   }
+
+  // ~edges of the scan that just went through the odometer (feature_extractor.cc:70-75); liodom_mapping subscribes to it
+  void publish_edges(const std_msgs::Header& header) {
+    if (edges_pub.getNumSubscribers() == 0) return;
+    liodom::PointCloud edges;
+    extractor->lastEdges(edges);
+    sensor_msgs::PointCloud2 out;
+    liodom_ros::to_msg(edges, header, out);
+    edges_pub.publish(out);
+  }
+
+#ifdef LIODOM_WITH_OUSTER
+  ros::Subscriber packets_sub;
+  ouster::sensor::sensor_info ouster_info;
+  std::unique_ptr<ouster::ScanBatcher> batcher;
+  std::unique_ptr<ouster::LidarScan> ls;
+  liodom_polar_layout_t lay;
+  std::vector<uint8_t> blob;
+
+  // ~ouster_metadata: the sensor's metadata file (beam angles, beam origin, columns per frame)
+  void setup_ouster() {
+    std::string meta;
+    nh.param<std::string>("ouster_metadata", meta, "");
+    ouster_info = ouster::sensor::metadata_from_json(meta);
+    const int H = (int)ouster_info.format.pixels_per_column, W = (int)ouster_info.format.columns_per_frame;
+    const int T = 90112;                                                     // encoder counts per revolution, clockwise
+    const double rad = M_PI / 180.0;
+    std::vector<double> alt, baz, enc;
+    for (int r = 0; r < H; r++) { alt.push_back(ouster_info.beam_altitude_angles[r] * rad); baz.push_back(-ouster_info.beam_azimuth_angles[r] * rad); }
+    for (int t = 0; t < T; t++) enc.push_back(-2.0 * M_PI * t / T);
+    const liodom::PolarGeometry g = liodom::PolarGeometry::fromAngles(H, W, alt, baz, enc, 32, 16, 0.001f,
+                                                                      (float)(ouster_info.lidar_origin_to_beam_origin_mm * 0.001));
+    engine->setPolarGeometry(g);
+    lay = g.layout();
+    blob.assign(g.blobBytes(), 0);
+    batcher.reset(new ouster::ScanBatcher(ouster_info));
+    ls.reset(new ouster::LidarScan(W, H, ouster_info.format.udp_profile_lidar));
+    packets_sub = nh.subscribe("lidar_packets", 2048, &Node::ouster_cb, this);
+  }
+
+  void ouster_cb(const ouster_ros::PacketMsg::ConstPtr& pm) {
+    if (!(*batcher)(pm->buf.data(), *ls)) return;                            // scan not complete yet
+    const int H = (int)ls->h, W = (int)ls->w;
+    uint32_t* tick = reinterpret_cast<uint32_t*>(blob.data() + lay.tick_offset);
+    uint32_t* range = reinterpret_cast<uint32_t*>(blob.data() + lay.range_offset);
+    uint16_t* signal = reinterpret_cast<uint16_t*>(blob.data() + lay.intensity_offset);
+    // a column the sensor did not deliver keeps status 0: its tick leaves the table, the column becomes NaN points
+    for (int c = 0; c < W; c++) tick[c] = (ls->status()(c) & 1) ? (uint32_t)(((uint64_t)ls->measurement_id()(c) * 90112u) / (uint32_t)W) : 0xFFFFFFFFu;
+    const auto rg = ls->field<uint32_t>(ouster::sensor::ChanField::RANGE);   // [H x W], row-major, staggered: beam_azimuth is in the tables
+    const auto sg = ls->field<uint16_t>(ouster::sensor::ChanField::SIGNAL);
+    std::memcpy(range, rg.data(), sizeof(uint32_t) * (size_t)H * W);
+    std::memcpy(signal, sg.data(), sizeof(uint16_t) * (size_t)H * W);
+    // the scan's stamp is its first delivered column's, on the sensor's clock (ouster_ros: timestamp_mode TIME_FROM_SENSOR-style
+    // stamps; a node that wants ROS time adds its own offset here, as ouster_ros does)
+    std_msgs::Header header;
+    header.stamp = ros::Time::now();
+    for (int c = 0; c < W; c++) if (ls->status()(c) & 1) { header.stamp.fromNSec(ls->timestamp()(c)); break; }
+    header.frame_id = params->laser_frame_;
+    if (!have_laser_to_base) lookup_laser_to_base(header);
+    liodom_step_info_t info;
+    liodom::Pose pose;
+    try {
+      pose = odometer->processScanPolar(blob, header.stamp.toSec(), &info);
+    } catch (const std::exception& e) {
+      ROS_ERROR("%s", e.what());
+      return;
+    }
+    publish_edges(header);
+    publish(header, odometer->publishOdom(header.stamp.toSec(), pose));
+  }
+#endif
 
   void publish(const std_msgs::Header& header, const liodom::OdometryMsg& m) {   // laser_odometry.cc:395-446
     nav_msgs::Odometry odom;
@@ -147,7 +224,21 @@ struct Node {
     edges_pub = nh.advertise<sensor_msgs::PointCloud2>("edges", 10);
     odom_pub = nh.advertise<nav_msgs::Odometry>("odom", 10);
     twist_pub = nh.advertise<geometry_msgs::TwistStamped>("twist", 10);
-    points_sub = nh.subscribe("points", 1, &Node::points_cb, this);
+    bool polar = false;
+    nh.param("polar_input", polar, false);                 // true: ~lidar_packets of an Ouster instead of ~points
+#ifdef LIODOM_WITH_OUSTER
+    if (polar) {
+      try {                                                // a bad ~ouster_metadata or a geometry the handle refuses
+        setup_ouster();
+      } catch (const std::exception& e) {
+        ROS_FATAL("polar_input: %s", e.what());
+        return 1;
+      }
+    }
+#else
+    if (polar) { ROS_FATAL("polar_input needs a build with LIODOM_WITH_OUSTER"); return 1; }
+#endif
+    if (!polar) points_sub = nh.subscribe("points", 1, &Node::points_cb, this);
     if (params->mapping_ && !mapper) map_sub = nh.subscribe("map", 1, &Node::map_cb, this);
     if (params->use_imu_) imu_sub = nh.subscribe("imu", 1, &Node::imu_cb, this);
     ros::spin();
