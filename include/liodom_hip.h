@@ -416,7 +416,8 @@ int liodom_reset(liodom_handle_t* h);
  *       use_imu, pose_rotation_mode, lm_apply_step_on_ftol), poses, counters and flags, the window frames oldest first as
  *       liodom_get_window orders them, with mapping the received map, with use_imu the last IMU orientation; layout in
  *       DESIGN.md §3.  Derived structures (cell hash, filtered local map) and tuning state do not travel, so a blob fits any
- *       handle with the same parameters, whatever its n_streams and code paths.  An attached liodom_map_t is not part of it.
+ *       handle with the same parameters, whatever its n_streams and code paths.  An attached liodom_map_t is not part of it: it has a
+ *       blob of its own (liodom_map_export_state / liodom_map_import_state below).
  *       cap too small: LIODOM_ERR_CAPACITY with *bytes = the size needed.
  *   liodom_import_stream_state   puts a blob's state into a stream (no counterpart in the reference) and rebuilds what the
  *       stream's next scan searches.  The stream's scan_index, pose log and covariance log carry on from the blob's scan count.
@@ -527,6 +528,37 @@ int liodom_map_num_cells(liodom_map_t* m, int* n_cells);
 int liodom_attach_mapper(liodom_handle_t* h, int stream, liodom_map_t* m, int cells_xy, int cells_z);
 /* Sticky LIODOM_MAP_* bits raised by the device since creation. */
 int liodom_map_status(liodom_map_t* m, uint32_t* status);
+
+/* ---- the map as a blob (no counterpart in the reference: a Map lives and dies with its node there) ----
+ * A map's LOGICAL state as one blob: header (magic "LIODOMMP", version, size, and the three sizes voxel_xysize, voxel_zsize,
+ * resolution, which must match bit for bit on import; n_cells, the sticky LIODOM_MAP_* bits, n_points), one 32-byte record per
+ * cell in creation order (key, leaf coordinates of the cell's lower corner, count, index of its first point), then the cells'
+ * clouds back to back: the bytes liodom_map_get_all returns.  Layout in liodom_amd/csrc/map_state_format.h and DESIGN.md §3.
+ * Capacities do not travel: the importing map may have another max_cells, cell_capacity, max_update_points and
+ * max_modified_cells than the exporting one.  None of these calls is on the per-scan path.
+ *
+ *   liodom_map_state_size     exact size, in bytes, of a blob of the map as it is now (no counterpart in the reference).
+ *       Synchronises the stream the map's work is enqueued on.
+ *   liodom_map_export_state   writes the blob (no counterpart in the reference).  Works on a detached map and on one attached to
+ *       a handle; it synchronises the stream the map's work is enqueued on, and — as with liodom_map_update — the caller must not
+ *       step the handle from another thread during the call.  cap too small: LIODOM_ERR_CAPACITY with *bytes = the size needed
+ *       and nothing written to the buffer.
+ *   liodom_map_import_state   makes the map what the blob says (no counterpart in the reference).  The blob is validated on the
+ *       host before anything is launched: truncation, bad magic / version / sizes, a negative count, counts that do not add up,
+ *       a key beyond +-2^20, a duplicate key or other voxel sizes / resolution: LIODOM_ERR_INVALID_ARG; more cells than max_cells
+ *       or a cell larger than cell_capacity: LIODOM_ERR_CAPACITY.  On any error the map is untouched and liodom_last_error names
+ *       the reason.  Importing a blob of 0 cells equals liodom_map_reset.
+ *   liodom_map_reset          the map as liodom_map_create left it — no cells, status 0 (no counterpart in the reference);
+ *       capacities and allocations are kept.
+ * Import and reset on a map that is attached to a handle return LIODOM_ERR_BUSY: detach (liodom_attach_mapper with NULL), import,
+ * attach.  A mapping-mode stream is checkpointed with liodom_export_stream_state + liodom_map_export_state and resumed with
+ * liodom_map_import_state, liodom_import_stream_state, liodom_attach_mapper, in this order.
+ * After an import, the imported map and an uninterrupted one give bit-identical answers to every later liodom_map_update,
+ * liodom_map_get_all, liodom_map_get_local and liodom_map_num_cells (tests/test_gpu_map_state.py). */
+int liodom_map_state_size(liodom_map_t* m, int64_t* bytes);
+int liodom_map_export_state(liodom_map_t* m, void* blob, int64_t cap, int64_t* bytes);
+int liodom_map_import_state(liodom_map_t* m, const void* blob, int64_t bytes);
+int liodom_map_reset(liodom_map_t* m);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ _BUILD_INFO = {"rebuilt": None, "source_hash": None}
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kernels.h", "kernels_extract.h", "kernels_sync.h",
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
                                                   "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "liodom_math.h", "wave_ops.h",
-                                                  "liodom_map.h", "liodom_map_host.h")] + [
+                                                  "liodom_map.h", "liodom_map_host.h", "map_state_format.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -214,6 +214,104 @@ def parse_stream_state(blob):
     return out
 
 
+# ---- map-state blob (liodom_map_export_state; layout in csrc/map_state_format.h and DESIGN.md §3) ----
+MAP_STATE_MAGIC = b"LIODOMMP"
+MAP_STATE_VERSION = 1
+MAP_STATE_HEADER_BYTES = 64
+MAP_STATE_RECORD_BYTES = 32
+MAP_KEY_LIMIT = 1 << 20
+
+
+def parse_map_state(blob, sizes=None):
+    """A map-state blob as a dict of NumPy arrays and scalars (pure Python: no library, no GPU).  Keys: version, total_bytes,
+    voxel_xysize, voxel_zsize, resolution, status, keys [n, 3], corner_leaf [n, 3], counts (n,), points [n_points, 4] (what
+    liodom_map_get_all returns) and cells (a list of [count, 4] float32 arrays in creation order).  Raises ValueError on everything
+    the library's map_state_validate rejects as malformed, and — with sizes = (voxel_xysize, voxel_zsize, resolution) of the map
+    that is to take the blob — on a fingerprint that differs in any bit.  (Capacities are the importing map's to check.)"""
+    b = bytes(blob)
+    if len(b) < MAP_STATE_HEADER_BYTES:
+        raise ValueError("map-state blob truncated (%d bytes)" % len(b))
+    if b[:8] != MAP_STATE_MAGIC:
+        raise ValueError("not a map-state blob (bad magic)")
+    version, header_bytes = (int(x) for x in np.frombuffer(b, "<u4", 2, 8))
+    total = int(np.frombuffer(b, "<u8", 1, 16)[0])
+    if version != MAP_STATE_VERSION or header_bytes != MAP_STATE_HEADER_BYTES:
+        raise ValueError("map-state blob of version %d (this code reads %d)" % (version, MAP_STATE_VERSION))
+    if total != len(b):
+        raise ValueError("map-state blob says %d bytes, has %d" % (total, len(b)))
+    xy, z, res = (float(x) for x in np.frombuffer(b, "<f8", 3, 24))
+    if sizes is not None and np.array(sizes, "<f8").tobytes() != b[24:48]:
+        raise ValueError("map-state blob comes from a map with other sizes (%r, %r, %r)" % (xy, z, res))
+    n_cells = int(np.frombuffer(b, "<i4", 1, 48)[0])
+    status = int(np.frombuffer(b, "<u4", 1, 52)[0])
+    n_points = int(np.frombuffer(b, "<i8", 1, 56)[0])
+    if n_cells < 0 or n_points < 0 or total != MAP_STATE_HEADER_BYTES + MAP_STATE_RECORD_BYTES * n_cells + 16 * n_points:
+        raise ValueError("map-state blob: sizes do not add up")
+    rec = np.frombuffer(b, "<i4", 8 * n_cells, MAP_STATE_HEADER_BYTES).reshape(n_cells, 8)
+    keys, corner, counts, first = rec[:, 0:3].copy(), rec[:, 3:6].copy(), rec[:, 6].copy(), rec[:, 7].copy()
+    if (counts < 0).any():
+        raise ValueError("map-state blob: negative cell count")
+    starts = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+    if not np.array_equal(first.astype(np.int64), starts[:-1]):
+        raise ValueError("map-state blob: first is not the prefix sum of the counts")
+    if int(starts[-1]) != n_points:
+        raise ValueError("map-state blob: cell counts do not add up to n_points")
+    if ((keys < -MAP_KEY_LIMIT) | (keys >= MAP_KEY_LIMIT)).any():
+        raise ValueError("map-state blob: cell key beyond +-2^20")
+    if n_cells and len(np.unique(keys, axis=0)) != n_cells:
+        raise ValueError("map-state blob: duplicate cell key")
+    pts = np.frombuffer(b, "<f4", 4 * n_points, MAP_STATE_HEADER_BYTES + MAP_STATE_RECORD_BYTES * n_cells).reshape(n_points, 4).copy()
+    return dict(version=version, total_bytes=total, voxel_xysize=xy, voxel_zsize=z, resolution=res, status=status, keys=keys,
+                corner_leaf=corner, counts=counts, points=pts,
+                cells=[pts[int(starts[c]):int(starts[c + 1])] for c in range(n_cells)])
+
+
+def map_cell_key(xyz, xy, z):
+    """The reference's coarse-cell key of a float32 point (map.cc:103-105): int(floor(x * inv) * size + size / 2) in FP64."""
+    p = np.asarray(xyz, np.float32).astype(np.float64)
+    out = []
+    for a, size in enumerate((xy, xy, z)):
+        size = float(size)
+        out.append(int(np.floor(p[a] * (1.0 / size)) * size + size / 2.0))      # int(): truncation, as the C cast
+    return out
+
+
+def map_cell_corner_leaf(xyz, xy, z, res):
+    """Leaf coordinates of the lower corner of the coarse cell of a float32 point, with the float arithmetic of k_map_assign:
+    floorf(float(floor(x * inv) * size) * leaf_inv), leaf_inv = 1.0f / float(resolution)."""
+    p = np.asarray(xyz, np.float32).astype(np.float64)
+    leaf_inv = np.float32(1.0) / np.float32(res)
+    out = []
+    for a, size in enumerate((xy, xy, z)):
+        size = float(size)
+        out.append(int(np.floor(np.float32(np.floor(p[a] * (1.0 / size)) * size) * leaf_inv)))
+    return out
+
+
+def build_map_state(xy, z, res, cells, status=0):
+    """Writes a map-state blob from `cells`, a list of [count, 4] float32 arrays in creation order (count >= 1): the key of a
+    cell comes from its first point with the reference's formula, corner_leaf with the float arithmetic of k_map_assign.  The
+    writer the tests design maps with that no sequence of updates is needed for; it does not check that the points of a cell
+    share its key or hold one point per leaf."""
+    cells = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 4) for c in cells]
+    counts = [c.shape[0] for c in cells]
+    if any(n < 1 for n in counts):
+        raise ValueError("build_map_state: a cell needs at least one point (its key comes from the first)")
+    n_points = int(sum(counts))
+    total = MAP_STATE_HEADER_BYTES + MAP_STATE_RECORD_BYTES * len(cells) + 16 * n_points
+    out = [MAP_STATE_MAGIC, np.array([MAP_STATE_VERSION, MAP_STATE_HEADER_BYTES], "<u4").tobytes(), np.array([total], "<u8").tobytes(),
+           np.array([xy, z, res], "<f8").tobytes(), np.array([len(cells)], "<i4").tobytes(), np.array([status], "<u4").tobytes(),
+           np.array([n_points], "<i8").tobytes()]
+    first = 0
+    for c in cells:
+        out.append(np.array(map_cell_key(c[0, :3], xy, z) + map_cell_corner_leaf(c[0, :3], xy, z, res) + [c.shape[0], first], "<i4").tobytes())
+        first += c.shape[0]
+    out.extend(c.astype("<f4").tobytes() for c in cells)
+    blob = b"".join(out)
+    assert len(blob) == total
+    return blob
+
+
 class PolarGeometry(C.Structure):
     """liodom_polar_geometry_t: a polar scan's shape, number widths and tables (include/liodom_hip.h)."""
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("range_bits", C.c_int32), ("intensity_bits", C.c_int32),
@@ -396,6 +494,14 @@ def load():
     L.liodom_map_num_cells.argtypes = [vp, ip]
     L.liodom_map_status.restype = C.c_int
     L.liodom_map_status.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.liodom_map_state_size.restype = C.c_int
+    L.liodom_map_state_size.argtypes = [vp, i64p]
+    L.liodom_map_export_state.restype = C.c_int
+    L.liodom_map_export_state.argtypes = [vp, vp, C.c_int64, i64p]
+    L.liodom_map_import_state.restype = C.c_int
+    L.liodom_map_import_state.argtypes = [vp, vp, C.c_int64]
+    L.liodom_map_reset.restype = C.c_int
+    L.liodom_map_reset.argtypes = [vp]
     tp = C.POINTER(EdgeTicket)
     L.liodom_scan_buffer.restype = C.c_int
     L.liodom_scan_buffer.argtypes = [vp, C.c_int, C.POINTER(fp), i64p]
@@ -469,6 +575,7 @@ EXPORTED_SYMBOLS = [
     "liodom_reset_stream", "liodom_stream_state_size", "liodom_export_stream_state", "liodom_import_stream_state",
     "liodom_polar_layout", "liodom_set_polar_geometry", "liodom_project_polar", "liodom_upload_scan_polar", "liodom_process_scan_polar",
     "liodom_scan_buffer_polar", "liodom_extract_edges_device_polar",
+    "liodom_map_state_size", "liodom_map_export_state", "liodom_map_import_state", "liodom_map_reset",
 ]
 
 
@@ -960,7 +1067,9 @@ class Map:
 
     def _chk(self, rc):
         if rc != 0:
-            raise LiodomError("liodom_map error %d: %s" % (rc, (self._L.liodom_last_error() or b"").decode()))
+            e = LiodomError("liodom_map error %d: %s" % (rc, (self._L.liodom_last_error() or b"").decode()))
+            e.code = rc      # LIODOM_ERR_* (ERR_INVALID_ARG, ERR_CAPACITY, ERR_BUSY, ...)
+            raise e
 
     def close(self):
         if self.h:
@@ -1004,3 +1113,29 @@ class Map:
         s = C.c_uint32(0)
         self._chk(self._L.liodom_map_status(self.h, C.byref(s)))
         return s.value
+
+    # --- the map as a blob ---
+    def state_size(self):
+        """Exact size, in bytes, of a blob of the map as it is now (liodom_map_state_size)."""
+        n = C.c_int64(0)
+        self._chk(self._L.liodom_map_state_size(self.h, C.byref(n)))
+        return n.value
+
+    def export_state(self):
+        """The map's logical state as bytes (liodom_map_export_state); parse_map_state reads it.  Works on an attached map too."""
+        cap = self.state_size()
+        buf = (C.c_ubyte * cap)()
+        n = C.c_int64(0)
+        self._chk(self._L.liodom_map_export_state(self.h, buf, cap, C.byref(n)))
+        return bytes(memoryview(buf)[:n.value])
+
+    def import_state(self, blob):
+        """Makes the map what `blob` says (liodom_map_import_state): any map with the same voxel sizes and resolution will do,
+        whatever its capacities.  LiodomError with .code ERR_INVALID_ARG / ERR_CAPACITY (map untouched), ERR_BUSY while attached."""
+        b = bytes(blob)
+        self._chk(self._L.liodom_map_import_state(self.h, b, len(b)))
+
+    def reset(self):
+        """The map as it was created: no cells, status 0; capacities and allocations kept (liodom_map_reset).  ERR_BUSY while
+        attached."""
+        self._chk(self._L.liodom_map_reset(self.h))

@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "liodom_math.h"
+#include "map_state_format.h"
 
 namespace liodom_dev {
 
@@ -530,6 +531,106 @@ __global__ __launch_bounds__(256) void k_map_init(MapView m) {
   if (i < m.ctable) { m.ckey[i] = kMapEmptyKey; m.cslot_cell[i] = -1; m.cfirst[i] = 0x7fffffff; }
   if (i < m.max_cells) { m.mod_of_cell[i] = -1; m.cell_n[i] = 0; m.cell_buf[i] = 0; }
   if (i == 0) { MapState z = {}; *m.st = z; }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The map as a blob (map_state_format.h): liodom_map_export_state / liodom_map_import_state / liodom_map_reset.  None of this is
+// on the per-scan path: a map that never calls those entry points launches none of these kernels and allocates nothing for them.
+// The blob's head (header + cell records) and its point section are two device buffers; the host writes the rest of the header.
+// ---------------------------------------------------------------------------------------------
+// Export, step 1 (one workgroup): exclusive prefix over cell_n in creation order as in k_map_all_plan, but for any number of
+// cells (no plan entries: the records are the plan).  Writes the cell records behind the header and n_cells, status and
+// n_points into the header, where the host reads them.  `head` holds kMapStateHeaderBytes + max_cells records.
+__global__ __launch_bounds__(1024) void k_map_pack_plan(MapView m, unsigned char* head) {
+  __shared__ int sh_w[16];
+  __shared__ long long sh_carry;
+  const MapState& st = *m.st;
+  const int tid = threadIdx.x;
+  const int nc = max(0, min(st.n_cells, m.max_cells));
+  MapStateRecord* rec = reinterpret_cast<MapStateRecord*>(head + kMapStateHeaderBytes);
+  if (tid == 0) sh_carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nc; base += 1024) {
+    const int c = base + tid;
+    const int cnt = c < nc ? max(0, min(m.cell_n[c], m.cell_cap)) : 0;
+    int incl = cnt;
+    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if ((tid & 63) >= off) incl += t; }
+    if ((tid & 63) == 63) sh_w[tid >> 6] = incl;
+    __syncthreads();
+    long long run = sh_carry + (incl - cnt);
+    for (int q = 0; q < (tid >> 6); q++) run += sh_w[q];
+    if (c < nc) {
+      MapStateRecord r;
+      for (int a = 0; a < 3; a++) { r.key[a] = m.cell_key[c * 3 + a]; r.corner_leaf[a] = m.cell_org[c * 3 + a] + kMapLeafMargin; }
+      r.count = cnt;
+      r.first = (int)run;
+      rec[c] = r;
+    }
+    __syncthreads();
+    if (tid == 1023) sh_carry = run + cnt;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    MapStateHeader* hd = reinterpret_cast<MapStateHeader*>(head);
+    hd->n_cells = nc;
+    hd->status = (uint32_t)st.status;
+    hd->n_points = sh_carry;
+  }
+}
+
+// Export, step 2, grid (x, y): gathers every cell's current slab into the point section — one 16-byte load and one 16-byte store
+// per point, consecutive lanes on consecutive points.  Reads the plan from the records k_map_pack_plan wrote.
+__global__ __launch_bounds__(256) void k_map_pack(MapView m, const unsigned char* head, float4* pts, int pts_cap) {
+  const MapStateHeader* hd = reinterpret_cast<const MapStateHeader*>(head);
+  const MapStateRecord* rec = reinterpret_cast<const MapStateRecord*>(head + kMapStateHeaderBytes);
+  const int nc = max(0, min(hd->n_cells, m.max_cells));
+  for (int c = blockIdx.y; c < nc; c += gridDim.y) {
+    const int first = rec[c].first, cnt = min(rec[c].count, m.cell_cap);
+    const float4* src = map_cell_cur(m, c);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256) {
+      const long long o = (long long)first + i;
+      if (o >= 0 && o < pts_cap) pts[o] = src[i];
+    }
+  }
+}
+
+// Import, grid (x, y), launched behind k_map_init (which leaves the map empty: hash, cell_n, cell_buf, mod_of_cell = -1, every
+// counter 0; liodom_map_reset is that launch alone).  For every record: the key goes into the hash with the map_hash / linear
+// probe map_find_cell and k_map_assign read (keys are distinct — the host's map_state_validate has seen to it — so the slots are
+// claimed in parallel; which slot a key lands in is invisible to every later lookup), then cslot_cell, cell_key, cell_org =
+// corner_leaf - kMapLeafMargin, cell_n; cell_buf stays 0 and the points go into slab 0.  Any number of cells: nothing here is
+// sized by kMapNewCellsMax.  The host has validated the blob against this map's capacities; counts are clamped all the same.
+__global__ __launch_bounds__(256) void k_map_unpack(MapView m, const unsigned char* head, const float4* pts, int n_cells, int n_points,
+                                                    int status) {
+  const MapStateRecord* rec = reinterpret_cast<const MapStateRecord*>(head + kMapStateHeaderBytes);
+  const int nc = max(0, min(n_cells, m.max_cells));
+  const unsigned int mask = (unsigned int)m.ctable - 1u;
+  const int nthreads = gridDim.x * gridDim.y * 256;
+  for (int c = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; c < nc; c += nthreads) {
+    const MapStateRecord r = rec[c];
+    unsigned long long key;
+    if (map_pack_key(r.key[0], r.key[1], r.key[2], &key)) {
+      unsigned int h = map_hash(key, mask);
+      for (int probe = 0; probe < m.ctable; probe++) {
+        if (atomicCAS(&m.ckey[h], kMapEmptyKey, key) == kMapEmptyKey) { m.cslot_cell[h] = c; break; }
+        h = (h + 1) & mask;
+      }
+    }
+    for (int a = 0; a < 3; a++) {
+      m.cell_key[c * 3 + a] = r.key[a];
+      m.cell_org[c * 3 + a] = (int)((unsigned int)r.corner_leaf[a] - (unsigned int)kMapLeafMargin);
+    }
+    m.cell_n[c] = max(0, min(r.count, m.cell_cap));
+  }
+  for (int c = blockIdx.y; c < nc; c += gridDim.y) {
+    const int first = rec[c].first, cnt = min(rec[c].count, m.cell_cap);
+    float4* dst = m.slab + (size_t)c * m.cell_cap;          // slab 0
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256) {
+      const long long o = (long long)first + i;
+      if (o >= 0 && o < n_points) dst[i] = pts[o];
+    }
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { m.st->n_cells = nc; m.st->status = status; }
 }
 
 }  // namespace liodom_dev

@@ -17,6 +17,7 @@ struct liodom_map {
   float4* d_out = nullptr;
   int out_cap = 0;
   int* d_out_n = nullptr;
+  unsigned char* d_head = nullptr;   // header + max_cells cell records of a map-state blob (first export / import allocates it)
 };
 
 namespace {
@@ -136,6 +137,81 @@ int map_fetch_result(liodom_map* mp, float* xyzi, int64_t cap, int64_t* n_points
   return LIODOM_OK;
 }
 
+
+// ---- the map as a blob (map_state_format.h; kernels at the end of liodom_map.h) ----
+int map_ensure_head(liodom_map* mp) {
+  if (mp->d_head) return LIODOM_OK;
+  void* raw = nullptr;
+  int rc = map_alloc(mp, &raw, (size_t)liodom_dev::map_state_bytes(mp->m.max_cells, 0));
+  if (rc) return rc;
+  mp->d_head = static_cast<unsigned char*>(raw);
+  return LIODOM_OK;
+}
+
+// LIODOM_MAP_STATE_TIMING=1: export and import report the HIP-event time of their kernels on stderr (the figures of DESIGN.md §3)
+struct MapStateTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  hipStream_t q;
+  const char* what;
+  MapStateTimer(hipStream_t q_, const char* what_) : q(q_), what(what_) {
+    const char* e = std::getenv("LIODOM_MAP_STATE_TIMING");
+    if (e && e[0] == '1' && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(a, q);
+  }
+  void stop() { if (b) (void)hipEventRecord(b, q); }
+  ~MapStateTimer() {
+    float ms = 0.f;
+    if (b && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) std::fprintf(stderr, "%s: kernels %.3f ms\n", what, ms);
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+
+// Plans a blob of the map as it is now: the cell records into d_head, the header's n_cells / status / n_points to the host.
+int map_state_plan(liodom_map* mp, liodom_dev::MapStateHeader* hd, const char* who) {
+  int rc = map_ensure_head(mp);
+  if (rc) return rc;
+  hipLaunchKernelGGL(liodom_dev::k_map_pack_plan, dim3(1), dim3(1024), 0, mp->stream, mp->m, mp->d_head);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(hd, mp->d_head, sizeof(*hd), hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  if (hd->n_cells < 0 || hd->n_cells > mp->m.max_cells || hd->n_points < 0 || hd->n_points > (int64_t)hd->n_cells * mp->m.cell_cap) {
+    g_last_error = std::string(who) + ": inconsistent map state"; return LIODOM_ERR_HIP;
+  }
+  if (hd->n_points > 0x7fffffff) { g_last_error = std::string(who) + ": more than 2^31 - 1 points do not fit the blob format"; return LIODOM_ERR_CAPACITY; }
+  return LIODOM_OK;
+}
+
+// The empty map of liodom_map_create (k_map_init), then — with a validated blob — its cells and points (k_map_unpack).
+int map_install_state(liodom_map* mp, const unsigned char* blob, const liodom_dev::MapStateHeader* hd) {
+  using namespace liodom_dev;
+  const MapView& m = mp->m;
+  const int n_cells = hd ? hd->n_cells : 0, n_points = hd ? (int)hd->n_points : 0;
+  if (n_cells > 0) {
+    // everything that can fail comes before the map is touched
+    int rc = map_ensure_head(mp);
+    if (rc) return rc;
+    if ((rc = map_ensure_out(mp, n_points))) return rc;
+    HIP_TRY(hipMemcpyAsync(mp->d_head, blob, (size_t)map_state_bytes(n_cells, 0), hipMemcpyHostToDevice, mp->stream));
+    if (n_points > 0)
+      HIP_TRY(hipMemcpyAsync(mp->d_out, blob + map_state_bytes(n_cells, 0), sizeof(float4) * (size_t)n_points, hipMemcpyHostToDevice, mp->stream));
+  }
+  {
+    MapStateTimer tm(mp->stream, hd ? "liodom_map_import_state" : "liodom_map_reset");
+    const int n_init = std::max(m.ctable, m.max_cells);
+    hipLaunchKernelGGL(k_map_init, dim3((n_init + 255) / 256), dim3(256), 0, mp->stream, m);
+    if (n_cells > 0) {
+      const int xb = std::min(16, (m.cell_cap + 255) / 256), yb = std::min(n_cells, 256);
+      hipLaunchKernelGGL(k_map_unpack, dim3(xb, yb), dim3(256), 0, mp->stream, m, mp->d_head, mp->d_out, n_cells, n_points, (int)hd->status);
+    } else if (hd && hd->status) {
+      HIP_TRY(hipMemcpyAsync(&m.st->status, &hd->status, sizeof(int), hipMemcpyHostToDevice, mp->stream));
+    }
+    tm.stop();
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(mp->stream));      // the caller's blob must not be read after the call returns
+  return LIODOM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -241,6 +317,74 @@ int liodom_map_status(liodom_map_t* mp, uint32_t* status) {
   HIP_TRY(hipMemcpy(&st, mp->m.st, sizeof(st), hipMemcpyDeviceToHost));
   *status = (uint32_t)st.status;
   return LIODOM_OK;
+}
+
+int liodom_map_state_size(liodom_map_t* mp, int64_t* bytes) {
+  if (!mp || !bytes) { g_last_error = "liodom_map_state_size: null argument"; return LIODOM_ERR_INVALID_ARG; }
+  HIP_TRY(hipSetDevice(mp->device));
+  liodom_dev::MapStateHeader hd;
+  int rc = map_state_plan(mp, &hd, "liodom_map_state_size");
+  if (rc) return rc;
+  *bytes = liodom_dev::map_state_bytes(hd.n_cells, hd.n_points);
+  return LIODOM_OK;
+}
+
+int liodom_map_export_state(liodom_map_t* mp, void* blob, int64_t cap, int64_t* bytes) {
+  using namespace liodom_dev;
+  if (!mp || !bytes || cap < 0 || (cap > 0 && !blob)) { g_last_error = "liodom_map_export_state: invalid argument"; return LIODOM_ERR_INVALID_ARG; }
+  HIP_TRY(hipSetDevice(mp->device));
+  MapStateHeader hd;
+  MapStateTimer tm(mp->stream, "liodom_map_export_state");
+  int rc = map_state_plan(mp, &hd, "liodom_map_export_state");      // (synchronises the stream the map's work is enqueued on)
+  if (rc) return rc;
+  const int64_t need = map_state_bytes(hd.n_cells, hd.n_points);
+  *bytes = need;
+  if (need > cap) { g_last_error = "liodom_map_export_state: blob buffer too small"; return LIODOM_ERR_CAPACITY; }
+  unsigned char* out = static_cast<unsigned char*>(blob);
+  const int n_points = (int)hd.n_points;
+  if (n_points > 0) {
+    if ((rc = map_ensure_out(mp, n_points))) return rc;
+    const int xb = std::min(16, (mp->m.cell_cap + 255) / 256), yb = std::min(hd.n_cells, 256);
+    hipLaunchKernelGGL(k_map_pack, dim3(xb, yb), dim3(256), 0, mp->stream, mp->m, mp->d_head, mp->d_out, mp->out_cap);
+    HIP_TRY(hipGetLastError());
+  }
+  tm.stop();
+  if (hd.n_cells > 0)
+    HIP_TRY(hipMemcpyAsync(out + kMapStateHeaderBytes, mp->d_head + kMapStateHeaderBytes, (size_t)kMapStateRecordBytes * (size_t)hd.n_cells,
+                           hipMemcpyDeviceToHost, mp->stream));
+  if (n_points > 0)
+    HIP_TRY(hipMemcpyAsync(out + map_state_bytes(hd.n_cells, 0), mp->d_out, sizeof(float4) * (size_t)n_points, hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  // the header is the host's
+  std::memset(hd.magic, 0, sizeof(hd.magic));
+  std::memcpy(hd.magic, "LIODOMMP", 8);
+  hd.version = kMapStateVersion; hd.header_bytes = (uint32_t)kMapStateHeaderBytes; hd.total_bytes = (uint64_t)need;
+  hd.voxel_xysize = mp->cfg.voxel_xysize; hd.voxel_zsize = mp->cfg.voxel_zsize; hd.resolution = mp->cfg.resolution;
+  std::memcpy(out, &hd, sizeof(hd));
+  return LIODOM_OK;
+}
+
+int liodom_map_import_state(liodom_map_t* mp, const void* blob, int64_t bytes) {
+  if (!mp || !blob) { g_last_error = "liodom_map_import_state: null argument"; return LIODOM_ERR_INVALID_ARG; }
+  if (!mp->own_stream) { g_last_error = "liodom_map_import_state: the map is attached to a handle: detach it (liodom_attach_mapper with NULL), import, attach"; return LIODOM_ERR_BUSY; }
+  // every rejection comes before anything is launched
+  const char* why = "";
+  int rc = liodom_dev::map_state_validate(blob, bytes, mp->cfg.voxel_xysize, mp->cfg.voxel_zsize, mp->cfg.resolution, mp->m.max_cells,
+                                          mp->m.cell_cap, &why);
+  if (rc) { g_last_error = std::string("liodom_map_import_state: ") + why; return rc; }
+  liodom_dev::MapStateHeader hd;
+  std::memcpy(&hd, blob, sizeof(hd));
+  HIP_TRY(hipSetDevice(mp->device));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  return map_install_state(mp, static_cast<const unsigned char*>(blob), &hd);
+}
+
+int liodom_map_reset(liodom_map_t* mp) {
+  if (!mp) { g_last_error = "liodom_map_reset: null argument"; return LIODOM_ERR_INVALID_ARG; }
+  if (!mp->own_stream) { g_last_error = "liodom_map_reset: the map is attached to a handle: detach it first (liodom_attach_mapper with NULL)"; return LIODOM_ERR_BUSY; }
+  HIP_TRY(hipSetDevice(mp->device));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  return map_install_state(mp, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -361,6 +361,18 @@ PointCloud Map::fetch(int which, const double* T, int cells_xy, int cells_z) {
   return out;
 }
 PointCloud Map::getMap() { return fetch(0, nullptr, 0, 0); }
+std::vector<uint8_t> Map::exportState() {
+  int64_t n = 0;
+  check(liodom_map_state_size(m_, &n), "liodom_map_state_size");
+  std::vector<uint8_t> blob((size_t)n);
+  check(liodom_map_export_state(m_, blob.data(), n, &n), "liodom_map_export_state");
+  blob.resize((size_t)n);
+  return blob;
+}
+void Map::importState(const std::vector<uint8_t>& blob) {
+  check(liodom_map_import_state(m_, blob.data(), (int64_t)blob.size()), "liodom_map_import_state");
+}
+void Map::reset() { check(liodom_map_reset(m_), "liodom_map_reset"); }
 PointCloud Map::getLocalMap(const std::array<double, 12>& pose, int cells_xy, int cells_z) {
   return fetch(1, pose.data(), cells_xy, cells_z);
 }

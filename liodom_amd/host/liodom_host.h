@@ -217,6 +217,11 @@ class Map {
   void updateMap(const PointCloud& pc_in, const std::array<double, 12>& pose);                  // :90-129
   PointCloud getMap();                                                                          // :131-139
   PointCloud getLocalMap(const std::array<double, 12>& pose, int cells_xy = 2, int cells_z = 1); // :141-189
+  // The map as one blob (no counterpart in the reference; layout in csrc/map_state_format.h).  exportState works on an attached
+  // map too; importState and reset need a detached one (detach, import, attachMapper).
+  std::vector<uint8_t> exportState();
+  void importState(const std::vector<uint8_t>& blob);
+  void reset();
   liodom_map_t* handle() const { return m_; }
  private:
   PointCloud fetch(int which, const double* T, int cells_xy, int cells_z);

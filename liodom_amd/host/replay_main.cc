@@ -5,7 +5,8 @@
 //   liodom_replay <scan_dir> <out_dir/> [name=value ...]     e.g. scan_lines=64 prev_frames=20
 // With mapping=true the liodom_mapping node (launch/liodom.launch:41-56) is replayed on the device
 // with its launch-file parameters (voxel_xysize= voxel_zsize= resolution= cells_xy= cells_z=); the
-// final map is written to <out_dir>map.bin (float32 x y z i).
+// final map is written to <out_dir>map.bin (float32 x y z i).  map_state_in=FILE starts the mapper from a saved map state
+// (liodom::Map::importState, before it is attached); map_state_out=FILE writes the mapper's state at the end, before map.bin.
 // threads=true runs the reference's own structure instead of the fused per-scan call: the clouds are
 // pushed into SharedData (lidarClb), a FeatureExtractor thread and a LaserOdometer thread work side by
 // side on the same handle (src/liodom_node.cc:89-91) and hand edge clouds over through the queue — the clouds stay on the
@@ -64,6 +65,14 @@ int main(int argc, char** argv) {
     auto eng = std::make_shared<liodom::Engine>(*params, 0, (int)max_pts, (int)(max_pts / (size_t)params->scan_lines_ + 1), 1, covariance ? 1 : 0);
     liodom::LaserOdometer odometer(eng);
     std::unique_ptr<liodom::Map> mapper;
+    std::string map_state_in, map_state_out;
+    for (const std::string& a : kv) {
+      if (a.rfind("map_state_in=", 0) == 0) map_state_in = a.substr(13);
+      if (a.rfind("map_state_out=", 0) == 0) map_state_out = a.substr(14);
+    }
+    if ((!map_state_in.empty() || !map_state_out.empty()) && !params->mapping_) {
+      std::fprintf(stderr, "liodom_replay: map_state_in / map_state_out need mapping=true\n"); return 2;
+    }
     if (params->mapping_) {
       double xy = 40.0, z = 50.0, res = 0.4; int cells_xy = 2, cells_z = 1;      // liodom_mapping_node.cc:115-134
       for (const std::string& a : kv) {
@@ -75,6 +84,14 @@ int main(int argc, char** argv) {
         else if (k == "cells_z") cells_z = std::stoi(v);
       }
       mapper.reset(new liodom::Map(xy, z, res));
+      if (!map_state_in.empty()) {
+        std::ifstream f(map_state_in, std::ios::binary | std::ios::ate);
+        if (!f) { std::fprintf(stderr, "liodom_replay: cannot read %s\n", map_state_in.c_str()); return 1; }
+        std::vector<uint8_t> st((size_t)f.tellg());
+        f.seekg(0);
+        f.read(reinterpret_cast<char*>(st.data()), (std::streamsize)st.size());
+        mapper->importState(st);
+      }
       odometer.attachMapper(mapper.get(), cells_xy, cells_z);
     }
     std::ofstream odom_log(out + "odom.txt");      // stamp, orientation xyzw, position, twist linear, twist angular
@@ -190,6 +207,12 @@ int main(int argc, char** argv) {
     liodom::Stats::getInstance()->writeResults(out);
     if (mapper) {
       odometer.attachMapper(nullptr);
+      if (!map_state_out.empty()) {
+        const std::vector<uint8_t> st = mapper->exportState();
+        std::ofstream f(map_state_out, std::ios::binary);
+        f.write(reinterpret_cast<const char*>(st.data()), (std::streamsize)st.size());
+        std::printf("map state: %zu bytes -> %s\n", st.size(), map_state_out.c_str());
+      }
       const liodom::PointCloud m = mapper->getMap();
       std::ofstream f(out + "map.bin", std::ios::binary);
       f.write(reinterpret_cast<const char*>(m.points.data()), (std::streamsize)(m.points.size() * sizeof(liodom::Point)));
