@@ -466,6 +466,7 @@ def test_multi_workgroup_solve(orc, synth):
     H, W, R, epr, P, K = 16, 900, 6, 10, 5, 10
     cfg = synth.make_cfg(H, W, 0)
     po, g8 = mk(orc, H, W, 0, R, epr, P, lm_workgroups=8)
+    assert g8.modes()["lm_groups"] == "8"
     od = orc.Odometer(po)
     for k in range(K):
         x, _ = synth.scan(cfg, 0, k)
@@ -474,7 +475,9 @@ def test_multi_workgroup_solve(orc, synth):
         assert np.linalg.norm(pose_g[4:] - pose_o[4:]) <= POSE_TOL_T and rot_angle(pose_g[:4], pose_o[:4]) <= POSE_TOL_R
         assert not (info_g.status & 8)
         if k > 0:
+            assert list(info_g.matches) == list(info_o.matches), k
             assert [info_g.lm[0].iterations, info_g.lm[1].iterations] == [info_o.lm[0].iterations, info_o.lm[1].iterations]
+            assert [info_g.lm[0].termination, info_g.lm[1].termination] == [info_o.lm[0].termination, info_o.lm[1].termination], k
     g8.close()
 
 
