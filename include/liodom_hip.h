@@ -526,6 +526,39 @@ int liodom_map_num_cells(liodom_map_t* m, int* n_cells);
  * case.)  The map must live on the handle's device; from here on it uses the handle's HIP stream.
  * Pass map = NULL to detach. */
 int liodom_attach_mapper(liodom_handle_t* h, int stream, liodom_map_t* m, int cells_xy, int cells_z);
+/* How a map is wired to a stream (no counterpart in the reference: its mapper is a node of its own, fed every scan). */
+typedef struct liodom_mapper_options_t {
+  int32_t cells_xy, cells_z;   /* getLocalMap extent, as liodom_attach_mapper (defaults 2, 1) */
+  int32_t lag;                 /* 0 (default): the reference replay, insert scan k after scan k.
+                                  1: insert a frame when it leaves the sliding window */
+  int32_t prune_period;        /* 0 (default): never.  n > 0: prune after the map update of every scan
+                                  with (scan_index + 1) % n == 0, around that scan's pose */
+  int32_t keep_cells_xy, keep_cells_z;   /* the box pruning keeps (liodom_map_prune) */
+  int32_t reserved[2];
+} liodom_mapper_options_t;
+/* cells 2 / 1, lag 0, no pruning: what liodom_attach_mapper does (no counterpart in the reference). */
+void liodom_mapper_options_default(liodom_mapper_options_t* options);
+/* liodom_attach_mapper with options (no counterpart in the reference); liodom_attach_mapper(h, s, m, cxy, cz) IS this call with
+ * the defaults and those two extents.  options = NULL: the defaults.  map = NULL detaches.
+ *   lag = 0  the synchronous replay above.  Faithful, and degenerate: single-point leaves of the map are bit-copies of window
+ *            points, the line through NN0 == NN1 has zero length, both solves end with termination 5 and every pose is the
+ *            constant-velocity prediction.
+ *   lag = 1  scan-to-map odometry that solves: the map holds only what has LEFT the sliding window.  One step of stream s, scan k:
+ *            (1) if the window is full, the frame scan k's append will overwrite — the oldest frame liodom_get_window shows before
+ *            the step — is copied aside with its count; (2) scan k's odometry runs as ever, against window ++ received map;
+ *            (3) the copy enters the map as it is: the window's own world-frame float points, bit for bit, no transform (nothing
+ *            while the window is not full); (4) the optional prune; (5) getLocalMap(pose_k, cells_xy, cells_z) into the stream's
+ *            received-map buffer.  Ordered by HIP stream order alone; nothing is pending between two steps, so the blobs of
+ *            liodom_export_stream_state / liodom_map_export_state and the checkpoint order stay as they are — give the options
+ *            again at attach.  Costs one edge-capacity frame per stream of the handle, allocated by the first such attach.
+ *   prune_period = n > 0  liodom_map_prune(pose_k, keep_cells_xy, keep_cells_z) on the device after the map update of every scan
+ *            with (scan_index + 1) % n == 0.  Needs keep_cells_xy >= cells_xy and keep_cells_z * voxel_zsize >= cells_z *
+ *            voxel_xysize (the reference's z column takes its extent from the xy size): the keep box then holds every cell
+ *            getLocalMap visits for the same pose, and pruning cannot change what the next scan sees.
+ * LIODOM_ERR_INVALID_ARG (attachment unchanged) for a negative extent or period, lag other than 0 / 1, or options that break the
+ * auto-prune conditions.  Streams without a mapper, streams that sit a subset step out and liodom_reset_stream are untouched by
+ * all of this.  liodom_get_modes reports mapper_lag=<streams with a lagged mapper>. */
+int liodom_attach_mapper_ex(liodom_handle_t* h, int stream, liodom_map_t* m, const liodom_mapper_options_t* options);
 /* Sticky LIODOM_MAP_* bits raised by the device since creation. */
 int liodom_map_status(liodom_map_t* m, uint32_t* status);
 
@@ -559,6 +592,18 @@ int liodom_map_state_size(liodom_map_t* m, int64_t* bytes);
 int liodom_map_export_state(liodom_map_t* m, void* blob, int64_t cap, int64_t* bytes);
 int liodom_map_import_state(liodom_map_t* m, const void* blob, int64_t bytes);
 int liodom_map_reset(liodom_map_t* m);
+
+/* Drops every cell outside a box of cells around a pose (no counterpart in the reference, whose map only grows until
+ * LIODOM_MAP_CELLS_FULL).  T = 3 x 4 pose, row-major; the centre cell (vx, vy, vz) is computed from it as Map::getLocalMap does
+ * (src/map.cc:144-151: the translation truncated to int first, then the cell key).  A cell with key (kx, ky, kz) is kept iff
+ * |kx - vx| <= keep_cells_xy * voxel_xysize, |ky - vy| <= keep_cells_xy * voxel_xysize and |kz - vz| <= keep_cells_z * voxel_zsize
+ * (compared in double; a plain box, not getLocalMap's cross-shaped visit).  Afterwards the map is what liodom_map_import_state
+ * would make of its own exported blob with the dropped cells' records and points taken out: survivors keep their relative
+ * creation order, slots an earlier LIODOM_MAP_CELLS_FULL marked "no room" are gone (new cells can be created again), sticky status
+ * bits stay.  *n_removed (optional) = cells dropped.  Works on a detached map and on an attached one, where it is enqueued on the
+ * stream the map's work is on; it synchronises, with the threading rule of liodom_map_export_state.  LIODOM_ERR_INVALID_ARG for a
+ * null map or T or a negative keep: the map is untouched.  The first prune of a map allocates 16 bytes per max_cells. */
+int liodom_map_prune(liodom_map_t* m, const double* T /*3x4*/, int keep_cells_xy, int keep_cells_z, int* n_removed);
 
 #ifdef __cplusplus
 }

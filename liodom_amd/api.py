@@ -12,7 +12,7 @@ _HASH = _LIB + ".srchash"
 _BUILD_INFO = {"rebuilt": None, "source_hash": None}
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kernels.h", "kernels_extract.h", "kernels_sync.h",
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
-                                                  "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "liodom_math.h", "wave_ops.h",
+                                                  "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -147,6 +147,12 @@ class MapConfig(C.Structure):
                 ("voxel_xysize", C.c_double), ("voxel_zsize", C.c_double), ("resolution", C.c_double),
                 ("cell_capacity", C.c_int32), ("max_update_points", C.c_int32), ("max_modified_cells", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class MapperOptions(C.Structure):
+    """liodom_mapper_options_t: how liodom_attach_mapper_ex wires a map to a stream (include/liodom_hip.h)."""
+    _fields_ = [("cells_xy", C.c_int32), ("cells_z", C.c_int32), ("lag", C.c_int32), ("prune_period", C.c_int32),
+                ("keep_cells_xy", C.c_int32), ("keep_cells_z", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class EdgeTicket(C.Structure):
@@ -480,6 +486,12 @@ def load():
     L.liodom_set_laser_to_base.argtypes = [vp, dp]
     L.liodom_attach_mapper.restype = C.c_int
     L.liodom_attach_mapper.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+    L.liodom_mapper_options_default.restype = None
+    L.liodom_mapper_options_default.argtypes = [C.POINTER(MapperOptions)]
+    L.liodom_attach_mapper_ex.restype = C.c_int
+    L.liodom_attach_mapper_ex.argtypes = [vp, C.c_int, vp, C.POINTER(MapperOptions)]
+    L.liodom_map_prune.restype = C.c_int
+    L.liodom_map_prune.argtypes = [vp, dp, C.c_int, C.c_int, ip]
     L.liodom_map_config_default.argtypes = [C.POINTER(MapConfig)]
     L.liodom_map_create.restype = C.c_int
     L.liodom_map_create.argtypes = [C.POINTER(MapConfig), C.POINTER(vp)]
@@ -576,6 +588,7 @@ EXPORTED_SYMBOLS = [
     "liodom_polar_layout", "liodom_set_polar_geometry", "liodom_project_polar", "liodom_upload_scan_polar", "liodom_process_scan_polar",
     "liodom_scan_buffer_polar", "liodom_extract_edges_device_polar",
     "liodom_map_state_size", "liodom_map_export_state", "liodom_map_import_state", "liodom_map_reset",
+    "liodom_mapper_options_default", "liodom_attach_mapper_ex", "liodom_map_prune",
 ]
 
 
@@ -612,6 +625,15 @@ def make_config(**kw):
     for k, v in kw.items():
         setattr(c, k, v)
     return c
+
+
+def make_mapper_options(**kw):
+    """MapperOptions with the defaults of liodom_mapper_options_default (cells 2 / 1, lag 0, no pruning)."""
+    o = MapperOptions()
+    load().liodom_mapper_options_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, int(v))
+    return o
 
 
 def _fp(a):
@@ -991,10 +1013,14 @@ class Liodom:
         self._check(self.L.liodom_get_received_map(self.h, stream, _fp(w), cap, C.byref(n)))
         return w[:n.value].copy()
 
-    def attach_mapper(self, mapper, cells_xy=2, cells_z=1, stream=0):
-        """Synchronous on-device replay of the liodom_mapping node for this stream (see
-        liodom_attach_mapper in include/liodom_hip.h)."""
-        self._check(self.L.liodom_attach_mapper(self.h, stream, mapper.h if mapper is not None else None, cells_xy, cells_z))
+    def attach_mapper(self, mapper, cells_xy=2, cells_z=1, stream=0, lag=0, prune_period=0, keep_cells_xy=0, keep_cells_z=0):
+        """On-device mapper for this stream (liodom_attach_mapper_ex in include/liodom_hip.h).  lag = 0: the synchronous replay
+        of the liodom_mapping node (faithful, and degenerate: every pose is the prediction); lag = 1: the map takes a frame when
+        it leaves the sliding window (scan-to-map odometry that solves).  prune_period = n > 0: the map is pruned to the keep box
+        around the pose every n-th scan.  mapper = None detaches."""
+        o = make_mapper_options(cells_xy=cells_xy, cells_z=cells_z, lag=lag, prune_period=prune_period, keep_cells_xy=keep_cells_xy,
+                                keep_cells_z=keep_cells_z)
+        self._check(self.L.liodom_attach_mapper_ex(self.h, stream, mapper.h if mapper is not None else None, C.byref(o)))
         self._mappers = getattr(self, "_mappers", {})
         self._mappers[stream] = mapper      # keep it alive while attached
 
@@ -1097,6 +1123,16 @@ class Map:
         n = C.c_int64(0)
         self._chk(self._L.liodom_map_get_local(self.h, _dp(T), cells_xy, cells_z, _fp(out), out.shape[0], C.byref(n)))
         return out[:n.value].copy()
+
+    get_local = local
+
+    def prune(self, T34=None, keep_xy=2, keep_z=1):
+        """Drops every cell outside the box of keep_xy / keep_z cells around the pose's cell (liodom_map_prune); returns the
+        number of cells removed.  Works on an attached map too.  LiodomError with .code ERR_INVALID_ARG for a negative keep."""
+        T = self._T(T34)
+        n = C.c_int32(0)
+        self._chk(self._L.liodom_map_prune(self.h, _dp(T), int(keep_xy), int(keep_z), C.byref(n)))
+        return n.value
 
     def all(self):
         out = np.zeros((self.result_capacity, 4), dtype=np.float32)

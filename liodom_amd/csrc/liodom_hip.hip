@@ -163,7 +163,12 @@ struct liodom_handle {
   // profiling
   std::atomic<bool> profiling{false};   // read without a lock by SideLocks / extract_queue, written under both mutexes
   std::vector<liodom_map*> mappers;   // per stream: attached device map (mapping replay) or null
-  std::vector<int> mapper_cells_xy, mapper_cells_z;
+  std::vector<liodom_mapper_options_t> mapper_opts;   // per stream: what its mapper was attached with (liodom_attach_mapper_ex)
+  // lagged mappers (lag = 1; all null / 0 until the first such attach): per stream, the frame the step's append overwrites
+  float4* lag_stash = nullptr;        // [S][edge_cap]
+  int* lag_stash_n = nullptr;         // [S] its points (0 while the window is not full)
+  int* lag_on = nullptr;              // [S] the stream has a lagged mapper (read by k_window_stash)
+  int n_lagged = 0;                   // streams with a lagged mapper
   std::vector<int> hb_since;    // hash_incr, per stream: scans since the stream's last k_hash_build (-1: none yet)
   int knn8_grid = 1;            // k_knn8 workgroups per stream (each walks the blocks b, b + grid, ... of 32 queries)
   bool knn8 = false;            // lock-step batches: k_knn8 (eight lanes per query) instead of k_knn<128>; LIODOM_KNN8=0 keeps the latter
@@ -342,6 +347,18 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
     ProfScope ps(h, KID_OTHER);
     by_rows([&](auto L) { hipLaunchKernelGGL((k_imu_override<decltype(L)::value>), dim3(cdiv(count, 64)), dim3(64), 0, h->stream, v, s0, count); });
   }
+  if (h->n_lagged > 0) {
+    // Lagged mappers: the frame this scan's append will overwrite is set aside before anything of the step runs (one launch for
+    // the step's streams; k_window_stash skips those without a lagged mapper).  A mapping handle runs neither the streamed
+    // rebuild nor chain mode nor the overlapped pass (early_rebuild = 0): the previous scan's append, this launch, the solves, the
+    // map update and this scan's append are all on the odometry stream, in this order.
+    bool any = false;
+    for (int i = 0; i < count; i++) { const int s = stream_at(i); any = any || (h->mappers[s] && h->mapper_opts[s].lag == 1); }
+    if (any) {
+      ProfScope ps(h, KID_OTHER);
+      by_rows([&](auto L) { hipLaunchKernelGGL((k_window_stash<decltype(L)::value>), dim3(std::min(16, cdiv(v.edge_cap, 256)), count), dim3(256), 0, h->stream, v, s0, h->lag_on, h->lag_stash, h->lag_stash_n); });
+    }
+  }
   // early rebuild ("streamed rebuild", kernels_rebuild.h): the four launches of a scan carry extra workgroups that build
   // the next scan's cell hash in the second table; nothing follows the finalising solve
   const int map_blocks = cdiv(h->v.map_cap, 256);
@@ -459,16 +476,25 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
   }
   if (v.mapping) {
     // synchronous replay of the mapping node for the streams with an attached map: updateMap(edges_k,
-    // pose_k), then getLocalMap(pose_k) straight into the stream's received-map buffer
+    // pose_k), then getLocalMap(pose_k) straight into the stream's received-map buffer.
+    // lag = 1: the map takes the frame that left the window instead (stashed above; world frame already: no transform), then the
+    // optional prune around pose_k, then the same getLocalMap.
     for (int i = 0; i < count; i++) {
       const int s = stream_at(i);
       liodom_map* mp = h->mappers[s];
       if (!mp) continue;
       ProfScope ps(h, KID_OTHER);
       StreamState* st = v.state + s;
-      int rc = map_enqueue_update(mp, v.edges + ((size_t)eb * v.n_streams + s) * v.edge_cap, &st->n_edges_buf[eb], st->final_odom, h->stream);
+      const liodom_mapper_options_t& mo = h->mapper_opts[s];
+      int rc = mo.lag == 1 ? map_enqueue_update(mp, h->lag_stash + (size_t)s * v.edge_cap, h->lag_stash_n + s, nullptr, h->stream)
+                           : map_enqueue_update(mp, v.edges + ((size_t)eb * v.n_streams + s) * v.edge_cap, &st->n_edges_buf[eb], st->final_odom, h->stream);
       if (rc) return rc;
-      rc = map_enqueue_local(mp, st->final_odom, h->mapper_cells_xy[s], h->mapper_cells_z[s], v.recv_pts + (size_t)s * v.recv_cap,
+      // (scans_enqueued[s] is this scan's index: launch_odometry counts it when the step has been enqueued)
+      if (mo.prune_period > 0 && (h->scans_enqueued[s] + 1) % mo.prune_period == 0) {
+        rc = map_enqueue_prune(mp, st->final_odom, mo.keep_cells_xy, mo.keep_cells_z, h->stream);
+        if (rc) return rc;
+      }
+      rc = map_enqueue_local(mp, st->final_odom, mo.cells_xy, mo.cells_z, v.recv_pts + (size_t)s * v.recv_cap,
                              v.recv_cap, &st->n_recv, h->stream, 1);
       if (rc) return rc;
     }
@@ -1069,7 +1095,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     v.host_out = static_cast<HostOut*>(dp);
     h->scans_enqueued.assign(S, 0);
     h->last_eb.assign(S, 0);
-    h->mappers.assign(S, nullptr); h->mapper_cells_xy.assign(S, 2); h->mapper_cells_z.assign(S, 1);
+    h->mappers.assign(S, nullptr); h->mapper_opts.assign(S, liodom_mapper_options_t{2, 1, 0, 0, 0, 0, {0, 0}});
   }
   if (config->pose_covariance) {
     // per-scan pose covariance (kernels_cov.h): nothing of it exists on handles created without it
@@ -1970,28 +1996,67 @@ int liodom_get_received_map(liodom_handle_t* h, int stream, float* xyzi, int64_t
   return LIODOM_OK;
 }
 
-int liodom_attach_mapper(liodom_handle_t* h, int stream, liodom_map_t* m, int cells_xy, int cells_z) {
+void liodom_mapper_options_default(liodom_mapper_options_t* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->cells_xy = 2; o->cells_z = 1;      // liodom_mapping_node.cc:130-134
+}
+
+int liodom_attach_mapper_ex(liodom_handle_t* h, int stream, liodom_map_t* m, const liodom_mapper_options_t* options) {
   int rc = check_stream(h, stream);
   if (rc) return rc;
   if (!h->v.mapping) { g_last_error = "liodom_attach_mapper: the handle was created with mapping = 0"; return LIODOM_ERR_UNSUPPORTED; }
+  liodom_mapper_options_t o;
+  liodom_mapper_options_default(&o);
+  if (options) o = *options;
+  if (m) {      // every rejection comes before the attachment is touched
+    if (m->device != h->config.device) { g_last_error = "liodom_attach_mapper: map and handle live on different devices"; return LIODOM_ERR_INVALID_ARG; }
+    if (o.cells_xy < 0 || o.cells_z < 0 || o.lag < 0 || o.lag > 1 || o.prune_period < 0 || o.keep_cells_xy < 0 || o.keep_cells_z < 0) {
+      g_last_error = "liodom_attach_mapper_ex: negative extent or period, or lag not 0 / 1"; return LIODOM_ERR_INVALID_ARG;
+    }
+    // auto-prune must not change getLocalMap(pose_k): the keep box has to hold every key that visit reaches — its square, and
+    // its z column, whose extent the reference takes from the xy size (map.cc:175-178)
+    if (o.prune_period > 0 && !(o.keep_cells_xy >= o.cells_xy && (double)o.keep_cells_z * m->cfg.voxel_zsize >= (double)o.cells_z * m->cfg.voxel_xysize)) {
+      g_last_error = "liodom_attach_mapper_ex: prune_period needs keep_cells_xy >= cells_xy and keep_cells_z * voxel_zsize >= cells_z * voxel_xysize";
+      return LIODOM_ERR_INVALID_ARG;
+    }
+  }
   SideLocks lk(h, true, false);
   HIP_TRY(sync_odometry(h));
+  if (m && o.lag == 1 && !h->lag_stash) {      // one edge_cap frame per stream, from the first lagged attach on
+    if ((rc = dev_alloc(h, &h->lag_stash, (size_t)h->S * (size_t)h->v.edge_cap))) return rc;
+    if ((rc = dev_alloc(h, &h->lag_stash_n, (size_t)h->S))) return rc;
+    if ((rc = dev_alloc(h, &h->lag_on, (size_t)h->S))) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  if (m && o.prune_period > 0 && (rc = map_ensure_prune(m))) return rc;
   if (liodom_map* old = h->mappers[stream]) {       // detach: the map gets a stream of its own again
     h->mappers[stream] = nullptr;
+    if (h->mapper_opts[stream].lag == 1) h->n_lagged--;
     old->stream = nullptr; old->own_stream = false;
     HIP_TRY(hipStreamCreateWithFlags(&old->stream, hipStreamNonBlocking));
     old->own_stream = true;
   }
-  if (!m) return LIODOM_OK;
-  if (m->device != h->config.device) { g_last_error = "liodom_attach_mapper: map and handle live on different devices"; return LIODOM_ERR_INVALID_ARG; }
-  if (cells_xy < 0 || cells_z < 0) return LIODOM_ERR_INVALID_ARG;
-  HIP_TRY(hipStreamSynchronize(m->stream));
-  if (m->own_stream) { (void)hipStreamDestroy(m->stream); m->own_stream = false; }
-  m->stream = h->stream;
-  h->mappers[stream] = m;
-  h->mapper_cells_xy[stream] = cells_xy;
-  h->mapper_cells_z[stream] = cells_z;
+  if (m) {
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (m->own_stream) { (void)hipStreamDestroy(m->stream); m->own_stream = false; }
+    m->stream = h->stream;
+    h->mappers[stream] = m;
+    h->mapper_opts[stream] = o;
+    if (o.lag == 1) h->n_lagged++;
+  }
+  if (h->lag_on) {
+    const int on = (m && o.lag == 1) ? 1 : 0;
+    HIP_TRY(hipMemcpy(h->lag_on + stream, &on, sizeof(int), hipMemcpyHostToDevice));
+  }
   return LIODOM_OK;
+}
+
+int liodom_attach_mapper(liodom_handle_t* h, int stream, liodom_map_t* m, int cells_xy, int cells_z) {
+  liodom_mapper_options_t o;
+  liodom_mapper_options_default(&o);
+  o.cells_xy = cells_xy; o.cells_z = cells_z;
+  return liodom_attach_mapper_ex(h, stream, m, &o);
 }
 
 int liodom_alloc_resident(liodom_handle_t* h, int n_slots) {
@@ -2585,6 +2650,10 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   if (v.cov_raw) {
     const size_t len = std::strlen(buf);
     snprintf(buf + len, (size_t)cap - len, " pose_cov=1");
+  }
+  if (h->n_lagged > 0) {      // streams with a lagged mapper (liodom_attach_mapper_ex); their steps run on the odometry stream alone, as every mapping handle's
+    const size_t len = std::strlen(buf);
+    snprintf(buf + len, (size_t)cap - len, " mapper_lag=%d", h->n_lagged);
   }
   {
     const size_t len = std::strlen(buf);      // (steps liodom_process_resident_subset ran over a stream list, i.e. did not hand to the plain step)

@@ -25,7 +25,8 @@
 //   k_pose_cov               (pose_covariance = 1) covariance + eigen-decomposition of the finalising solve's H, one wave per stream
 //   k_state_pack / k_state_unpack / k_stream_clear   a stream's odometry state as one blob (liodom_export_stream_state /
 //                            liodom_import_stream_state / liodom_reset_stream; kernels_state.h): never on the per-scan path
-//   (liodom_map.h)    A12-A14 the mapping node's Map: updateMap / getLocalMap / getMap
+//   k_window_stash           (lagged mapper, liodom_attach_mapper_ex; kernels_mapper.h) the frame a scan's append overwrites, set aside for the map
+//   (liodom_map.h)    A12-A14 the mapping node's Map: updateMap / getLocalMap / getMap; pruning
 //
 // All FP on the parity-critical paths is compiled with -ffp-contract=off.
 #pragma once
@@ -442,5 +443,6 @@ __device__ __forceinline__ void inject_delay(unsigned int site) {
 #include "kernels_cov.h"
 #include "kernels_state.h"
 #include "kernels_polar.h"
+#include "kernels_mapper.h"
 
 }  // namespace liodom_dev

@@ -143,13 +143,16 @@ __device__ __forceinline__ int map_leaf_bit(const MapView& m, int cell, const fl
 // updateMap, step 1 (one workgroup): transform, cell keys, creation of missing cells in
 // first-appearance order, list of modified cells.
 // ---------------------------------------------------------------------------------------------
+// kTransform = false (the lagged mapper, liodom_attach_mapper_ex with lag = 1): the input is in the world frame already — a frame
+// that left a sliding window — and enters the map bit for bit; T_ptr is not read.
+template <bool kTransform = true>
 __global__ __launch_bounds__(1024) void k_map_assign(MapView m, const float4* in, const int* n_ptr, const double* T_ptr) {
   __shared__ double T[12];
   __shared__ int sh_newslot[kMapNewCellsMax];
   __shared__ int sh_nnew, sh_nmod, sh_n;
   const int tid = threadIdx.x;
   MapState& st = *m.st;
-  if (tid < 12) T[tid] = T_ptr[tid];
+  if (kTransform && tid < 12) T[tid] = T_ptr[tid];
   if (tid == 0) {
     int n = *n_ptr;
     if (n > m.upd_cap) { n = m.upd_cap; atomicOr(&st.status, MAP_STATUS_UPDATE_OVERFLOW); }
@@ -162,9 +165,8 @@ __global__ __launch_bounds__(1024) void k_map_assign(MapView m, const float4* in
   // phase A: claim / find the hash slot of every point's cell
   for (int i = tid; i < n; i += 1024) {
     const float4 e = in[i];
-    float4 p;
-    transform_point(T, e.x, e.y, e.z, &p.x, &p.y, &p.z);        // map.cc:93-94
-    p.w = e.w;
+    float4 p = e;
+    if (kTransform) transform_point(T, e.x, e.y, e.z, &p.x, &p.y, &p.z);        // map.cc:93-94
     m.new_pts[i] = p;
     const int kx = map_cell_key((double)p.x, m.inv_xy, m.xy, m.half_xy);      // :103
     const int ky = map_cell_key((double)p.y, m.inv_xy, m.xy, m.half_xy);      // :104
@@ -631,6 +633,112 @@ __global__ __launch_bounds__(256) void k_map_unpack(MapView m, const unsigned ch
     }
   }
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { m.st->n_cells = nc; m.st->status = status; }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Pruning (liodom_map_prune, the auto-prune of liodom_attach_mapper_ex; no counterpart in the reference, whose map only grows):
+// every cell outside a box of cells around a pose is dropped.  Afterwards the map is what liodom_map_import_state would make of
+// its own blob with the dropped cells' records and points taken out: the survivors keep their relative creation order and are
+// renumbered densely, the cell hash (open addressing, no tombstones: nothing can be deleted in place) is rebuilt from them — which
+// also drops the "no room" slots an earlier CELLS_FULL left —, sticky status bits stay.  A map that never prunes launches none of
+// this and allocates nothing for it.
+//
+// Moving the slabs without a hazard: survivor c -> new id j <= c.  Its points are copied from its CURRENT slab (cell_buf[c], c) to
+// the NON-current slab of id j, (cell_buf[j] ^ 1, j), and cell_buf[j] is flipped.  Every source of the move is a current slab
+// (b_c, c); a destination (b_j ^ 1, j) could only be a source if c' = j and b_j = b_j ^ 1.  So the move is one grid, in any order.
+// A survivor whose id does not change (j = c) stays where it is.
+// ---------------------------------------------------------------------------------------------
+constexpr int kMapPruneThreads = 1024;
+// One entry per survivor (16 bytes, one load in the move grid): old id, slab it is read from, slab of id j it goes to, points.
+// Entry [max_cells] is the host's: {cells removed, cells before, cells after, 0}.
+struct __attribute__((aligned(16))) MapPruneMove { int src, src_buf, dst_buf, count; };
+
+// Step 1.  Workgroup 0 plans: centre cell from T exactly as k_map_local_plan (translation truncated to int first, map.cc:144-151),
+// keep flags, exclusive scan over creation order (the scan of k_map_all_plan, any number of cells), and the bookkeeping arrays
+// compacted in place, chunk after chunk: a chunk's threads hold their cells' records in registers across the scan's barrier and
+// write to ids j <= c, i.e. to places of this chunk or of earlier ones, all read already; no place is written twice.
+// Workgroups 1 .. : the cell hash back to the state k_map_init leaves (independent of the plan; the move grid re-inserts).
+__global__ __launch_bounds__(kMapPruneThreads) void k_map_prune_plan(MapView m, const double* T_ptr, int keep_xy, int keep_z, MapPruneMove* mv) {
+  const int tid = threadIdx.x;
+  if (blockIdx.x > 0) {
+    for (int i = ((int)blockIdx.x - 1) * kMapPruneThreads + tid; i < m.ctable; i += ((int)gridDim.x - 1) * kMapPruneThreads) {
+      m.ckey[i] = kMapEmptyKey; m.cslot_cell[i] = -1; m.cfirst[i] = 0x7fffffff;
+    }
+    return;
+  }
+  __shared__ int sh_w[16];
+  __shared__ int sh_carry;
+  MapState& st = *m.st;
+  const int nc = max(0, min(st.n_cells, m.max_cells));
+  const int x = (int)T_ptr[3], y = (int)T_ptr[7], z = (int)T_ptr[11];                 // map.cc:144,147,150
+  const int vx = map_cell_key((double)x, m.inv_xy, m.xy, m.half_xy);
+  const int vy = map_cell_key((double)y, m.inv_xy, m.xy, m.half_xy);
+  const int vz = map_cell_key((double)z, m.inv_z, m.z, m.half_z);
+  const double lim_xy = (double)keep_xy * m.xy, lim_z = (double)keep_z * m.z;
+  if (tid == 0) sh_carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nc; base += kMapPruneThreads) {
+    const int c = base + tid;
+    int key[3] = {0, 0, 0}, org[3] = {0, 0, 0}, cnt = 0, buf = 0, keep = 0;
+    if (c < nc) {
+      for (int a = 0; a < 3; a++) { key[a] = m.cell_key[c * 3 + a]; org[a] = m.cell_org[c * 3 + a]; }
+      cnt = max(0, min(m.cell_n[c], m.cell_cap));
+      buf = m.cell_buf[c] & 1;
+      keep = (fabs((double)key[0] - (double)vx) <= lim_xy && fabs((double)key[1] - (double)vy) <= lim_xy &&
+              fabs((double)key[2] - (double)vz) <= lim_z) ? 1 : 0;
+    }
+    int incl = keep;
+    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if ((tid & 63) >= off) incl += t; }
+    if ((tid & 63) == 63) sh_w[tid >> 6] = incl;
+    __syncthreads();                      // (every record of the chunk is in registers from here on)
+    int j = sh_carry + incl - keep;
+    for (int q = 0; q < (tid >> 6); q++) j += sh_w[q];
+    if (keep) {
+      for (int a = 0; a < 3; a++) { m.cell_key[j * 3 + a] = key[a]; m.cell_org[j * 3 + a] = org[a]; }
+      m.cell_n[j] = cnt;
+      MapPruneMove e;
+      e.src = c; e.src_buf = buf; e.count = cnt;
+      e.dst_buf = (j == c) ? buf : ((m.cell_buf[j] & 1) ^ 1);      // (cell_buf[j] is written by id j's survivor alone: this thread)
+      m.cell_buf[j] = e.dst_buf;
+      mv[j] = e;
+    }
+    __syncthreads();
+    if (tid == kMapPruneThreads - 1) sh_carry = j + keep;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const int kept = sh_carry;
+    MapPruneMove info; info.src = nc - kept; info.src_buf = nc; info.dst_buf = kept; info.count = 0;
+    mv[m.max_cells] = info;
+    st.n_cells = kept;
+  }
+}
+
+// Step 2, grid (chunk, survivor): the survivors' keys into the cleared hash (distinct keys, slots claimed in parallel as in
+// k_map_unpack), and the slabs of those whose id changed — one 16-byte load and one 16-byte store per point, consecutive lanes on
+// consecutive points, only cell_n points of a cell.
+__global__ __launch_bounds__(256) void k_map_prune_move(MapView m, const MapPruneMove* mv) {
+  const int nc = max(0, min(m.st->n_cells, m.max_cells));
+  const unsigned int mask = (unsigned int)m.ctable - 1u;
+  const int nthreads = gridDim.x * gridDim.y * 256;
+  for (int c = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; c < nc; c += nthreads) {
+    unsigned long long key;
+    if (map_pack_key(m.cell_key[c * 3 + 0], m.cell_key[c * 3 + 1], m.cell_key[c * 3 + 2], &key)) {
+      unsigned int h = map_hash(key, mask);
+      for (int probe = 0; probe < m.ctable; probe++) {
+        if (atomicCAS(&m.ckey[h], kMapEmptyKey, key) == kMapEmptyKey) { m.cslot_cell[h] = c; break; }
+        h = (h + 1) & mask;
+      }
+    }
+  }
+  for (int j = blockIdx.y; j < nc; j += gridDim.y) {
+    const MapPruneMove e = mv[j];
+    if (e.src == j || e.src < 0 || e.src >= m.max_cells) continue;
+    const int cnt = min(e.count, m.cell_cap);
+    const float4* src = m.slab + ((size_t)(e.src_buf & 1) * m.max_cells + e.src) * m.cell_cap;
+    float4* dst = m.slab + ((size_t)(e.dst_buf & 1) * m.max_cells + j) * m.cell_cap;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256) dst[i] = src[i];
+  }
 }
 
 }  // namespace liodom_dev

@@ -18,6 +18,7 @@ struct liodom_map {
   int out_cap = 0;
   int* d_out_n = nullptr;
   unsigned char* d_head = nullptr;   // header + max_cells cell records of a map-state blob (first export / import allocates it)
+  liodom_dev::MapPruneMove* d_prune = nullptr;   // max_cells + 1 move records of a prune (the first prune, or an attach with auto-prune, allocates it)
 };
 
 namespace {
@@ -78,12 +79,14 @@ int map_build(liodom_map* mp, const liodom_map_config_t* c, hipStream_t stream) 
 }
 
 // Map::updateMap enqueued on `q`: points, their count and the pose are read from device memory.
+// d_T == nullptr: the points are in the world frame already and enter the map as they are (the lagged mapper).
 int map_enqueue_update(liodom_map* mp, const float4* d_pts, const int* d_n, const double* d_T, hipStream_t q) {
   using namespace liodom_dev;
   const MapView& m = mp->m;
   const int xb_old = (m.cell_cap + 255) / 256, xb_new = (m.upd_cap + 255) / 256;
   const int xb = std::max(xb_old, xb_new);
-  hipLaunchKernelGGL(k_map_assign, dim3(1), dim3(1024), 0, q, m, d_pts, d_n, d_T);
+  if (d_T) hipLaunchKernelGGL(k_map_assign<true>, dim3(1), dim3(1024), 0, q, m, d_pts, d_n, d_T);
+  else hipLaunchKernelGGL(k_map_assign<false>, dim3(1), dim3(1024), 0, q, m, d_pts, d_n, d_T);
   hipLaunchKernelGGL(k_map_clear, dim3(std::min(64, std::max((m.words + 255) / 256, xb_old)), m.mod_cap), dim3(256), 0, q, m);
   hipLaunchKernelGGL(k_map_setbits, dim3(xb, m.mod_cap + 1), dim3(256), 0, q, m);
   hipLaunchKernelGGL(k_map_prefix, dim3(m.mod_cap), dim3(1024), 0, q, m);
@@ -145,6 +148,27 @@ int map_ensure_head(liodom_map* mp) {
   int rc = map_alloc(mp, &raw, (size_t)liodom_dev::map_state_bytes(mp->m.max_cells, 0));
   if (rc) return rc;
   mp->d_head = static_cast<unsigned char*>(raw);
+  return LIODOM_OK;
+}
+
+// ---- pruning (kernels at the end of liodom_map.h) ----
+int map_ensure_prune(liodom_map* mp) {
+  if (mp->d_prune) return LIODOM_OK;
+  void* raw = nullptr;
+  int rc = map_alloc(mp, &raw, sizeof(liodom_dev::MapPruneMove) * ((size_t)mp->m.max_cells + 1));
+  if (rc) return rc;
+  mp->d_prune = static_cast<liodom_dev::MapPruneMove*>(raw);
+  return LIODOM_OK;
+}
+
+// Drops every cell outside the keep box around the pose at d_T (device memory), enqueued on `q`; map_ensure_prune has run.
+int map_enqueue_prune(liodom_map* mp, const double* d_T, int keep_xy, int keep_z, hipStream_t q) {
+  using namespace liodom_dev;
+  const MapView& m = mp->m;
+  const int clear_blocks = std::min(64, (m.ctable + kMapPruneThreads - 1) / kMapPruneThreads);
+  hipLaunchKernelGGL(k_map_prune_plan, dim3(1 + clear_blocks), dim3(kMapPruneThreads), 0, q, m, d_T, keep_xy, keep_z, mp->d_prune);
+  hipLaunchKernelGGL(k_map_prune_move, dim3(std::min(16, (m.cell_cap + 255) / 256), std::min(m.max_cells, 256)), dim3(256), 0, q, m, mp->d_prune);
+  HIP_TRY(hipGetLastError());
   return LIODOM_OK;
 }
 
@@ -377,6 +401,20 @@ int liodom_map_import_state(liodom_map_t* mp, const void* blob, int64_t bytes) {
   HIP_TRY(hipSetDevice(mp->device));
   HIP_TRY(hipStreamSynchronize(mp->stream));
   return map_install_state(mp, static_cast<const unsigned char*>(blob), &hd);
+}
+
+int liodom_map_prune(liodom_map_t* mp, const double* T, int keep_cells_xy, int keep_cells_z, int* n_removed) {
+  if (!mp || !T || keep_cells_xy < 0 || keep_cells_z < 0) { g_last_error = "liodom_map_prune: null map or pose, or a negative keep extent"; return LIODOM_ERR_INVALID_ARG; }
+  HIP_TRY(hipSetDevice(mp->device));
+  int rc = map_ensure_prune(mp);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(mp->d_T, T, sizeof(double) * 12, hipMemcpyHostToDevice, mp->stream));
+  if ((rc = map_enqueue_prune(mp, mp->d_T, keep_cells_xy, keep_cells_z, mp->stream))) return rc;
+  liodom_dev::MapPruneMove info{};
+  HIP_TRY(hipMemcpyAsync(&info, mp->d_prune + mp->m.max_cells, sizeof(info), hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));      // (the staged pose and `info` are this frame's)
+  if (n_removed) *n_removed = info.src;
+  return LIODOM_OK;
 }
 
 int liodom_map_reset(liodom_map_t* mp) {

@@ -445,6 +445,22 @@ void LaserOdometer::reset() {
   prev_odom_ = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
   prev_stamp_ = 0.0; published_ = false; init_ = false; last_scan_ = -1;
 }
+int Map::prune(const std::array<double, 12>& pose, int keep_xy, int keep_z) {
+  int n = 0;
+  check(liodom_map_prune(m_, pose.data(), keep_xy, keep_z, &n), "liodom_map_prune");
+  return n;
+}
+
+int Map::numCells() {
+  int n = 0;
+  check(liodom_map_num_cells(m_, &n), "liodom_map_num_cells");
+  return n;
+}
+
+void LaserOdometer::attachMapper(Map* map, const liodom_mapper_options_t& options) {
+  check(liodom_attach_mapper_ex(eng_->handle(), 0, map ? map->handle() : nullptr, &options), "liodom_attach_mapper_ex");
+}
+
 void LaserOdometer::attachMapper(Map* map, int cells_xy, int cells_z) {
   check(liodom_attach_mapper(eng_->handle(), 0, map ? map->handle() : nullptr, cells_xy, cells_z), "liodom_attach_mapper");
 }

@@ -222,6 +222,10 @@ class Map {
   std::vector<uint8_t> exportState();
   void importState(const std::vector<uint8_t>& blob);
   void reset();
+  // Drops every cell outside the box of keep_xy / keep_z cells around the pose's cell (liodom_map_prune; no counterpart in the
+  // reference); returns the number of cells removed.  Works on an attached map too.
+  int prune(const std::array<double, 12>& pose, int keep_xy, int keep_z);
+  int numCells();
   liodom_map_t* handle() const { return m_; }
  private:
   PointCloud fetch(int which, const double* T, int cells_xy, int cells_z);
@@ -258,6 +262,9 @@ class LaserOdometer {
   void setLaserToBase(const std::array<double, 12>& T);
   // Zero-latency on-device replay of the liodom_mapping node (liodom_attach_mapper); mapping_ only
   void attachMapper(Map* map, int cells_xy = 2, int cells_z = 1);
+  // ... with options (liodom_attach_mapper_ex): lag = 1 makes the map take a frame when it leaves the sliding window — the mode
+  // that solves; lag = 0 is the faithful, degenerate replay above —, prune_period > 0 prunes the map around the pose as it goes
+  void attachMapper(Map* map, const liodom_mapper_options_t& options);
   // One pass of the loop body of LaserOdometer::operator() (laser_odometry.cc:107-267).
   Pose process(const PointCloud& feats, double stamp, liodom_step_info_t* info = nullptr);
   // The same on an edge cloud the extractor left on the device (Features::ticket)

@@ -5,7 +5,10 @@
 //   liodom_replay <scan_dir> <out_dir/> [name=value ...]     e.g. scan_lines=64 prev_frames=20
 // With mapping=true the liodom_mapping node (launch/liodom.launch:41-56) is replayed on the device
 // with its launch-file parameters (voxel_xysize= voxel_zsize= resolution= cells_xy= cells_z=); the
-// final map is written to <out_dir>map.bin (float32 x y z i).  map_state_in=FILE starts the mapper from a saved map state
+// final map is written to <out_dir>map.bin (float32 x y z i) and its cell count printed.  mapper_lag=1 inserts a frame when it
+// leaves the sliding window instead of right after its scan (liodom_attach_mapper_ex: the mode that solves; the default 0 is the
+// reference's loop, whose poses are the prediction); map_prune_period=N map_keep_xy= map_keep_z= prune the map to that box of
+// cells around the pose every N-th scan.  map_state_in=FILE starts the mapper from a saved map state
 // (liodom::Map::importState, before it is attached); map_state_out=FILE writes the mapper's state at the end, before map.bin.
 // threads=true runs the reference's own structure instead of the fused per-scan call: the clouds are
 // pushed into SharedData (lidarClb), a FeatureExtractor thread and a LaserOdometer thread work side by
@@ -74,14 +77,18 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "liodom_replay: map_state_in / map_state_out need mapping=true\n"); return 2;
     }
     if (params->mapping_) {
-      double xy = 40.0, z = 50.0, res = 0.4; int cells_xy = 2, cells_z = 1;      // liodom_mapping_node.cc:115-134
+      double xy = 40.0, z = 50.0, res = 0.4;      // liodom_mapping_node.cc:115-134
+      liodom_mapper_options_t mo;
+      liodom_mapper_options_default(&mo);
       for (const std::string& a : kv) {
         const size_t eq = a.find('=');
         if (eq == std::string::npos) continue;
         const std::string k = a.substr(0, eq), v = a.substr(eq + 1);
         if (k == "voxel_xysize") xy = std::stod(v); else if (k == "voxel_zsize") z = std::stod(v);
-        else if (k == "resolution") res = std::stod(v); else if (k == "cells_xy") cells_xy = std::stoi(v);
-        else if (k == "cells_z") cells_z = std::stoi(v);
+        else if (k == "resolution") res = std::stod(v); else if (k == "cells_xy") mo.cells_xy = std::stoi(v);
+        else if (k == "cells_z") mo.cells_z = std::stoi(v); else if (k == "mapper_lag") mo.lag = std::stoi(v);
+        else if (k == "map_prune_period") mo.prune_period = std::stoi(v); else if (k == "map_keep_xy") mo.keep_cells_xy = std::stoi(v);
+        else if (k == "map_keep_z") mo.keep_cells_z = std::stoi(v);
       }
       mapper.reset(new liodom::Map(xy, z, res));
       if (!map_state_in.empty()) {
@@ -92,7 +99,7 @@ int main(int argc, char** argv) {
         f.read(reinterpret_cast<char*>(st.data()), (std::streamsize)st.size());
         mapper->importState(st);
       }
-      odometer.attachMapper(mapper.get(), cells_xy, cells_z);
+      odometer.attachMapper(mapper.get(), mo);
     }
     std::ofstream odom_log(out + "odom.txt");      // stamp, orientation xyzw, position, twist linear, twist angular
     odom_log.precision(17);
@@ -216,7 +223,7 @@ int main(int argc, char** argv) {
       const liodom::PointCloud m = mapper->getMap();
       std::ofstream f(out + "map.bin", std::ios::binary);
       f.write(reinterpret_cast<const char*>(m.points.data()), (std::streamsize)(m.points.size() * sizeof(liodom::Point)));
-      std::printf("map: %zu points\n", m.size());
+      std::printf("map: %zu points in %d cells\n", m.size(), mapper->numCells());
     }
   } catch (const std::exception& e) {
     std::fprintf(stderr, "liodom_replay: %s\n", e.what());

@@ -211,11 +211,18 @@ struct Node {
       bool in_process = false;
       nh.param("in_process_mapper", in_process, false);
       if (params->mapping_ && in_process) {
-        double xy, z, res; int cxy, cz;
+        double xy, z, res;
+        liodom_mapper_options_t mo;
+        liodom_mapper_options_default(&mo);
         nh.param("voxel_xysize", xy, 40.0); nh.param("voxel_zsize", z, 50.0); nh.param("resolution", res, 0.4);
-        nh.param("cells_xy", cxy, 2); nh.param("cells_z", cz, 1);
+        nh.param("cells_xy", mo.cells_xy, 2); nh.param("cells_z", mo.cells_z, 1);
+        // ~mapper_lag 1: the map takes a frame when it leaves the sliding window (the mode that solves; 0 replays the reference's
+        // loop, whose poses are the prediction); ~map_prune_period n > 0: the map is pruned to ~map_keep_xy / ~map_keep_z cells
+        // around the pose every n-th scan
+        nh.param("mapper_lag", mo.lag, 0); nh.param("map_prune_period", mo.prune_period, 0);
+        nh.param("map_keep_xy", mo.keep_cells_xy, 0); nh.param("map_keep_z", mo.keep_cells_z, 0);
         mapper.reset(new liodom::Map(xy, z, res));
-        odometer->attachMapper(mapper.get(), cxy, cz);
+        odometer->attachMapper(mapper.get(), mo);
       }
     } catch (const std::exception& e) {
       ROS_FATAL("%s", e.what());
