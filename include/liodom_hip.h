@@ -605,6 +605,30 @@ int liodom_map_reset(liodom_map_t* m);
  * null map or T or a negative keep: the map is untouched.  The first prune of a map allocates 16 bytes per max_cells. */
 int liodom_map_prune(liodom_map_t* m, const double* T /*3x4*/, int keep_cells_xy, int keep_cells_z, int* n_removed);
 
+/* Paging: the device map as a window onto a larger map the caller keeps on the host (liodom_amd/pager.py, liodom::MapPager).
+ *
+ *   liodom_map_evict          liodom_map_prune whose dropped cells come out (no counterpart in the reference).  Same centre cell and
+ *       keep box, bit for bit.  `blob` receives a well-formed map-state blob of this map's three sizes that holds exactly the
+ *       dropped cells, in their relative creation order: each with its own key and corner_leaf and the points of its current cloud,
+ *       `first` recomputed, status 0 (a tile has no history).  Afterwards the map is what liodom_map_prune would have left.
+ *       *bytes is always the size needed, and it is known before anything is modified: with cap too small the call returns
+ *       LIODOM_ERR_CAPACITY, writes nothing to `blob` and leaves the map untouched (cap = 0, blob = NULL asks for the size).  When
+ *       nothing is dropped the blob is a 64-byte header with 0 cells.  *n_evicted (optional) = cells dropped.  Works on a detached
+ *       map and on an attached one, where it is enqueued on the stream the map's work is on; it synchronises, with the threading
+ *       rule of liodom_map_export_state.  LIODOM_ERR_INVALID_ARG for a null map, T or bytes, or a negative keep.
+ *   liodom_map_merge_state    appends a blob's cells to a map that may already hold cells (no counterpart in the reference).  The
+ *       blob is validated on the host first, as liodom_map_import_state does: LIODOM_ERR_INVALID_ARG for malformed bytes or other
+ *       sizes, LIODOM_ERR_CAPACITY for a cell larger than cell_capacity or more cells than max_cells.  A blob cell whose key is
+ *       already a cell of the map is skipped (taken[i] = 0; that cell of the map is untouched); the others (taken[i] = 1) are
+ *       appended behind the map's cells in blob order.  Afterwards the map is what liodom_map_import_state would make of its own
+ *       blob with the taken cells' records and points appended; sticky status = the map's OR the blob's.  Not enough free cell ids
+ *       for the taken cells: LIODOM_ERR_CAPACITY, map untouched.  Merging into an empty map equals liodom_map_import_state; a blob
+ *       of 0 cells is a no-op.  `taken` (optional) has room for the blob's n_cells entries; *n_added (optional) = cells taken.
+ *       Allowed on an attached map (unlike liodom_map_import_state), enqueued and synchronised as liodom_map_prune is. */
+int liodom_map_evict(liodom_map_t* m, const double* T /*3x4*/, int keep_cells_xy, int keep_cells_z, void* blob, int64_t cap,
+                     int64_t* bytes, int* n_evicted);
+int liodom_map_merge_state(liodom_map_t* m, const void* blob, int64_t bytes, int32_t* taken /*optional, [blob n_cells]*/, int* n_added);
+
 #ifdef __cplusplus
 }
 #endif

@@ -318,6 +318,30 @@ def build_map_state(xy, z, res, cells, status=0):
     return blob
 
 
+def join_map_state(xy, z, res, keys, corner_leaf, cells, status=0):
+    """Writes a map-state blob from records as parse_map_state returns them: keys [n, 3], corner_leaf [n, 3] and cells, a list of
+    [count, 4] float32 arrays, in the order given.  Unlike build_map_state nothing is derived from the points: corner_leaf cannot
+    be (map_state_format.h), so a store of cells has to keep it.  Cells may be empty."""
+    cells = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1, 4) for c in cells]
+    keys = np.asarray(keys, np.int64).reshape(-1, 3)
+    corner = np.asarray(corner_leaf, np.int64).reshape(-1, 3)
+    if not (len(keys) == len(corner) == len(cells)):
+        raise ValueError("join_map_state: keys, corner_leaf and cells differ in length")
+    counts = np.array([c.shape[0] for c in cells], np.int64)
+    first = np.concatenate([[0], np.cumsum(counts)])
+    n_points = int(first[-1])
+    total = MAP_STATE_HEADER_BYTES + MAP_STATE_RECORD_BYTES * len(cells) + 16 * n_points
+    rec = np.zeros((len(cells), 8), "<i4")
+    rec[:, 0:3], rec[:, 3:6], rec[:, 6], rec[:, 7] = keys, corner, counts, first[:-1]
+    out = [MAP_STATE_MAGIC, np.array([MAP_STATE_VERSION, MAP_STATE_HEADER_BYTES], "<u4").tobytes(), np.array([total], "<u8").tobytes(),
+           np.array([xy, z, res], "<f8").tobytes(), np.array([len(cells)], "<i4").tobytes(), np.array([status], "<u4").tobytes(),
+           np.array([n_points], "<i8").tobytes(), rec.tobytes()]
+    out.extend(c.astype("<f4").tobytes() for c in cells)
+    blob = b"".join(out)
+    assert len(blob) == total
+    return blob
+
+
 class PolarGeometry(C.Structure):
     """liodom_polar_geometry_t: a polar scan's shape, number widths and tables (include/liodom_hip.h)."""
     _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("range_bits", C.c_int32), ("intensity_bits", C.c_int32),
@@ -492,6 +516,10 @@ def load():
     L.liodom_attach_mapper_ex.argtypes = [vp, C.c_int, vp, C.POINTER(MapperOptions)]
     L.liodom_map_prune.restype = C.c_int
     L.liodom_map_prune.argtypes = [vp, dp, C.c_int, C.c_int, ip]
+    L.liodom_map_evict.restype = C.c_int
+    L.liodom_map_evict.argtypes = [vp, dp, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), ip]
+    L.liodom_map_merge_state.restype = C.c_int
+    L.liodom_map_merge_state.argtypes = [vp, vp, C.c_int64, ip, ip]
     L.liodom_map_config_default.argtypes = [C.POINTER(MapConfig)]
     L.liodom_map_create.restype = C.c_int
     L.liodom_map_create.argtypes = [C.POINTER(MapConfig), C.POINTER(vp)]
@@ -589,6 +617,7 @@ EXPORTED_SYMBOLS = [
     "liodom_scan_buffer_polar", "liodom_extract_edges_device_polar",
     "liodom_map_state_size", "liodom_map_export_state", "liodom_map_import_state", "liodom_map_reset",
     "liodom_mapper_options_default", "liodom_attach_mapper_ex", "liodom_map_prune",
+    "liodom_map_evict", "liodom_map_merge_state",
 ]
 
 
@@ -1090,6 +1119,8 @@ class Map:
         self._L = L
         self._chk(L.liodom_map_create(C.byref(c), C.byref(self.h)))
         self.result_capacity = 1 << 18
+        self.sizes = (float(xy), float(z), float(res))
+        self.max_update_points = int(c.max_update_points)
 
     def _chk(self, rc):
         if rc != 0:
@@ -1133,6 +1164,30 @@ class Map:
         n = C.c_int32(0)
         self._chk(self._L.liodom_map_prune(self.h, _dp(T), int(keep_xy), int(keep_z), C.byref(n)))
         return n.value
+
+    def evict(self, T34=None, keep_xy=2, keep_z=1):
+        """liodom_map_prune whose dropped cells come out (liodom_map_evict): -> (blob of the dropped cells, their number).  The
+        buffer is sized by the library's ERR_CAPACITY reply, which leaves the map untouched.  Works on an attached map too."""
+        T = self._T(T34)
+        need, n = C.c_int64(0), C.c_int32(0)
+        rc = self._L.liodom_map_evict(self.h, _dp(T), int(keep_xy), int(keep_z), None, 0, C.byref(need), C.byref(n))
+        if rc != ERR_CAPACITY:           # (a blob is never smaller than its 64-byte header: success cannot happen here)
+            self._chk(rc)
+        buf = (C.c_ubyte * need.value)()
+        self._chk(self._L.liodom_map_evict(self.h, _dp(T), int(keep_xy), int(keep_z), buf, need.value, C.byref(need), C.byref(n)))
+        return bytes(memoryview(buf)[:need.value]), n.value
+
+    def merge_state(self, blob):
+        """Appends the cells of `blob` whose keys are not cells of the map yet (liodom_map_merge_state); -> taken, an int32 array
+        with one flag per blob cell.  Allowed on an attached map.  LiodomError with .code ERR_INVALID_ARG / ERR_CAPACITY: map
+        untouched."""
+        b = bytes(blob)
+        n_cells = int(np.frombuffer(b, "<i4", 1, 48)[0]) if len(b) >= MAP_STATE_HEADER_BYTES else 0
+        taken = np.zeros(max(0, min(n_cells, (len(b) - MAP_STATE_HEADER_BYTES) // MAP_STATE_RECORD_BYTES)), np.int32)
+        n = C.c_int32(0)
+        self._chk(self._L.liodom_map_merge_state(self.h, b, len(b), _ip(taken) if taken.size else None, C.byref(n)))
+        assert int(taken.sum()) == n.value
+        return taken
 
     def all(self):
         out = np.zeros((self.result_capacity, 4), dtype=np.float32)

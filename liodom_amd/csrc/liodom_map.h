@@ -653,6 +653,23 @@ constexpr int kMapPruneThreads = 1024;
 // Entry [max_cells] is the host's: {cells removed, cells before, cells after, 0}.
 struct __attribute__((aligned(16))) MapPruneMove { int src, src_buf, dst_buf, count; };
 
+// The keep box, shared by k_map_prune_plan and k_map_evict_plan so that the two cannot drift: centre cell from T exactly as
+// k_map_local_plan (translation truncated to int first, map.cc:144-151), extents in double.
+struct MapKeepBox { int vx, vy, vz; double lim_xy, lim_z; };
+__device__ __forceinline__ MapKeepBox map_keep_box(const MapView& m, const double* T_ptr, int keep_xy, int keep_z) {
+  const int x = (int)T_ptr[3], y = (int)T_ptr[7], z = (int)T_ptr[11];                 // map.cc:144,147,150
+  MapKeepBox b;
+  b.vx = map_cell_key((double)x, m.inv_xy, m.xy, m.half_xy);
+  b.vy = map_cell_key((double)y, m.inv_xy, m.xy, m.half_xy);
+  b.vz = map_cell_key((double)z, m.inv_z, m.z, m.half_z);
+  b.lim_xy = (double)keep_xy * m.xy; b.lim_z = (double)keep_z * m.z;
+  return b;
+}
+__device__ __forceinline__ int map_keep_cell(const MapKeepBox& b, const int* key) {
+  return (fabs((double)key[0] - (double)b.vx) <= b.lim_xy && fabs((double)key[1] - (double)b.vy) <= b.lim_xy &&
+          fabs((double)key[2] - (double)b.vz) <= b.lim_z) ? 1 : 0;
+}
+
 // Step 1.  Workgroup 0 plans: centre cell from T exactly as k_map_local_plan (translation truncated to int first, map.cc:144-151),
 // keep flags, exclusive scan over creation order (the scan of k_map_all_plan, any number of cells), and the bookkeeping arrays
 // compacted in place, chunk after chunk: a chunk's threads hold their cells' records in registers across the scan's barrier and
@@ -670,11 +687,7 @@ __global__ __launch_bounds__(kMapPruneThreads) void k_map_prune_plan(MapView m, 
   __shared__ int sh_carry;
   MapState& st = *m.st;
   const int nc = max(0, min(st.n_cells, m.max_cells));
-  const int x = (int)T_ptr[3], y = (int)T_ptr[7], z = (int)T_ptr[11];                 // map.cc:144,147,150
-  const int vx = map_cell_key((double)x, m.inv_xy, m.xy, m.half_xy);
-  const int vy = map_cell_key((double)y, m.inv_xy, m.xy, m.half_xy);
-  const int vz = map_cell_key((double)z, m.inv_z, m.z, m.half_z);
-  const double lim_xy = (double)keep_xy * m.xy, lim_z = (double)keep_z * m.z;
+  const MapKeepBox box = map_keep_box(m, T_ptr, keep_xy, keep_z);
   if (tid == 0) sh_carry = 0;
   __syncthreads();
   for (int base = 0; base < nc; base += kMapPruneThreads) {
@@ -684,8 +697,7 @@ __global__ __launch_bounds__(kMapPruneThreads) void k_map_prune_plan(MapView m, 
       for (int a = 0; a < 3; a++) { key[a] = m.cell_key[c * 3 + a]; org[a] = m.cell_org[c * 3 + a]; }
       cnt = max(0, min(m.cell_n[c], m.cell_cap));
       buf = m.cell_buf[c] & 1;
-      keep = (fabs((double)key[0] - (double)vx) <= lim_xy && fabs((double)key[1] - (double)vy) <= lim_xy &&
-              fabs((double)key[2] - (double)vz) <= lim_z) ? 1 : 0;
+      keep = map_keep_cell(box, key);
     }
     int incl = keep;
     for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if ((tid & 63) >= off) incl += t; }
@@ -739,6 +751,174 @@ __global__ __launch_bounds__(256) void k_map_prune_move(MapView m, const MapPrun
     float4* dst = m.slab + ((size_t)(e.dst_buf & 1) * m.max_cells + j) * m.cell_cap;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256) dst[i] = src[i];
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Paging (liodom_map_evict / liodom_map_merge_state; no counterpart in the reference): the device map as a window onto a larger
+// map the caller keeps on the host.  Evict = prune whose dropped cells come out as a blob first; merge = import that appends to
+// the cells already there.  Not on the per-scan path: a map that never calls those entry points launches none of this and
+// allocates nothing for it.  Order is stream order, as for prune.
+// ---------------------------------------------------------------------------------------------
+// Evict, step 1 (one workgroup, read-only on the map): keep flags with the keep box of k_map_prune_plan, then the chunked scan of
+// k_map_pack_plan over the DROPPED cells — rank among the dropped and exclusive prefix of their counts — so any number of cells.
+// Writes the dropped cells' records behind the header in `head` (relative creation order, `first` recomputed), the header counts
+// where the host reads them (status 0: a tile has no history), and each record's source cell id into `src` (the prune scratch,
+// which the prune that follows overwrites only after the pack has read it: stream order).
+__global__ __launch_bounds__(1024) void k_map_evict_plan(MapView m, const double* T_ptr, int keep_xy, int keep_z, unsigned char* head, int* src) {
+  __shared__ int sh_wr[16];
+  __shared__ int sh_wc[16];
+  __shared__ int sh_rank;
+  __shared__ long long sh_carry;
+  const MapState& st = *m.st;
+  const int tid = threadIdx.x;
+  const int nc = max(0, min(st.n_cells, m.max_cells));
+  const MapKeepBox box = map_keep_box(m, T_ptr, keep_xy, keep_z);
+  MapStateRecord* rec = reinterpret_cast<MapStateRecord*>(head + kMapStateHeaderBytes);
+  if (tid == 0) { sh_carry = 0; sh_rank = 0; }
+  __syncthreads();
+  for (int base = 0; base < nc; base += 1024) {
+    const int c = base + tid;
+    int key[3] = {0, 0, 0}, drop = 0, cnt = 0;
+    if (c < nc) {
+      for (int a = 0; a < 3; a++) key[a] = m.cell_key[c * 3 + a];
+      drop = map_keep_cell(box, key) ^ 1;
+      cnt = drop ? max(0, min(m.cell_n[c], m.cell_cap)) : 0;
+    }
+    int ir = drop, ic = cnt;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int tr = __shfl_up(ir, off), tc = __shfl_up(ic, off);
+      if ((tid & 63) >= off) { ir += tr; ic += tc; }
+    }
+    if ((tid & 63) == 63) { sh_wr[tid >> 6] = ir; sh_wc[tid >> 6] = ic; }
+    __syncthreads();
+    int j = sh_rank + ir - drop;
+    long long run = sh_carry + (ic - cnt);
+    for (int q = 0; q < (tid >> 6); q++) { j += sh_wr[q]; run += sh_wc[q]; }
+    if (drop) {                       // j < nc <= max_cells: inside `head` and `src`
+      MapStateRecord r;
+      for (int a = 0; a < 3; a++) { r.key[a] = key[a]; r.corner_leaf[a] = m.cell_org[c * 3 + a] + kMapLeafMargin; }
+      r.count = cnt;
+      r.first = (int)run;
+      rec[j] = r;
+      src[j] = c;
+    }
+    __syncthreads();
+    if (tid == 1023) { sh_rank = j + drop; sh_carry = run + cnt; }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    MapStateHeader* hd = reinterpret_cast<MapStateHeader*>(head);
+    hd->n_cells = sh_rank;
+    hd->status = 0u;
+    hd->n_points = sh_carry;
+  }
+}
+
+// Evict, step 2, grid (chunk, record): k_map_pack for records that name their source cell — gathers each dropped cell's CURRENT
+// slab into the point section, one 16-byte load and one 16-byte store per point, consecutive lanes on consecutive points.
+__global__ __launch_bounds__(256) void k_map_evict_pack(MapView m, const unsigned char* head, const int* src, float4* pts, int pts_cap) {
+  const MapStateHeader* hd = reinterpret_cast<const MapStateHeader*>(head);
+  const MapStateRecord* rec = reinterpret_cast<const MapStateRecord*>(head + kMapStateHeaderBytes);
+  const int nr = max(0, min(hd->n_cells, m.max_cells));
+  for (int j = blockIdx.y; j < nr; j += gridDim.y) {
+    const int c = src[j];
+    if (c < 0 || c >= m.max_cells) continue;
+    const int first = rec[j].first, cnt = min(rec[j].count, m.cell_cap);
+    const float4* from = map_cell_cur(m, c);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < cnt; i += gridDim.x * 256) {
+      const long long o = (long long)first + i;
+      if (o >= 0 && o < pts_cap) pts[o] = from[i];
+    }
+  }
+}
+
+// Entry [0] of the merge scratch is the host's; the blob cells' ranks follow from entry [4] on.
+struct MapMergeInfo { int n_taken, n_before, pad0, pad1; };
+
+// Merge, step 1 (one workgroup, read-only on the map).  Every blob key is looked up through map_hash / the linear probe; a key
+// that is a cell of the map (a slot whose cslot_cell is an id in [0, n_cells)) is skipped, every other one is taken.  rank[i] =
+// rank among the taken cells, or -1; the chunked scan again, so any number of blob cells.  info = {taken, cells of the map}.
+__global__ __launch_bounds__(1024) void k_map_merge_plan(MapView m, const unsigned char* head, int n_blob, MapMergeInfo* info, int* rank) {
+  __shared__ int sh_w[16];
+  __shared__ int sh_carry;
+  const int tid = threadIdx.x;
+  const int nc = max(0, min(m.st->n_cells, m.max_cells));
+  const MapStateRecord* rec = reinterpret_cast<const MapStateRecord*>(head + kMapStateHeaderBytes);
+  const int nb = max(0, min(n_blob, m.max_cells));
+  if (tid == 0) sh_carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nb; base += 1024) {
+    const int i = base + tid;
+    int take = 0;
+    if (i < nb) {
+      const int id = map_find_cell(m, rec[i].key[0], rec[i].key[1], rec[i].key[2]);
+      take = (id >= 0 && id < nc) ? 0 : 1;
+    }
+    int incl = take;
+    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if ((tid & 63) >= off) incl += t; }
+    if ((tid & 63) == 63) sh_w[tid >> 6] = incl;
+    __syncthreads();
+    int j = sh_carry + incl - take;
+    for (int q = 0; q < (tid >> 6); q++) j += sh_w[q];
+    if (i < nb) rank[i] = take ? j : -1;
+    __syncthreads();
+    if (tid == 1023) sh_carry = j + take;
+    __syncthreads();
+  }
+  if (tid == 0) { MapMergeInfo o; o.n_taken = sh_carry; o.n_before = nc; o.pad0 = 0; o.pad1 = 0; *info = o; }
+}
+
+// Merge, step 2, grid (chunk, blob cell), launched only when the taken cells fit (the host has read `info`).  Taken cell i gets id
+// n_before + rank[i].  Its key claims a hash slot as in k_map_unpack — the taken keys are distinct among themselves (the host's
+// map_state_validate) and none is a cell of the map, so the slots are claimed in parallel.  A taken key can already SIT in the
+// hash without being a cell: k_map_assign leaves such slots behind when one update creates more than kMapNewCellsMax cells
+// (cslot_cell stays -1) or when the map is full (cslot_cell = max_cells, "no room").  The probe stops at that slot and takes it
+// over, so every later lookup finds the merged cell.  ("No room" while the map has free ids is unreachable — the marker is only
+// written when n_cells reaches max_cells, and everything that lowers n_cells rebuilds the hash — but the take-over covers it as
+// well.)  cfirst is only read for slots an update creates itself and is left alone.
+// cell_buf = 0 and mod_of_cell = -1 are written explicitly: ids >= n_cells hold whatever the cells pruned away left there.
+// The points go into slab 0 of the new id.  One thread bumps n_cells and ORs the blob's status; nothing here reads n_cells.
+__global__ __launch_bounds__(256) void k_map_merge(MapView m, const unsigned char* head, const float4* pts, int n_blob, int n_points,
+                                                   const MapMergeInfo* info, const int* rank, int status) {
+  const MapStateRecord* rec = reinterpret_cast<const MapStateRecord*>(head + kMapStateHeaderBytes);
+  const int nb = max(0, min(n_blob, m.max_cells));
+  const int base = info->n_before, n_taken = info->n_taken;
+  if (base < 0 || n_taken < 0 || base + n_taken > m.max_cells) return;       // (the host does not launch this then)
+  const unsigned int mask = (unsigned int)m.ctable - 1u;
+  const int nthreads = gridDim.x * gridDim.y * 256;
+  for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < nb; i += nthreads) {
+    const int r = rank[i];
+    if (r < 0 || r >= n_taken) continue;
+    const int id = base + r;
+    const MapStateRecord rc = rec[i];
+    unsigned long long key;
+    if (map_pack_key(rc.key[0], rc.key[1], rc.key[2], &key)) {
+      unsigned int h = map_hash(key, mask);
+      for (int probe = 0; probe < m.ctable; probe++) {
+        const unsigned long long prev = atomicCAS(&m.ckey[h], kMapEmptyKey, key);
+        if (prev == kMapEmptyKey || prev == key) { m.cslot_cell[h] = id; break; }
+        h = (h + 1) & mask;
+      }
+    }
+    for (int a = 0; a < 3; a++) {
+      m.cell_key[id * 3 + a] = rc.key[a];
+      m.cell_org[id * 3 + a] = (int)((unsigned int)rc.corner_leaf[a] - (unsigned int)kMapLeafMargin);
+    }
+    m.cell_n[id] = max(0, min(rc.count, m.cell_cap));
+    m.cell_buf[id] = 0;
+    m.mod_of_cell[id] = -1;
+  }
+  for (int i = blockIdx.y; i < nb; i += gridDim.y) {
+    const int r = rank[i];
+    if (r < 0 || r >= n_taken) continue;
+    const int first = rec[i].first, cnt = min(rec[i].count, m.cell_cap);
+    float4* dst = m.slab + (size_t)(base + r) * m.cell_cap;          // slab 0
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < cnt; k += gridDim.x * 256) {
+      const long long o = (long long)first + k;
+      if (o >= 0 && o < n_points) dst[k] = pts[o];
+    }
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { m.st->n_cells = base + n_taken; if (status) atomicOr(&m.st->status, status); }
 }
 
 }  // namespace liodom_dev

@@ -181,10 +181,12 @@ struct MapStateTimer {
     const char* e = std::getenv("LIODOM_MAP_STATE_TIMING");
     if (e && e[0] == '1' && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess) (void)hipEventRecord(a, q);
   }
-  void stop() { if (b) (void)hipEventRecord(b, q); }
+  bool stopped = false;
+  void stop() { if (b) { (void)hipEventRecord(b, q); stopped = true; } }
   ~MapStateTimer() {
     float ms = 0.f;
-    if (b && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) std::fprintf(stderr, "%s: kernels %.3f ms\n", what, ms);
+    // (a call that returned early never recorded `b`: asking for its time would leave a HIP error for the next launch check to find)
+    if (stopped && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms, a, b) == hipSuccess) std::fprintf(stderr, "%s: kernels %.3f ms\n", what, ms);
     if (a) (void)hipEventDestroy(a);
     if (b) (void)hipEventDestroy(b);
   }
@@ -414,6 +416,106 @@ int liodom_map_prune(liodom_map_t* mp, const double* T, int keep_cells_xy, int k
   HIP_TRY(hipMemcpyAsync(&info, mp->d_prune + mp->m.max_cells, sizeof(info), hipMemcpyDeviceToHost, mp->stream));
   HIP_TRY(hipStreamSynchronize(mp->stream));      // (the staged pose and `info` are this frame's)
   if (n_removed) *n_removed = info.src;
+  return LIODOM_OK;
+}
+
+int liodom_map_evict(liodom_map_t* mp, const double* T, int keep_cells_xy, int keep_cells_z, void* blob, int64_t cap, int64_t* bytes,
+                     int* n_evicted) {
+  using namespace liodom_dev;
+  if (!mp || !T || !bytes || keep_cells_xy < 0 || keep_cells_z < 0 || cap < 0 || (cap > 0 && !blob)) {
+    g_last_error = "liodom_map_evict: null map, pose or bytes, a negative keep extent, or a capacity without a buffer"; return LIODOM_ERR_INVALID_ARG;
+  }
+  HIP_TRY(hipSetDevice(mp->device));
+  // everything that can fail comes before the map is touched: the plan is read-only, and it gives the size
+  int rc = map_ensure_head(mp);
+  if (rc || (rc = map_ensure_prune(mp))) return rc;
+  const MapView& m = mp->m;
+  int* d_src = reinterpret_cast<int*>(mp->d_prune);
+  MapStateHeader hd;
+  MapStateTimer tm(mp->stream, "liodom_map_evict");
+  HIP_TRY(hipMemcpyAsync(mp->d_T, T, sizeof(double) * 12, hipMemcpyHostToDevice, mp->stream));
+  hipLaunchKernelGGL(k_map_evict_plan, dim3(1), dim3(1024), 0, mp->stream, m, mp->d_T, keep_cells_xy, keep_cells_z, mp->d_head, d_src);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(&hd, mp->d_head, sizeof(hd), hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  if (hd.n_cells < 0 || hd.n_cells > m.max_cells || hd.n_points < 0 || hd.n_points > (int64_t)hd.n_cells * m.cell_cap) {
+    g_last_error = "liodom_map_evict: inconsistent map state"; return LIODOM_ERR_HIP;
+  }
+  if (hd.n_points > 0x7fffffff) { g_last_error = "liodom_map_evict: more than 2^31 - 1 points do not fit the blob format"; return LIODOM_ERR_CAPACITY; }
+  const int64_t need = map_state_bytes(hd.n_cells, hd.n_points);
+  *bytes = need;
+  if (need > cap) { g_last_error = "liodom_map_evict: blob buffer too small"; return LIODOM_ERR_CAPACITY; }
+  unsigned char* out = static_cast<unsigned char*>(blob);
+  const int n_points = (int)hd.n_points;
+  if (n_points > 0 && (rc = map_ensure_out(mp, n_points))) return rc;
+  if (n_points > 0) {
+    const int xb = std::min(16, (m.cell_cap + 255) / 256), yb = std::min(hd.n_cells, 256);
+    hipLaunchKernelGGL(k_map_evict_pack, dim3(xb, yb), dim3(256), 0, mp->stream, m, mp->d_head, d_src, mp->d_out, mp->out_cap);
+  }
+  if ((rc = map_enqueue_prune(mp, mp->d_T, keep_cells_xy, keep_cells_z, mp->stream))) return rc;
+  tm.stop();
+  if (hd.n_cells > 0)
+    HIP_TRY(hipMemcpyAsync(out + kMapStateHeaderBytes, mp->d_head + kMapStateHeaderBytes, (size_t)kMapStateRecordBytes * (size_t)hd.n_cells,
+                           hipMemcpyDeviceToHost, mp->stream));
+  if (n_points > 0)
+    HIP_TRY(hipMemcpyAsync(out + map_state_bytes(hd.n_cells, 0), mp->d_out, sizeof(float4) * (size_t)n_points, hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  // the header is the host's
+  std::memset(hd.magic, 0, sizeof(hd.magic));
+  std::memcpy(hd.magic, "LIODOMMP", 8);
+  hd.version = kMapStateVersion; hd.header_bytes = (uint32_t)kMapStateHeaderBytes; hd.total_bytes = (uint64_t)need;
+  hd.voxel_xysize = mp->cfg.voxel_xysize; hd.voxel_zsize = mp->cfg.voxel_zsize; hd.resolution = mp->cfg.resolution;
+  hd.status = 0u;
+  std::memcpy(out, &hd, sizeof(hd));
+  if (n_evicted) *n_evicted = hd.n_cells;
+  return LIODOM_OK;
+}
+
+int liodom_map_merge_state(liodom_map_t* mp, const void* blob, int64_t bytes, int32_t* taken, int* n_added) {
+  using namespace liodom_dev;
+  if (!mp || !blob) { g_last_error = "liodom_map_merge_state: null argument"; return LIODOM_ERR_INVALID_ARG; }
+  // every rejection comes before anything is launched
+  const char* why = "";
+  int rc = map_state_validate(blob, bytes, mp->cfg.voxel_xysize, mp->cfg.voxel_zsize, mp->cfg.resolution, mp->m.max_cells, mp->m.cell_cap, &why);
+  if (rc) { g_last_error = std::string("liodom_map_merge_state: ") + why; return rc; }
+  MapStateHeader hd;
+  std::memcpy(&hd, blob, sizeof(hd));
+  if (n_added) *n_added = 0;
+  if (hd.n_cells == 0) return LIODOM_OK;
+  if (hd.n_points > 0x7fffffff) { g_last_error = "liodom_map_merge_state: more than 2^31 - 1 points"; return LIODOM_ERR_CAPACITY; }
+  HIP_TRY(hipSetDevice(mp->device));
+  const MapView& m = mp->m;
+  const unsigned char* src = static_cast<const unsigned char*>(blob);
+  const int n_cells = hd.n_cells, n_points = (int)hd.n_points;
+  if ((rc = map_ensure_head(mp)) || (rc = map_ensure_prune(mp)) || (rc = map_ensure_out(mp, n_points))) return rc;
+  MapMergeInfo* d_info = reinterpret_cast<MapMergeInfo*>(mp->d_prune);      // the prune scratch: 4 ints per max_cells + 1
+  int* d_rank = reinterpret_cast<int*>(mp->d_prune) + 4;
+  HIP_TRY(hipMemcpyAsync(mp->d_head, src, (size_t)map_state_bytes(n_cells, 0), hipMemcpyHostToDevice, mp->stream));
+  if (n_points > 0)
+    HIP_TRY(hipMemcpyAsync(mp->d_out, src + map_state_bytes(n_cells, 0), sizeof(float4) * (size_t)n_points, hipMemcpyHostToDevice, mp->stream));
+  MapStateTimer tm(mp->stream, "liodom_map_merge_state");
+  hipLaunchKernelGGL(k_map_merge_plan, dim3(1), dim3(1024), 0, mp->stream, m, mp->d_head, n_cells, d_info, d_rank);
+  HIP_TRY(hipGetLastError());
+  MapMergeInfo info{};
+  std::vector<int> rank((size_t)n_cells);
+  HIP_TRY(hipMemcpyAsync(&info, d_info, sizeof(info), hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipMemcpyAsync(rank.data(), d_rank, sizeof(int) * (size_t)n_cells, hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  if (info.n_taken < 0 || info.n_taken > n_cells || info.n_before < 0 || info.n_before > m.max_cells) {
+    g_last_error = "liodom_map_merge_state: inconsistent map state"; return LIODOM_ERR_HIP;
+  }
+  if (info.n_before + info.n_taken > m.max_cells) {
+    g_last_error = "liodom_map_merge_state: not enough free cells for the blob's cells (max_cells)"; return LIODOM_ERR_CAPACITY;
+  }
+  if (info.n_taken > 0 || hd.status) {
+    const int xb = std::min(16, (m.cell_cap + 255) / 256), yb = std::min(n_cells, 256);
+    hipLaunchKernelGGL(k_map_merge, dim3(xb, yb), dim3(256), 0, mp->stream, m, mp->d_head, mp->d_out, n_cells, n_points, d_info, d_rank, (int)hd.status);
+    HIP_TRY(hipGetLastError());
+  }
+  tm.stop();
+  HIP_TRY(hipStreamSynchronize(mp->stream));      // the caller's blob must not be read after the call returns
+  if (taken) for (int i = 0; i < n_cells; i++) taken[i] = rank[(size_t)i] >= 0 ? 1 : 0;
+  if (n_added) *n_added = info.n_taken;
   return LIODOM_OK;
 }
 

@@ -1,7 +1,9 @@
 #include "liodom_host.h"
 #include "../csrc/liodom_math.h"   // odom_message: the same header the kernels use
+#include "../csrc/map_state_cells.h"   // blobs of paged-out cells, taken apart and put together
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <fstream>
 #include <stdexcept>
@@ -338,6 +340,7 @@ Map::Map(const double xy_size, const double z_size, const double res, int device
   liodom_map_config_default(&c);
   c.device = device; c.voxel_xysize = xy_size; c.voxel_zsize = z_size; c.resolution = res;
   check(liodom_map_create(&c, &m_), "liodom_map_create");
+  xy_ = xy_size; z_ = z_size; res_ = res; max_update_points_ = c.max_update_points;
 }
 Map::~Map() { liodom_map_destroy(m_); }
 
@@ -449,6 +452,117 @@ int Map::prune(const std::array<double, 12>& pose, int keep_xy, int keep_z) {
   int n = 0;
   check(liodom_map_prune(m_, pose.data(), keep_xy, keep_z, &n), "liodom_map_prune");
   return n;
+}
+
+std::vector<uint8_t> Map::evict(const std::array<double, 12>& pose, int keep_xy, int keep_z, int* n_evicted) {
+  int64_t need = 0;
+  int n = 0;
+  // the size query: LIODOM_ERR_CAPACITY with the size filled in and the map untouched
+  const int rc = liodom_map_evict(m_, pose.data(), keep_xy, keep_z, nullptr, 0, &need, &n);
+  if (rc != LIODOM_ERR_CAPACITY) check(rc, "liodom_map_evict");
+  std::vector<uint8_t> blob((size_t)need);
+  check(liodom_map_evict(m_, pose.data(), keep_xy, keep_z, blob.data(), need, &need, &n), "liodom_map_evict");
+  blob.resize((size_t)need);
+  if (n_evicted) *n_evicted = n;
+  return blob;
+}
+std::vector<int32_t> Map::mergeState(const std::vector<uint8_t>& blob) {
+  int32_t n_cells = 0;
+  if (blob.size() >= 64) std::memcpy(&n_cells, blob.data() + 48, sizeof(n_cells));
+  // (a count the blob's size cannot hold is rejected by the library before `taken` is written)
+  std::vector<int32_t> taken((size_t)std::max<int64_t>(0, std::min<int64_t>(n_cells, ((int64_t)blob.size() - 64) / 32)));
+  check(liodom_map_merge_state(m_, blob.data(), (int64_t)blob.size(), taken.empty() ? nullptr : taken.data(), nullptr), "liodom_map_merge_state");
+  return taken;
+}
+
+MapPager::MapPager(Map* map, int keep_xy, int keep_z, int load_xy, int load_z)
+    : map_(map), keep_xy_(keep_xy), keep_z_(keep_z), load_xy_(load_xy), load_z_(load_z) {
+  if (!map || load_xy < 0 || load_z < 0 || keep_xy < load_xy || keep_z < load_z) throw std::invalid_argument("MapPager: needs keep >= load >= 0 on both axes");
+}
+bool MapPager::inBox(const std::array<int32_t, 3>& key, const std::array<int32_t, 3>& centre, int n_xy, int n_z) const {
+  // the keep rule of liodom_map_prune, compared in double
+  const double lim_xy = (double)n_xy * map_->xySize(), lim_z = (double)n_z * map_->zSize();
+  return std::fabs((double)key[0] - (double)centre[0]) <= lim_xy && std::fabs((double)key[1] - (double)centre[1]) <= lim_xy &&
+         std::fabs((double)key[2] - (double)centre[2]) <= lim_z;
+}
+void MapPager::reobserve(const std::vector<float>& xyzi) {
+  const std::array<double, 12> I{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
+  const size_t n = xyzi.size() / 4, cap = (size_t)std::max(1, map_->maxUpdatePoints());
+  for (size_t lo = 0; lo < n; lo += cap) {
+    PointCloud pc;
+    pc.points.resize(std::min(cap, n - lo));
+    std::memcpy(pc.points.data(), xyzi.data() + 4 * lo, sizeof(Point) * pc.points.size());
+    pc.width = (uint32_t)pc.points.size();
+    map_->updateMap(pc, I);
+  }
+}
+void MapPager::step(const std::array<double, 12>& pose) {
+  using liodom_dev::MapStateCell;
+  const double xy = map_->xySize(), z = map_->zSize(), res = map_->resolution();
+  int n = 0;
+  const std::vector<uint8_t> blob = map_->evict(pose, keep_xy_, keep_z_, &n);
+  std::vector<MapStateCell> out;
+  const char* why = "";
+  if (liodom_dev::map_state_split(blob.data(), (int64_t)blob.size(), xy, z, res, &out, nullptr, &why) != LIODOM_OK)
+    throw std::runtime_error(std::string("MapPager: evicted blob: ") + why);
+  evicted += n;
+  std::vector<MapStateCell> back;                  // evicted cells whose key is stored already
+  for (MapStateCell& c : out) {
+    if (index_.count(c.key)) { back.push_back(std::move(c)); continue; }
+    store_.push_back(Cell{c.key, c.corner_leaf, std::move(c.xyzi)});
+    index_[store_.back().key] = std::prev(store_.end());
+  }
+  if (!back.empty()) {                             // the device gets its cells back, the stored ones are re-observed into them
+    std::vector<const MapStateCell*> ptrs;
+    for (const MapStateCell& c : back) ptrs.push_back(&c);
+    map_->mergeState(liodom_dev::map_state_join(xy, z, res, ptrs, 0));
+    for (const MapStateCell& c : back) {
+      auto it = index_.find(c.key);
+      conflicts++;
+      const std::vector<float> pts = std::move(it->second->xyzi);
+      store_.erase(it->second);
+      index_.erase(it);
+      reobserve(pts);
+    }
+  }
+  // the centre cell as liodom_map_prune / Map::getLocalMap compute it: the translation truncated to int first (map.cc:144-151)
+  auto cell_key = [](double x, double size) { return (int32_t)(std::floor(x * (1.0 / size)) * size + size / 2.0); };
+  const std::array<int32_t, 3> centre{{cell_key((double)(int)pose[3], xy), cell_key((double)(int)pose[7], xy), cell_key((double)(int)pose[11], z)}};
+  std::vector<std::list<Cell>::iterator> want;
+  for (auto it = store_.begin(); it != store_.end(); ++it)
+    if (inBox(it->key, centre, load_xy_, load_z_)) want.push_back(it);
+  if (want.empty()) return;
+  std::vector<MapStateCell> cells(want.size());
+  std::vector<const MapStateCell*> ptrs;
+  for (size_t i = 0; i < want.size(); i++) {
+    cells[i].key = want[i]->key; cells[i].corner_leaf = want[i]->corner_leaf; cells[i].xyzi = want[i]->xyzi;      // (a copy: a merge that fails leaves the store whole)
+    ptrs.push_back(&cells[i]);
+  }
+  const std::vector<int32_t> taken = map_->mergeState(liodom_dev::map_state_join(xy, z, res, ptrs, 0));
+  for (size_t i = 0; i < want.size(); i++) {
+    index_.erase(want[i]->key);
+    store_.erase(want[i]);
+    if (taken[i]) { loaded++; continue; }
+    conflicts++;
+    reobserve(cells[i].xyzi);
+  }
+}
+std::vector<uint8_t> MapPager::exportAll() {
+  using liodom_dev::MapStateCell;
+  const double xy = map_->xySize(), z = map_->zSize(), res = map_->resolution();
+  const std::vector<uint8_t> dev = map_->exportState();
+  std::vector<MapStateCell> cells;
+  uint32_t status = 0;
+  const char* why = "";
+  if (liodom_dev::map_state_split(dev.data(), (int64_t)dev.size(), xy, z, res, &cells, &status, &why) != LIODOM_OK)
+    throw std::runtime_error(std::string("MapPager: exported blob: ") + why);
+  const size_t n_dev = cells.size();
+  cells.resize(n_dev + store_.size());
+  size_t i = n_dev;
+  for (const Cell& c : store_) { cells[i].key = c.key; cells[i].corner_leaf = c.corner_leaf; cells[i].xyzi = c.xyzi; i++; }
+  std::vector<const MapStateCell*> ptrs;
+  for (const MapStateCell& c : cells) ptrs.push_back(&c);
+  return liodom_dev::map_state_join(xy, z, res, ptrs, status);
 }
 
 int Map::numCells() {

@@ -18,6 +18,8 @@
 #include <chrono>
 #include <cstdint>
 #include <functional>
+#include <list>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <queue>
@@ -225,11 +227,46 @@ class Map {
   // Drops every cell outside the box of keep_xy / keep_z cells around the pose's cell (liodom_map_prune; no counterpart in the
   // reference); returns the number of cells removed.  Works on an attached map too.
   int prune(const std::array<double, 12>& pose, int keep_xy, int keep_z);
+  // Paging (liodom_map_evict / liodom_map_merge_state; no counterpart in the reference).  evict: prune whose dropped cells come out
+  // as a blob of their own (*n_evicted: how many).  mergeState: appends the cells of a blob whose keys are not cells of the map
+  // yet; returns one taken flag per blob cell.  Both work on an attached map too.
+  std::vector<uint8_t> evict(const std::array<double, 12>& pose, int keep_xy, int keep_z, int* n_evicted = nullptr);
+  std::vector<int32_t> mergeState(const std::vector<uint8_t>& blob);
   int numCells();
   liodom_map_t* handle() const { return m_; }
+  double xySize() const { return xy_; }
+  double zSize() const { return z_; }
+  double resolution() const { return res_; }
+  int maxUpdatePoints() const { return max_update_points_; }
  private:
   PointCloud fetch(int which, const double* T, int cells_xy, int cells_z);
   liodom_map_t* m_ = nullptr;
+  double xy_ = 0, z_ = 0, res_ = 0;
+  int max_update_points_ = 0;
+};
+
+// The device map as a window onto a larger map on the host (no counterpart in the reference; the rule set of
+// liodom_amd/pager.py).  step(pose) after a scan: the cells outside the keep box around the pose leave the
+// device (Map::evict) and are stored; the stored cells inside the load box come back (Map::mergeState).  A stored cell whose key
+// is a cell of the device map as well — a merge that reports taken = 0, or an evicted key that is stored already — is a conflict:
+// the device keeps (gets back) its cell, the stored cell's points go through Map::updateMap with the identity pose in chunks of
+// max_update_points, and the stored cell is dropped.  exportAll: the blob of device map U store, device cells first.
+// keep >= load on both axes, else std::invalid_argument.
+class MapPager {
+ public:
+  MapPager(Map* map, int keep_xy, int keep_z, int load_xy, int load_z);
+  void step(const std::array<double, 12>& pose);
+  std::vector<uint8_t> exportAll();
+  size_t stored() const { return store_.size(); }
+  long long evicted = 0, loaded = 0, conflicts = 0;
+ private:
+  struct Cell { std::array<int32_t, 3> key, corner_leaf; std::vector<float> xyzi; };
+  bool inBox(const std::array<int32_t, 3>& key, const std::array<int32_t, 3>& centre, int n_xy, int n_z) const;
+  void reobserve(const std::vector<float>& xyzi);
+  Map* map_;
+  int keep_xy_, keep_z_, load_xy_, load_z_;
+  std::list<Cell> store_;                                                  // eviction order
+  std::map<std::array<int32_t, 3>, std::list<Cell>::iterator> index_;
 };
 
 // The numbers LaserOdometer::publishOdom puts into nav_msgs/Odometry, geometry_msgs/TwistStamped

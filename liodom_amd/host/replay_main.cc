@@ -10,6 +10,9 @@
 // reference's loop, whose poses are the prediction); map_prune_period=N map_keep_xy= map_keep_z= prune the map to that box of
 // cells around the pose every N-th scan.  map_state_in=FILE starts the mapper from a saved map state
 // (liodom::Map::importState, before it is attached); map_state_out=FILE writes the mapper's state at the end, before map.bin.
+// map_pager=KEEP_XY,KEEP_Z,LOAD_XY,LOAD_Z runs a liodom::MapPager after every scan: the device map is a window onto a map kept on
+// the host (cells outside the keep box are paged out, stored cells inside the load box paged in); map_state_out= then writes the
+// whole map (MapPager::exportAll) and the run prints the pager's counters.  Fused per-scan path only.
 // threads=true runs the reference's own structure instead of the fused per-scan call: the clouds are
 // pushed into SharedData (lidarClb), a FeatureExtractor thread and a LaserOdometer thread work side by
 // side on the same handle (src/liodom_node.cc:89-91) and hand edge clouds over through the queue — the clouds stay on the
@@ -68,11 +71,14 @@ int main(int argc, char** argv) {
     auto eng = std::make_shared<liodom::Engine>(*params, 0, (int)max_pts, (int)(max_pts / (size_t)params->scan_lines_ + 1), 1, covariance ? 1 : 0);
     liodom::LaserOdometer odometer(eng);
     std::unique_ptr<liodom::Map> mapper;
-    std::string map_state_in, map_state_out;
+    std::unique_ptr<liodom::MapPager> pager;
+    std::string map_state_in, map_state_out, map_pager;
     for (const std::string& a : kv) {
       if (a.rfind("map_state_in=", 0) == 0) map_state_in = a.substr(13);
       if (a.rfind("map_state_out=", 0) == 0) map_state_out = a.substr(14);
+      if (a.rfind("map_pager=", 0) == 0) map_pager = a.substr(10);
     }
+    if (!map_pager.empty() && !params->mapping_) { std::fprintf(stderr, "liodom_replay: map_pager needs mapping=true\n"); return 2; }
     if ((!map_state_in.empty() || !map_state_out.empty()) && !params->mapping_) {
       std::fprintf(stderr, "liodom_replay: map_state_in / map_state_out need mapping=true\n"); return 2;
     }
@@ -100,6 +106,13 @@ int main(int argc, char** argv) {
         mapper->importState(st);
       }
       odometer.attachMapper(mapper.get(), mo);
+      if (!map_pager.empty()) {
+        int b[4] = {0, 0, 0, 0};
+        if (std::sscanf(map_pager.c_str(), "%d,%d,%d,%d", &b[0], &b[1], &b[2], &b[3]) != 4) {
+          std::fprintf(stderr, "liodom_replay: map_pager=KEEP_XY,KEEP_Z,LOAD_XY,LOAD_Z\n"); return 2;
+        }
+        pager.reset(new liodom::MapPager(mapper.get(), b[0], b[1], b[2], b[3]));
+      }
     }
     std::ofstream odom_log(out + "odom.txt");      // stamp, orientation xyzw, position, twist linear, twist angular
     odom_log.precision(17);
@@ -133,7 +146,8 @@ int main(int argc, char** argv) {
         if (a.rfind("last=", 0) == 0) has_last = true;
       }
       const char* bad = nullptr;
-      if (want_threads && (!save_state.empty() || !load_state.empty() || save_at >= 0 || has_first || has_last))
+      if (want_threads && pager) bad = "map_pager works on the fused per-scan path only, not with threads=true";
+      else if (want_threads && (!save_state.empty() || !load_state.empty() || save_at >= 0 || has_first || has_last))
         bad = "save_state / load_state / save_at / first / last work on the fused per-scan path only, not with threads=true";
       else if (save_state.empty() != (save_at < 0)) bad = "save_state=FILE and save_at=K go together";
       else if (save_at >= (long)clouds.size()) bad = "save_at names a scan behind the last one";
@@ -203,6 +217,7 @@ int main(int argc, char** argv) {
       for (double v : msg.angular) odom_log << ' ' << v;
       odom_log << '\n';
       write_cov(msg);
+      if (pager) pager->step(p.matrix34());
       if (i % 50 == 0) std::printf("scan %zu: %d edges, %d matches, t = %.3f %.3f %.3f\n", i, info.n_edges, info.matches[1], p.t[0], p.t[1], p.t[2]);
       if ((long)i == save_at && !save_state.empty()) {
         const std::vector<uint8_t> st = odometer.saveState();
@@ -214,8 +229,9 @@ int main(int argc, char** argv) {
     liodom::Stats::getInstance()->writeResults(out);
     if (mapper) {
       odometer.attachMapper(nullptr);
+      if (pager) std::printf("pager: %lld evicted, %lld loaded, %lld conflicts, %zu cells stored\n", pager->evicted, pager->loaded, pager->conflicts, pager->stored());
       if (!map_state_out.empty()) {
-        const std::vector<uint8_t> st = mapper->exportState();
+        const std::vector<uint8_t> st = pager ? pager->exportAll() : mapper->exportState();
         std::ofstream f(map_state_out, std::ios::binary);
         f.write(reinterpret_cast<const char*>(st.data()), (std::streamsize)st.size());
         std::printf("map state: %zu bytes -> %s\n", st.size(), map_state_out.c_str());
