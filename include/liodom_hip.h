@@ -559,6 +559,42 @@ void liodom_mapper_options_default(liodom_mapper_options_t* options);
  * auto-prune conditions.  Streams without a mapper, streams that sit a subset step out and liodom_reset_stream are untouched by
  * all of this.  liodom_get_modes reports mapper_lag=<streams with a lagged mapper>. */
 int liodom_attach_mapper_ex(liodom_handle_t* h, int stream, liodom_map_t* m, const liodom_mapper_options_t* options);
+/* ---- localising in a saved map (no counterpart in the reference: its odometer starts at the identity and its mapper always
+ * writes).  mapping = 1 handles only; nothing of the kNN passes, the solve or the rebuild changes: a seeded stream's first scan
+ * and every scan of a reader are ordinary steady-state scans against window ++ received map. ----
+ *
+ *   liodom_attach_map_reader   wires a map to a stream READ-ONLY (no counterpart in the reference).  After every scan k of the
+ *       stream the handle enqueues getLocalMap(pose_k, cells_xy, cells_z) into the stream's received-map buffer and nothing else:
+ *       no update, no prune, nothing set aside.  The map stays fixed: liodom_map_export_state before and after a run is the same
+ *       bytes.  One map may be read by any number of streams of ONE handle; a step costs one launch per distinct map over the
+ *       step's reader rows (k_map_local_rows; a reader whose extents visit more than 1024 keys takes the two launches of
+ *       liodom_map_get_local).  The map uses the handle's HIP stream from its first attachment until its last one goes.  A map
+ *       is read or written, not both: attaching a reader to a map that liodom_attach_mapper[_ex] holds, or the reverse, in
+ *       either order, is LIODOM_ERR_INVALID_ARG with the attachments unchanged; so are a negative extent and a map another handle
+ *       holds.  liodom_attach_mapper(h, s, NULL, ..) detaches either kind, as does map = NULL here.  liodom_map_update, _prune,
+ *       _evict and _merge_state from the host keep working on a read-attached map between steps, as on any attached map (a pager
+ *       can window a site map under its readers).  Streams that sit a subset step out are untouched.  liodom_get_modes reports
+ *       map_readers=<streams with a reader>.
+ *   liodom_seed_stream         the stream's next scan is its first AND it solves (no counterpart in the reference).  pose =
+ *       [qx qy qz qw tx ty tz]; the quaternion is normalised in double, the matrix T made from it as the solve makes its own.
+ *       The call takes both sides of the handle and waits for its HIP streams, like liodom_reset_stream, then installs a fresh
+ *       state: initialised, an empty window, scan_index 0, odom = prev_odom = final_odom = T, the solve's start point = the
+ *       seed.  The first scan therefore searches and solves from the seed itself (a zero-velocity prediction, no arithmetic
+ *       applied to it), gets a pose-log entry and — with pose_covariance = 1 — a LIODOM_COV_VALID record.  If a mapper or a
+ *       reader is attached to the stream, its received map becomes getLocalMap(T, cells_xy, cells_z) of that map; a result
+ *       larger than recv_capacity is LIODOM_ERR_CAPACITY and leaves the stream untouched.  Without an attachment the received
+ *       map is empty and liodom_set_received_map may follow.  mapping = 0: LIODOM_ERR_UNSUPPORTED; a non-finite pose or
+ *       | |q| - 1 | > 1e-6: LIODOM_ERR_INVALID_ARG; outstanding edge tickets: LIODOM_ERR_BUSY.  The other streams keep
+ *       everything to the bit.  The state of a seeded stream exports and imports like any other, before its first scan too.
+ *   liodom_map_get_local_batch liodom_map_get_local for n poses in one launch (no counterpart in the reference).  T = n x 12
+ *       doubles; row i's cloud goes to xyzi + 4 * i * cap_per_row, its FULL size to n_points[i].  Every row is what
+ *       liodom_map_get_local returns for that pose, bit for bit.  If any row is larger than cap_per_row the call returns
+ *       LIODOM_ERR_CAPACITY with every size reported and nothing written to xyzi (cap_per_row = 0, xyzi = NULL asks for the
+ *       sizes).  Works on a detached map and on an attached one, with the threading rule of liodom_map_export_state. */
+int liodom_attach_map_reader(liodom_handle_t* h, int stream, liodom_map_t* m, int cells_xy, int cells_z);
+int liodom_seed_stream(liodom_handle_t* h, int stream, const double* pose /*[7]*/);
+int liodom_map_get_local_batch(liodom_map_t* m, const double* T /*n x 12*/, int n, int cells_xy, int cells_z, float* xyzi,
+                               int64_t cap_per_row, int64_t* n_points /*[n]*/);
 /* Sticky LIODOM_MAP_* bits raised by the device since creation. */
 int liodom_map_status(liodom_map_t* m, uint32_t* status);
 

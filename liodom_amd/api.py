@@ -514,6 +514,12 @@ def load():
     L.liodom_mapper_options_default.argtypes = [C.POINTER(MapperOptions)]
     L.liodom_attach_mapper_ex.restype = C.c_int
     L.liodom_attach_mapper_ex.argtypes = [vp, C.c_int, vp, C.POINTER(MapperOptions)]
+    L.liodom_attach_map_reader.restype = C.c_int
+    L.liodom_attach_map_reader.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+    L.liodom_seed_stream.restype = C.c_int
+    L.liodom_seed_stream.argtypes = [vp, C.c_int, dp]
+    L.liodom_map_get_local_batch.restype = C.c_int
+    L.liodom_map_get_local_batch.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int, fp, C.c_int64, C.POINTER(C.c_int64)]
     L.liodom_map_prune.restype = C.c_int
     L.liodom_map_prune.argtypes = [vp, dp, C.c_int, C.c_int, ip]
     L.liodom_map_evict.restype = C.c_int
@@ -618,6 +624,7 @@ EXPORTED_SYMBOLS = [
     "liodom_map_state_size", "liodom_map_export_state", "liodom_map_import_state", "liodom_map_reset",
     "liodom_mapper_options_default", "liodom_attach_mapper_ex", "liodom_map_prune",
     "liodom_map_evict", "liodom_map_merge_state",
+    "liodom_attach_map_reader", "liodom_seed_stream", "liodom_map_get_local_batch",
 ]
 
 
@@ -1053,6 +1060,20 @@ class Liodom:
         self._mappers = getattr(self, "_mappers", {})
         self._mappers[stream] = mapper      # keep it alive while attached
 
+    def attach_map_reader(self, map, cells_xy=2, cells_z=1, stream=0):
+        """Read-only attachment (liodom_attach_map_reader): after every scan the stream receives getLocalMap(pose) of `map`, and
+        the map is never written.  Any number of streams of this handle may read one map.  map = None detaches (as
+        attach_mapper(None) does, for either kind)."""
+        self._check(self.L.liodom_attach_map_reader(self.h, stream, map.h if map is not None else None, int(cells_xy), int(cells_z)))
+        self._mappers = getattr(self, "_mappers", {})
+        self._mappers[stream] = map      # keep it alive while attached
+
+    def seed_stream(self, pose7, stream=0):
+        """The stream's next scan is its first and solves from pose7 = [qx qy qz qw tx ty tz] (liodom_seed_stream); with a mapper
+        or reader attached the stream receives that map's local map at the seed."""
+        p = np.ascontiguousarray(pose7, dtype=np.float64).reshape(7)
+        self._check(self.L.liodom_seed_stream(self.h, int(stream), _dp(p)))
+
     def local_map(self, stream=0):
         cap = self.edge_cap * int(self.params.local_map_size) + (max(int(self.config.recv_capacity), 262144) if self.params.mapping else 0)
         w = np.zeros((cap, 4), np.float32)
@@ -1156,6 +1177,28 @@ class Map:
         return out[:n.value].copy()
 
     get_local = local
+
+    def get_local_batch(self, T, cells_xy=2, cells_z=1, cap_per_row=None):
+        """local() for n poses in one launch (liodom_map_get_local_batch): T = [n, 3, 4] (or [n, 12]) -> a list of n [count, 4]
+        arrays.  cap_per_row = None sizes the buffer by the library's ERR_CAPACITY reply; with a number, a larger row raises
+        LiodomError with .code ERR_CAPACITY and .sizes = the rows' sizes."""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1, 12)
+        n = T.shape[0]
+        sizes = np.zeros(max(n, 1), np.int64)
+        sp = sizes.ctypes.data_as(C.POINTER(C.c_int64))
+        if cap_per_row is None:
+            rc = self._L.liodom_map_get_local_batch(self.h, _dp(T), n, int(cells_xy), int(cells_z), None, 0, sp)
+            if rc != ERR_CAPACITY:
+                self._chk(rc)
+            cap_per_row = int(sizes[:n].max()) if n else 0
+        cap = int(cap_per_row)
+        out = np.zeros((max(n, 1), max(cap, 1), 4), dtype=np.float32)
+        try:
+            self._chk(self._L.liodom_map_get_local_batch(self.h, _dp(T), n, int(cells_xy), int(cells_z), _fp(out), cap, sp))
+        except LiodomError as e:
+            e.sizes = sizes[:n].copy()
+            raise
+        return [out[i, :int(sizes[i])].copy() for i in range(n)]
 
     def prune(self, T34=None, keep_xy=2, keep_z=1):
         """Drops every cell outside the box of keep_xy / keep_z cells around the pose's cell (liodom_map_prune); returns the

@@ -169,6 +169,14 @@ struct liodom_handle {
   int* lag_stash_n = nullptr;         // [S] its points (0 while the window is not full)
   int* lag_on = nullptr;              // [S] the stream has a lagged mapper (read by k_window_stash)
   int n_lagged = 0;                   // streams with a lagged mapper
+  // map readers (liodom_attach_map_reader; all empty / null until the first such attach): streams that localise in a map they
+  // never write.  A step enqueues one k_map_local_rows launch per distinct map over the step's rows.
+  std::vector<liodom_map*> readers;   // per stream: the map it reads, or null
+  std::vector<int> reader_xy, reader_z;   // per stream: getLocalMap extents of its reader
+  std::vector<liodom_map*> read_maps; // distinct maps with readers; a map's tag is its index + 1 (freed places are null and taken again)
+  int4* reader_sel = nullptr;         // [S] device: {tag of the map the stream reads (0: none), cells_xy, cells_z, 0}
+  int n_readers = 0;                  // streams with a reader
+  bool map_rows = true;               // readers go through k_map_local_rows; LIODOM_MAP_ROWS=0: the two launches of liodom_map_get_local per stream (equality test, cost tool)
   std::vector<int> hb_since;    // hash_incr, per stream: scans since the stream's last k_hash_build (-1: none yet)
   int knn8_grid = 1;            // k_knn8 workgroups per stream (each walks the blocks b, b + grid, ... of 32 queries)
   bool knn8 = false;            // lock-step batches: k_knn8 (eight lanes per query) instead of k_knn<128>; LIODOM_KNN8=0 keeps the latter
@@ -497,6 +505,34 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
       rc = map_enqueue_local(mp, st->final_odom, mo.cells_xy, mo.cells_z, v.recv_pts + (size_t)s * v.recv_cap,
                              v.recv_cap, &st->n_recv, h->stream, 1);
       if (rc) return rc;
+    }
+    // map readers: getLocalMap(pose_k) of the step's reader rows, one launch per distinct map (k_map_local_rows plans in LDS and
+    // writes nothing of the map, so the rows share it); nothing else — no stash, no update, no prune.  A reader whose extents
+    // the LDS plan cannot hold takes the two old launches.
+    if (h->n_readers > 0) {
+      ProfScope ps(h, KID_OTHER);
+      for (size_t t = 0; t < h->read_maps.size(); t++) {
+        liodom_map* mp = h->read_maps[t];
+        if (!mp) continue;
+        bool rows = false;
+        for (int i = 0; i < count; i++) {
+          const int s = stream_at(i);
+          if (h->readers[s] != mp) continue;
+          if (h->map_rows && map_rows_fit(mp, h->reader_xy[s], h->reader_z[s])) { rows = true; continue; }
+          StreamState* st = v.state + s;
+          const int rc = map_enqueue_local(mp, st->final_odom, h->reader_xy[s], h->reader_z[s], v.recv_pts + (size_t)s * v.recv_cap, v.recv_cap, &st->n_recv, h->stream, 1);
+          if (rc) return rc;
+        }
+        if (!rows) continue;
+        MapRows r{};
+        r.T = v.state[0].final_odom; r.T_stride = (long long)(sizeof(StreamState) / sizeof(double));
+        r.out = v.recv_pts; r.out_stride = v.recv_cap;
+        r.n_out = &v.state[0].n_recv; r.n_stride = (long long)(sizeof(StreamState) / sizeof(int));
+        r.total = nullptr; r.sel = h->reader_sel; r.tag = (int)t + 1; r.cap = v.recv_cap; r.sticky = 1;
+        r.s0 = s0; r.list = s0 < 0 ? reinterpret_cast<const int*>(v.pipe_flags) + kStreamListBase + (size_t)(-s0 - 1) * (size_t)v.n_streams : nullptr;
+        const dim3 grid(map_rows_grid_x(count, v.recv_cap), count);
+        by_rows([&](auto L) { hipLaunchKernelGGL((k_map_local_rows<decltype(L)::value>), grid, dim3(kMapRowsThreads), 0, h->stream, mp->m, r); });
+      }
     }
   }
   if (early) {
@@ -857,6 +893,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     }
     if (env_int("LIODOM_PIPE_FLAGS", 1) == 0) h->use_flags = false;
   }
+  h->map_rows = env_int("LIODOM_MAP_ROWS", 1) != 0;
   if (const char* e = std::getenv("LIODOM_HASH_BUILD")) h->lds_hash_build = std::strcmp(e, "global") != 0;
   v.lds_cells_max = std::max(1, std::min(kLdsCellsMax, env_int("LIODOM_LDS_CELLS_MAX", kLdsCellsMax)));
   // solve split over G workgroups (partial sums exchanged inside the launch, ~3 us per evaluation under load): pays once an
@@ -1212,10 +1249,13 @@ void liodom_destroy(liodom_handle_t* h) {
   if (h->stream_k) { hipStreamSynchronize(h->stream_k); hipStreamDestroy(h->stream_k); }
   if (h->ev_ov) hipEventDestroy(h->ev_ov);
   if (h->ev_ch) hipEventDestroy(h->ev_ch);
-  for (liodom_map* mp : h->mappers) {          // attached maps outlive the handle: give them a stream of their own again
-    if (!mp) continue;
-    mp->stream = nullptr; mp->own_stream = false;
-    if (hipStreamCreateWithFlags(&mp->stream, hipStreamNonBlocking) == hipSuccess) mp->own_stream = true;
+  for (int kind = 0; kind < 2; kind++) {       // attached maps outlive the handle: give them a stream of their own again
+    for (liodom_map* mp : (kind == 0 ? h->mappers : h->readers)) {
+      if (!mp || mp->n_attached == 0 || mp->attached_to != h) continue;      // (a map several streams held: done already; or one that has moved to another handle)
+      mp->n_attached = 0; mp->n_readers = 0; mp->attached_to = nullptr;
+      mp->stream = nullptr; mp->own_stream = false;
+      if (hipStreamCreateWithFlags(&mp->stream, hipStreamNonBlocking) == hipSuccess) mp->own_stream = true;
+    }
   }
   for (void* p : h->allocs) hipFree(p);
   if (h->resident) hipFree(h->resident);
@@ -1282,7 +1322,7 @@ static void state_fingerprint(const liodom_handle* h, StateBlobHeader* hd) {
 // the structure its next scan searches is rebuilt from the window for the variant this handle runs.  Streams are idle (state_quiesce).
 // Left alone: the handle-wide pipeline state (pf_slot, parity, edge buffers, eb_seq / eb_reader, ext_seq / odo_seq, pipe_flags):
 // an extraction issued ahead stays valid for every stream.
-static int install_stream_state(liodom_handle* h, int stream, const unsigned char* blob, int n_frames, int scan_counter) {
+static int install_stream_state(liodom_handle* h, int stream, const unsigned char* blob, int n_frames, int scan_counter, int n_recv = 0) {
   const DevView& v = h->v;
   const size_t S = (size_t)h->S, s = (size_t)stream;
   const int map_blocks = cdiv(v.map_cap, 256);
@@ -1300,7 +1340,7 @@ static int install_stream_state(liodom_handle* h, int stream, const unsigned cha
     HIP_TRY(hipMemsetAsync(v.knn_done0, 0, sizeof(unsigned int) * (S + 64), h->stream));
     h->ov_warm = 0; h->ov_prev = false; h->chain_prev = false; h->chain_count = 0; h->chain_fix_pending = false; h->verdict_scan = -1;
   }
-  if (n_frames > 0) {
+  if (n_frames > 0 || n_recv > 0) {      // (a received map without a frame — a seeded stream before its first scan — is searched too)
     if (h->lds_hash_build) {
       hipLaunchKernelGGL(k_hash_build<>, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
     } else {
@@ -1430,7 +1470,59 @@ int liodom_import_stream_state(liodom_handle_t* h, int stream, const void* blob,
   if ((rc = ensure_state_stage(h))) return rc;
   std::memcpy(h->state_stage_host, b, (size_t)bytes);
   HIP_TRY(hipMemcpyAsync(h->state_stage, h->state_stage_host, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
-  return install_stream_state(h, stream, h->state_stage, rec.n_frames, rec.scan_counter);
+  return install_stream_state(h, stream, h->state_stage, rec.n_frames, rec.scan_counter, rec.n_recv);
+}
+
+// The attachment of a stream, whichever kind: its writing mapper's map and extents, or its reader's.
+static liodom_map* stream_map(const liodom_handle* h, int stream, int* cells_xy, int* cells_z) {
+  if (liodom_map* mp = h->mappers[(size_t)stream]) { *cells_xy = h->mapper_opts[(size_t)stream].cells_xy; *cells_z = h->mapper_opts[(size_t)stream].cells_z; return mp; }
+  if (!h->readers.empty() && h->readers[(size_t)stream]) { *cells_xy = h->reader_xy[(size_t)stream]; *cells_z = h->reader_z[(size_t)stream]; return h->readers[(size_t)stream]; }
+  return nullptr;
+}
+
+int liodom_seed_stream(liodom_handle_t* h, int stream, const double* pose) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if ((rc = check_usable(h))) return rc;
+  if (!h->v.mapping) { g_last_error = "liodom_seed_stream: the handle was created with mapping = 0"; return LIODOM_ERR_UNSUPPORTED; }
+  if (!pose) { g_last_error = "liodom_seed_stream: null pose"; return LIODOM_ERR_INVALID_ARG; }
+  double nn = 0.0;
+  for (int i = 0; i < 7; i++) if (!std::isfinite(pose[i])) { g_last_error = "liodom_seed_stream: non-finite pose"; return LIODOM_ERR_INVALID_ARG; }
+  for (int i = 0; i < 4; i++) nn += pose[i] * pose[i];
+  const double norm = std::sqrt(nn);
+  if (!(std::fabs(norm - 1.0) <= 1e-6)) { g_last_error = "liodom_seed_stream: the quaternion is not normalised (| |q| - 1 | > 1e-6)"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, true, true);
+  if ((rc = state_quiesce(h))) return rc;
+  if ((rc = ensure_state_stage(h))) return rc;
+  // the seed: quaternion normalised in double, the matrix by iso_from_qt — what the first scan's queries are transformed with and
+  // what its solve starts from, with no arithmetic in between (a zero-velocity prediction)
+  StateBlobRecord rec;
+  std::memset(&rec, 0, sizeof(rec));
+  for (int i = 0; i < 4; i++) rec.param_q[i] = pose[i] / norm;
+  for (int i = 0; i < 3; i++) rec.param_t[i] = pose[4 + i];
+  iso_from_qt(rec.param_q, rec.param_t, rec.odom);
+  std::memcpy(rec.prev_odom, rec.odom, sizeof(rec.odom));
+  std::memcpy(rec.final_odom, rec.odom, sizeof(rec.odom));
+  rec.initialized = 1;
+  rec.imu_q[3] = 1.0;
+  const int P = h->P;
+  const size_t prefix = state_points_offset(P);
+  // the received map: getLocalMap(T(pose)) of the stream's attachment, planned and gathered straight into the staging blob's
+  // received-map section (the window is empty: it follows the counts); its size is read before anything of the stream is touched
+  int cxy = 0, cz = 0;
+  if (liodom_map* mp = stream_map(h, stream, &cxy, &cz)) {
+    HIP_TRY(hipMemcpyAsync(mp->d_T, rec.odom, sizeof(double) * 12, hipMemcpyHostToDevice, h->stream));
+    if ((rc = map_enqueue_local(mp, mp->d_T, cxy, cz, reinterpret_cast<float4*>(h->state_stage + prefix), h->v.recv_cap, mp->d_out_n, h->stream, 0))) return rc;
+    MapState ms;
+    HIP_TRY(hipMemcpyAsync(&ms, mp->m.st, sizeof(ms), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (ms.n_result > h->v.recv_cap) { g_last_error = "liodom_seed_stream: the local map at the seed is larger than recv_capacity"; return LIODOM_ERR_CAPACITY; }
+    rec.n_recv = ms.n_result < 0 ? 0 : ms.n_result;
+  }
+  std::memset(h->state_stage_host, 0, prefix);
+  std::memcpy(h->state_stage_host + kStateHeaderBytes, &rec, sizeof(rec));
+  HIP_TRY(hipMemcpyAsync(h->state_stage, h->state_stage_host, prefix, hipMemcpyHostToDevice, h->stream));
+  return install_stream_state(h, stream, h->state_stage, 0, 0, rec.n_recv);
 }
 
 static int copy_edges_out(liodom_handle_t* h, int stream, int eb, hipStream_t q, float* edges_xyzi, int32_t* edge_ring,
@@ -2002,6 +2094,97 @@ void liodom_mapper_options_default(liodom_mapper_options_t* o) {
   o->cells_xy = 2; o->cells_z = 1;      // liodom_mapping_node.cc:130-134
 }
 
+// One attachment of `m` to a stream of `h` comes (+1) or goes (-1).  The first one moves the map onto the handle's HIP stream; the
+// map gets a stream of its own again only when the last one goes.  The odometry stream has drained (the callers synchronise).
+static int map_attachment(liodom_handle* h, liodom_map* m, int delta, bool reader) {
+  if (delta > 0) {
+    if (m->n_attached == 0 || m->attached_to != h) {      // (a map another handle still names moves here, as it always did)
+      HIP_TRY(hipStreamSynchronize(m->stream));
+      if (m->own_stream) { (void)hipStreamDestroy(m->stream); m->own_stream = false; }
+      m->stream = h->stream;
+      m->attached_to = h; m->n_attached = 0; m->n_readers = 0;
+    }
+    m->n_attached++;
+    if (reader) m->n_readers++;
+    return LIODOM_OK;
+  }
+  if (m->attached_to != h) return LIODOM_OK;      // (the map has moved to another handle since)
+  if (reader && m->n_readers > 0) m->n_readers--;
+  if (m->n_attached > 0) m->n_attached--;
+  if (m->n_attached == 0) {
+    m->n_readers = 0; m->attached_to = nullptr;
+    m->stream = nullptr; m->own_stream = false;
+    HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    m->own_stream = true;
+  }
+  return LIODOM_OK;
+}
+// Attachments of `m` other than the one stream `stream` of `h` holds now (which an attach call replaces): writers, readers.
+static void other_attachments(const liodom_handle* h, int stream, const liodom_map* m, int* writers, int* readers) {
+  int own_w = (h->mappers[(size_t)stream] == m) ? 1 : 0;
+  int own_r = (!h->readers.empty() && h->readers[(size_t)stream] == m) ? 1 : 0;
+  if (m->attached_to != h) { own_w = 0; own_r = 0; }
+  *readers = m->n_readers - own_r;
+  *writers = (m->n_attached - m->n_readers) - own_w;
+}
+// Takes the stream's attachment away, whichever kind it is.
+static int detach_stream_map(liodom_handle* h, int stream) {
+  if (liodom_map* old = h->mappers[(size_t)stream]) {
+    h->mappers[(size_t)stream] = nullptr;
+    if (h->mapper_opts[(size_t)stream].lag == 1) h->n_lagged--;
+    const int rc = map_attachment(h, old, -1, false);
+    if (rc) return rc;
+  }
+  if (!h->readers.empty() && h->readers[(size_t)stream]) {
+    liodom_map* old = h->readers[(size_t)stream];
+    h->readers[(size_t)stream] = nullptr;
+    h->n_readers--;
+    const int4 none = make_int4(0, 0, 0, 0);
+    HIP_TRY(hipMemcpy(h->reader_sel + stream, &none, sizeof(none), hipMemcpyHostToDevice));
+    bool still = false;
+    for (liodom_map* q : h->readers) still = still || q == old;
+    if (!still) for (liodom_map*& q : h->read_maps) if (q == old) q = nullptr;
+    const int rc = map_attachment(h, old, -1, true);
+    if (rc) return rc;
+  }
+  return LIODOM_OK;
+}
+
+int liodom_attach_map_reader(liodom_handle_t* h, int stream, liodom_map_t* m, int cells_xy, int cells_z) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if (!h->v.mapping) { g_last_error = "liodom_attach_map_reader: the handle was created with mapping = 0"; return LIODOM_ERR_UNSUPPORTED; }
+  if (!m) return liodom_attach_mapper_ex(h, stream, nullptr, nullptr);
+  // every rejection comes before the attachment is touched
+  if (m->device != h->config.device) { g_last_error = "liodom_attach_map_reader: map and handle live on different devices"; return LIODOM_ERR_INVALID_ARG; }
+  if (cells_xy < 0 || cells_z < 0) { g_last_error = "liodom_attach_map_reader: negative extent"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, true, false);
+  int writers = 0, readers = 0;
+  other_attachments(h, stream, m, &writers, &readers);
+  if (writers > 0) { g_last_error = "liodom_attach_map_reader: the map is attached writing (liodom_attach_mapper): a map is read or written, not both"; return LIODOM_ERR_INVALID_ARG; }
+  if (m->n_attached > 0 && m->attached_to != h) { g_last_error = "liodom_attach_map_reader: the map is attached to another handle"; return LIODOM_ERR_INVALID_ARG; }
+  HIP_TRY(sync_odometry(h));
+  if (!h->reader_sel) {      // one int4 per stream, from the first reader on
+    if ((rc = dev_alloc(h, &h->reader_sel, (size_t)h->S))) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->readers.assign((size_t)h->S, nullptr); h->reader_xy.assign((size_t)h->S, 0); h->reader_z.assign((size_t)h->S, 0);
+  }
+  // (attach first, detach second: a stream that re-attaches the map it reads keeps the map on the handle's stream throughout)
+  if ((rc = map_attachment(h, m, +1, true))) return rc;
+  if ((rc = detach_stream_map(h, stream))) return rc;
+  size_t t = 0;
+  for (; t < h->read_maps.size() && h->read_maps[t] != m; t++) {}
+  if (t == h->read_maps.size()) {
+    for (t = 0; t < h->read_maps.size() && h->read_maps[t]; t++) {}
+    if (t == h->read_maps.size()) h->read_maps.push_back(m); else h->read_maps[t] = m;
+  }
+  h->readers[(size_t)stream] = m; h->reader_xy[(size_t)stream] = cells_xy; h->reader_z[(size_t)stream] = cells_z;
+  h->n_readers++;
+  const int4 sel = make_int4((int)t + 1, cells_xy, cells_z, 0);
+  HIP_TRY(hipMemcpy(h->reader_sel + stream, &sel, sizeof(sel), hipMemcpyHostToDevice));
+  return LIODOM_OK;
+}
+
 int liodom_attach_mapper_ex(liodom_handle_t* h, int stream, liodom_map_t* m, const liodom_mapper_options_t* options) {
   int rc = check_stream(h, stream);
   if (rc) return rc;
@@ -2022,6 +2205,11 @@ int liodom_attach_mapper_ex(liodom_handle_t* h, int stream, liodom_map_t* m, con
     }
   }
   SideLocks lk(h, true, false);
+  if (m) {
+    int writers = 0, readers = 0;
+    other_attachments(h, stream, m, &writers, &readers);
+    if (readers > 0) { g_last_error = "liodom_attach_mapper: the map is attached reading (liodom_attach_map_reader): a map is read or written, not both"; return LIODOM_ERR_INVALID_ARG; }
+  }
   HIP_TRY(sync_odometry(h));
   if (m && o.lag == 1 && !h->lag_stash) {      // one edge_cap frame per stream, from the first lagged attach on
     if ((rc = dev_alloc(h, &h->lag_stash, (size_t)h->S * (size_t)h->v.edge_cap))) return rc;
@@ -2030,17 +2218,11 @@ int liodom_attach_mapper_ex(liodom_handle_t* h, int stream, liodom_map_t* m, con
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
   if (m && o.prune_period > 0 && (rc = map_ensure_prune(m))) return rc;
-  if (liodom_map* old = h->mappers[stream]) {       // detach: the map gets a stream of its own again
-    h->mappers[stream] = nullptr;
-    if (h->mapper_opts[stream].lag == 1) h->n_lagged--;
-    old->stream = nullptr; old->own_stream = false;
-    HIP_TRY(hipStreamCreateWithFlags(&old->stream, hipStreamNonBlocking));
-    old->own_stream = true;
-  }
+  // (attach first, detach second: re-attaching the stream's own map keeps it on the handle's stream; a map whose last attachment
+  //  goes gets a stream of its own again)
+  if (m && (rc = map_attachment(h, m, +1, false))) return rc;
+  if ((rc = detach_stream_map(h, stream))) return rc;
   if (m) {
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    if (m->own_stream) { (void)hipStreamDestroy(m->stream); m->own_stream = false; }
-    m->stream = h->stream;
     h->mappers[stream] = m;
     h->mapper_opts[stream] = o;
     if (o.lag == 1) h->n_lagged++;
@@ -2654,6 +2836,10 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   if (h->n_lagged > 0) {      // streams with a lagged mapper (liodom_attach_mapper_ex); their steps run on the odometry stream alone, as every mapping handle's
     const size_t len = std::strlen(buf);
     snprintf(buf + len, (size_t)cap - len, " mapper_lag=%d", h->n_lagged);
+  }
+  if (h->n_readers > 0) {     // streams that read a map they never write (liodom_attach_map_reader)
+    const size_t len = std::strlen(buf);
+    snprintf(buf + len, (size_t)cap - len, " map_readers=%d map_rows=%d", h->n_readers, h->map_rows ? 1 : 0);
   }
   {
     const size_t len = std::strlen(buf);      // (steps liodom_process_resident_subset ran over a stream list, i.e. did not hand to the plain step)

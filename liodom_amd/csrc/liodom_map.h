@@ -527,6 +527,141 @@ __global__ __launch_bounds__(256) void k_map_gather(MapView m, float4* out, int 
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// getLocalMap for a batch of poses against ONE map in one launch (liodom_map_get_local_batch, and the per-scan path of the map
+// readers of liodom_attach_map_reader; no counterpart in the reference, which asks one pose at a time).  grid (x, rows).  Every
+// workgroup plans its row in LDS — no MapView::entries, no MapState::n_entries / n_result: nothing of the map is written, so
+// any number of rows, of this launch or of others, can share a map — and copies its slice of the row's result.
+//   plan    one lane enumerates the keys with the loops of k_map_local_plan as they stand (translation truncated to int first,
+//           i = (int)(i + m.xy), the z column's extent from the xy size, the centre cell visited twice); the lanes look the keys
+//           up in parallel; a scan over (found, count) in key order gives the entries k_map_local_plan would have written and
+//           their offsets.
+//   copy    the row's n = min(total, cap) output points are dealt to the row's workgroups in contiguous slices (the x extent is
+//           capped by the host; a slice is walked 256 points at a time); one 16-byte load and one 16-byte store per point,
+//           consecutive lanes on consecutive points.
+// Output of a row: what k_map_local_plan + k_map_gather leave for the same pose and capacity, bit for bit — order, duplicates,
+// truncation at cap, n = min(total, cap), the sticky MAP_STATUS_LOCAL_OVERFLOW (sticky != 0 only).
+// The LDS plan holds kMapRowsKeysMax keys.  The host launches this kernel only for extents whose visit cannot exceed that
+// (map_rows_fit in liodom_map_host.h: a bound over every pose) and runs the two old launches per row otherwise; should a row
+// get here with more keys all the same, the plan stops at the cap and raises MAP_STATUS_LOCAL_OVERFLOW.
+// ---------------------------------------------------------------------------------------------
+constexpr int kMapRowsKeysMax = 1024;
+constexpr int kMapRowsThreads = 256;
+constexpr int kMapRowsGridX = 16;       // most workgroups a row is dealt to
+constexpr int kMapRowsGridMax = 2048;   // most workgroups of a launch
+
+// Where the rows of a launch live.  Row `row` works for index idx = s0 + row, or list[row] (kList: a subset step's stream list).
+// sel != nullptr (step path): idx is a stream; it takes part iff sel[idx].x == tag (it reads THIS map), with the extents
+// sel[idx].y / .z it was attached with.  sel == nullptr (batch call): every row takes part with cells_xy / cells_z.
+struct MapRows {
+  const double* T;  long long T_stride;      // pose of idx: T + idx * T_stride, 12 doubles (row-major 3 x 4)
+  float4* out;      long long out_stride;    // result of idx: out + idx * out_stride, room for `cap` points
+  int* n_out;       long long n_stride;      // points written: n_out[idx * n_stride]
+  int* total;                                // (optional) [idx] size of the full result, whatever cap is
+  const int4* sel;
+  const int* list;
+  int tag, s0, cap, cells_xy, cells_z, sticky;
+};
+
+template <bool kList = false>
+__global__ __launch_bounds__(kMapRowsThreads) void k_map_local_rows(MapView m, MapRows r) {
+  __shared__ int sh_key[3][kMapRowsKeysMax];
+  __shared__ int sh_cell[kMapRowsKeysMax];          // the entries, compacted: cell id
+  __shared__ int sh_off[kMapRowsKeysMax + 1];       // ... and offset; [ne] = total
+  __shared__ int sh_wf[kMapRowsThreads / 64], sh_wc[kMapRowsThreads / 64];
+  __shared__ int sh_nk, sh_over, sh_ne, sh_total;
+  const int tid = threadIdx.x;
+  const int row = blockIdx.y;
+  const int idx = kList ? r.list[row] : r.s0 + row;
+  int cells_xy = r.cells_xy, cells_z = r.cells_z;
+  if (r.sel) {
+    const int4 sl = r.sel[idx];
+    if (sl.x != r.tag) return;                      // (uniform) not a reader of this map
+    cells_xy = sl.y; cells_z = sl.z;
+  }
+  if (tid == 0) {
+    const double* T_ptr = r.T + (long long)idx * r.T_stride;
+    int nk = 0, over = 0;
+    auto add = [&](int kx, int ky, int kz) {
+      if (nk < kMapRowsKeysMax) { sh_key[0][nk] = kx; sh_key[1][nk] = ky; sh_key[2][nk] = kz; nk++; }
+      else over = 1;
+    };
+    const int x = (int)T_ptr[3];                                                       // :144
+    const int voxel_x = map_cell_key((double)x, m.inv_xy, m.xy, m.half_xy);
+    const int y = (int)T_ptr[7];                                                       // :147
+    const int voxel_y = map_cell_key((double)y, m.inv_xy, m.xy, m.half_xy);
+    const int z = (int)T_ptr[11];                                                      // :150
+    const int voxel_z = map_cell_key((double)z, m.inv_z, m.z, m.half_z);
+    const int init_x = (int)(voxel_x - cells_xy * m.xy);                               // :157-160
+    const int end_x = (int)(voxel_x + cells_xy * m.xy);
+    const int init_y = (int)(voxel_y - cells_xy * m.xy);
+    const int end_y = (int)(voxel_y + cells_xy * m.xy);
+    int guard = 0;
+    for (int i = init_x; i <= end_x && guard < 65536 && !over; i = (int)(i + m.xy), guard++) {          // :162
+      for (int j = init_y; j <= end_y && guard < 65536 && !over; j = (int)(j + m.xy), guard++) {        // :163
+        add(i, j, voxel_z);
+      }
+    }
+    const int init_z = (int)(voxel_z - cells_z * m.xy);                                // :175 (xy size)
+    const int end_z = (int)(voxel_z + cells_z * m.xy);                                 // :176
+    for (int i = init_z; i <= end_z && guard < 65536 && !over; i = (int)(i + m.z), guard++) {   // :178
+      add(voxel_x, voxel_y, i);
+    }
+    sh_nk = nk; sh_over = over; sh_ne = 0; sh_total = 0;
+  }
+  __syncthreads();
+  const int nk = sh_nk;
+  // lookups in parallel, then the scan of k_map_evict_plan over (found, count) in key order, chunk after chunk
+  for (int base = 0; base < nk; base += kMapRowsThreads) {
+    const int k = base + tid;
+    int cell = -1, cnt = 0;
+    if (k < nk) {
+      const int c = map_find_cell(m, sh_key[0][k], sh_key[1][k], sh_key[2][k]);
+      if (c >= 0 && c < m.max_cells) { cell = c; cnt = m.cell_n[c]; }
+    }
+    const int f = cell >= 0 ? 1 : 0;
+    int inf = f, inc = cnt;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int tf = __shfl_up(inf, off), tc = __shfl_up(inc, off);
+      if ((tid & 63) >= off) { inf += tf; inc += tc; }
+    }
+    if ((tid & 63) == 63) { sh_wf[tid >> 6] = inf; sh_wc[tid >> 6] = inc; }
+    __syncthreads();
+    int j = sh_ne + inf - f, o = sh_total + inc - cnt;
+    for (int q = 0; q < (tid >> 6); q++) { j += sh_wf[q]; o += sh_wc[q]; }
+    if (f) { sh_cell[j] = cell; sh_off[j] = o; }      // j < nk <= kMapRowsKeysMax
+    __syncthreads();
+    if (tid == kMapRowsThreads - 1) { sh_ne = j + f; sh_total = o + cnt; }
+    __syncthreads();
+  }
+  const int ne = sh_ne, total = sh_total;
+  if (tid == 0) sh_off[ne] = total;
+  __syncthreads();
+  const int n = total > r.cap ? r.cap : total;
+  if (blockIdx.x == 0 && tid == 0) {
+    if ((total > r.cap && r.sticky) || sh_over) atomicOr(&m.st->status, MAP_STATUS_LOCAL_OVERFLOW);
+    r.n_out[(long long)idx * r.n_stride] = n;
+    if (r.total) r.total[idx] = total;
+  }
+  // this workgroup's slice [lo, hi) of the row's n output points
+  const int per = (n + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int lo = min(n, (int)blockIdx.x * per), hi = min(n, lo + per);
+  if (lo >= hi) return;
+  int e = 0;
+  {                                                   // first entry that reaches past lo (entries of 0 points share an offset)
+    int a = 0, b = ne;                                // invariant: sh_off[a] <= lo < sh_off[b]
+    while (b - a > 1) { const int mid = (a + b) >> 1; if (sh_off[mid] <= lo) a = mid; else b = mid; }
+    e = a;
+  }
+  float4* out = r.out + (long long)idx * r.out_stride;
+  for (; e < ne && sh_off[e] < hi; e++) {
+    const int o0 = sh_off[e];
+    const int a = max(o0, lo), b = min(sh_off[e + 1], hi);
+    const float4* src = map_cell_cur(m, sh_cell[e]);
+    for (int o = a + tid; o < b; o += kMapRowsThreads) out[o] = src[o - o0];
+  }
+}
+
 // fills the bookkeeping arrays at creation
 __global__ __launch_bounds__(256) void k_map_init(MapView m) {
   const int i = blockIdx.x * 256 + threadIdx.x;

@@ -19,6 +19,12 @@ struct liodom_map {
   int* d_out_n = nullptr;
   unsigned char* d_head = nullptr;   // header + max_cells cell records of a map-state blob (first export / import allocates it)
   liodom_dev::MapPruneMove* d_prune = nullptr;   // max_cells + 1 move records of a prune (the first prune, or an attach with auto-prune, allocates it)
+  unsigned char* d_batch = nullptr;  // liodom_map_get_local_batch: n poses, then 2 n counts (the first call allocates it, a larger one regrows it)
+  size_t batch_bytes = 0;
+  // attachments to a handle's streams (liodom_attach_mapper* / liodom_attach_map_reader): the map runs on the handle's HIP stream
+  // while n_attached > 0 and gets one of its own again when the last attachment goes
+  int n_attached = 0, n_readers = 0;
+  const void* attached_to = nullptr;
 };
 
 namespace {
@@ -109,6 +115,26 @@ int map_enqueue_local(liodom_map* mp, const double* d_T, int cells_xy, int cells
   return LIODOM_OK;
 }
 
+// Whether the visit of getLocalMap(., cells_xy, cells_z) fits the LDS plan of k_map_local_rows for EVERY pose.  With both sizes
+// >= 1 a loop variable advances by at least floor(size) per iteration ((int)(i + size) >= i + floor(size) on either side of 0),
+// and a loop's ends lie at most 2 * cells * xy + 2 apart (each end is truncated once).  So the square visits at most nx * nx keys
+// and the column nz, with the bounds below; anything else takes k_map_local_plan + k_map_gather.
+bool map_rows_fit(const liodom_map* mp, int cells_xy, int cells_z) {
+  const double xy = mp->cfg.voxel_xysize, z = mp->cfg.voxel_zsize;
+  if (!(xy >= 1.0) || !(z >= 1.0) || cells_xy < 0 || cells_z < 0) return false;
+  const double nx = std::floor((2.0 * cells_xy * xy + 2.0) / std::floor(xy)) + 1.0;
+  const double nz = std::floor((2.0 * cells_z * xy + 2.0) / std::floor(z)) + 1.0;
+  return nx * nx + nz <= (double)liodom_dev::kMapRowsKeysMax;
+}
+
+// x extent of a k_map_local_rows launch over `rows` rows of up to `cap` points: a row's copy is dealt to at most kMapRowsGridX
+// workgroups, the launch stays within kMapRowsGridMax, and no workgroup is launched for less than one round of its threads.
+int map_rows_grid_x(int rows, int cap) {
+  using namespace liodom_dev;
+  const int by_cap = std::max(1, (cap + kMapRowsThreads - 1) / kMapRowsThreads);
+  return std::max(1, std::min(std::min(kMapRowsGridX, by_cap), kMapRowsGridMax / std::max(1, rows)));
+}
+
 int map_ensure_out(liodom_map* mp, int64_t cap) {
   if (cap > 0x7fffffff) cap = 0x7fffffff;
   if (mp->d_out && mp->out_cap >= cap) return LIODOM_OK;
@@ -124,6 +150,7 @@ void map_free(liodom_map* mp) {
   if (mp->stream) (void)hipStreamSynchronize(mp->stream);
   for (void* p : mp->allocs) (void)hipFree(p);
   if (mp->d_out) (void)hipFree(mp->d_out);
+  if (mp->d_batch) (void)hipFree(mp->d_batch);
   if (mp->own_stream && mp->stream) (void)hipStreamDestroy(mp->stream);
   delete mp;
 }
@@ -311,6 +338,60 @@ int liodom_map_get_local(liodom_map_t* mp, const double* T, int cells_xy, int ce
   rc = map_enqueue_local(mp, mp->d_T, cells_xy, cells_z, mp->d_out, mp->out_cap, mp->d_out_n, mp->stream, 0);
   if (rc) return rc;
   return map_fetch_result(mp, xyzi, cap, n_points);
+}
+
+int liodom_map_get_local_batch(liodom_map_t* mp, const double* T, int n, int cells_xy, int cells_z, float* xyzi, int64_t cap_per_row,
+                               int64_t* n_points) {
+  using namespace liodom_dev;
+  if (!mp || n < 0 || (n > 0 && (!T || !n_points)) || cap_per_row < 0 || (cap_per_row > 0 && n > 0 && !xyzi) || cells_xy < 0 || cells_z < 0) {
+    g_last_error = "liodom_map_get_local_batch: invalid argument"; return LIODOM_ERR_INVALID_ARG;
+  }
+  if (n == 0) return LIODOM_OK;
+  if (cap_per_row > 0x7fffffff || (int64_t)n * std::max<int64_t>(cap_per_row, 1) > 0x7fffffff) {
+    g_last_error = "liodom_map_get_local_batch: n * cap_per_row beyond 2^31 - 1 points"; return LIODOM_ERR_CAPACITY;
+  }
+  HIP_TRY(hipSetDevice(mp->device));
+  const int cap = (int)cap_per_row;
+  int rc = map_ensure_out(mp, (int64_t)n * std::max(cap, 1));
+  if (rc) return rc;
+  const size_t t_bytes = sizeof(double) * 12 * (size_t)n, need = t_bytes + sizeof(int) * 2 * (size_t)n;
+  if (mp->batch_bytes < need) {
+    HIP_TRY(hipStreamSynchronize(mp->stream));
+    if (mp->d_batch) { (void)hipFree(mp->d_batch); mp->d_batch = nullptr; mp->batch_bytes = 0; }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&mp->d_batch), need));
+    mp->batch_bytes = need;
+  }
+  double* d_T = reinterpret_cast<double*>(mp->d_batch);
+  int* d_n = reinterpret_cast<int*>(mp->d_batch + t_bytes);      // [n] points written, [n] sizes
+  HIP_TRY(hipMemcpyAsync(d_T, T, t_bytes, hipMemcpyHostToDevice, mp->stream));
+  if (map_rows_fit(mp, cells_xy, cells_z)) {
+    MapRows r{};
+    r.T = d_T; r.T_stride = 12; r.out = mp->d_out; r.out_stride = cap; r.n_out = d_n; r.n_stride = 1; r.total = d_n + n;
+    r.sel = nullptr; r.list = nullptr; r.tag = 0; r.s0 = 0; r.cap = cap; r.cells_xy = cells_xy; r.cells_z = cells_z; r.sticky = 0;
+    // (rows beyond the grid's y limit: launches of 32768 rows)
+    for (int first = 0; first < n; first += 32768) {
+      const int rows = std::min(32768, n - first);
+      r.s0 = first;
+      hipLaunchKernelGGL(k_map_local_rows<false>, dim3(map_rows_grid_x(rows, cap), rows), dim3(kMapRowsThreads), 0, mp->stream, mp->m, r);
+    }
+    HIP_TRY(hipGetLastError());
+  } else {
+    // a visit the LDS plan cannot hold: the two launches of liodom_map_get_local, row after row (one plan scratch: stream order)
+    for (int i = 0; i < n; i++) {
+      rc = map_enqueue_local(mp, d_T + 12 * (size_t)i, cells_xy, cells_z, mp->d_out + (size_t)i * cap, cap, d_n + i, mp->stream, 0);
+      if (rc) return rc;
+      HIP_TRY(hipMemcpyAsync(d_n + n + i, &mp->m.st->n_result, sizeof(int), hipMemcpyDeviceToDevice, mp->stream));
+    }
+  }
+  std::vector<int> cnt(2 * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), d_n, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));      // (the staged poses are the caller's memory)
+  bool fits = true;
+  for (int i = 0; i < n; i++) { n_points[i] = cnt[(size_t)n + i]; fits = fits && cnt[(size_t)n + i] <= cap; }
+  if (!fits) { g_last_error = "liodom_map_get_local_batch: a row is larger than cap_per_row"; return LIODOM_ERR_CAPACITY; }
+  for (int i = 0; i < n; i++)
+    if (cnt[(size_t)i] > 0) HIP_TRY(hipMemcpy(xyzi + 4 * (size_t)i * (size_t)cap, mp->d_out + (size_t)i * cap, sizeof(float4) * (size_t)cnt[(size_t)i], hipMemcpyDeviceToHost));
+  return LIODOM_OK;
 }
 
 int liodom_map_get_all(liodom_map_t* mp, float* xyzi, int64_t cap, int64_t* n_points) {

@@ -575,6 +575,40 @@ void LaserOdometer::attachMapper(Map* map, const liodom_mapper_options_t& option
   check(liodom_attach_mapper_ex(eng_->handle(), 0, map ? map->handle() : nullptr, &options), "liodom_attach_mapper_ex");
 }
 
+void LaserOdometer::attachMapReader(Map* map, int cells_xy, int cells_z) {
+  check(liodom_attach_map_reader(eng_->handle(), 0, map ? map->handle() : nullptr, cells_xy, cells_z), "liodom_attach_map_reader");
+}
+
+void LaserOdometer::seed(const Pose& pose) {
+  const double p[7] = {pose.q[0], pose.q[1], pose.q[2], pose.q[3], pose.t[0], pose.t[1], pose.t[2]};
+  check(liodom_seed_stream(eng_->handle(), 0, p), "liodom_seed_stream");
+  // what publishOdom keeps on the host starts over, as after reset(); the seeded scan is no first frame of the reference's kind
+  // (it solves), so the rate watchdog runs from it on
+  prev_odom_ = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
+  prev_stamp_ = 0.0; published_ = false; init_ = true; last_scan_ = -1;
+}
+
+std::vector<PointCloud> Map::getLocalBatch(const std::vector<std::array<double, 12>>& poses, int cells_xy, int cells_z) {
+  const int n = (int)poses.size();
+  std::vector<PointCloud> out((size_t)n);
+  if (n == 0) return out;
+  std::vector<double> T(12 * (size_t)n);
+  for (int i = 0; i < n; i++) std::memcpy(&T[12 * (size_t)i], poses[(size_t)i].data(), sizeof(double) * 12);
+  std::vector<int64_t> sizes((size_t)n, 0);
+  // size query first (LIODOM_ERR_CAPACITY with the sizes filled in), then the copy
+  const int rc = liodom_map_get_local_batch(m_, T.data(), n, cells_xy, cells_z, nullptr, 0, sizes.data());
+  if (rc != LIODOM_ERR_CAPACITY) check(rc, "liodom_map_get_local_batch");
+  const int64_t cap = *std::max_element(sizes.begin(), sizes.end());
+  if (cap == 0) return out;
+  std::vector<Point> buf((size_t)n * (size_t)cap);
+  check(liodom_map_get_local_batch(m_, T.data(), n, cells_xy, cells_z, reinterpret_cast<float*>(buf.data()), cap, sizes.data()), "liodom_map_get_local_batch");
+  for (int i = 0; i < n; i++) {
+    out[(size_t)i].points.assign(buf.begin() + (std::ptrdiff_t)((size_t)i * (size_t)cap), buf.begin() + (std::ptrdiff_t)((size_t)i * (size_t)cap + (size_t)sizes[(size_t)i]));
+    out[(size_t)i].width = (uint32_t)sizes[(size_t)i]; out[(size_t)i].height = 1;
+  }
+  return out;
+}
+
 void LaserOdometer::attachMapper(Map* map, int cells_xy, int cells_z) {
   check(liodom_attach_mapper(eng_->handle(), 0, map ? map->handle() : nullptr, cells_xy, cells_z), "liodom_attach_mapper");
 }

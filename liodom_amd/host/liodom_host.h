@@ -219,6 +219,9 @@ class Map {
   void updateMap(const PointCloud& pc_in, const std::array<double, 12>& pose);                  // :90-129
   PointCloud getMap();                                                                          // :131-139
   PointCloud getLocalMap(const std::array<double, 12>& pose, int cells_xy = 2, int cells_z = 1); // :141-189
+  // getLocalMap for several poses in one launch (liodom_map_get_local_batch; no counterpart in the reference): one cloud per pose,
+  // each what getLocalMap returns for it.
+  std::vector<PointCloud> getLocalBatch(const std::vector<std::array<double, 12>>& poses, int cells_xy = 2, int cells_z = 1);
   // The map as one blob (no counterpart in the reference; layout in csrc/map_state_format.h).  exportState works on an attached
   // map too; importState and reset need a detached one (detach, import, attachMapper).
   std::vector<uint8_t> exportState();
@@ -302,6 +305,11 @@ class LaserOdometer {
   // ... with options (liodom_attach_mapper_ex): lag = 1 makes the map take a frame when it leaves the sliding window — the mode
   // that solves; lag = 0 is the faithful, degenerate replay above —, prune_period > 0 prunes the map around the pose as it goes
   void attachMapper(Map* map, const liodom_mapper_options_t& options);
+  // Localising in a saved map (liodom_attach_map_reader / liodom_seed_stream; no counterpart in the reference).  attachMapReader:
+  // after every scan the odometer receives getLocalMap(pose) of `map`, which is never written; attachMapper(nullptr) detaches.
+  // seed: the next scan is the first and solves from `pose`; with a map attached the odometer receives its local map there.
+  void attachMapReader(Map* map, int cells_xy = 2, int cells_z = 1);
+  void seed(const Pose& pose);
   // One pass of the loop body of LaserOdometer::operator() (laser_odometry.cc:107-267).
   Pose process(const PointCloud& feats, double stamp, liodom_step_info_t* info = nullptr);
   // The same on an edge cloud the extractor left on the device (Features::ticket)

@@ -13,6 +13,10 @@
 // map_pager=KEEP_XY,KEEP_Z,LOAD_XY,LOAD_Z runs a liodom::MapPager after every scan: the device map is a window onto a map kept on
 // the host (cells outside the keep box are paged out, stored cells inside the load box paged in); map_state_out= then writes the
 // whole map (MapPager::exportAll) and the run prints the pager's counters.  Fused per-scan path only.
+// localize=1 (with mapping=true map_state_in=FILE) runs the traversal AGAINST the saved map instead of building one: the map is
+// attached read-only (LaserOdometer::attachMapReader: it is never written), seed_pose=qx,qy,qz,qw,tx,ty,tz places the first scan
+// in it (LaserOdometer::seed; default: the identity) and every scan solves against window ++ local map.  Not with mapper_lag,
+// map_prune_period or map_pager, which write.
 // threads=true runs the reference's own structure instead of the fused per-scan call: the clouds are
 // pushed into SharedData (lidarClb), a FeatureExtractor thread and a LaserOdometer thread work side by
 // side on the same handle (src/liodom_node.cc:89-91) and hand edge clouds over through the queue — the clouds stay on the
@@ -72,8 +76,11 @@ int main(int argc, char** argv) {
     liodom::LaserOdometer odometer(eng);
     std::unique_ptr<liodom::Map> mapper;
     std::unique_ptr<liodom::MapPager> pager;
-    std::string map_state_in, map_state_out, map_pager;
+    std::string map_state_in, map_state_out, map_pager, seed_pose;
+    bool localize = false;
     for (const std::string& a : kv) {
+      if (a == "localize=1" || a == "localize=true") localize = true;
+      if (a.rfind("seed_pose=", 0) == 0) seed_pose = a.substr(10);
       if (a.rfind("map_state_in=", 0) == 0) map_state_in = a.substr(13);
       if (a.rfind("map_state_out=", 0) == 0) map_state_out = a.substr(14);
       if (a.rfind("map_pager=", 0) == 0) map_pager = a.substr(10);
@@ -82,6 +89,8 @@ int main(int argc, char** argv) {
     if ((!map_state_in.empty() || !map_state_out.empty()) && !params->mapping_) {
       std::fprintf(stderr, "liodom_replay: map_state_in / map_state_out need mapping=true\n"); return 2;
     }
+    if (localize && (!params->mapping_ || map_state_in.empty())) { std::fprintf(stderr, "liodom_replay: localize=1 needs mapping=true map_state_in=FILE\n"); return 2; }
+    if (!seed_pose.empty() && !localize) { std::fprintf(stderr, "liodom_replay: seed_pose needs localize=1\n"); return 2; }
     if (params->mapping_) {
       double xy = 40.0, z = 50.0, res = 0.4;      // liodom_mapping_node.cc:115-134
       liodom_mapper_options_t mo;
@@ -105,7 +114,17 @@ int main(int argc, char** argv) {
         f.read(reinterpret_cast<char*>(st.data()), (std::streamsize)st.size());
         mapper->importState(st);
       }
-      odometer.attachMapper(mapper.get(), mo);
+      if (localize) {
+        if (mo.lag != 0 || mo.prune_period != 0 || !map_pager.empty()) { std::fprintf(stderr, "liodom_replay: localize=1 reads the map: not with mapper_lag, map_prune_period or map_pager\n"); return 2; }
+        liodom::Pose sp;
+        if (!seed_pose.empty() && std::sscanf(seed_pose.c_str(), "%lf,%lf,%lf,%lf,%lf,%lf,%lf", &sp.q[0], &sp.q[1], &sp.q[2], &sp.q[3], &sp.t[0], &sp.t[1], &sp.t[2]) != 7) {
+          std::fprintf(stderr, "liodom_replay: seed_pose=qx,qy,qz,qw,tx,ty,tz\n"); return 2;
+        }
+        odometer.attachMapReader(mapper.get(), mo.cells_xy, mo.cells_z);
+        odometer.seed(sp);
+      } else {
+        odometer.attachMapper(mapper.get(), mo);
+      }
       if (!map_pager.empty()) {
         int b[4] = {0, 0, 0, 0};
         if (std::sscanf(map_pager.c_str(), "%d,%d,%d,%d", &b[0], &b[1], &b[2], &b[3]) != 4) {
