@@ -665,6 +665,56 @@ int liodom_map_evict(liodom_map_t* m, const double* T /*3x4*/, int keep_cells_xy
                      int64_t* bytes, int* n_evicted);
 int liodom_map_merge_state(liodom_map_t* m, const void* blob, int64_t bytes, int32_t* taken /*optional, [blob n_cells]*/, int* n_added);
 
+/* ---- relocalising in a saved map: candidate poses of one scan's edge cloud scored against the map's leaf occupancy (no
+ * counterpart in the reference).  liodom_seed_stream wants a pose right to within decimetres; these calls find one from a guess
+ * that is metres and tenths of a radian off (DESIGN.md §3 "Relocalising in a saved map").
+ *
+ * Occupancy: for every cell of the map and every finite point p of its current cloud, the leaf of p in the cell's dense leaf grid
+ * (the grid liodom_map_update filters with: PCL VoxelGrid leaves of `resolution`) is occupied; a point whose leaf falls outside
+ * the grid occupies nothing.  It is rebuilt from the map as it is by every call: nothing is cached between calls.
+ * An edge e under a candidate T (3 x 4 doubles, row-major): q = float(T * e), computed as liodom_map_update transforms an inserted
+ * point.  A probe at a float point p hits iff p is finite, its coarse-cell key lies within +-2^20, the map holds that cell, and
+ * p's leaf lies inside the cell's grid and is occupied.  The centre probe is q; with radius = 1 there are 27 probes
+ * q + d * float(resolution), d in {-1, 0, 1}^3 (float multiply, then float add, per axis), each keyed as a point in its own right:
+ * a probe displaced across a coarse-cell face is looked up in the neighbour cell.  Per candidate two counts:
+ *   hits_r = edges with at least one hitting probe, hits_0 = edges whose centre probe hits (radius = 0: hits_r == hits_0).
+ * Ranking: score = hits_r + hits_0; the best candidate has the largest score, ties go to the lowest index.
+ *
+ *   liodom_map_score_poses   hits[2 i], hits[2 i + 1] = hits_r, hits_0 of candidate T + 12 i (no counterpart in the reference).
+ *   liodom_pose_search_default   centre = identity, steps 0.4 m / 0.4 m / 0.02 rad, all half counts 0, radius 1 (no counterpart
+ *       in the reference).
+ *   liodom_map_search_pose   scores a grid of candidates around `centre` and returns the best (no counterpart in the reference).
+ *       Candidate (ix, iy, ia, iz), each index from -n to n, ix fastest, then iy, then ia (yaw), iz slowest:
+ *         T = [ Rz(ia * step_yaw) * R_c | t_c + (ix * step_xy, iy * step_xy, iz * step_z) ],
+ *       yaw about the world z axis, R_c from the centre's quaternion, normalised in double, as liodom_seed_stream makes its matrix.
+ *       The matrices are made on the host in double (liodom_amd/csrc/reloc_candidates.h); only the result record and the optional
+ *       arrays come back.  out->pose is the best candidate as liodom_seed_stream takes it.
+ * Limits: n_edges <= the map's max_update_points; n and n_candidates <= 2^20.  n = 0 or n_edges = 0: LIODOM_OK with zero counts
+ * (the search then reports index 0).  LIODOM_ERR_INVALID_ARG, with nothing computed: a null where one is required, radius not 0 or
+ * 1, a negative count, a non-positive (or non-finite) step whose half count is > 0, a non-finite centre, | |q| - 1 | > 1e-6,
+ * anything beyond the limits.  Non-finite edges are no error: they miss.
+ * Both calls only read the map (no status bit, no cell, no plan entry changes): they work on a detached map and on an attached one
+ * — reading or writing — between steps, on the stream the map's work is on, and synchronise it before returning, with the threading
+ * rule of liodom_map_export_state.  The first call allocates the occupancy, 4 bytes per 32 leaves of the cells the map holds. */
+typedef struct liodom_pose_search_t {
+  double centre[7];            /* qx qy qz qw tx ty tz; normalised in double as liodom_seed_stream does */
+  double step_xy, step_z, step_yaw;
+  int32_t nx, ny, nz, nyaw;    /* half counts: the grid has (2nx+1)(2ny+1)(2nz+1)(2nyaw+1) candidates */
+  int32_t radius;              /* 0 | 1 */
+  int32_t reserved[3];
+} liodom_pose_search_t;
+typedef struct liodom_pose_search_result_t {
+  int32_t best_index, hits_r, hits_0, n_candidates;
+  double pose[7];              /* best candidate, quaternion normalised: what liodom_seed_stream takes */
+  double T[12];
+} liodom_pose_search_result_t;
+int liodom_map_score_poses(liodom_map_t* m, const float* edges_xyzi, int n_edges, const double* T /*n x 12*/, int n,
+                           int radius /*0 | 1*/, int32_t* hits /*n x 2: hits_r, hits_0*/);
+void liodom_pose_search_default(liodom_pose_search_t* s);
+int liodom_map_search_pose(liodom_map_t* m, const float* edges_xyzi, int n_edges, const liodom_pose_search_t* s,
+                           liodom_pose_search_result_t* out, double* T_out /*optional, n_candidates x 12*/,
+                           int32_t* hits_out /*optional, n_candidates x 2*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ _BUILD_INFO = {"rebuilt": None, "source_hash": None}
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kernels.h", "kernels_extract.h", "kernels_sync.h",
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
                                                   "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
-                                                  "liodom_map.h", "liodom_map_host.h", "map_state_format.h")] + [
+                                                  "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -153,6 +153,19 @@ class MapperOptions(C.Structure):
     """liodom_mapper_options_t: how liodom_attach_mapper_ex wires a map to a stream (include/liodom_hip.h)."""
     _fields_ = [("cells_xy", C.c_int32), ("cells_z", C.c_int32), ("lag", C.c_int32), ("prune_period", C.c_int32),
                 ("keep_cells_xy", C.c_int32), ("keep_cells_z", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class PoseSearch(C.Structure):
+    """liodom_pose_search_t: the candidate grid of liodom_map_search_pose (include/liodom_hip.h)."""
+    _fields_ = [("centre", C.c_double * 7), ("step_xy", C.c_double), ("step_z", C.c_double), ("step_yaw", C.c_double),
+                ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("nyaw", C.c_int32), ("radius", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class PoseSearchResult(C.Structure):
+    """liodom_pose_search_result_t: the best candidate of liodom_map_search_pose."""
+    _fields_ = [("best_index", C.c_int32), ("hits_r", C.c_int32), ("hits_0", C.c_int32), ("n_candidates", C.c_int32),
+                ("pose", C.c_double * 7), ("T", C.c_double * 12)]
 
 
 class EdgeTicket(C.Structure):
@@ -526,6 +539,11 @@ def load():
     L.liodom_map_evict.argtypes = [vp, dp, C.c_int, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64), ip]
     L.liodom_map_merge_state.restype = C.c_int
     L.liodom_map_merge_state.argtypes = [vp, vp, C.c_int64, ip, ip]
+    L.liodom_map_score_poses.restype = C.c_int
+    L.liodom_map_score_poses.argtypes = [vp, fp, C.c_int, dp, C.c_int, C.c_int, ip]
+    L.liodom_pose_search_default.argtypes = [C.POINTER(PoseSearch)]
+    L.liodom_map_search_pose.restype = C.c_int
+    L.liodom_map_search_pose.argtypes = [vp, fp, C.c_int, C.POINTER(PoseSearch), C.POINTER(PoseSearchResult), dp, ip]
     L.liodom_map_config_default.argtypes = [C.POINTER(MapConfig)]
     L.liodom_map_create.restype = C.c_int
     L.liodom_map_create.argtypes = [C.POINTER(MapConfig), C.POINTER(vp)]
@@ -625,6 +643,7 @@ EXPORTED_SYMBOLS = [
     "liodom_mapper_options_default", "liodom_attach_mapper_ex", "liodom_map_prune",
     "liodom_map_evict", "liodom_map_merge_state",
     "liodom_attach_map_reader", "liodom_seed_stream", "liodom_map_get_local_batch",
+    "liodom_map_score_poses", "liodom_pose_search_default", "liodom_map_search_pose",
 ]
 
 
@@ -670,6 +689,19 @@ def make_mapper_options(**kw):
     for k, v in kw.items():
         setattr(o, k, int(v))
     return o
+
+
+def make_pose_search(centre, **kw):
+    """PoseSearch with the defaults of liodom_pose_search_default (steps 0.4 m / 0.4 m / 0.02 rad, half counts 0, radius 1) around
+    centre = [qx qy qz qw tx ty tz]; keywords set step_xy, step_z, step_yaw, nx, ny, nz, nyaw, radius."""
+    s = PoseSearch()
+    load().liodom_pose_search_default(C.byref(s))
+    s.centre[:] = [float(v) for v in np.asarray(centre, np.float64).reshape(7)]
+    for k, v in kw.items():
+        if k not in ("step_xy", "step_z", "step_yaw", "nx", "ny", "nz", "nyaw", "radius"):
+            raise KeyError(k)
+        setattr(s, k, v)
+    return s
 
 
 def _fp(a):
@@ -1074,6 +1106,27 @@ class Liodom:
         p = np.ascontiguousarray(pose7, dtype=np.float64).reshape(7)
         self._check(self.L.liodom_seed_stream(self.h, int(stream), _dp(p)))
 
+    def relocalize(self, map, scan, height, width, centre, levels, min_fraction=0.5, stream=0):
+        """Finds the stream's pose in a saved map from a rough guess and seeds the stream with it.  The scan's edges
+        (extract_edges) are scored against `map` on one candidate grid per level (Map.search_pose; `levels` is a list of dicts of its
+        grid keywords), the first around `centre` = [qx qy qz qw tx ty tz], each later one around the level before's best.  If the last
+        level's score / (2 * n_edges) >= min_fraction the stream is seeded with the best pose (seed_stream) and
+        dict(pose, hits_r, hits_0, n_edges, fraction, levels=[each level's result]) comes back: process the SAME scan next.  Otherwise
+        None, and the stream is as it was but for the edges extract_edges left in it."""
+        edges = self.extract_edges(scan, height, width, stream=stream)["edges"]
+        pose, found = np.array(centre, dtype=np.float64).reshape(7), []
+        for grid in levels:
+            found.append(map.search_pose(edges, pose, **grid))
+            pose = found[-1]["pose"]
+        if not found or edges.shape[0] == 0:
+            return None
+        last = found[-1]
+        fraction = (last["hits_r"] + last["hits_0"]) / (2.0 * edges.shape[0])
+        if not fraction >= min_fraction:
+            return None
+        self.seed_stream(pose, stream=stream)
+        return dict(pose=pose, hits_r=last["hits_r"], hits_0=last["hits_0"], n_edges=int(edges.shape[0]), fraction=fraction, levels=found)
+
     def local_map(self, stream=0):
         cap = self.edge_cap * int(self.params.local_map_size) + (max(int(self.config.recv_capacity), 262144) if self.params.mapping else 0)
         w = np.zeros((cap, 4), np.float32)
@@ -1199,6 +1252,37 @@ class Map:
             e.sizes = sizes[:n].copy()
             raise
         return [out[i, :int(sizes[i])].copy() for i in range(n)]
+
+    def score_poses(self, edges, T, radius=1):
+        """hits_r, hits_0 of every candidate pose T = [n, 3, 4] (or [n, 12]) for the edge cloud `edges` [E, 4] against the map's leaf
+        occupancy (liodom_map_score_poses) -> int32 [n, 2].  Read-only on the map; works on an attached map between steps."""
+        e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1, 12)
+        hits = np.zeros((T.shape[0], 2), np.int32)
+        self._chk(self._L.liodom_map_score_poses(self.h, _fp(e), e.shape[0], _dp(T), T.shape[0], int(radius), _ip(hits)))
+        return hits
+
+    def search_pose(self, edges, centre, want_T=False, want_hits=False, **grid):
+        """Scores the candidate grid around centre = [qx qy qz qw tx ty tz] (liodom_map_search_pose; grid keywords as
+        make_pose_search: step_xy, step_z, step_yaw, nx, ny, nz, nyaw, radius) -> dict(best_index, hits_r, hits_0, n_candidates,
+        pose [7] — what Liodom.seed_stream takes —, T [3, 4]) plus, when asked for, T_all [n, 3, 4] and hits [n, 2]."""
+        e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
+        s = make_pose_search(centre, **grid)
+        n = max(1, (2 * int(s.nx) + 1) * (2 * int(s.ny) + 1) * (2 * int(s.nz) + 1) * (2 * int(s.nyaw) + 1))
+        if n > (1 << 20):
+            n = 1          # (the library refuses the grid before it writes anything)
+        T_all = np.zeros((n, 12)) if want_T else None
+        hits = np.zeros((n, 2), np.int32) if want_hits else None
+        r = PoseSearchResult()
+        self._chk(self._L.liodom_map_search_pose(self.h, _fp(e), e.shape[0], C.byref(s), C.byref(r), _dp(T_all) if want_T else None,
+                                                 _ip(hits) if want_hits else None))
+        out = dict(best_index=int(r.best_index), hits_r=int(r.hits_r), hits_0=int(r.hits_0), n_candidates=int(r.n_candidates),
+                   pose=np.array(r.pose[:]), T=np.array(r.T[:]).reshape(3, 4))
+        if want_T:
+            out["T_all"] = T_all.reshape(-1, 3, 4)
+        if want_hits:
+            out["hits"] = hits
+        return out
 
     def prune(self, T34=None, keep_xy=2, keep_z=1):
         """Drops every cell outside the box of keep_xy / keep_z cells around the pose's cell (liodom_map_prune); returns the

@@ -1057,3 +1057,5 @@ __global__ __launch_bounds__(256) void k_map_merge(MapView m, const unsigned cha
 }
 
 }  // namespace liodom_dev
+
+#include "kernels_reloc.h"

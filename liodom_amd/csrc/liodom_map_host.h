@@ -2,6 +2,7 @@
 // liodom_hip.hip (same translation unit: shares HIP_TRY / g_last_error).
 #pragma once
 #include "liodom_map.h"
+#include "reloc_candidates.h"
 
 struct liodom_map {
   liodom_map_config_t cfg;
@@ -21,6 +22,8 @@ struct liodom_map {
   liodom_dev::MapPruneMove* d_prune = nullptr;   // max_cells + 1 move records of a prune (the first prune, or an attach with auto-prune, allocates it)
   unsigned char* d_batch = nullptr;  // liodom_map_get_local_batch: n poses, then 2 n counts (the first call allocates it, a larger one regrows it)
   size_t batch_bytes = 0;
+  unsigned int* d_occ = nullptr;     // liodom_map_score_poses / _search_pose: leaf occupancy [occ_cells][words] (the first call allocates it for
+  int occ_cells = 0;                 // the cells the map holds then, a map that has grown since regrows it)
   // attachments to a handle's streams (liodom_attach_mapper* / liodom_attach_map_reader): the map runs on the handle's HIP stream
   // while n_attached > 0 and gets one of its own again when the last attachment goes
   int n_attached = 0, n_readers = 0;
@@ -144,6 +147,16 @@ int map_ensure_out(liodom_map* mp, int64_t cap) {
   return LIODOM_OK;
 }
 
+// d_batch with room for `need` bytes: n poses, then per-pose ints (liodom_map_get_local_batch, liodom_map_score_poses)
+int map_ensure_batch(liodom_map* mp, size_t need) {
+  if (mp->batch_bytes >= need) return LIODOM_OK;
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  if (mp->d_batch) { (void)hipFree(mp->d_batch); mp->d_batch = nullptr; mp->batch_bytes = 0; }
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&mp->d_batch), need));
+  mp->batch_bytes = need;
+  return LIODOM_OK;
+}
+
 void map_free(liodom_map* mp) {
   if (!mp) return;
   (void)hipSetDevice(mp->device);
@@ -151,6 +164,7 @@ void map_free(liodom_map* mp) {
   for (void* p : mp->allocs) (void)hipFree(p);
   if (mp->d_out) (void)hipFree(mp->d_out);
   if (mp->d_batch) (void)hipFree(mp->d_batch);
+  if (mp->d_occ) (void)hipFree(mp->d_occ);
   if (mp->own_stream && mp->stream) (void)hipStreamDestroy(mp->stream);
   delete mp;
 }
@@ -265,6 +279,67 @@ int map_install_state(liodom_map* mp, const unsigned char* blob, const liodom_de
   return LIODOM_OK;
 }
 
+// ---- relocalising (kernels_reloc.h) ----
+// The occupancy buffer with a row for each of n_cells cells.
+int map_ensure_occ(liodom_map* mp, int n_cells) {
+  if (mp->d_occ && mp->occ_cells >= n_cells) return LIODOM_OK;
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  if (mp->d_occ) { (void)hipFree(mp->d_occ); mp->d_occ = nullptr; mp->occ_cells = 0; }
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&mp->d_occ), sizeof(unsigned int) * std::max<size_t>((size_t)n_cells * (size_t)mp->m.words, 4)));
+  mp->occ_cells = n_cells;
+  return LIODOM_OK;
+}
+
+int map_score_check(const liodom_map* mp, const float* edges, int n_edges, const char* who) {
+  if (!mp || n_edges < 0 || (n_edges > 0 && !edges)) { g_last_error = std::string(who) + ": null map or edges, or a negative count"; return LIODOM_ERR_INVALID_ARG; }
+  if (n_edges > mp->cfg.max_update_points) { g_last_error = std::string(who) + ": more edges than the map's max_update_points"; return LIODOM_ERR_INVALID_ARG; }
+  return LIODOM_OK;
+}
+
+// Occupancy of the map as it is now, the two counts of each of the n >= 1 candidates T (host memory) and — with `best` — the best
+// candidate {index, hits_r, hits_0, n}, on the map's current stream; synchronises.  The arguments have been validated.
+// LIODOM_MAP_STATE_TIMING=1 reports the three parts' kernel times (tools/relocalize_cost.py reads them).
+int map_score(liodom_map* mp, const float* edges, int n_edges, const double* T, int n, int radius, int32_t* hits, int32_t* best) {
+  using namespace liodom_dev;
+  HIP_TRY(hipSetDevice(mp->device));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  MapState st;
+  HIP_TRY(hipMemcpy(&st, mp->m.st, sizeof(st), hipMemcpyDeviceToHost));
+  const MapView& m = mp->m;
+  const int n_cells = std::max(0, std::min(st.n_cells, m.max_cells));
+  const size_t t_bytes = sizeof(double) * 12 * (size_t)n, h_bytes = sizeof(int) * 2 * (size_t)n;
+  int rc = map_ensure_occ(mp, n_cells);
+  if (rc || (rc = map_ensure_batch(mp, t_bytes + h_bytes + sizeof(int) * 4))) return rc;
+  double* d_T = reinterpret_cast<double*>(mp->d_batch);
+  int* d_best = reinterpret_cast<int*>(mp->d_batch + t_bytes);      // the best candidate's record (16 bytes, 16-byte aligned), then
+  int* d_hits = d_best + 4;                                         // the counts [n][2]
+  if (n_edges > 0) HIP_TRY(hipMemcpyAsync(mp->d_in, edges, sizeof(float4) * (size_t)n_edges, hipMemcpyHostToDevice, mp->stream));
+  HIP_TRY(hipMemcpyAsync(d_T, T, t_bytes, hipMemcpyHostToDevice, mp->stream));
+  if (n_cells > 0) {
+    MapStateTimer tm(mp->stream, "liodom_map_score_poses occupancy");
+    const size_t n16 = ((size_t)n_cells * (size_t)m.words + 3) / 4;
+    hipLaunchKernelGGL(k_map_occ_clear, dim3((unsigned)std::min<size_t>(2048, (n16 + 255) / 256)), dim3(256), 0, mp->stream, m, mp->d_occ, mp->occ_cells);
+    hipLaunchKernelGGL(k_map_occ_build, dim3(std::min(16, (m.cell_cap + 255) / 256), std::min(n_cells, 256)), dim3(256), 0, mp->stream, m, mp->d_occ, mp->occ_cells);
+    tm.stop();
+  }
+  {
+    MapStateTimer tm(mp->stream, "liodom_map_score_poses score");
+    hipLaunchKernelGGL(k_map_score_poses, dim3((n + kRelocWaves - 1) / kRelocWaves), dim3(kRelocThreads), 0, mp->stream, m, mp->d_occ, mp->occ_cells, mp->d_in,
+                       n_edges, d_T, n, radius, (float)mp->cfg.resolution, d_hits);
+    tm.stop();
+  }
+  if (best) {
+    MapStateTimer tm(mp->stream, "liodom_map_score_poses best");
+    hipLaunchKernelGGL(k_map_score_best, dim3(1), dim3(kRelocBestThreads), 0, mp->stream, d_hits, n, d_best);
+    tm.stop();
+  }
+  HIP_TRY(hipGetLastError());
+  if (hits) HIP_TRY(hipMemcpyAsync(hits, d_hits, h_bytes, hipMemcpyDeviceToHost, mp->stream));
+  if (best) HIP_TRY(hipMemcpyAsync(best, d_best, sizeof(int) * 4, hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));      // (the staged edges and poses are the caller's memory)
+  return LIODOM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -354,13 +429,8 @@ int liodom_map_get_local_batch(liodom_map_t* mp, const double* T, int n, int cel
   const int cap = (int)cap_per_row;
   int rc = map_ensure_out(mp, (int64_t)n * std::max(cap, 1));
   if (rc) return rc;
-  const size_t t_bytes = sizeof(double) * 12 * (size_t)n, need = t_bytes + sizeof(int) * 2 * (size_t)n;
-  if (mp->batch_bytes < need) {
-    HIP_TRY(hipStreamSynchronize(mp->stream));
-    if (mp->d_batch) { (void)hipFree(mp->d_batch); mp->d_batch = nullptr; mp->batch_bytes = 0; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&mp->d_batch), need));
-    mp->batch_bytes = need;
-  }
+  const size_t t_bytes = sizeof(double) * 12 * (size_t)n;
+  if ((rc = map_ensure_batch(mp, t_bytes + sizeof(int) * 2 * (size_t)n))) return rc;
   double* d_T = reinterpret_cast<double*>(mp->d_batch);
   int* d_n = reinterpret_cast<int*>(mp->d_batch + t_bytes);      // [n] points written, [n] sizes
   HIP_TRY(hipMemcpyAsync(d_T, T, t_bytes, hipMemcpyHostToDevice, mp->stream));
@@ -597,6 +667,44 @@ int liodom_map_merge_state(liodom_map_t* mp, const void* blob, int64_t bytes, in
   HIP_TRY(hipStreamSynchronize(mp->stream));      // the caller's blob must not be read after the call returns
   if (taken) for (int i = 0; i < n_cells; i++) taken[i] = rank[(size_t)i] >= 0 ? 1 : 0;
   if (n_added) *n_added = info.n_taken;
+  return LIODOM_OK;
+}
+
+int liodom_map_score_poses(liodom_map_t* mp, const float* edges_xyzi, int n_edges, const double* T, int n, int radius, int32_t* hits) {
+  int rc = map_score_check(mp, edges_xyzi, n_edges, "liodom_map_score_poses");
+  if (rc) return rc;
+  if (n < 0 || n > liodom_dev::kRelocCandidatesMax || (n > 0 && (!T || !hits)) || (radius != 0 && radius != 1)) {
+    g_last_error = "liodom_map_score_poses: null poses or hits, a count that is negative or above 2^20, or a radius that is not 0 or 1"; return LIODOM_ERR_INVALID_ARG;
+  }
+  if (n == 0) return LIODOM_OK;
+  return map_score(mp, edges_xyzi, n_edges, T, n, radius, hits, nullptr);
+}
+
+void liodom_pose_search_default(liodom_pose_search_t* s) {
+  if (!s) return;
+  std::memset(s, 0, sizeof(*s));
+  s->centre[3] = 1.0;
+  s->step_xy = 0.4; s->step_z = 0.4; s->step_yaw = 0.02;
+  s->radius = 1;
+}
+
+int liodom_map_search_pose(liodom_map_t* mp, const float* edges_xyzi, int n_edges, const liodom_pose_search_t* s, liodom_pose_search_result_t* out,
+                           double* T_out, int32_t* hits_out) {
+  int rc = map_score_check(mp, edges_xyzi, n_edges, "liodom_map_search_pose");
+  if (rc) return rc;
+  if (!s || !out) { g_last_error = "liodom_map_search_pose: null search or result"; return LIODOM_ERR_INVALID_ARG; }
+  const char* why = "";
+  const int64_t n = liodom_dev::reloc_candidate_count(s, &why);
+  if (n <= 0) { g_last_error = std::string("liodom_map_search_pose: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  std::vector<double> T(12 * (size_t)n);
+  liodom_dev::reloc_candidates(s, n, T.data());
+  int32_t best[4] = {0, 0, 0, 0};
+  if ((rc = map_score(mp, edges_xyzi, n_edges, T.data(), (int)n, s->radius, hits_out, best))) return rc;
+  if (best[0] < 0 || best[0] >= n) { g_last_error = "liodom_map_search_pose: inconsistent result"; return LIODOM_ERR_HIP; }
+  out->best_index = best[0]; out->hits_r = best[1]; out->hits_0 = best[2]; out->n_candidates = (int32_t)n;
+  liodom_dev::reloc_candidate_pose(s, best[0], out->pose);
+  std::memcpy(out->T, &T[12 * (size_t)best[0]], sizeof(double) * 12);
+  if (T_out) std::memcpy(T_out, T.data(), sizeof(double) * 12 * (size_t)n);
   return LIODOM_OK;
 }
 

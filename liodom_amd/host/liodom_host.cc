@@ -609,6 +609,23 @@ std::vector<PointCloud> Map::getLocalBatch(const std::vector<std::array<double, 
   return out;
 }
 
+std::vector<int32_t> Map::scorePoses(const PointCloud& edges, const std::vector<std::array<double, 12>>& poses, int radius) {
+  const int n = (int)poses.size();
+  std::vector<int32_t> hits(2 * (size_t)n, 0);
+  std::vector<double> T(12 * (size_t)n);
+  for (int i = 0; i < n; i++) std::memcpy(&T[12 * (size_t)i], poses[(size_t)i].data(), sizeof(double) * 12);
+  check(liodom_map_score_poses(m_, reinterpret_cast<const float*>(edges.points.data()), (int)edges.points.size(), T.data(), n, radius, hits.data()),
+        "liodom_map_score_poses");
+  return hits;
+}
+
+liodom_pose_search_result_t Map::searchPose(const PointCloud& edges, const liodom_pose_search_t& search) {
+  liodom_pose_search_result_t out{};
+  check(liodom_map_search_pose(m_, reinterpret_cast<const float*>(edges.points.data()), (int)edges.points.size(), &search, &out, nullptr, nullptr),
+        "liodom_map_search_pose");
+  return out;
+}
+
 void LaserOdometer::attachMapper(Map* map, int cells_xy, int cells_z) {
   check(liodom_attach_mapper(eng_->handle(), 0, map ? map->handle() : nullptr, cells_xy, cells_z), "liodom_attach_mapper");
 }

@@ -235,6 +235,12 @@ class Map {
   // yet; returns one taken flag per blob cell.  Both work on an attached map too.
   std::vector<uint8_t> evict(const std::array<double, 12>& pose, int keep_xy, int keep_z, int* n_evicted = nullptr);
   std::vector<int32_t> mergeState(const std::vector<uint8_t>& blob);
+  // Relocalising (liodom_map_score_poses / liodom_map_search_pose; no counterpart in the reference).  scorePoses: hits_r, hits_0 of
+  // each candidate pose for the edge cloud against the map's leaf occupancy, 2 ints per pose.  searchPose: the best candidate of the
+  // grid `search` describes (liodom_pose_search_default fills one in); its pose is what LaserOdometer::seed takes.  Both only read
+  // the map and work on an attached one between scans.
+  std::vector<int32_t> scorePoses(const PointCloud& edges, const std::vector<std::array<double, 12>>& poses, int radius = 1);
+  liodom_pose_search_result_t searchPose(const PointCloud& edges, const liodom_pose_search_t& search);
   int numCells();
   liodom_map_t* handle() const { return m_; }
   double xySize() const { return xy_; }
