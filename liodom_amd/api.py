@@ -13,7 +13,8 @@ _BUILD_INFO = {"rebuilt": None, "source_hash": None}
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kernels.h", "kernels_extract.h", "kernels_sync.h",
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
                                                   "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
-                                                  "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h")] + [
+                                                  "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
+                                                  "liodom_sizes.h", "handle_plan.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",

@@ -15,9 +15,8 @@
 //                 every ring is contiguous for k_ring_extract (no H-fold id scan, no strided
 //                 gathers: 8x less fabric traffic than the first version, profiles/r01_c_*).
 // =============================================================================================
-constexpr int kTilePts = 2048;
+// (kTilePts = 2048, kTileChunks = 32: liodom_sizes.h)
 constexpr int kTileThreads = 512;
-constexpr int kTileChunks = kTilePts / 64;   // 32
 
 // isValidPoint + ring id of one point (feature_extractor.cc:84-102,115-175); 0xFF: dropped.
 __device__ __forceinline__ unsigned char classify_point(const DevView& v, const float4& pt, int i, int H, int height, int width) {
@@ -93,21 +92,7 @@ __global__ __launch_bounds__(kTileThreads) void k_classify(DevView v, int s0, co
 
 // Row stride of the (chunk, ring) tables in LDS: odd, so that the per-ring prefix pass (32 lanes =
 // 32 chunks of one ring) does not land all its 8-byte reads on one bank pair.
-__host__ __device__ __forceinline__ int ring_scatter_stride(int H) { return H | 1; }
-// LDS: phase A = lane masks [32][Hp] u64 + chunk prefixes [32][Hp] u16; phase B reuses the same
-// bytes as the staging tile {float4 point, int dst, int src} x 2048; then rbase / lofs / wtot.
-__host__ __device__ __forceinline__ size_t ring_scatter_stage_bytes(int H) {
-  const int Hp = ring_scatter_stride(H);
-  const size_t a = (size_t)kTileChunks * Hp * 8 + (size_t)((kTileChunks * Hp * 2 + 15) & ~15);
-  const size_t b = (size_t)kTilePts * 24;
-  return a > b ? a : b;
-}
-__host__ __device__ __forceinline__ size_t ring_scatter_lds_bytes(int H) {
-  return ring_scatter_stage_bytes(H) + (size_t)(2 * H + 2 * 16) * 4;
-}
-__host__ __device__ __forceinline__ size_t ring_split_lb_lds_bytes(int H) {      // + rlim [H]
-  return ring_scatter_stage_bytes(H) + (size_t)(3 * H + 16) * 4;
-}
+// (ring_scatter_stride and the LDS sizes ring_scatter_lds_bytes / ring_split_lb_lds_bytes: liodom_sizes.h)
 
 // staging-slot swizzles of k_ring_scatter (bijections on [0, 2048)): 16-byte elements have 16 bank groups (low 4 bits of
 // the slot), 4-byte elements 64 banks (low 6 bits); the XOR term is constant over an aligned run of 32 / 64 slots
@@ -749,24 +734,7 @@ __global__ __launch_bounds__(kRowThreads) void k_row_compact(DevView v, int s0, 
 // than 64 regions, rings longer than kGapBitsCap) take the generic path: curvature and marks in global
 // scratch, regions walked in order by one wave — any ring length, no capacity flag.
 // =============================================================================================
-constexpr int kExLPR = 16;               // lanes per region (one DPP row)
-constexpr int kExIPL = 16;               // items per lane -> regions of up to 256 items ...
-constexpr int kExIPLBig = 24;            // ... or 384 (the last region takes the remainder of the split: Ouster 2048 / 8 -> 260); the host
-                                         // picks the instance from the expected ring width, longer regions take the generic path
-constexpr int kGapBitsCap = 16384;       // points per ring covered by the LDS continuity bits (2 KB)
-constexpr int kExMaxRegions = 64;
-
-__host__ __device__ __forceinline__ int ring_extract_threads(int regions) {
-  const int waves = (regions + 3) / 4;
-  return 64 * (waves < 1 ? 1 : (waves > 16 ? 16 : waves));
-}
-__host__ __device__ __forceinline__ size_t ring_extract_lds_bytes(int slots, int regions) {
-  size_t b = (size_t)(kGapBitsCap / 32 + 4) * 4;          // continuity bits + pad words
-  b += (size_t)slots * 4;                                 // pick_idx
-  b += (size_t)((slots + 15) / 16 * 16);                  // pick_nfnb
-  b += (size_t)regions * 4 + 2 * kExMaxRegions * 4 + 64;  // region_cnt, masks, flags
-  return (b + 15) / 16 * 16;
-}
+// (kExLPR, kExIPL, kExIPLBig, kGapBitsCap, kExMaxRegions, ring_extract_threads, ring_extract_lds_bytes: liodom_sizes.h)
 
 __device__ __forceinline__ unsigned int row_max_u32(unsigned int v) {
   unsigned int o;

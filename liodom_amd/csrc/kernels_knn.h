@@ -119,7 +119,7 @@ template <bool kDeep> struct KnnTune {
   static constexpr bool kHoistLoads = kDeep;
   static constexpr bool kCursor = kDeep ? false : LIODOM_TUNE_B_CURSOR;      // flat list: per-lane cursor instead of the binary search
 };
-constexpr int kKnnGridDiv = 2;         // k_knn grid = half of the query blocks the edge capacity allows: a workgroup takes block b and, if the scan has that many edges, b + grid
+// (kKnnGridDiv = 2, liodom_sizes.h: a workgroup takes block b and, if the scan has that many edges, b + grid)
 // Candidate distance with packed FP32 arithmetic (experiment LIODOM_KNN_PK, round 5): dx and dy of one candidate share a
 // v_pk_add_f32 and a v_pk_mul_f32 (x and y of a loaded float4 are an aligned register pair); the same operations in the same
 // order as sqdist_f, each rounded on its own: bit-identical.

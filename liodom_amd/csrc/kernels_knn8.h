@@ -41,12 +41,7 @@
 // (instrumented builds, LIODOM_DEBUG_CLOCKS bit 8: shader cycles per phase of k_knn8, summed over the first lanes of the working waves of
 //  all streams — dbg_clk[64 + 8 * pass + phase]; tools/gpu_debug.py knn8phases)
 #define KNN8_PHASE(i) do { if (kInstrument && (v.debug & 256) && (threadIdx.x & 63) == 0) { const unsigned long long t_now = __builtin_readcyclecounter(); atomicAdd(&v.dbg_clk[64 + 8 * outer_it + (i)], t_now - t_ph); t_ph = t_now; } } while (0)
-constexpr int kG8 = 8;                    // lanes per query
-#ifndef LIODOM_KNN8_THREADS
-#define LIODOM_KNN8_THREADS 256
-#endif
-constexpr int kKnn8Threads = LIODOM_KNN8_THREADS;      // 4 waves = 32 queries per workgroup (512 threads: the sort below balances better, but the workgroups pack worse — 373 us against 334 for a first pass at 256 streams)
-constexpr int kKnn8Queries = kKnn8Threads / kG8;
+// (kG8 = 8 lanes per query, kKnn8Threads, kKnn8Queries: liodom_sizes.h)
 constexpr int kKnn8Save = 3 * kG8;        // candidates kept per query for the second pass
 
 // ---- 8-lane group primitives (every lane of the group active) ----

@@ -26,11 +26,8 @@
 // =============================================================================================
 // Indices of the edges with an accepted correspondence, in edge order (deterministic), built once
 // per solve in LDS so that every evaluation runs over C dense items instead of E sparse ones.
-// dynamic LDS of k_lm_solve: the index list (the reduction's per-wave sums, sh_wsum, are static: 1 KiB)
+// (dynamic LDS of k_lm_solve, lm_lds_bytes: liodom_sizes.h)
 constexpr int kLmWaves = kLmThreads / 64;
-__host__ __device__ __forceinline__ size_t lm_lds_bytes(int edge_cap) {
-  return (size_t)((edge_cap + 3) & ~3) * sizeof(int);
-}
 
 
 // Compaction of the accepted correspondences from the validity bytes k_knn left (bit q of byte b = query q of

@@ -709,11 +709,9 @@ __device__ __forceinline__ KeyRun wave_key_runs(bool valid, unsigned long long k
   return r;
 }
 
-constexpr int kLdsSlots = 8192;
-constexpr int kLdsCellsMax = 6144;
+// (kLdsSlots = 8192, kLdsCellsMax = 6144, hash_build_lds_bytes: liodom_sizes.h)
 constexpr int kBuildThreads = 1024;
 constexpr int kBuildUnroll = 4;
-__host__ __device__ __forceinline__ size_t hash_build_lds_bytes() { return (size_t)kLdsSlots * 16 + 64; }
 
 // (jc: optional frame cursor of a thread whose m only grows: replaces the binary search by a step)
 __device__ __forceinline__ float4 window_point_produce(const DevView& v, int s, const StreamState& st, int eb,
@@ -809,12 +807,7 @@ __device__ __forceinline__ void hash_build_global(const DevView& v, int s, Strea
 //  a pole coming into range —, and three frames arrive between rebuilds: with a quarter of the population / 8 / 16 a cell ran out of
 //  room in every period, with this rule in none of 24; the point array then holds ~195 000 places per stream for 36 600 points.)
 __host__ __device__ __forceinline__ int hash_cell_slack(unsigned int cnt, int slack_min) { return cnt ? ((int)cnt > slack_min ? (int)cnt : slack_min) : 0; }
-#ifndef LIODOM_HB_PERIOD
-#define LIODOM_HB_PERIOD 4
-#endif
-constexpr int kHbPeriod = LIODOM_HB_PERIOD;       // scans between two rebuilds from the whole window (<= 8: hb_base)
-constexpr int kHbNewRoom = 96;     // room of a cell that k_hash_append creates (DevView::hb_new_room; kHbSlackMin = 32: hb_slack_min)
-constexpr int kHbSlackMin = 32;
+// (kHbPeriod, kHbNewRoom, kHbSlackMin: liodom_sizes.h)
 
 // =============================================================================================
 // k_hash_append (lock-step batches, round 6): the reference appends one frame to the window and drops the oldest

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "liodom_kernels.h"
+#include "handle_plan.h"
 
 using namespace liodom_dev;
 
@@ -59,7 +60,8 @@ struct liodom_handle {
   }
   liodom_params_t params;
   liodom_config_t config;
-  DevView v{};
+  HandlePlan plan;                   // what liodom_create decided: code paths, capacities (handle_plan.h); safe mode is the only later change
+  DevView v{};                       // its scalar members are the plan's, written by plan_to_view alone
   DevView* d_view = nullptr;         // device copy: kernels take a pointer (8-byte kernarg)
   // Two sides, as in the reference's liodom_node (src/liodom_node.cc:89-91: one FeatureExtractor thread,
   // one LaserOdometer thread).  The EXTRACTION side owns stream_x, the ring-split scratch, stage_in and
@@ -71,7 +73,6 @@ struct liodom_handle {
   hipStream_t stream = nullptr;      // odometry side
   hipStream_t stream_k = nullptr;    // overlapped second kNN pass of a scan (kernels_sync.h "Overlapped second kNN pass"): beside the first solve
   bool counted_live = false;         // this handle is part of g_live_handles
-  bool ov_ok = false;                // the handle qualifies for it (one stream, streamed rebuild, the pass leaves 2/3 of the wave slots free)
   unsigned int ov_seq = 0;           // launch sequence number its flags carry
   hipEvent_t ev_ov = nullptr;        // recorded on the odometry stream in front of the first overlapped scan after scans that were not
   bool stream_c_shared = false;      // stream_c is stream_k
@@ -81,9 +82,6 @@ struct liodom_handle {
   // solving workgroups alone — on `stream`; the first solve's launch is resident beside the first pass.
   double replay_enq_ns = 0.0, replay_wait_ns = 0.0;      // depth-1 resident replay: host time per scan spent enqueueing / waiting for the previous pose
   long long replay_timed = 0;
-  bool chain_ok = false;             // the handle qualifies (one stream, streamed rebuild, flags, no IMU override; the passes' waiting workgroups
-                                     // may take up to half of the wave slots: the rebuild's workgroups are light there and the solve is resident
-                                     // before the second pass is dispatched; LIODOM_CHAIN=0 switches it off)
   bool chain_prev = false;           // the previous scan was enqueued in chain mode
   unsigned int chain_count = 0;      // first-pass workgroups launched in chain mode since the last reset (what knn_done0 counts up to)
   int verdict_scan = -1;             // scans completed when the host last collected stream 0's pose, and whether that scan's speculative
@@ -132,11 +130,7 @@ struct liodom_handle {
   hipEvent_t ev_polpin[kEdgePipeBufs] = {nullptr, nullptr, nullptr};
   bool ev_polpin_valid[kEdgePipeBufs] = {false, false, false};
   int pol_pin_next = 0;
-  bool safe_mode = false;            // no in-kernel waits at all: events between the streams, one workgroup per solve, three-kernel hash rebuild
-  bool ring_split_lb = false;        // lock-step batches: k_ring_split_lb (one pass, rings at a fixed pitch, predecessors' counts summed as they appear); LIODOM_RING_SPLIT_LB=0: k_classify + k_ring_scatter
   unsigned int lb_tag = 0;           // launch tag its count words carry
-  bool ring_split = true;            // ring split in one pass (k_ring_split) where every workgroup of the launch is resident at once; LIODOM_RING_SPLIT=0: always k_classify + k_ring_scatter
-  int ring_split_max_wgs = 0;        // ... i.e. launches of at most this many workgroups (liodom_create: occupancy of k_ring_split x CUs, with headroom for the odometry chain's kernels)
   bool streams_concurrent = true;    // liodom_create's probe: kernels of two streams of this handle ran side by side
   std::atomic<bool> pipe_active{false};        // scans went through the pipeline edge buffers by ticket since the last drain
   std::atomic<bool> replay_live{false};        // scans went through them by the pipelined replay since the last drain (their odometries may not have been collected)
@@ -148,8 +142,6 @@ struct liodom_handle {
   std::vector<int> last_eb;          // per stream: edge buffer of the stream's most recent scan that entered odometry (inspection)
   hipEvent_t pose_event = nullptr;
   int S = 1, H = 0, P = 0;
-  bool lockstep = false;             // n_streams >= 16: a lock-step batch (throughput-bound; picks the hash build, the kNN kernels, events between the streams)
-  size_t ring_lds_bytes = 0;
   // staging
   float4* stage_in = nullptr;        // [S][max_points]  (host-provided scans / edges)
   float4* resident = nullptr;        // [S][n_slots][max_points]
@@ -176,13 +168,7 @@ struct liodom_handle {
   std::vector<liodom_map*> read_maps; // distinct maps with readers; a map's tag is its index + 1 (freed places are null and taken again)
   int4* reader_sel = nullptr;         // [S] device: {tag of the map the stream reads (0: none), cells_xy, cells_z, 0}
   int n_readers = 0;                  // streams with a reader
-  bool map_rows = true;               // readers go through k_map_local_rows; LIODOM_MAP_ROWS=0: the two launches of liodom_map_get_local per stream (equality test, cost tool)
   std::vector<int> hb_since;    // hash_incr, per stream: scans since the stream's last k_hash_build (-1: none yet)
-  int knn8_grid = 1;            // k_knn8 workgroups per stream (each walks the blocks b, b + grid, ... of 32 queries)
-  bool knn8 = false;            // lock-step batches: k_knn8 (eight lanes per query) instead of k_knn<128>; LIODOM_KNN8=0 keeps the latter
-  bool lds_hash_build = false;  // k_hash_build (one workgroup per stream, LDS) instead of the 3 global-atomic kernels
-  bool use_flags = false;       // pipelined replay: dependencies between the two streams through flags in device memory instead of events
-  bool flag_gate = false;       // ... polled by a one-wave gate launch in front of the scan's first k_knn launch instead of by that launch itself
   std::vector<EventPair> ev_pool;
   size_t ev_used = 0;
   double k_ms[LIODOM_NUM_KERNELS] = {0};
@@ -276,13 +262,13 @@ int launch_extract(liodom_handle* h, hipStream_t q, int eb, int s0, int count, c
     ProfScope ps(h, KID_RING_SCATTER, q);
     by_rows([&](auto L) { hipLaunchKernelGGL((k_row_compact<decltype(L)::value>), dim3(h->H, count), dim3(kRowThreads), 0, q, v, s0, in, in_stride, n, height, width); });
   } else {
-    if (h->ring_split_lb && !((long long)tiles * count <= h->ring_split_max_wgs && h->ring_split)) {
+    if (h->plan.ring_split_lb && !((long long)tiles * count <= h->plan.ring_split_max_wgs && h->plan.ring_split)) {
       // lock-step batches: one pass, rings at a fixed pitch, tiles sum their predecessors' counts (booked as the scatter)
       ProfScope ps(h, KID_RING_SCATTER, q);
       if (++h->lb_tag == 0u) h->lb_tag = 1u;
       by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split_lb<decltype(L)::value>), dim3(tiles * count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles, h->lb_tag); });
       by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split_fix<decltype(L)::value>), dim3(1, count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles); });
-    } else if (h->ring_split && (long long)tiles * count <= h->ring_split_max_wgs) {      // (every workgroup resident at once: k_ring_split waits inside the launch)
+    } else if (h->plan.ring_split && (long long)tiles * count <= h->plan.ring_split_max_wgs) {      // (every workgroup resident at once: k_ring_split waits inside the launch)
       // one pass: classification and scatter in one kernel (booked as the scatter)
       ProfScope ps(h, KID_RING_SCATTER, q);
       by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split<decltype(L)::value>), dim3(tiles, count), dim3(kTileThreads), ring_scatter_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width); });
@@ -306,11 +292,11 @@ int launch_extract(liodom_handle* h, hipStream_t q, int eb, int s0, int count, c
     const bool big = total - sector * (v.scan_regions - 1) > kExLPR * kExIPL;
     const dim3 grid(h->H, count), block(ext);
     if (ext <= 256) {
-      if (big) by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<256, kExIPLBig, decltype(L)::value>), grid, block, h->ring_lds_bytes, q, v, s0); });
-      else by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<256, kExIPL, decltype(L)::value>), grid, block, h->ring_lds_bytes, q, v, s0); });
+      if (big) by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<256, kExIPLBig, decltype(L)::value>), grid, block, h->plan.ring_lds_bytes, q, v, s0); });
+      else by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<256, kExIPL, decltype(L)::value>), grid, block, h->plan.ring_lds_bytes, q, v, s0); });
     } else {
-      if (big) by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<1024, kExIPLBig, decltype(L)::value>), grid, block, h->ring_lds_bytes, q, v, s0); });
-      else by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<1024, kExIPL, decltype(L)::value>), grid, block, h->ring_lds_bytes, q, v, s0); });
+      if (big) by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<1024, kExIPLBig, decltype(L)::value>), grid, block, h->plan.ring_lds_bytes, q, v, s0); });
+      else by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<1024, kExIPL, decltype(L)::value>), grid, block, h->plan.ring_lds_bytes, q, v, s0); });
     }
   }
   {
@@ -340,17 +326,13 @@ int launch_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wa
 // The handle's part of the decision to overlap the second kNN pass (ov) and to run a scan in chain mode (chain): the streamed
 // rebuild, flags between the streams, and the GPU to this handle alone — its waiting workgroups and those of a second handle of
 // the process could end up behind each other in a shared hardware queue.  enqueue_odometry adds the scan's own conditions.
-struct OverlapModes { bool ov, chain; };
-OverlapModes overlap_modes(const liodom_handle* h) {
-  const bool base = h->v.early_rebuild && h->use_flags && g_live_handles.load() <= 1;
-  return {base && h->ov_ok, base && h->chain_ok && !h->flag_gate};
-}
+OverlapModes overlap_modes(const liodom_handle* h) { return plan_overlap_modes(h->plan, g_live_handles.load() <= 1); }
 
 int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges, unsigned int signal_odo, const int32_t* list) {
   const DevView& v = h->v;
   auto stream_at = [&](int i) { return list ? (int)list[i] : s0 + i; };
   auto by_rows = [&](auto launch) { if (s0 < 0) launch(std::true_type{}); else launch(std::false_type{}); };      // (as in launch_extract)
-  const bool knn_small = h->lockstep;           // 4 queries per workgroup, else 8
+  const bool knn_small = h->plan.lockstep;           // 4 queries per workgroup, else 8
   if (v.use_imu) {
     ProfScope ps(h, KID_OTHER);
     by_rows([&](auto L) { hipLaunchKernelGGL((k_imu_override<decltype(L)::value>), dim3(cdiv(count, 64)), dim3(64), 0, h->stream, v, s0, count); });
@@ -449,9 +431,9 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
     {
       ProfScope ps(h, KID_KNN);
       const int kx = v.knn_grid + ((early && it == 1 && !seq_k) ? kRebuildAuxBlocks : 0);     // it 1: + ALLOC (overlapped pass: k_rebuild_alloc below)
-      if (knn_small && h->knn8) {
+      if (knn_small && h->plan.knn8) {
         // lock-step batches: eight lanes per query (kernels_knn8.h); the workgroups of a stream walk its blocks of 32 queries
-        const dim3 g8(h->knn8_grid, count);
+        const dim3 g8(h->plan.knn8_grid, count);
         if (it == 0) by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8<0, decltype(L)::value>), g8, dim3(kKnn8Threads), 0, h->stream, v, s0, eb); });
         else by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8<1, decltype(L)::value>), g8, dim3(kKnn8Threads), 0, h->stream, v, s0, eb); });
         by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8_exact<decltype(L)::value>), dim3(kKnn8ExactBlocks, count), dim3(kKnn8Threads), 0, h->stream, v, s0, it, eb); });      // (the ~1 % of the queries the fast path cannot certify)
@@ -518,7 +500,7 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
         for (int i = 0; i < count; i++) {
           const int s = stream_at(i);
           if (h->readers[s] != mp) continue;
-          if (h->map_rows && map_rows_fit(mp, h->reader_xy[s], h->reader_z[s])) { rows = true; continue; }
+          if (h->plan.map_rows && map_rows_fit(mp, h->reader_xy[s], h->reader_z[s])) { rows = true; continue; }
           StreamState* st = v.state + s;
           const int rc = map_enqueue_local(mp, st->final_odom, h->reader_xy[s], h->reader_z[s], v.recv_pts + (size_t)s * v.recv_cap, v.recv_cap, &st->n_recv, h->stream, 1);
           if (rc) return rc;
@@ -537,7 +519,7 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
   }
   if (early) {
     // (nothing: the next cell hash is complete when the finalising solve launch ends)
-  } else if (h->lds_hash_build) {
+  } else if (h->plan.lds_hash_build) {
     ProfScope ps(h, KID_HASH_BUILD);        // window append + LDS-built cell hash, one workgroup per stream
     // (hash_incr: the new frame is appended to the table of the last rebuild; k_hash_build only works when that says so)
     // (hash_incr: k_hash_build every kHbPeriod-th scan, k_hash_append — the new frame into the cells of the last rebuild — in between)
@@ -624,13 +606,6 @@ struct SideLocks {
 };
 hipStream_t extract_queue(liodom_handle* h) { return h->profiling ? h->stream : h->stream_x; }
 
-int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-int env_int(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
-
 // The plain (non-pipelined) entry points run everything on h->stream with edge buffer 0; make
 // sure no extraction issued ahead by the pipelined replay is still in flight.
 int tickets_idle(liodom_handle* h) {      // the plain entry points use pipeline edge buffer 0 themselves
@@ -656,11 +631,11 @@ int drain_pipeline(liodom_handle* h) {
 int enqueue_pipeline_odometry(liodom_handle* h, int eb, unsigned int wait_seq, int s0 = 0, int count = -1, const int32_t* list = nullptr) {
   int rc;
   if (count < 0) count = h->S;
-  if (h->use_flags) {
+  if (h->plan.use_flags) {
     // no cross-stream events (they cost ~11 us of idle odometry stream per scan, with the host far ahead as well): the
     // first kNN launch waits for the extraction's flag and signals that the previous odometry has completed
     const unsigned int m = ++h->odo_seq == 0 ? ++h->odo_seq : h->odo_seq;
-    if (h->flag_gate) {
+    if (h->plan.flag_gate) {
       if (s0 < 0) hipLaunchKernelGGL(k_pipe_gate<true>, dim3(1), dim3(64), 0, h->stream, h->v, s0, eb, wait_seq, m - 1u);
       else hipLaunchKernelGGL(k_pipe_gate<>, dim3(1), dim3(64), 0, h->stream, h->v, s0, eb, wait_seq, m - 1u);
       rc = launch_odometry(h, eb, s0, count, 0u, 0u, list);
@@ -687,7 +662,7 @@ int issue_extract(liodom_handle* h, int slot, int eb, int n, int height, int wid
   // durations are not inflated by kernels of the other stream sharing the GPU
   hipStream_t q = extract_queue(h);
   const float4* in = h->resident + (size_t)slot * h->S * (size_t)h->v.max_points;
-  if (h->use_flags) {
+  if (h->plan.use_flags) {
     // dependencies through flags in device memory (pipe_wait): the buffer's last reader must have
     // completed before k_compact_edges rewrites it; the last workgroup of k_compact_edges sets the flag of this extraction
     h->eb_seq[eb] = ++h->ext_seq;
@@ -702,25 +677,11 @@ int issue_extract(liodom_handle* h, int slot, int eb, int n, int height, int wid
   return LIODOM_OK;
 }
 
-// Safe mode: every dependency that a kernel of this handle would wait for INSIDE a kernel is replaced by one the runtime orders.
-// In-kernel waits need the producer to run beside the waiter; a GPU saturated by another process (or a tool that serialises
-// kernels) breaks that, the bounded waits give up (LIODOM_STATUS_PIPE_TIMEOUT / LM_SYNC_TIMEOUT) and the scan is lost.  Afterwards:
-//   stream dependencies   flags polled by kernels            -> hipEvent pairs
-//   second kNN pass       beside the first solve, polling     -> behind it in stream order
-//   pose solve            G workgroups exchanging partial sums in the launch -> one workgroup (sums in a different order: poses
-//                         agree with the G-workgroup solve to rounding, not to the bit)
-//   ring split            one pass whose tiles wait for each other's histograms -> k_classify + k_ring_scatter (bit-identical)
-//   hash rebuild          workgroups inside the solve launches waiting for its pose -> k_window_insert / k_hash_alloc /
-//                         k_hash_scatter behind the solve (bit-identical: test_early_rebuild_equals_three_kernel_rebuild)
-// Entered by liodom_reset() after a timeout, or at creation with LIODOM_SAFE_MODE=1.
+// Safe mode (plan_enter_safe_mode, handle_plan.h) after an in-kernel wait gave up: the plan changes, the view follows; every
+// buffer stays as allocated.
 void enter_safe_mode(liodom_handle* h) {
-  h->safe_mode = true;
-  h->use_flags = false;
-  h->chain_ok = false;
-  h->v.lm_groups = 1;
-  h->v.early_rebuild = 0;      // (the second table, the padding and the overflow list stay allocated and unused)
-  h->ring_split = false;       // k_ring_split's workgroups wait for each other inside the launch: k_classify + k_ring_scatter instead
-  h->ring_split_lb = false;    // (k_ring_split_lb's tiles wait for their predecessors' counts; the pitched buffers stay allocated)
+  plan_enter_safe_mode(&h->plan);
+  plan_to_view(h->plan, &h->v);
 }
 
 int reset_state(liodom_handle* h) {
@@ -780,6 +741,16 @@ int reset_state(liodom_handle* h) {
   return LIODOM_OK;
 }
 
+// A kernel's dynamic LDS above the 48 KiB every kernel may have needs the function attribute (liodom_create).
+struct LdsNeed {
+  const void* fn;
+  size_t bytes;
+  bool always;          // set the attribute below 48 KiB as well
+  bool list;            // a list instance (subset steps, stream_of): handles with more than one stream only
+  const bool* when;     // null, or the path the kernel belongs to: skipped while it is off
+  bool* clears;         // null: a failure fails the create; else the path a failure switches off
+};
+
 }  // namespace
 
 extern "C" {
@@ -818,12 +789,8 @@ void liodom_config_default(liodom_config_t* c) {
 int liodom_create(const liodom_params_t* params, const liodom_config_t* config, liodom_handle_t** out) {
   if (!params || !config || !out) return LIODOM_ERR_INVALID_ARG;
   *out = nullptr;
-  if (params->scan_lines < 1 || params->scan_lines > 254 || params->scan_regions < 1 ||
-      params->edges_per_region < 0 || params->local_map_size < 1 || params->local_map_size > (uint64_t)kMaxFrames ||
-      config->n_streams < 1 || config->max_points < 1 || !(params->max_range > params->min_range)) {
-    g_last_error = "liodom_create: parameter out of range";
-    return LIODOM_ERR_INVALID_ARG;
-  }
+  const char* why = nullptr;
+  if (int rc = plan_check_params(params, config, &why)) { g_last_error = why; return rc; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     g_last_error = "no HIP device available (libliodom_hip has no CPU fallback)";
@@ -831,11 +798,31 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   }
   if (config->device < 0 || config->device >= ndev) { g_last_error = "bad device ordinal"; return LIODOM_ERR_INVALID_ARG; }
   HIP_TRY(hipSetDevice(config->device));
+  const int H = params->scan_lines;
+  // what the device contributes to the plan
+  HandleCaps caps;
+  caps.instrumented = kInstrument;
+  (void)hipDeviceGetAttribute(&caps.cus, hipDeviceAttributeMultiprocessorCount, config->device);
+  {
+    const size_t lds = ring_scatter_lds_bytes(H);
+    const void* fn = reinterpret_cast<const void*>(&k_ring_split<>);
+    if ((lds > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&caps.ring_split_wgs_per_cu, fn, kTileThreads, lds) != hipSuccess) {
+      (void)hipGetLastError(); caps.ring_split_wgs_per_cu = 0;
+    }
+  }
+  HandlePlan plan;
+  if (int rc = plan_handle(params, config, caps, read_handle_env(), &plan, &why)) { g_last_error = why; return rc; }
+
   liodom_handle* h = new liodom_handle();
   h->params = *params;
   h->config = *config;
-  h->S = config->n_streams; h->H = params->scan_lines; h->P = (int)params->local_map_size;
-  h->lockstep = config->n_streams >= 16;
+  h->S = config->n_streams; h->H = H; h->P = (int)params->local_map_size;
+  h->plan = plan;
+  HandlePlan& p = h->plan;
+  DevView& v = h->v;
+  plan_to_view(p, &v);
+  iso_identity(v.laser_to_base);
   int rc = LIODOM_OK;
   auto fail = [&](int code) { liodom_destroy(h); return code; };
   // The odometry chain is the critical path; the extraction of the next scan only has to finish
@@ -848,210 +835,77 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
   auto make_stream = [&](hipStream_t* st, int prio) {
     return use_prio ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio) : hipStreamCreateWithFlags(st, hipStreamNonBlocking);
   };
-  if (make_stream(&h->stream, prio_greatest) != hipSuccess) { g_last_error = "hipStreamCreate failed"; return fail(LIODOM_ERR_HIP); }
-  if (hipEventCreateWithFlags(&h->ev_ov, hipEventDisableTiming) != hipSuccess) { g_last_error = "hipEventCreate failed"; return fail(LIODOM_ERR_HIP); }
-  if (hipEventCreateWithFlags(&h->pose_event, hipEventDisableTiming) != hipSuccess) { g_last_error = "hipEventCreate failed"; return fail(LIODOM_ERR_HIP); }
+  auto make_event = [&](hipEvent_t* ev) { return hipEventCreateWithFlags(ev, hipEventDisableTiming); };
   // (extraction: one level below the odometry stream, not the lowest: kernels of the odometry stream may wait in-kernel for it)
   const int prio_x = (prio_least - prio_greatest >= 2) ? prio_greatest + 1 : prio_least;
-  if (make_stream(&h->stream_x, prio_x) != hipSuccess) { g_last_error = "hipStreamCreate failed"; return fail(LIODOM_ERR_HIP); }
-  for (int b = 0; b < kEdgePipeBufs; b++) {
-    if (hipEventCreateWithFlags(&h->ev_edges[b], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_free[b], hipEventDisableTiming) != hipSuccess) { g_last_error = "hipEventCreate failed"; return fail(LIODOM_ERR_HIP); }
-  }
-
-  DevView& v = h->v;
-  v.min_range = params->min_range; v.max_range = params->max_range;
-  v.lidar_type = params->lidar_type; v.scan_lines = params->scan_lines;
-  v.scan_regions = params->scan_regions; v.edges_per_region = params->edges_per_region;
-  v.min_points_per_scan = (long long)params->min_points_per_scan;
-  v.prev_frames = h->P;
-  v.apply_on_ftol = config->lm_apply_step_on_ftol;
-  v.rotation_mode = config->pose_rotation_mode != 0 ? 1 : 0;
-  v.filter_local_map = (params->filter_local_map && !params->mapping) ? 1 : 0;   // laser_odometry.cc:286
-  // auto: several CUs per solve pay off only when one CU would spend >> the ~4.5 us in-launch
-  // exchange on an evaluation (measured: ~2000 edges -> no gain; Ouster-128 shape -> yes)
-  // Measured on MI355X (headline shape): one stream rebuilds its hash in 28 us with the three
-  // global-atomic kernels (many workgroups) but needs 86 us as a single LDS workgroup; 64 lock-step
-  // streams need 247 us (L2-atomic bound) against 103 us with one LDS workgroup each.
-  h->lds_hash_build = h->lockstep;
-  {
-    // Flags instead of events between the extraction and the odometry stream: the first kNN launch of a scan polls the
-    // extraction's flag in every workgroup, so all its workgroups must fit on the GPU with ample room left for the
-    // extraction kernels they may be waiting for (512-thread workgroups): one stream only, and at most 12 of the 24
-    // wave slots per CU the kernel's 74 VGPRs allow — HDL-64 (2 816 waves of 3 072) qualifies, Ouster-128 (5 632) does
-    // not: with 24 it starved the extraction in the non-pipelined replay until the bounded waits gave up.
-    // (Lock-step batches are throughput-bound: 11 us per multi-millisecond step do not matter there.)
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, config->device);
-    const int ecap = round_up(std::max(1, params->scan_lines * params->scan_regions * (params->edges_per_region + 1)), 64);
-    h->use_flags = !h->lockstep;
-    h->flag_gate = !(config->n_streams == 1 && cdiv(cdiv(ecap, 8), 2) * 4 <= cus * 12);     // (larger launches: a one-wave gate launch polls instead)
-    // kernels of different streams never run side by side under these: the in-kernel waits could only time out
-    for (const char* name : {"AMD_SERIALIZE_KERNEL", "HIP_LAUNCH_BLOCKING", "ROCPROFILER_PMC", "ROCPROF_COUNTERS"}) {
-      const char* e = std::getenv(name);
-      if (e && e[0] && std::strcmp(e, "0") != 0) h->use_flags = false;
-    }
-    if (env_int("LIODOM_PIPE_FLAGS", 1) == 0) h->use_flags = false;
-  }
-  h->map_rows = env_int("LIODOM_MAP_ROWS", 1) != 0;
-  if (const char* e = std::getenv("LIODOM_HASH_BUILD")) h->lds_hash_build = std::strcmp(e, "global") != 0;
-  v.lds_cells_max = std::max(1, std::min(kLdsCellsMax, env_int("LIODOM_LDS_CELLS_MAX", kLdsCellsMax)));
-  // solve split over G workgroups (partial sums exchanged inside the launch, ~3 us per evaluation under load): pays once an
-  // evaluation is long enough.  Measured (scans/s, G = 1 / 4 / 8): HDL-64 10.1k / 10.35k / 10.34k, Ouster-128 7.3k / 8.1k / 8.3k,
-  // VLP-16 12.2k / 12.1k / -.
-  {
-    const int ecap = params->scan_lines * params->scan_regions * (params->edges_per_region + 1);
-    // (round 3, A/B on one box, scans/s: HDL-64 G = 2 / 4 / 8: 11.4k / 11.9k / 12.1k; VLP-16 G = 1 / 2 / 4 / 8: 13.2k / 13.5k / 14.0k / 14.0k;
-    //  16 workgroups — a build with kLmGroupsMax = 16 — lose: the exchange's fan-in grows, HDL-64 11.4k, Ouster-128 8.8k vs 9.05k)
-    const int auto_g = config->n_streams > 4 ? 1 : (ecap >= 2048 ? kLmGroupsMax : (ecap >= 512 ? 4 : 1));
-    v.lm_groups = config->lm_workgroups == 0 ? auto_g
-                                             : (config->lm_workgroups >= kLmGroupsMax ? kLmGroupsMax : (config->lm_workgroups < 1 ? 1 : config->lm_workgroups));
-  }
-  v.vox_inv = 1.0f / 0.4f;                                                          // setLeafSize(0.4) :290
-  v.n_streams = h->S;
-  v.max_points = config->max_points;
-  // (k_ring_extract stages nothing per point in LDS, so there is no per-ring capacity — a ring may hold up to max_points
-  // points; config.max_width only picks the kernel instance, launch_extract)
-  v.ring_cap = config->max_points;
-  v.slots_per_ring = params->scan_regions * (params->edges_per_region + 1);
-  h->ring_lds_bytes = ring_extract_lds_bytes(v.slots_per_ring, params->scan_regions);
-  if (h->ring_lds_bytes > 160 * 1024) { g_last_error = "pick lists (scan_regions * (edges_per_region + 1)) exceed 160 KiB of LDS"; return fail(LIODOM_ERR_CAPACITY); }
-  v.edge_cap = round_up(std::max(1, h->H * v.slots_per_ring), 64);
-  v.use_imu = params->use_imu ? 1 : 0;
-  iso_identity(v.laser_to_base);
-  v.mapping = params->mapping ? 1 : 0;
-  // (after lds_hash_build and filter_local_map are known)
-  // (measured, scans/s aggregate, streamed / three-kernel rebuild: 4 streams 27.6k / 27.3k, 8 streams 40.4k / 41.1k, 12 streams
-  //  47.3k / 51.3k — with many streams the waiting workgroups of one stream hold the CUs the next stream's solve needs)
-  v.early_rebuild = (!h->lds_hash_build && !v.filter_local_map && !params->mapping && config->n_streams <= 4) ? 1 : 0;
-  if (env_int("LIODOM_EARLY_REBUILD", 1) == 0) v.early_rebuild = 0;
-  if (env_int("LIODOM_SAFE_MODE", 0) != 0) enter_safe_mode(h);
-  v.recv_cap = v.mapping ? (config->recv_capacity > 0 ? config->recv_capacity : 262144) : 0;
-  v.map_cap = v.edge_cap * h->P + v.recv_cap;
-  int ts = 1024;
-  while (ts < 2 * (v.map_cap + (v.early_rebuild ? 8 * v.edge_cap : 0))) ts <<= 1;    // (early rebuild: cells that only the padding touches)
-  // k_hash_build publishes its LDS table into slots [0, kLdsSlots) of the stream's table (keys, occupancy bits, cell_cap), however
-  // small the window: a lock-step handle with fewer than 2048 window points wrote into the next stream's table and past the last one
-  if (h->lds_hash_build && ts < kLdsSlots) ts = kLdsSlots;
-  v.table_size = ts;
-  v.pose_log_cap = std::max(1, config->pose_log_capacity);
-  v.debug = config->debug_buffers & 1;
-  // in-kernel phase timestamps (tools/gpu_debug.py clocks): they change no result.  The result-changing ablation bits
-  // of earlier rounds (LIODOM_ABLATE) are gone from the product build.
-  // instrumented builds only (-DLIODOM_INSTRUMENT, tools/variant_build.sh): 1: stamps, 65: + histograms (shared-counter atomics: they perturb the timing)
-  if (kInstrument) { const int dc = env_int("LIODOM_DEBUG_CLOCKS", 0); if (dc != 0) v.debug |= ((dc & (128 | 256)) ? (dc & 32) : 32) | (dc & (64 | 128)) | ((dc >> 8) << 8); }
-  v.ring_id_stride = (size_t)round_up(config->max_points + 512, 256);
+  // (stream_k exists only on handles that use it: HIP multiplexes its streams onto a few hardware queues, and one more
+  //  stream made the host-fed replay's copy stream share a queue — 11.3k -> 7.5k scans/s on every workload)
+  if (make_stream(&h->stream, prio_greatest) != hipSuccess || make_stream(&h->stream_x, prio_x) != hipSuccess ||
+      ((p.ov_ok || p.chain_ok) && make_stream(&h->stream_k, prio_greatest) != hipSuccess)) { g_last_error = "hipStreamCreate failed"; return fail(LIODOM_ERR_HIP); }
+  bool events = make_event(&h->ev_ov) == hipSuccess && make_event(&h->pose_event) == hipSuccess && (!p.chain_ok || make_event(&h->ev_ch) == hipSuccess);
+  for (int b = 0; b < kEdgePipeBufs; b++) events = events && make_event(&h->ev_edges[b]) == hipSuccess && make_event(&h->ev_free[b]) == hipSuccess;
+  if (!events) { g_last_error = "hipEventCreate failed"; return fail(LIODOM_ERR_HIP); }
 
   const size_t S = (size_t)h->S;
 #define ALLOC(ptr, count, fill) do { rc = dev_alloc(h, &(ptr), (count), (fill)); if (rc != LIODOM_OK) return fail(rc); } while (0)
   ALLOC(v.state, S, 0);
-  ALLOC(v.ring_id, S * v.ring_id_stride, 0xFF);
-  v.tile_cap = std::max(1, cdiv(config->max_points, kTilePts));
-  ALLOC(v.tile_hist, S * (size_t)v.tile_cap * h->H, 0);
+  ALLOC(v.ring_id, S * p.ring_id_stride, 0xFF);
+  ALLOC(v.tile_hist, S * (size_t)p.tile_cap * H, 0);
+  if (p.ring_split_lb) { ALLOC(v.lb_desc, S * (size_t)p.tile_cap * p.lb_hpad, 0); ALLOC(v.lb_ticket, 1, 0); ALLOC(v.lb_ovf, S, 0); }
   // + padding: region_keys_load reads unconditionally up to 16 * IPL + 10 points past the start of a ring's last region,
   // i.e. up to kExLPR * kExIPLBig + 10 points past the end of the last ring of the last stream (values never used)
-  // k_ring_split_lb (lock-step batches of Velodyne-type clouds): rings at a fixed pitch of 9/8 of the nominal ring length
-  h->ring_split_lb = h->lockstep && params->lidar_type == 0 && !h->safe_mode && env_int("LIODOM_RING_SPLIT_LB", 1) != 0;
-  v.ring_pitch = round_up(cdiv((long long)config->max_points * 9, (long long)std::max(1, h->H) * 8), 8);
-  if (const char* e = std::getenv("LIODOM_RING_PITCH")) v.ring_pitch = std::max(8, std::atoi(e));      // (tests: a pitch that real rings outgrow)
-  v.ring_stride = h->ring_split_lb ? std::max((size_t)config->max_points, (size_t)h->H * (size_t)v.ring_pitch) : (size_t)config->max_points;
-  v.lb_hpad = round_up(h->H, 64);
-  if (h->ring_split_lb) {
-    ALLOC(v.lb_desc, S * (size_t)v.tile_cap * v.lb_hpad, 0); ALLOC(v.lb_ticket, 1, 0); ALLOC(v.lb_ovf, S, 0);
-    const size_t lds = ring_split_lb_lds_bytes(h->H);
-    if (lds > 48 * 1024 && (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split_lb<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-                            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split_fix<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)) {
-      (void)hipGetLastError(); h->ring_split_lb = false;
-    }
-  } else { v.lb_desc = nullptr; v.lb_ticket = nullptr; v.lb_ovf = nullptr; }
-  ALLOC(v.ring_pts, S * v.ring_stride + kExLPR * kExIPLBig + 64, 0);
-  ALLOC(v.ring_src, S * v.ring_stride, 0);
-  ALLOC(v.ring_start, S * (size_t)(h->H + 1), 0);
-  ALLOC(v.ring_len, S * (size_t)h->H, 0);
-  ALLOC(v.edges_pad, S * h->H * v.slots_per_ring, 0);
-  ALLOC(v.edges_pad_meta, S * h->H * v.slots_per_ring, 0);
-  ALLOC(v.ring_nedges, S * h->H, 0);
-  {
-    h->ring_split = env_int("LIODOM_RING_SPLIT", 1) != 0 && !h->safe_mode;      // (safe mode = no in-kernel waits at all: it overrides the switch, whatever the order of the variables)
-    if (h->ring_split) {
-      // k_ring_split's tiles wait for each other inside the launch, so EVERY workgroup of a launch must be resident at once.  How
-      // many fit is a property of the device (CUs, LDS per CU: a tile holds ~50 KB), not a constant: occupancy query x CU count,
-      // half of it left to the odometry chain's kernels that run beside the extraction.  Launches above the budget — and devices
-      // or partitions where a single scan's tiles do not fit (CPX partitions, CU-masked runs) — take k_classify + k_ring_scatter.
-      int cus = 0, per_cu = 0;
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, config->device);
-      const size_t lds = ring_scatter_lds_bytes(h->H);
-      if (lds > 48 * 1024 &&
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_split<>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        (void)hipGetLastError(); per_cu = 0;
-      } else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_ring_split<>), kTileThreads, lds) != hipSuccess) {
-        (void)hipGetLastError(); per_cu = 0;
-      }
-      long long budget = (long long)std::max(0, per_cu) * std::max(0, cus) / 2;
-      if (budget > 256) budget = 256;                    // (measured: above ~4 HDL-64 streams per launch the waiting tiles lose to the two-kernel split anyway)
-      h->ring_split_max_wgs = (int)budget;
-      const int tiles_one = std::max(1, cdiv(config->max_points, kTilePts));
-      if (tiles_one > h->ring_split_max_wgs) h->ring_split = false;      // not even one stream's scan fits: never use it
-    }
-    v.split_ctr = nullptr;
-    v.split_hist = nullptr; v.split_pad = round_up(v.tile_cap, 8);
-    if (h->ring_split) { ALLOC(v.split_ctr, 2 * S, 0); ALLOC(v.split_hist, S * (size_t)h->H * v.split_pad + 64, 0); }      // (+ one batch of 64 tiles: k_ring_split reads whole batches)
-  }
-  ALLOC(v.ring_npoints, S * h->H, 0);
-  ALLOC(v.ring_c, S * v.ring_stride, 0);
-  ALLOC(v.ring_picked, S * v.ring_stride, 0);
-  ALLOC(v.edges, kEdgeBufs * S * v.edge_cap, 0);
-  ALLOC(v.edges_meta, kEdgeBufs * S * v.edge_cap, 0);
-  ALLOC(v.corr_a, S * 2 * v.edge_cap, 0);
-  ALLOC(v.corr_b, S * 2 * v.edge_cap, 0);
-  ALLOC(v.corr_idx, S * 2 * v.edge_cap, 0xFF);
-  if (v.debug & 1) ALLOC(v.knn_q, S * 2 * v.edge_cap, 0); else v.knn_q = nullptr;
-  ALLOC(v.win_pts, S * h->P * v.edge_cap, 0);
-  ALLOC(v.win_n, S * h->P, 0);
-  ALLOC(v.win_base, S * (h->P + 1), 0);
-  ALLOC(v.win_slot, S * h->P, 0);
-  const size_t ntab = v.early_rebuild ? 2 : 1;     // early_rebuild: two cell hashes per stream (index s + parity * S)
-  ALLOC(v.cells, ntab * S * v.table_size, 0);
-  ALLOC(v.pt_rank, S * v.map_cap, 0);
-  ALLOC(v.cell_bits, ntab * S * (size_t)(v.table_size / 32), 0);
-  v.used_cap = v.early_rebuild ? v.map_cap + 8 * v.edge_cap : v.map_cap;
-  ALLOC(v.used_cells, ntab * S * (size_t)v.used_cap, 0);
-  ALLOC(v.pt_cell, S * v.map_cap, 0xFF);
-  if (v.recv_cap) ALLOC(v.recv_pts, S * v.recv_cap, 0);
+  ALLOC(v.ring_pts, S * p.ring_stride + kExLPR * kExIPLBig + 64, 0);
+  ALLOC(v.ring_src, S * p.ring_stride, 0);
+  ALLOC(v.ring_start, S * (size_t)(H + 1), 0);
+  ALLOC(v.ring_len, S * (size_t)H, 0);
+  ALLOC(v.edges_pad, S * H * p.slots_per_ring, 0);
+  ALLOC(v.edges_pad_meta, S * H * p.slots_per_ring, 0);
+  ALLOC(v.ring_nedges, S * H, 0);
+  if (p.ring_split) { ALLOC(v.split_ctr, 2 * S, 0); ALLOC(v.split_hist, S * (size_t)H * p.split_pad + 64, 0); }      // (+ one batch of 64 tiles: k_ring_split reads whole batches)
+  ALLOC(v.ring_npoints, S * H, 0);
+  ALLOC(v.ring_c, S * p.ring_stride, 0);
+  ALLOC(v.ring_picked, S * p.ring_stride, 0);
+  ALLOC(v.edges, kEdgeBufs * S * p.edge_cap, 0);
+  ALLOC(v.edges_meta, kEdgeBufs * S * p.edge_cap, 0);
+  ALLOC(v.corr_a, S * 2 * p.edge_cap, 0);
+  ALLOC(v.corr_b, S * 2 * p.edge_cap, 0);
+  ALLOC(v.corr_idx, S * 2 * p.edge_cap, 0xFF);
+  if (p.debug & 1) ALLOC(v.knn_q, S * 2 * p.edge_cap, 0);
+  ALLOC(v.win_pts, S * p.prev_frames * p.edge_cap, 0);
+  ALLOC(v.win_n, S * p.prev_frames, 0);
+  ALLOC(v.win_base, S * (p.prev_frames + 1), 0);
+  ALLOC(v.win_slot, S * p.prev_frames, 0);
+  const size_t ntab = p.early_rebuild ? 2 : 1;     // early_rebuild: two cell hashes per stream (index s + parity * S)
+  ALLOC(v.cells, ntab * S * p.table_size, 0);
+  ALLOC(v.pt_rank, S * p.map_cap, 0);
+  ALLOC(v.cell_bits, ntab * S * (size_t)(p.table_size / 32), 0);
+  ALLOC(v.used_cells, ntab * S * (size_t)p.used_cap, 0);
+  ALLOC(v.pt_cell, S * p.map_cap, 0xFF);
+  if (p.recv_cap) ALLOC(v.recv_pts, S * p.recv_cap, 0);
   ALLOC(v.imu_q, S * 4, 0);
-  v.ovf_base = v.early_rebuild ? v.map_cap + 8 * v.edge_cap : v.map_cap;
-  v.sorted_cap = v.early_rebuild ? v.ovf_base + v.edge_cap : v.map_cap;
-  // incremental cell hash (k_hash_append; decided for good below, once the kNN instance is known): every cell keeps room for the
-  // points of the frames that arrive before the next rebuild — twice the window + 64k places per stream
-  const bool hash_incr_on = env_int("LIODOM_HASH_INCR", 1) != 0;
-  if (hash_incr_on && h->lockstep && h->lds_hash_build && !params->mapping && !params->filter_local_map && !v.early_rebuild)
-    v.sorted_cap = 2 * v.map_cap + 65536 + (kHbPeriod - 1) * v.edge_cap;      // (+ the spill list)
-  ALLOC(v.sorted_pts, (v.early_rebuild ? 2 : 1) * S * (size_t)v.sorted_cap, 0);
-  if (v.early_rebuild) ALLOC(v.cell_pad, 2 * S * (size_t)v.table_size, 0); else v.cell_pad = nullptr;
-  v.rebuild_delta = 0.25f;
-  if (const char* e = std::getenv("LIODOM_REBUILD_DELTA")) { const float d = (float)std::atof(e); if (d > 0.0f && d <= 0.45f) v.rebuild_delta = d; }
-  if (v.filter_local_map) {
-    ALLOC(v.vox_cells, S * v.table_size, 0);
-    ALLOC(v.vox_fill, S * v.table_size, 0);
-    ALLOC(v.vox_used_list, S * v.map_cap, 0);
-    ALLOC(v.pt_vox, S * v.map_cap, 0xFF);
-    ALLOC(v.vox_pts, S * v.map_cap, 0);
-    ALLOC(v.filt_pts, S * v.map_cap, 0);
-    ALLOC(v.filt_int, S * v.map_cap, 0);
+  ALLOC(v.sorted_pts, ntab * S * (size_t)p.sorted_cap, 0);
+  if (p.early_rebuild) ALLOC(v.cell_pad, 2 * S * (size_t)p.table_size, 0);
+  if (p.filter_local_map) {
+    ALLOC(v.vox_cells, S * p.table_size, 0);
+    ALLOC(v.vox_fill, S * p.table_size, 0);
+    ALLOC(v.vox_used_list, S * p.map_cap, 0);
+    ALLOC(v.pt_vox, S * p.map_cap, 0xFF);
+    ALLOC(v.vox_pts, S * p.map_cap, 0);
+    ALLOC(v.filt_pts, S * p.map_cap, 0);
+    ALLOC(v.filt_int, S * p.map_cap, 0);
   }
-  ALLOC(v.pose_log, S * v.pose_log_cap * 7, 0);
-  ALLOC(v.info_log, S * v.pose_log_cap, 0);
-  ALLOC(h->stage_in, S * (size_t)config->max_points, 0);
+  ALLOC(v.pose_log, S * p.pose_log_cap * 7, 0);
+  ALLOC(v.info_log, S * p.pose_log_cap, 0);
+  ALLOC(h->stage_in, S * (size_t)p.max_points, 0);
   ALLOC(v.dbg_clk, 16 * 32, 0);
-  if (v.debug & 32) ALLOC(v.dbg_q, 2 * (size_t)v.edge_cap * 12, 0); else v.dbg_q = nullptr;
+  if (p.debug & 32) ALLOC(v.dbg_q, 2 * (size_t)p.edge_cap * 12, 0);
   ALLOC(v.lm_xch, S * 2 * kLmGroupsMax * 64, 0);
   ALLOC(v.pose_xch, S * 64, 0);
   ALLOC(v.redo_sync, 64, 0);
   ALLOC(v.pipe_flags, (size_t)kStreamListBase + (size_t)kStreamLists * S, 0);      // (+ the stream lists of subset steps, stream_of)
-  v.host_edges = nullptr; v.host_edges_meta = nullptr; v.host_edges_hdr = nullptr;
   if (S == 1) {
     // device-resident hand-off (liodom_extract_edges_device): host-mapped mirror of the dense edges of the three pipeline buffers
-    const size_t ne = (size_t)kEdgePipeBufs * v.edge_cap;
+    const size_t ne = (size_t)kEdgePipeBufs * p.edge_cap;
     void *he = nullptr, *hm = nullptr, *hh = nullptr;
     if (hipHostMalloc(&he, sizeof(float4) * ne, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
         hipHostMalloc(&hm, sizeof(int4) * ne, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
@@ -1067,8 +921,88 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
         hipHostGetDevicePointer(&dh, hh, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
     v.host_edges = static_cast<float4*>(de); v.host_edges_meta = static_cast<int4*>(dm); v.host_edges_hdr = static_cast<unsigned int*>(dh);
   }
-  if (h->use_flags) {
-    // Flags need kernels of the handle's streams to run side by side.  Known serialisers are caught by name above; this probe
+  if (p.lockstep) ALLOC(v.knn_nn, S * (size_t)p.edge_cap * 5, 0);      // lock-step batches: line gates in their own launch (k_line_gate)
+  if (p.hash_incr) ALLOC(v.cell_cap, S * (size_t)p.table_size, 0);
+  if (p.knn8) { ALLOC(v.knn8_cnt, S, 0); ALLOC(v.knn8_list, S * (size_t)p.edge_cap, 0); }
+  if (p.knn_save >= 1) ALLOC(v.knn_save_q, S * (size_t)p.edge_cap, 0);
+  if (p.knn_save >= 2) { ALLOC(v.knn_save_pos, S * (size_t)p.edge_cap * kKnnGroup, 0xFF); ALLOC(v.knn_save_g, S * (size_t)p.edge_cap, 0); }
+  ALLOC(v.knn_part, S * 2 * (size_t)p.knn_blocks * 32, 0);
+  ALLOC(v.ov_flags, S, 0);
+  ALLOC(v.pose_xch0, S * (size_t)kOvReplicas * 512, 0);
+  ALLOC(v.knn_done, S * (size_t)p.knn_grid, 0);
+  ALLOC(v.knn_done0, S + 64, 0);
+  if (p.early_rebuild) ALLOC(v.pred_xch, S * (size_t)kOvReplicas * 512, 0);
+  ALLOC(v.edge_cnt, (size_t)kEdgeBufs * 32, 0);
+  ALLOC(v.pub_counter, (size_t)kEdgeBufs, 0);
+  if (p.early_rebuild) ALLOC(v.edges_keep, S * (size_t)p.edge_cap, 0);
+  ALLOC(v.corr_mask, S * 2 * (size_t)p.mask_stride, 0);
+  {
+    void* hp = nullptr;
+    if (hipHostMalloc(&hp, sizeof(HostOut) * 2 * S, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { g_last_error = "hipHostMalloc failed"; return fail(LIODOM_ERR_HIP); }
+    h->host_out = static_cast<HostOut*>(hp);
+    std::memset(hp, 0, sizeof(HostOut) * 2 * S);
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
+    v.host_out = static_cast<HostOut*>(dp);
+    h->scans_enqueued.assign(S, 0);
+    h->last_eb.assign(S, 0);
+    h->mappers.assign(S, nullptr); h->mapper_opts.assign(S, liodom_mapper_options_t{2, 1, 0, 0, 0, 0, {0, 0}});
+  }
+  if (p.pose_covariance) {
+    // per-scan pose covariance (kernels_cov.h): nothing of it exists on handles created without it
+    ALLOC(v.cov_raw, S, 0);
+    ALLOC(v.cov_log, S * (size_t)p.pose_log_cap, 0);
+    void* hp = nullptr;
+    if (hipHostMalloc(&hp, sizeof(HostCov) * 2 * S, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { g_last_error = "hipHostMalloc failed"; return fail(LIODOM_ERR_HIP); }
+    h->cov_host = static_cast<HostCov*>(hp);
+    std::memset(hp, 0, sizeof(HostCov) * 2 * S);
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
+    v.cov_host = static_cast<HostCov*>(dp);
+  }
+  {
+    // dynamic LDS: one entry per kernel instance a handle may launch (k_ring_split<> has its attribute from the caps above).
+    // k_ring_split_lb comes first: it is the one path a failure only switches off — its pitched buffers, sized from the
+    // planned value, stay allocated — and its list instances further down are then skipped.
+    const size_t scatter = ring_scatter_lds_bytes(H), split_lb = ring_split_lb_lds_bytes(H), build = hash_build_lds_bytes();
+    const size_t solve = lm_lds_bytes(p.edge_cap), extract = p.ring_lds_bytes;
+#define FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+    const LdsNeed needs[] = {
+        {FN(k_ring_split_lb<>), split_lb, false, false, &p.ring_split_lb, &p.ring_split_lb},
+        {FN(k_ring_split_fix<>), split_lb, false, false, &p.ring_split_lb, &p.ring_split_lb},
+        {FN(k_ring_scatter<>), scatter, false, false, nullptr, nullptr},
+        {FN(k_hash_build<>), build, true, false, nullptr, nullptr},
+        {FN(k_lm_solve<0, false>), solve, true, false, nullptr, nullptr},
+        {FN(k_lm_solve<1, false>), solve, true, false, nullptr, nullptr},
+        {FN(k_lm_solve<0, true>), solve, true, false, nullptr, nullptr},
+        {FN(k_lm_solve<1, true>), solve, true, false, nullptr, nullptr},
+        {FN(k_ring_extract<256, kExIPL>), extract, false, false, nullptr, nullptr},
+        {FN(k_ring_extract<256, kExIPLBig>), extract, false, false, nullptr, nullptr},
+        {FN(k_ring_extract<1024, kExIPL>), extract, false, false, nullptr, nullptr},
+        {FN(k_ring_extract<1024, kExIPLBig>), extract, false, false, nullptr, nullptr},
+        // the list instances of the kernels above (subset steps, stream_of) take the same dynamic LDS
+        {FN(k_ring_split_lb<true>), split_lb, false, true, &p.ring_split_lb, nullptr},
+        {FN(k_ring_split_fix<true>), split_lb, false, true, &p.ring_split_lb, nullptr},
+        {FN(k_ring_split<true>), scatter, false, true, &p.ring_split, nullptr},
+        {FN(k_ring_scatter<true>), scatter, false, true, nullptr, nullptr},
+        {FN(k_hash_build<true>), build, true, true, nullptr, nullptr},
+        {FN(k_lm_solve<0, false, true>), solve, true, true, nullptr, nullptr},
+        {FN(k_lm_solve<1, false, true>), solve, true, true, nullptr, nullptr},
+        {FN(k_ring_extract<256, kExIPL, true>), extract, false, true, nullptr, nullptr},
+        {FN(k_ring_extract<256, kExIPLBig, true>), extract, false, true, nullptr, nullptr},
+        {FN(k_ring_extract<1024, kExIPL, true>), extract, false, true, nullptr, nullptr},
+        {FN(k_ring_extract<1024, kExIPLBig, true>), extract, false, true, nullptr, nullptr},
+    };
+#undef FN
+    for (const LdsNeed& n : needs) {
+      if ((n.list && S == 1) || (n.when && !*n.when) || !(n.always || n.bytes > 48 * 1024)) continue;
+      if (hipFuncSetAttribute(n.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)n.bytes) == hipSuccess) continue;
+      if (!n.clears) { g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP); }
+      (void)hipGetLastError(); *n.clears = false;
+    }
+  }
+  if (p.use_flags) {
+    // Flags need kernels of the handle's streams to run side by side.  Known serialisers are caught by name (HandleEnv); this probe
     // catches the rest (a profiler collecting counters, a debugger): one wave on the odometry stream waits up to ~2 ms (k_probe_wait) for a flag
     // that a launch on the extraction stream sets.  If it gives up, the handle uses events from the start.
     unsigned int* probe = nullptr;
@@ -1082,154 +1016,10 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     if (hipStreamSynchronize(h->stream) != hipSuccess || hipStreamSynchronize(h->stream_x) != hipSuccess ||
         hipMemcpy(&res, probe + 1, sizeof(res), hipMemcpyDeviceToHost) != hipSuccess) { g_last_error = "stream probe failed"; return fail(LIODOM_ERR_HIP); }
     h->streams_concurrent = res == 1u;
-    if (!h->streams_concurrent) h->use_flags = false;
+    if (!h->streams_concurrent) p.use_flags = false;
   }
-  if (h->lockstep) ALLOC(v.knn_nn, S * (size_t)v.edge_cap * 5, 0); else v.knn_nn = nullptr;      // lock-step batches: line gates in their own launch (k_line_gate)
-  h->knn8 = h->lockstep && env_int("LIODOM_KNN8", 1) != 0;
-  h->knn8_grid = std::max(1, cdiv(cdiv(v.edge_cap, kKnn8Queries), kKnnGridDiv));
-  // incremental cell hash: lock-step batches that search with k_knn8 (it skips evicted points) on the LDS-built table, window only
-  v.hash_incr = (hash_incr_on && h->knn8 && h->lds_hash_build && !params->mapping && !params->filter_local_map && h->P > kHbPeriod &&
-                 v.sorted_cap >= 2 * v.map_cap + (kHbPeriod - 1) * v.edge_cap) ? 1 : 0;      // (windows of more frames than a period: the evicted frames are frames the rebuild knew)
-  v.hb_spill_base = v.sorted_cap - (kHbPeriod - 1) * v.edge_cap;
-  if (v.hash_incr) ALLOC(v.cell_cap, S * (size_t)v.table_size, 0); else v.cell_cap = nullptr;
-  v.hb_slack_min = kHbSlackMin; v.hb_new_room = kHbNewRoom;
-  if (const char* e = std::getenv("LIODOM_HB_SLACK")) v.hb_slack_min = std::max(0, std::atoi(e));            // (tests: cells that run out of room)
-  if (const char* e = std::getenv("LIODOM_HB_NEW_ROOM")) v.hb_new_room = std::max(1, std::atoi(e));
-  if (h->knn8) { ALLOC(v.knn8_cnt, S, 0); ALLOC(v.knn8_list, S * (size_t)v.edge_cap, 0); } else { v.knn8_cnt = nullptr; v.knn8_list = nullptr; }
-  v.knn_queries = h->lockstep ? 4 : 8;          // must match the k_knn instance launch_odometry picks (k_knn8 leaves k_line_gate the same layout)
-  v.knn_partials = h->lockstep ? 0 : 1;         // measured: +37 % on the VALU-bound 256-stream kNN pass, -2 us per solve on one stream
-  v.knn_blocks = round_up(cdiv(v.edge_cap, v.knn_queries), 4);
-  v.knn_grid = std::max(1, cdiv(v.knn_blocks, kKnnGridDiv));   // sized for the usual edge count (~1/3 of the capacity): a workgroup takes a second block if there are more
-  {
-    // LIODOM_KNN_SAVE: 2 (default) second pass re-ranks the first pass's kept candidates and prunes with its fifth distance;
-    // 1: pruning bound only; 0: the second pass searches like the first (all three give the same results)
-    const int save = env_int("LIODOM_KNN_SAVE", 2);
-    if (save >= 1) ALLOC(v.knn_save_q, S * (size_t)v.edge_cap, 0); else v.knn_save_q = nullptr;
-    if (save >= 2) { ALLOC(v.knn_save_pos, S * (size_t)v.edge_cap * kKnnGroup, 0xFF); ALLOC(v.knn_save_g, S * (size_t)v.edge_cap, 0); }
-    else { v.knn_save_pos = nullptr; v.knn_save_g = nullptr; }
-  }
-  v.knn_exact_only = env_int("LIODOM_KNN_EXACT_ONLY", 0) != 0 ? 1 : 0;
-  ALLOC(v.knn_part, S * 2 * (size_t)v.knn_blocks * 32, 0);
-  ALLOC(v.ov_flags, S, 0);
-  ALLOC(v.pose_xch0, S * (size_t)kOvReplicas * 512, 0);
-  ALLOC(v.knn_done, S * (size_t)v.knn_grid, 0);
-  ALLOC(v.knn_done0, S + 64, 0);
-  if (v.early_rebuild) ALLOC(v.pred_xch, S * (size_t)kOvReplicas * 512, 0); else v.pred_xch = nullptr;
-  ALLOC(v.edge_cnt, (size_t)kEdgeBufs * 32, 0);
-  ALLOC(v.pub_counter, (size_t)kEdgeBufs, 0);
-  if (v.early_rebuild) ALLOC(v.edges_keep, S * (size_t)v.edge_cap, 0); else v.edges_keep = nullptr;
-  // (the two passes' validity bytes never share a 128-byte line: the overlapped second pass writes its half while the finalising
-  //  solve's launch — which must not read it before ov_wait_knn_done — may hold the first pass's half in its caches)
-  v.mask_stride = round_up(v.knn_blocks, 128);
-  ALLOC(v.corr_mask, S * 2 * (size_t)v.mask_stride, 0);
-  {
-    void* hp = nullptr;
-    if (hipHostMalloc(&hp, sizeof(HostOut) * 2 * S, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { g_last_error = "hipHostMalloc failed"; return fail(LIODOM_ERR_HIP); }
-    h->host_out = static_cast<HostOut*>(hp);
-    std::memset(hp, 0, sizeof(HostOut) * 2 * S);
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
-    v.host_out = static_cast<HostOut*>(dp);
-    h->scans_enqueued.assign(S, 0);
-    h->last_eb.assign(S, 0);
-    h->mappers.assign(S, nullptr); h->mapper_opts.assign(S, liodom_mapper_options_t{2, 1, 0, 0, 0, 0, {0, 0}});
-  }
-  if (config->pose_covariance) {
-    // per-scan pose covariance (kernels_cov.h): nothing of it exists on handles created without it
-    ALLOC(v.cov_raw, S, 0);
-    ALLOC(v.cov_log, S * (size_t)v.pose_log_cap, 0);
-    void* hp = nullptr;
-    if (hipHostMalloc(&hp, sizeof(HostCov) * 2 * S, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { g_last_error = "hipHostMalloc failed"; return fail(LIODOM_ERR_HIP); }
-    h->cov_host = static_cast<HostCov*>(hp);
-    std::memset(hp, 0, sizeof(HostCov) * 2 * S);
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
-    v.cov_host = static_cast<HostCov*>(dp);
-  } else {
-    v.cov_raw = nullptr; v.cov_log = nullptr; v.cov_host = nullptr;
-  }
-  if (ring_scatter_lds_bytes(h->H) > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_scatter<>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)ring_scatter_lds_bytes(h->H)) != hipSuccess) {
-      g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP);
-    }
-  }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hash_build<>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)hash_build_lds_bytes()) != hipSuccess) {
-    g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP);
-  }
-  // (the solve's dynamic LDS is its index list, up to ~36 800 edges; 16 KiB are left for its static LDS, 8.7 KiB at most today)
-  if (lm_lds_bytes(v.edge_cap) + 16384 > 160 * 1024) { g_last_error = "liodom_create: edge capacity too large for the solve's LDS tile"; return fail(LIODOM_ERR_INVALID_ARG); }
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lm_solve<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds_bytes(h->v.edge_cap)) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lm_solve<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds_bytes(h->v.edge_cap)) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lm_solve<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds_bytes(h->v.edge_cap)) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lm_solve<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds_bytes(h->v.edge_cap)) != hipSuccess) {
-    g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP);
-  }
-  if (h->ring_lds_bytes > 48 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_extract<256, kExIPL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->ring_lds_bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_extract<256, kExIPLBig>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->ring_lds_bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_extract<1024, kExIPL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->ring_lds_bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ring_extract<1024, kExIPLBig>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->ring_lds_bytes) != hipSuccess) {
-      g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP);
-    }
-  }
-  if (S > 1) {
-    // the list instances of the kernels above (subset steps, stream_of) take the same dynamic LDS
-    bool ok = true;
-    auto allow = [&](const void* f, size_t bytes, bool always = false) {
-      if ((always || bytes > 48 * 1024) && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) ok = false;
-    };
-    if (h->ring_split_lb) {
-      allow(reinterpret_cast<const void*>(&k_ring_split_lb<true>), ring_split_lb_lds_bytes(h->H));
-      allow(reinterpret_cast<const void*>(&k_ring_split_fix<true>), ring_split_lb_lds_bytes(h->H));
-    }
-    if (h->ring_split) allow(reinterpret_cast<const void*>(&k_ring_split<true>), ring_scatter_lds_bytes(h->H));
-    allow(reinterpret_cast<const void*>(&k_ring_scatter<true>), ring_scatter_lds_bytes(h->H));
-    allow(reinterpret_cast<const void*>(&k_hash_build<true>), hash_build_lds_bytes(), true);
-    allow(reinterpret_cast<const void*>(&k_lm_solve<0, false, true>), lm_lds_bytes(v.edge_cap), true);
-    allow(reinterpret_cast<const void*>(&k_lm_solve<1, false, true>), lm_lds_bytes(v.edge_cap), true);
-    allow(reinterpret_cast<const void*>(&k_ring_extract<256, kExIPL, true>), h->ring_lds_bytes);
-    allow(reinterpret_cast<const void*>(&k_ring_extract<256, kExIPLBig, true>), h->ring_lds_bytes);
-    allow(reinterpret_cast<const void*>(&k_ring_extract<1024, kExIPL, true>), h->ring_lds_bytes);
-    allow(reinterpret_cast<const void*>(&k_ring_extract<1024, kExIPLBig, true>), h->ring_lds_bytes);
-    if (!ok) { g_last_error = "hipFuncSetAttribute(max dynamic LDS) failed"; return fail(LIODOM_ERR_HIP); }
-  }
-  {
-    // Overlapped second kNN pass: its workgroups wait inside the kernel for the first solve, so they must leave most of the GPU
-    // to the launches they wait for (and to the next scan's extraction): one stream, at most a third of the wave slots
-    // (HDL-64: 352 workgroups x 4 waves = 1 408 of 6 144).  LIODOM_KNN_OVERLAP=0 keeps the pass on the odometry stream.
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, config->device);
-    // (measured with half of the slots allowed: Ouster-128, 704 workgroups = 2 816 waves, loses — 9.0k -> 8.4k scans/s)
-    const int knn_overlap = env_int("LIODOM_KNN_OVERLAP", 1);      // (2: also where the pass takes more than a third of the wave slots)
-    h->ov_ok = knn_overlap != 0 && v.early_rebuild && S == 1 && v.knn_partials && (knn_overlap == 2 || (long long)v.knn_grid * 4 * 3 <= (long long)cus * 24);
-    // (the stream exists only on handles that use it: HIP multiplexes its streams onto a few hardware queues, and one more
-    //  stream made the host-fed replay's copy stream share a queue — 11.3k -> 7.5k scans/s on every workload)
-    // chain mode (kernels_sync.h): one-stream handles with the streamed rebuild whose passes leave at least half of the wave slots
-    // free; the IMU override rewrites the prediction between two scans on the odometry stream (k_imu_override), which the first
-    // pass on stream_k would not be ordered behind
-    h->chain_ok = v.early_rebuild && S == 1 && v.knn_partials && !v.use_imu && (long long)v.knn_grid * 4 * 2 <= (long long)cus * 24;
-    if (knn_overlap == 0 || env_int("LIODOM_CHAIN", 1) == 0) h->chain_ok = false;
-    // speculative hand-over of the solves' results (kernels_sync.h): LIODOM_SPECULATE=0 off, 1 by the model's predicted cost change
-    // (default), 2 (tests): as early as possible, i.e. practically always wrong — every receiver is then repeated from the confirmed
-    // result; 4 / 5 (debugging): only the first / only the finalising solve's hand-over.  LIODOM_SPEC_THETA: the predictor's threshold
-    // (fraction of the function tolerance, default 0.8)
-    v.speculate = (h->ov_ok || h->chain_ok) ? 1 : 0;
-    if (v.speculate) v.speculate = std::max(0, std::min(7, env_int("LIODOM_SPECULATE", 1)));
-    v.spec_backoff = 16;
-    v.spec_theta = 0.8;
-    if (const char* e = std::getenv("LIODOM_SPEC_THETA")) v.spec_theta = std::atof(e);
-    if ((h->ov_ok || h->chain_ok) && make_stream(&h->stream_k, prio_greatest) != hipSuccess) { g_last_error = "hipStreamCreate failed"; return fail(LIODOM_ERR_HIP); }
-    if (h->chain_ok && hipEventCreateWithFlags(&h->ev_ch, hipEventDisableTiming) != hipSuccess) { g_last_error = "hipEventCreate failed"; return fail(LIODOM_ERR_HIP); }
-  }
-  {
-    // wall-clock bound of every in-kernel wait (g_wait_ticks, 100 MHz ticks): LIODOM_WAIT_MS, default 50 ms
-    double ms = 50.0;
-    if (const char* e = std::getenv("LIODOM_WAIT_MS")) { const double x = std::atof(e); if (x >= 1.0 && x <= 10000.0) ms = x; }
-    const unsigned long long ticks = (unsigned long long)(ms * 1.0e5);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wait_ticks), &ticks, sizeof(ticks)) != hipSuccess) { g_last_error = "hipMemcpyToSymbol(g_wait_ticks) failed"; return fail(LIODOM_ERR_HIP); }
-  }
+  // wall-clock bound of every in-kernel wait (g_wait_ticks, 100 MHz ticks)
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_wait_ticks), &p.wait_ticks, sizeof(p.wait_ticks)) != hipSuccess) { g_last_error = "hipMemcpyToSymbol(g_wait_ticks) failed"; return fail(LIODOM_ERR_HIP); }
   ALLOC(h->d_view, 1, 0);
   if (hipMemcpy(h->d_view, &h->v, sizeof(DevView), hipMemcpyHostToDevice) != hipSuccess) { g_last_error = "DevView upload failed"; return fail(LIODOM_ERR_HIP); }
   rc = reset_state(h);
@@ -1341,7 +1131,7 @@ static int install_stream_state(liodom_handle* h, int stream, const unsigned cha
     h->ov_warm = 0; h->ov_prev = false; h->chain_prev = false; h->chain_count = 0; h->chain_fix_pending = false; h->verdict_scan = -1;
   }
   if (n_frames > 0 || n_recv > 0) {      // (a received map without a frame — a seeded stream before its first scan — is searched too)
-    if (h->lds_hash_build) {
+    if (h->plan.lds_hash_build) {
       hipLaunchKernelGGL(k_hash_build<>, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
     } else {
       // (early_rebuild: the three kernels fill the table of parity frame_count & 1, the one the next scan searches; the other one
@@ -1683,10 +1473,10 @@ static int ticket_extract(liodom_handle* h, hipStream_t q, int stream, const flo
   unsigned int* host_seq = h->v.host_edges_hdr ? h->v.host_edges_hdr + eb : nullptr;
   // (the slot is free: the odometry that last read buffer eb has been collected, i.e. has completed — no wait on the device,
   //  which would depend on when the other thread submits its next scan)
-  unsigned int* const dev_flag = h->use_flags ? h->v.pipe_flags + eb : (unsigned int*)nullptr;
+  unsigned int* const dev_flag = h->plan.use_flags ? h->v.pipe_flags + eb : (unsigned int*)nullptr;
   int rc = launch_extract(h, q, eb, stream, 1, in, 0, n, height, width, 0u, 1, dev_flag, host_seq, seq);
   if (rc) return rc;
-  if (!h->use_flags) HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
+  if (!h->plan.use_flags) HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
   h->eb_seq[eb] = seq;
   h->pipe_active.store(true);
   h->tk_seq[eb].store(seq);
@@ -2029,7 +1819,7 @@ static int rebuild_search_structure(liodom_handle* h, int stream) {
   const int map_blocks = cdiv(v.map_cap, 256);
   hipLaunchKernelGGL(k_hash_reset, dim3(64), dim3(256), 0, h->stream, v, stream);
   hipLaunchKernelGGL(k_hash_reset_done, dim3(1), dim3(1), 0, h->stream, v, stream);
-  if (h->lds_hash_build) {
+  if (h->plan.lds_hash_build) {
     hipLaunchKernelGGL(k_hash_build<>, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
   } else {
     hipLaunchKernelGGL(k_window_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream, -1);
@@ -2810,41 +2600,19 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   if (int rc = enter(h)) return rc;
   SideLocks lk(h, true, true);
   const DevView& v = h->v;
-  const OverlapModes om = overlap_modes(h);
+  ModesRuntime r;
+  r.alone = g_live_handles.load() <= 1;
+  r.streams_concurrent = h->streams_concurrent;
   // (speculative hand-overs of stream 0 since the last reset: the launches enqueued so far have to have run for the figures to mean
   //  anything — a caller that wants them synchronises first; this call does not)
-  int spec[4] = {0, 0, 0, 0}, hbs[4] = {0, 0, 0, 0};
   unsigned int done_cnt[64] = {0};      // (chain mode: the passes' done counters of stream 0 — first pass [0], second pass [32] — against the host's target)
   if (v.knn_done0) (void)hipMemcpy(done_cnt, v.knn_done0, sizeof(done_cnt), hipMemcpyDeviceToHost);
-  (void)hipMemcpy(spec, reinterpret_cast<const char*>(v.state) + offsetof(StreamState, spec_stats), sizeof(spec), hipMemcpyDeviceToHost);
-  (void)hipMemcpy(hbs, reinterpret_cast<const char*>(v.state) + offsetof(StreamState, hb_stats), sizeof(hbs), hipMemcpyDeviceToHost);
-  snprintf(buf, (size_t)cap,
-           "n_streams=%d early_rebuild=%d hash_build=%s pipe_flags=%d flag_gate=%d lm_groups=%d knn_instance=%d knn_queries=%d "
-           "knn_grid=%d/%d knn8=%d hash_incr=%d hash_rebuilds=%d hash_appends=%d hash_appends_spilled=%d hash_points_spilled=%d knn_partials=%d knn_saved_bound=%d knn_exact_only=%d line_gate_kernel=%d filter_local_map=%d mapping=%d "
-           "rotation_mode=%d table_size=%d sorted_cap=%d hb_spill_base=%d rebuild_delta=%.3f knn_overlap=%d streams_concurrent=%d safe_mode=%d ring_split=%d ring_split_max_wgs=%d ring_split_lb=%d chain=%d speculate=%d spec_early=%d/%d spec_unconfirmed=%d/%d chain_done=%u/%u/%u replay_enqueue_us=%.2f replay_wait_us=%.2f debug=%d",
-           h->S, v.early_rebuild, v.early_rebuild ? "streamed" : (h->lds_hash_build ? "lds" : "global"), h->use_flags ? 1 : 0,
-           (h->use_flags && h->flag_gate) ? 1 : 0, v.lm_groups, h->lockstep ? 128 : 256, v.knn_queries, v.knn_grid,
-           v.knn_blocks, h->knn8 ? 1 : 0, v.hash_incr, hbs[0], hbs[1], hbs[2], hbs[3], v.knn_partials, v.knn_save_pos ? 2 : (v.knn_save_q ? 1 : 0), v.knn_exact_only, v.knn_nn ? 1 : 0, v.filter_local_map, v.mapping,
-           v.rotation_mode, v.table_size, v.sorted_cap, v.hb_spill_base, (double)v.rebuild_delta,
-           (om.ov || om.chain) ? 1 : 0, h->streams_concurrent ? 1 : 0, h->safe_mode ? 1 : 0, h->ring_split ? 1 : 0, h->ring_split ? h->ring_split_max_wgs : 0, h->ring_split_lb ? 1 : 0,
-           om.chain ? 1 : 0, v.speculate, spec[0], spec[2], spec[1], spec[3], h->chain_count, done_cnt[0], done_cnt[32],
-           h->replay_timed ? h->replay_enq_ns / (1e3 * (double)h->replay_timed) : 0.0, h->replay_timed ? h->replay_wait_ns / (1e3 * (double)h->replay_timed) : 0.0, v.debug);
-  if (v.cov_raw) {
-    const size_t len = std::strlen(buf);
-    snprintf(buf + len, (size_t)cap - len, " pose_cov=1");
-  }
-  if (h->n_lagged > 0) {      // streams with a lagged mapper (liodom_attach_mapper_ex); their steps run on the odometry stream alone, as every mapping handle's
-    const size_t len = std::strlen(buf);
-    snprintf(buf + len, (size_t)cap - len, " mapper_lag=%d", h->n_lagged);
-  }
-  if (h->n_readers > 0) {     // streams that read a map they never write (liodom_attach_map_reader)
-    const size_t len = std::strlen(buf);
-    snprintf(buf + len, (size_t)cap - len, " map_readers=%d map_rows=%d", h->n_readers, h->map_rows ? 1 : 0);
-  }
-  {
-    const size_t len = std::strlen(buf);      // (steps liodom_process_resident_subset ran over a stream list, i.e. did not hand to the plain step)
-    snprintf(buf + len, (size_t)cap - len, " subset_steps=%lld", h->subset_steps);
-  }
+  (void)hipMemcpy(r.spec_stats, reinterpret_cast<const char*>(v.state) + offsetof(StreamState, spec_stats), sizeof(r.spec_stats), hipMemcpyDeviceToHost);
+  (void)hipMemcpy(r.hb_stats, reinterpret_cast<const char*>(v.state) + offsetof(StreamState, hb_stats), sizeof(r.hb_stats), hipMemcpyDeviceToHost);
+  r.chain_count = h->chain_count; r.done0 = done_cnt[0]; r.done1 = done_cnt[32];
+  if (h->replay_timed) { r.replay_enqueue_us = h->replay_enq_ns / (1e3 * (double)h->replay_timed); r.replay_wait_us = h->replay_wait_ns / (1e3 * (double)h->replay_timed); }
+  r.n_lagged = h->n_lagged; r.n_readers = h->n_readers; r.subset_steps = h->subset_steps;
+  plan_format_modes(h->plan, r, buf, cap);
   return LIODOM_OK;
 }
 

@@ -36,6 +36,7 @@
 
 #include "../../include/liodom_hip.h"
 #include "liodom_math.h"
+#include "liodom_sizes.h"
 #include "wave_ops.h"
 
 namespace liodom_dev {
@@ -48,25 +49,10 @@ namespace liodom_dev {
 #endif
 constexpr int kWave = 64;
 constexpr uint64_t kEmptyKey = 0xFFFFFFFFFFFFFFFFull;
-// Solving workgroups of 4 waves (round 6; 8 until then): one wave per SIMD with the whole register file to itself — no scratch in
-// any instance of k_lm_solve (512 threads: 256 registers per lane and 108-172 B of scratch in the controller's path), half as many
-// waves at every barrier.  Interleaved A/B against 512 (same box, bench.py): `value` 14 288 -> 14 577 (K = 200), 13 364 -> 13 503
-// (the driver's K = 20), strict-sync +0.9 %, 256 lock-step streams 203.8k -> 207.1k; round 5 had measured +-1 % for the same switch
-// (then one instance of the kernel per solve, now one per solve and mode).
-#ifndef LIODOM_LM_THREADS
-#define LIODOM_LM_THREADS 256
-#endif
-constexpr int kLmThreads = LIODOM_LM_THREADS;   // k_lm_solve: 4 waves, one per SIMD, all evaluate residual blocks
+// (kLmThreads, kLmGroupsMax, kMaxFrames, kEdgeBufs, kEdgePipeBufs: liodom_sizes.h)
 constexpr int kLmEvalThreads = kLmThreads;
 constexpr int kLmCtl = kLmThreads - 64;   // lane 0 of the last wave also runs the trust-region logic; the other waves prepare (compaction, register cache) meanwhile
-#ifndef LIODOM_LM_GROUPS_MAX
-#define LIODOM_LM_GROUPS_MAX 8
-#endif
-constexpr int kLmGroupsMax = LIODOM_LM_GROUPS_MAX;
 constexpr int kKnnGroup = 32;            // lanes cooperating on one query
-constexpr int kMaxFrames = 256;          // window frames supported by the LDS prefix tables
-constexpr int kEdgeBufs = 4;             // dense edge buffers: 0 / 1 / 2 odometry side (pipelined replay), 3 extraction side
-constexpr int kEdgePipeBufs = 3;
 constexpr int kEdgeBufX = 3;
 constexpr int kOvReplicas = 8;           // copies of the first solve's result, 4 KiB apart, for the polling k_knn workgroups
 constexpr int kOvGranules = 38;          // 19 doubles as {tag, 32 bits} granules
