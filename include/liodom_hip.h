@@ -490,7 +490,7 @@ typedef struct liodom_map_config_t {
   double voxel_zsize;          /* ~voxel_zsize,  :119-121  default 50 */
   double resolution;           /* ~resolution,   :123-125  default 0.4 */
   int32_t cell_capacity;       /* points per cell (after filtering, and filtered + appended during an update) */
-  int32_t max_update_points;   /* points per updateMap call */
+  int32_t max_update_points;   /* points per updateMap call; any value >= 1, whatever the other capacities are */
   int32_t max_modified_cells;  /* cells touched by one updateMap call (<= 256) */
   int32_t reserved;
 } liodom_map_config_t;
@@ -514,7 +514,9 @@ int liodom_map_update(liodom_map_t* m, const float* xyzi, int64_t n, const doubl
  * (liodom_mapping_node.cc:130-134, defaults 2 and 1).  Output order = the reference's loops. */
 int liodom_map_get_local(liodom_map_t* m, const double* T, int cells_xy, int cells_z, float* xyzi,
                          int64_t cap, int64_t* n_points);
-/* Map::getMap (src/map.cc:131-139): every cell in creation order. */
+/* Map::getMap (src/map.cc:131-139): every cell in creation order, for any number of cells up to max_cells: the point section
+ * of liodom_map_export_state's blob.  *n_points is the size of the whole result; LIODOM_ERR_CAPACITY (nothing written) if it
+ * is larger than cap. */
 int liodom_map_get_all(liodom_map_t* m, float* xyzi, int64_t cap, int64_t* n_points);
 int liodom_map_num_cells(liodom_map_t* m, int* n_cells);
 /* Wires a map to stream `stream` of an odometry handle created with mapping = 1, replaying the

@@ -89,9 +89,9 @@ struct MapView {
   int* old_rank;                 // [mod_cap][cell_cap]
   unsigned int* leaf_cnt;        // [mod_cap][cell_cap] points per output leaf
   unsigned int* leaf_start;      // [mod_cap][cell_cap] member list start (leaves with > 1 point)
-  int* members;                  // [mod_cap * cell_cap] cloud-order indices grouped by leaf
-  int2* multi;                   // [mod_cap * cell_cap] (mod index, output position) of the multi-point leaves
-  MapEntry* entries;             // [kMapLocalEntriesMax] plan of a concatenation
+  int* members;                  // [mod_cap * cell_cap + upd_cap] cloud-order indices grouped by leaf (bound: map_build)
+  int2* multi;                   // [(mod_cap * cell_cap + upd_cap + 1) / 2] (mod index, output position) of the multi-point leaves
+  MapEntry* entries;             // [kMapLocalEntriesMax] plan of a getLocalMap
 };
 
 __device__ __forceinline__ unsigned int map_hash(unsigned long long k, unsigned int mask) {
@@ -483,36 +483,8 @@ __global__ void k_map_local_plan(MapView m, const double* T_ptr, int cells_xy, i
   if (n_out) *n_out = total > out_cap ? out_cap : total;
 }
 
-// getMap (map.cc:131-139): every cell in cells_vector_ order.
-__global__ __launch_bounds__(1024) void k_map_all_plan(MapView m, int out_cap, int* n_out) {
-  __shared__ int sh_w[16];
-  __shared__ int sh_carry;
-  MapState& st = *m.st;
-  const int tid = threadIdx.x;
-  const int nc = min(st.n_cells, kMapLocalEntriesMax);
-  if (tid == 0) { sh_carry = 0; if (st.n_cells > kMapLocalEntriesMax) atomicOr(&st.status, MAP_STATUS_LOCAL_OVERFLOW); }
-  __syncthreads();
-  for (int base = 0; base < nc; base += 1024) {
-    const int c = base + tid;
-    const int cnt = c < nc ? m.cell_n[c] : 0;
-    int incl = cnt;
-    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if ((tid & 63) >= off) incl += t; }
-    if ((tid & 63) == 63) sh_w[tid >> 6] = incl;
-    __syncthreads();
-    int run = sh_carry + incl - cnt;
-    for (int q = 0; q < (tid >> 6); q++) run += sh_w[q];
-    if (c < nc) { MapEntry e; e.cell = c; e.offset = run; e.count = cnt; e.pad = 0; m.entries[c] = e; }
-    __syncthreads();
-    if (tid == 1023) sh_carry = run + cnt;
-    __syncthreads();
-  }
-  if (tid == 0) {
-    const int total = sh_carry;
-    st.n_entries = nc;
-    st.n_result = total;
-    if (n_out) *n_out = total > out_cap ? out_cap : total;
-  }
-}
+// getMap (map.cc:131-139), every cell in cells_vector_ order, has no plan of its own: liodom_map_get_all plans with k_map_pack_plan
+// and copies with k_map_pack (below), which hold any number of cells.  The entries above are getLocalMap's alone.
 
 // grid (x, entries): copies the planned cells to the output
 __global__ __launch_bounds__(256) void k_map_gather(MapView m, float4* out, int out_cap) {
@@ -675,9 +647,10 @@ __global__ __launch_bounds__(256) void k_map_init(MapView m) {
 // on the per-scan path: a map that never calls those entry points launches none of these kernels and allocates nothing for them.
 // The blob's head (header + cell records) and its point section are two device buffers; the host writes the rest of the header.
 // ---------------------------------------------------------------------------------------------
-// Export, step 1 (one workgroup): exclusive prefix over cell_n in creation order as in k_map_all_plan, but for any number of
-// cells (no plan entries: the records are the plan).  Writes the cell records behind the header and n_cells, status and
-// n_points into the header, where the host reads them.  `head` holds kMapStateHeaderBytes + max_cells records.
+// Export, step 1 (one workgroup): exclusive prefix over cell_n in creation order, chunk after chunk with a carry, for any number of
+// cells (no plan entries: the records are the plan); liodom_map_get_all plans with it too.  Writes the cell records behind the
+// header and n_cells, status and n_points into the header, where the host reads them.  `head` holds kMapStateHeaderBytes +
+// max_cells records.
 __global__ __launch_bounds__(1024) void k_map_pack_plan(MapView m, unsigned char* head) {
   __shared__ int sh_w[16];
   __shared__ long long sh_carry;
@@ -806,7 +779,7 @@ __device__ __forceinline__ int map_keep_cell(const MapKeepBox& b, const int* key
 }
 
 // Step 1.  Workgroup 0 plans: centre cell from T exactly as k_map_local_plan (translation truncated to int first, map.cc:144-151),
-// keep flags, exclusive scan over creation order (the scan of k_map_all_plan, any number of cells), and the bookkeeping arrays
+// keep flags, exclusive scan over creation order (the scan of k_map_pack_plan, any number of cells), and the bookkeeping arrays
 // compacted in place, chunk after chunk: a chunk's threads hold their cells' records in registers across the scan's barrier and
 // write to ids j <= c, i.e. to places of this chunk or of earlier ones, all read already; no place is written twice.
 // Workgroups 1 .. : the cell hash back to the state k_map_init leaves (independent of the plan; the move grid re-inserts).

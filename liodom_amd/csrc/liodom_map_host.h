@@ -78,8 +78,16 @@ int map_build(liodom_map* mp, const liodom_map_config_t* c, hipStream_t stream) 
   MAP_ALLOC(m.bitmap, (size_t)m.mod_cap * m.words); MAP_ALLOC(m.wprefix, (size_t)m.mod_cap * m.words);
   MAP_ALLOC(m.old_pos, (size_t)m.mod_cap * m.cell_cap); MAP_ALLOC(m.old_rank, (size_t)m.mod_cap * m.cell_cap);
   MAP_ALLOC(m.leaf_cnt, (size_t)m.mod_cap * m.cell_cap); MAP_ALLOC(m.leaf_start, (size_t)m.mod_cap * m.cell_cap);
-  MAP_ALLOC(m.members, (size_t)m.mod_cap * m.cell_cap);
-  MAP_ALLOC(m.multi, (size_t)m.mod_cap * m.cell_cap / 2 + 1);
+  // Member lists of one update.  k_map_alloc advances `cursor` by leaf_cnt for every output leaf with more than one point and
+  // counts such a leaf in n_multi.  Every item of the update — an old point of a modified cell or a new point — is counted into
+  // at most one leaf_cnt (k_map_count), so cursor <= items <= sum over the n_mod modified cells of cell_n + n_new
+  // <= mod_cap * cell_cap + upd_cap: old AND new points, e.g. a full cell of single-point leaves that each receive one more
+  // point.  A leaf in `multi` holds at least two items, so n_multi <= that / 2.  The three factors are the dimensions of the
+  // arrays the items are read from (mod_list, a slab, new_pts): the bound holds whatever an update contains and whichever
+  // status bits it raises, and needs no relation between max_update_points and the other capacities.
+  const size_t items_max = (size_t)m.mod_cap * m.cell_cap + (size_t)m.upd_cap;
+  MAP_ALLOC(m.members, items_max);
+  MAP_ALLOC(m.multi, (items_max + 1) / 2);
   MAP_ALLOC(m.entries, liodom_dev::kMapLocalEntriesMax);
   const int n_init = std::max(m.ctable, m.max_cells);
   hipLaunchKernelGGL(liodom_dev::k_map_init, dim3((n_init + 255) / 256), dim3(256), 0, mp->stream, m);
@@ -464,16 +472,26 @@ int liodom_map_get_local_batch(liodom_map_t* mp, const double* T, int n, int cel
   return LIODOM_OK;
 }
 
+// Map::getMap (map.cc:131-139): every cell in cells_vector_ order — a blob's point section.  Planned and copied by the export's
+// kernels, which hold any number of cells (the plan entries of getLocalMap hold kMapLocalEntriesMax).
 int liodom_map_get_all(liodom_map_t* mp, float* xyzi, int64_t cap, int64_t* n_points) {
+  using namespace liodom_dev;
   if (!mp || cap < 0 || (cap > 0 && !xyzi)) { g_last_error = "liodom_map_get_all: invalid argument"; return LIODOM_ERR_INVALID_ARG; }
   HIP_TRY(hipSetDevice(mp->device));
-  int rc = map_ensure_out(mp, cap);
+  MapStateHeader hd;
+  int rc = map_state_plan(mp, &hd, "liodom_map_get_all");      // (synchronises the stream the map's work is enqueued on)
   if (rc) return rc;
-  using namespace liodom_dev;
-  hipLaunchKernelGGL(k_map_all_plan, dim3(1), dim3(1024), 0, mp->stream, mp->m, mp->out_cap, mp->d_out_n);
-  hipLaunchKernelGGL(k_map_gather, dim3(16, 256), dim3(256), 0, mp->stream, mp->m, mp->d_out, mp->out_cap);
+  if (n_points) *n_points = hd.n_points;
+  if (hd.n_points > cap) { g_last_error = "liodom_map: output buffer too small"; return LIODOM_ERR_CAPACITY; }
+  const int n = (int)hd.n_points;
+  if (n == 0) return LIODOM_OK;
+  if ((rc = map_ensure_out(mp, n))) return rc;
+  const int xb = std::min(16, (mp->m.cell_cap + 255) / 256), yb = std::min(hd.n_cells, 256);
+  hipLaunchKernelGGL(k_map_pack, dim3(xb, yb), dim3(256), 0, mp->stream, mp->m, mp->d_head, mp->d_out, mp->out_cap);
   HIP_TRY(hipGetLastError());
-  return map_fetch_result(mp, xyzi, cap, n_points);
+  HIP_TRY(hipMemcpyAsync(xyzi, mp->d_out, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  return LIODOM_OK;
 }
 
 int liodom_map_num_cells(liodom_map_t* mp, int* n_cells) {
