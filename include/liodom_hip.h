@@ -717,6 +717,52 @@ int liodom_map_search_pose(liodom_map_t* m, const float* edges_xyzi, int n_edges
                            liodom_pose_search_result_t* out, double* T_out /*optional, n_candidates x 12*/,
                            int32_t* hits_out /*optional, n_candidates x 2*/);
 
+/* ---- relocalising over a wide window: the same grid, the same ranking, by branch-and-bound (no counterpart in the reference;
+ * DESIGN.md §3 "Branch-and-bound over the candidate grid").  liodom_map_search_pose scores every candidate and
+ * takes at most 2^20; this call takes up to 2^31 - 1 (per axis and in all) and scores few of them.
+ *
+ * A node is a rectangle of candidates ix0..ix1 x iy0..iy1 that share ia and iz.  T_lo is the matrix of (ix0, iy0), t_hi = T[3], T[7]
+ * of (ix1, iy1); the rest of the matrix is the same for the whole node.  Leaf of a float coordinate p: floorf(p * (1.f /
+ * (float)resolution)), "in range" iff it lies in [-2^20, 2^20).  Block set B_h, h = 1 .. 21: the keys (lx >> h, ly >> h, lz) of every
+ * finite point of the map whose three leaves are in range (arithmetic shift; blocks in x and y only), rebuilt from the map as it is by
+ * every call, for the levels the call uses: nothing is cached.  Per edge e with q_lo = float(T_lo * e), q_hi = float(T_hi * e):
+ *   ub_0 = 1 iff B_h holds a key (bx, by, lz) with bx in [leaf(q_lo.x) >> h, leaf(q_hi.x) >> h], by likewise, lz = leaf(q.z);
+ *   ub_r = the same with the ranges [leaf(q_lo.x + (-1.f) * leaf) >> h, leaf(q_hi.x + 1.f * leaf) >> h] and lz among the leaves of
+ *          q.z + (j - 1) * leaf, j = 0, 1, 2 (radius 0: ub_r = ub_0).
+ * An edge with a non-finite coordinate counts in neither.  A finite edge counts in both, with no lookup, if one of the leaves above
+ * is not in range (non-finite extremes included) or a range spans more than three blocks.  The node's bound is the sum of ub_r plus
+ * the sum of ub_0 over the edges: it is >= hits_r + hits_0 of every candidate of the node, whatever the map, the edges and the level.
+ *
+ *   liodom_map_bound_nodes   ub[2 i], ub[2 i + 1] = sums of ub_r, ub_0 of node i (T_lo + 12 i, t_hi + 2 i) at one level 1 .. 21.
+ *       n <= 2^20; n = 0 or n_edges = 0: LIODOM_OK (zero bounds).
+ *   liodom_pose_search_bnb_default   batch = 1024.
+ *   liodom_map_search_pose_bnb   the best candidate of the grid `s`: `out` is field for field what liodom_map_search_pose returns for
+ *       the same inputs.  Roots: one node per (ia, iz), 2^K wide, covering the xy grid; a node splits into up to four children
+ *       clipped to the grid, each bounded at the level liodom_amd/csrc/reloc_bnb.h gives for its width, a child's bound being
+ *       min(its own, its parent's).  Rounds: drop the open nodes that cannot win (bound < the best score, or equal with a lowest
+ *       index above the best's), take the `batch` with the largest bound (ties to the lowest index), score the width-1 nodes among
+ *       them exactly (k_map_score_poses, unchanged) and bound the children of the others; stop when nothing is left.  Yaw and z are
+ *       enumerated, not bounded.  opt = NULL or batch = 0: the default; batch 1 .. 65536.  stats (optional): what the search did.
+ *       n_edges = 0 or a map without points: index 0 and zero counts, nothing is searched.
+ * Argument rules, the limit on n_edges, the threading rule, the read-only guarantee and the error codes are those of
+ * liodom_map_search_pose; a grid above 2^31 - 1 candidates and a batch outside its range are LIODOM_ERR_INVALID_ARG with nothing
+ * computed.  The first call allocates the block tables: per level used, 8 bytes x the power of two >= 2 x the map's points. */
+typedef struct liodom_pose_search_bnb_t {
+  int32_t batch;               /* nodes taken per round; 0: the default */
+  int32_t reserved[7];
+} liodom_pose_search_bnb_t;
+typedef struct liodom_pose_search_stats_t {
+  int64_t n_candidates, nodes_bounded, candidates_scored;
+  int32_t rounds, levels_built;
+  int32_t reserved[2];
+} liodom_pose_search_stats_t;
+void liodom_pose_search_bnb_default(liodom_pose_search_bnb_t* opt);
+int liodom_map_bound_nodes(liodom_map_t* m, const float* edges_xyzi, int n_edges, const double* T_lo /*n x 12*/,
+                           const double* t_hi /*n x 2*/, int n, int level, int radius /*0 | 1*/, int32_t* ub /*n x 2: ub_r, ub_0*/);
+int liodom_map_search_pose_bnb(liodom_map_t* m, const float* edges_xyzi, int n_edges, const liodom_pose_search_t* s,
+                               const liodom_pose_search_bnb_t* opt /*NULL: defaults*/, liodom_pose_search_result_t* out,
+                               liodom_pose_search_stats_t* stats /*optional*/);
+
 #ifdef __cplusplus
 }
 #endif

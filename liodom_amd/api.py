@@ -14,6 +14,7 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
                                                   "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
+                                                  "kernels_reloc_bnb.h", "reloc_bnb.h",
                                                   "liodom_sizes.h", "handle_plan.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -167,6 +168,17 @@ class PoseSearchResult(C.Structure):
     """liodom_pose_search_result_t: the best candidate of liodom_map_search_pose."""
     _fields_ = [("best_index", C.c_int32), ("hits_r", C.c_int32), ("hits_0", C.c_int32), ("n_candidates", C.c_int32),
                 ("pose", C.c_double * 7), ("T", C.c_double * 12)]
+
+
+class PoseSearchBnb(C.Structure):
+    """liodom_pose_search_bnb_t: the options of liodom_map_search_pose_bnb."""
+    _fields_ = [("batch", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class PoseSearchStats(C.Structure):
+    """liodom_pose_search_stats_t: what a liodom_map_search_pose_bnb call did."""
+    _fields_ = [("n_candidates", C.c_int64), ("nodes_bounded", C.c_int64), ("candidates_scored", C.c_int64),
+                ("rounds", C.c_int32), ("levels_built", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class EdgeTicket(C.Structure):
@@ -545,6 +557,12 @@ def load():
     L.liodom_pose_search_default.argtypes = [C.POINTER(PoseSearch)]
     L.liodom_map_search_pose.restype = C.c_int
     L.liodom_map_search_pose.argtypes = [vp, fp, C.c_int, C.POINTER(PoseSearch), C.POINTER(PoseSearchResult), dp, ip]
+    L.liodom_pose_search_bnb_default.argtypes = [C.POINTER(PoseSearchBnb)]
+    L.liodom_map_bound_nodes.restype = C.c_int
+    L.liodom_map_bound_nodes.argtypes = [vp, fp, C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, ip]
+    L.liodom_map_search_pose_bnb.restype = C.c_int
+    L.liodom_map_search_pose_bnb.argtypes = [vp, fp, C.c_int, C.POINTER(PoseSearch), C.POINTER(PoseSearchBnb), C.POINTER(PoseSearchResult),
+                                             C.POINTER(PoseSearchStats)]
     L.liodom_map_config_default.argtypes = [C.POINTER(MapConfig)]
     L.liodom_map_create.restype = C.c_int
     L.liodom_map_create.argtypes = [C.POINTER(MapConfig), C.POINTER(vp)]
@@ -645,6 +663,7 @@ EXPORTED_SYMBOLS = [
     "liodom_map_evict", "liodom_map_merge_state",
     "liodom_attach_map_reader", "liodom_seed_stream", "liodom_map_get_local_batch",
     "liodom_map_score_poses", "liodom_pose_search_default", "liodom_map_search_pose",
+    "liodom_pose_search_bnb_default", "liodom_map_bound_nodes", "liodom_map_search_pose_bnb",
 ]
 
 
@@ -1110,14 +1129,16 @@ class Liodom:
     def relocalize(self, map, scan, height, width, centre, levels, min_fraction=0.5, stream=0):
         """Finds the stream's pose in a saved map from a rough guess and seeds the stream with it.  The scan's edges
         (extract_edges) are scored against `map` on one candidate grid per level (Map.search_pose; `levels` is a list of dicts of its
-        grid keywords), the first around `centre` = [qx qy qz qw tx ty tz], each later one around the level before's best.  If the last
+        grid keywords; a level with bnb=True goes to Map.search_pose_bnb instead, with its batch= if given), the first around `centre` = [qx qy qz qw tx ty tz], each later one around the level before's best.  If the last
         level's score / (2 * n_edges) >= min_fraction the stream is seeded with the best pose (seed_stream) and
         dict(pose, hits_r, hits_0, n_edges, fraction, levels=[each level's result]) comes back: process the SAME scan next.  Otherwise
         None, and the stream is as it was but for the edges extract_edges left in it."""
         edges = self.extract_edges(scan, height, width, stream=stream)["edges"]
         pose, found = np.array(centre, dtype=np.float64).reshape(7), []
         for grid in levels:
-            found.append(map.search_pose(edges, pose, **grid))
+            grid = dict(grid)
+            bnb, batch = grid.pop("bnb", False), grid.pop("batch", 0)
+            found.append(map.search_pose_bnb(edges, pose, batch=batch, **grid) if bnb else map.search_pose(edges, pose, **grid))
             pose = found[-1]["pose"]
         if not found or edges.shape[0] == 0:
             return None
@@ -1284,6 +1305,36 @@ class Map:
         if want_hits:
             out["hits"] = hits
         return out
+
+    def bound_nodes(self, edges, T_lo, t_hi, level, radius=1):
+        """Upper bounds of nodes of a candidate grid (liodom_map_bound_nodes): T_lo [n, 3, 4] (or [n, 12]) the matrices of the nodes'
+        lowest children, t_hi [n, 2] = T[3], T[7] of their highest, all at block level `level` (1 .. 21) -> int32 [n, 2] (ub_r, ub_0).
+        Read-only on the map."""
+        e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
+        T_lo = np.ascontiguousarray(T_lo, dtype=np.float64).reshape(-1, 12)
+        t_hi = np.ascontiguousarray(t_hi, dtype=np.float64).reshape(-1, 2)
+        if t_hi.shape[0] != T_lo.shape[0]:
+            raise ValueError("T_lo and t_hi differ in length")
+        ub = np.zeros((T_lo.shape[0], 2), np.int32)
+        self._chk(self._L.liodom_map_bound_nodes(self.h, _fp(e), e.shape[0], _dp(T_lo), _dp(t_hi), T_lo.shape[0], int(level), int(radius), _ip(ub)))
+        return ub
+
+    def search_pose_bnb(self, edges, centre, batch=0, **grid):
+        """Map.search_pose's result for the same grid by branch-and-bound (liodom_map_search_pose_bnb): up to 2^31 - 1 candidates,
+        few of them scored.  batch: nodes taken per round, 0 = the library's default.  -> search_pose's dict plus
+        stats = dict(n_candidates, nodes_bounded, candidates_scored, rounds, levels_built)."""
+        e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
+        s = make_pose_search(centre, **grid)
+        opt = PoseSearchBnb()
+        self._L.liodom_pose_search_bnb_default(C.byref(opt))
+        if batch:
+            opt.batch = int(batch)
+        r, st = PoseSearchResult(), PoseSearchStats()
+        self._chk(self._L.liodom_map_search_pose_bnb(self.h, _fp(e), e.shape[0], C.byref(s), C.byref(opt), C.byref(r), C.byref(st)))
+        return dict(best_index=int(r.best_index), hits_r=int(r.hits_r), hits_0=int(r.hits_0), n_candidates=int(r.n_candidates),
+                    pose=np.array(r.pose[:]), T=np.array(r.T[:]).reshape(3, 4),
+                    stats=dict(n_candidates=int(st.n_candidates), nodes_bounded=int(st.nodes_bounded), candidates_scored=int(st.candidates_scored),
+                               rounds=int(st.rounds), levels_built=int(st.levels_built)))
 
     def prune(self, T34=None, keep_xy=2, keep_z=1):
         """Drops every cell outside the box of keep_xy / keep_z cells around the pose's cell (liodom_map_prune); returns the

@@ -1032,3 +1032,4 @@ __global__ __launch_bounds__(256) void k_map_merge(MapView m, const unsigned cha
 }  // namespace liodom_dev
 
 #include "kernels_reloc.h"
+#include "kernels_reloc_bnb.h"

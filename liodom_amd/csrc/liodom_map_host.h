@@ -1,8 +1,11 @@
 // Host side of the device map (C-ABI liodom_map_* of include/liodom_hip.h).  Included by
 // liodom_hip.hip (same translation unit: shares HIP_TRY / g_last_error).
 #pragma once
+#include <chrono>
+
 #include "liodom_map.h"
 #include "reloc_candidates.h"
+#include "reloc_bnb.h"
 
 struct liodom_map {
   liodom_map_config_t cfg;
@@ -24,6 +27,10 @@ struct liodom_map {
   size_t batch_bytes = 0;
   unsigned int* d_occ = nullptr;     // liodom_map_score_poses / _search_pose: leaf occupancy [occ_cells][words] (the first call allocates it for
   int occ_cells = 0;                 // the cells the map holds then, a map that has grown since regrows it)
+  unsigned long long* d_blocks = nullptr;   // liodom_map_search_pose_bnb / _bound_nodes: the block tables of the levels a call uses (the
+  size_t blocks_entries = 0;               // first call allocates them, a call that needs more regrows them)
+  unsigned char* h_pin = nullptr;          // liodom_map_search_pose_bnb: pinned host staging of a round's nodes, candidates and counts
+  size_t pin_bytes = 0;
   // attachments to a handle's streams (liodom_attach_mapper* / liodom_attach_map_reader): the map runs on the handle's HIP stream
   // while n_attached > 0 and gets one of its own again when the last attachment goes
   int n_attached = 0, n_readers = 0;
@@ -173,6 +180,8 @@ void map_free(liodom_map* mp) {
   if (mp->d_out) (void)hipFree(mp->d_out);
   if (mp->d_batch) (void)hipFree(mp->d_batch);
   if (mp->d_occ) (void)hipFree(mp->d_occ);
+  if (mp->d_blocks) (void)hipFree(mp->d_blocks);
+  if (mp->h_pin) (void)hipHostFree(mp->h_pin);
   if (mp->own_stream && mp->stream) (void)hipStreamDestroy(mp->stream);
   delete mp;
 }
@@ -347,6 +356,68 @@ int map_score(liodom_map* mp, const float* edges, int n_edges, const double* T, 
   HIP_TRY(hipStreamSynchronize(mp->stream));      // (the staged edges and poses are the caller's memory)
   return LIODOM_OK;
 }
+
+// ---- relocalising over a wide window (kernels_reloc_bnb.h, reloc_bnb.h) ----
+// The cells the map holds now and the points in them (the sum of cell_n); synchronises the map's stream.
+int map_count_points(liodom_map* mp, int* n_cells, int64_t* n_points) {
+  HIP_TRY(hipSetDevice(mp->device));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  liodom_dev::MapState st;
+  HIP_TRY(hipMemcpy(&st, mp->m.st, sizeof(st), hipMemcpyDeviceToHost));
+  *n_cells = std::max(0, std::min(st.n_cells, mp->m.max_cells));
+  std::vector<int> cnt((size_t)*n_cells);
+  if (*n_cells > 0) HIP_TRY(hipMemcpy(cnt.data(), mp->m.cell_n, sizeof(int) * (size_t)*n_cells, hipMemcpyDeviceToHost));
+  *n_points = 0;
+  for (int c : cnt) *n_points += std::max(0, std::min(c, mp->m.cell_cap));
+  return LIODOM_OK;
+}
+
+// The leaf occupancy of the map as it is now, as map_score builds it (n_cells > 0), on the map's stream.
+int map_build_occ(liodom_map* mp, int n_cells) {
+  using namespace liodom_dev;
+  const MapView& m = mp->m;
+  int rc = map_ensure_occ(mp, n_cells);
+  if (rc) return rc;
+  const size_t n16 = ((size_t)n_cells * (size_t)m.words + 3) / 4;
+  hipLaunchKernelGGL(k_map_occ_clear, dim3((unsigned)std::min<size_t>(2048, (n16 + 255) / 256)), dim3(256), 0, mp->stream, m, mp->d_occ, mp->occ_cells);
+  hipLaunchKernelGGL(k_map_occ_build, dim3(std::min(16, (m.cell_cap + 255) / 256), std::min(n_cells, 256)), dim3(256), 0, mp->stream, m, mp->d_occ, mp->occ_cells);
+  HIP_TRY(hipGetLastError());
+  return LIODOM_OK;
+}
+
+// The block tables of the levels whose bit is set in `levels`, built from the map as it is now, on the map's stream: each a power
+// of two >= 2 * n_points (and >= 64) entries, zeroed and filled by this call.
+int map_build_blocks(liodom_map* mp, unsigned int levels, int n_cells, int64_t n_points, liodom_dev::BlockTables* bt) {
+  using namespace liodom_dev;
+  size_t entries = 64;
+  while ((int64_t)entries < 2 * n_points) entries <<= 1;
+  int n_levels = 0;
+  for (int h = 0; h <= kRelocBnbLevelMax; h++) bt->slot[h] = (h >= 1 && ((levels >> h) & 1u)) ? n_levels++ : -1;
+  const size_t total = entries * (size_t)std::max(n_levels, 1);
+  if (mp->blocks_entries < total) {
+    HIP_TRY(hipStreamSynchronize(mp->stream));
+    if (mp->d_blocks) { (void)hipFree(mp->d_blocks); mp->d_blocks = nullptr; mp->blocks_entries = 0; }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&mp->d_blocks), sizeof(unsigned long long) * total));
+    mp->blocks_entries = total;
+  }
+  bt->base = mp->d_blocks;
+  bt->mask = (unsigned int)(entries - 1);
+  hipLaunchKernelGGL(k_map_blocks_clear, dim3((unsigned)std::min<size_t>(2048, (total / 2 + 255) / 256)), dim3(256), 0, mp->stream, mp->d_blocks, total);
+  if (n_cells > 0 && n_levels > 0)
+    hipLaunchKernelGGL(k_map_blocks_build, dim3(std::min(16, (mp->m.cell_cap + 255) / 256), std::min(n_cells, 256)), dim3(256), 0, mp->stream, mp->m, *bt);
+  HIP_TRY(hipGetLastError());
+  return LIODOM_OK;
+}
+
+// LIODOM_MAP_STATE_TIMING=1: liodom_map_search_pose_bnb reports where its time went (tools/relocalize_bnb_cost.py reads the line).
+// A host clock around work that ends in a synchronise of the map's stream.
+struct MapBnbClock {
+  bool on;
+  double build = 0.0, bound = 0.0, exact = 0.0;
+  std::chrono::steady_clock::time_point t0;
+  MapBnbClock() { const char* e = std::getenv("LIODOM_MAP_STATE_TIMING"); on = e && e[0] == '1'; t0 = std::chrono::steady_clock::now(); }
+  double ms_since(std::chrono::steady_clock::time_point a) const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); }
+};
 
 }  // namespace
 
@@ -723,6 +794,145 @@ int liodom_map_search_pose(liodom_map_t* mp, const float* edges_xyzi, int n_edge
   liodom_dev::reloc_candidate_pose(s, best[0], out->pose);
   std::memcpy(out->T, &T[12 * (size_t)best[0]], sizeof(double) * 12);
   if (T_out) std::memcpy(T_out, T.data(), sizeof(double) * 12 * (size_t)n);
+  return LIODOM_OK;
+}
+
+void liodom_pose_search_bnb_default(liodom_pose_search_bnb_t* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof(*o));
+  o->batch = liodom_dev::kRelocBnbBatchDefault;
+}
+
+int liodom_map_bound_nodes(liodom_map_t* mp, const float* edges_xyzi, int n_edges, const double* T_lo, const double* t_hi, int n, int level, int radius,
+                           int32_t* ub) {
+  using namespace liodom_dev;
+  int rc = map_score_check(mp, edges_xyzi, n_edges, "liodom_map_bound_nodes");
+  if (rc) return rc;
+  if (n < 0 || n > kRelocCandidatesMax || (n > 0 && (!T_lo || !t_hi || !ub)) || (radius != 0 && radius != 1) || level < 1 || level > kRelocBnbLevelMax) {
+    g_last_error = "liodom_map_bound_nodes: null nodes or bounds, a count that is negative or above 2^20, a level outside 1 .. 21, or a radius that is not 0 or 1";
+    return LIODOM_ERR_INVALID_ARG;
+  }
+  if (n == 0) return LIODOM_OK;
+  int n_cells = 0;
+  int64_t n_points = 0;
+  if ((rc = map_count_points(mp, &n_cells, &n_points))) return rc;
+  const size_t lo_bytes = sizeof(double) * 12 * (size_t)n, hi_bytes = sizeof(double) * 2 * (size_t)n, ub_bytes = sizeof(int) * 2 * (size_t)n;
+  if ((rc = map_ensure_batch(mp, lo_bytes + hi_bytes + ub_bytes))) return rc;
+  double* d_lo = reinterpret_cast<double*>(mp->d_batch);
+  double* d_hi = reinterpret_cast<double*>(mp->d_batch + lo_bytes);
+  int* d_ub = reinterpret_cast<int*>(mp->d_batch + lo_bytes + hi_bytes);
+  BlockTables bt;
+  if ((rc = map_build_blocks(mp, 1u << level, n_cells, n_points, &bt))) return rc;
+  if (n_edges > 0) HIP_TRY(hipMemcpyAsync(mp->d_in, edges_xyzi, sizeof(float4) * (size_t)n_edges, hipMemcpyHostToDevice, mp->stream));
+  HIP_TRY(hipMemcpyAsync(d_lo, T_lo, lo_bytes, hipMemcpyHostToDevice, mp->stream));
+  HIP_TRY(hipMemcpyAsync(d_hi, t_hi, hi_bytes, hipMemcpyHostToDevice, mp->stream));
+  hipLaunchKernelGGL(k_map_bound_nodes, dim3((n + kRelocWaves - 1) / kRelocWaves), dim3(kRelocThreads), 0, mp->stream, mp->m, bt, mp->d_in, n_edges, d_lo, d_hi,
+                     (const int*)nullptr, level, n, radius, (float)mp->cfg.resolution, d_ub);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(ub, d_ub, ub_bytes, hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  return LIODOM_OK;
+}
+
+int liodom_map_search_pose_bnb(liodom_map_t* mp, const float* edges_xyzi, int n_edges, const liodom_pose_search_t* s, const liodom_pose_search_bnb_t* opt,
+                               liodom_pose_search_result_t* out, liodom_pose_search_stats_t* stats) {
+  using namespace liodom_dev;
+  int rc = map_score_check(mp, edges_xyzi, n_edges, "liodom_map_search_pose_bnb");
+  if (rc) return rc;
+  if (!s || !out) { g_last_error = "liodom_map_search_pose_bnb: null search or result"; return LIODOM_ERR_INVALID_ARG; }
+  int batch = opt ? opt->batch : 0;
+  if (batch == 0) batch = kRelocBnbBatchDefault;
+  if (batch < 1 || batch > kRelocBnbBatchMax) { g_last_error = "liodom_map_search_pose_bnb: batch outside 1 .. 65536"; return LIODOM_ERR_INVALID_ARG; }
+  const char* why = "";
+  const int64_t n = reloc_candidate_count(s, &why, kRelocBnbCandidatesMax);
+  if (n <= 0) { g_last_error = std::string("liodom_map_search_pose_bnb: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  MapBnbClock clk;
+  const RelocCentre centre = reloc_centre(s);
+  const RelocBnbGrid grid = reloc_bnb_grid(s);
+  int n_cells = 0;
+  int64_t n_points = 0;
+  if ((rc = map_count_points(mp, &n_cells, &n_points))) return rc;
+  RelocBnbResult res{0, 0, 0, 0, 0, 0};
+  int levels_built = 0;
+  if (n_edges > 0 && n_points > 0) {      // (otherwise every candidate scores 0: the lowest index wins)
+    const MapView& m = mp->m;
+    // One round's staging, the same layout in pinned host memory and in the batch buffer: the nodes to bound ([cnt x 12] T_lo,
+    // [cnt x 2] t_hi, [cnt] levels: one upload), their bounds, the candidates to score ([cnt x 12] T) and their counts.
+    const size_t nb = (size_t)batch, nk = 4 * nb;      // candidates scored, nodes bounded in one round at the most
+    const size_t node_bytes = sizeof(double) * 14 + sizeof(int);
+    const size_t off_ub = (nk * node_bytes + 15) / 16 * 16, off_T = off_ub + sizeof(int) * 2 * nk, off_hits = off_T + sizeof(double) * 12 * nb;
+    const size_t stage_bytes = off_hits + sizeof(int) * 2 * nb;
+    if ((rc = map_ensure_batch(mp, stage_bytes))) return rc;
+    if (mp->pin_bytes < stage_bytes) {
+      if (mp->h_pin) { (void)hipHostFree(mp->h_pin); mp->h_pin = nullptr; mp->pin_bytes = 0; }
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&mp->h_pin), stage_bytes, hipHostMallocDefault));
+      mp->pin_bytes = stage_bytes;
+    }
+    unsigned char* hp = mp->h_pin;
+    unsigned char* dp = mp->d_batch;
+    // the level of a node 2^k wide, and the tables of the levels the tree has (a root is never bounded: k < K)
+    int level_of_k[32];
+    unsigned int levels = 0;
+    for (int k = 0; k < grid.K; k++) { level_of_k[k] = reloc_bnb_level((int64_t)1 << k, s->step_xy, mp->cfg.resolution, s->radius); levels |= 1u << level_of_k[k]; }
+    for (int h = 1; h <= kRelocBnbLevelMax; h++) levels_built += (int)((levels >> h) & 1u);
+    const auto t_build = std::chrono::steady_clock::now();
+    BlockTables bt;
+    if ((rc = map_build_occ(mp, n_cells)) || (rc = map_build_blocks(mp, levels, n_cells, n_points, &bt))) return rc;
+    HIP_TRY(hipMemcpyAsync(mp->d_in, edges_xyzi, sizeof(float4) * (size_t)n_edges, hipMemcpyHostToDevice, mp->stream));
+    if (clk.on) { HIP_TRY(hipStreamSynchronize(mp->stream)); clk.build = clk.ms_since(t_build); }
+    const float leaf = (float)mp->cfg.resolution;
+    auto bound_fn = [&](const RelocBnbNode* nodes, size_t cnt, int32_t* ub) -> int {
+      const auto t = std::chrono::steady_clock::now();
+      const size_t hi_at = sizeof(double) * 12 * cnt, lv_at = sizeof(double) * 14 * cnt;
+      double* h_lo = reinterpret_cast<double*>(hp);
+      double* h_hi = reinterpret_cast<double*>(hp + hi_at);
+      int* h_lv = reinterpret_cast<int*>(hp + lv_at);
+      for (size_t i = 0; i < cnt; i++) {
+        reloc_bnb_extremes(s, centre, grid, nodes[i], h_lo + 12 * i, h_hi + 2 * i);
+        h_lv[i] = level_of_k[nodes[i].k];
+      }
+      HIP_TRY(hipMemcpyAsync(dp, hp, node_bytes * cnt, hipMemcpyHostToDevice, mp->stream));
+      hipLaunchKernelGGL(k_map_bound_nodes, dim3((unsigned)((cnt + kRelocWaves - 1) / kRelocWaves)), dim3(kRelocThreads), 0, mp->stream, m, bt, mp->d_in, n_edges,
+                         reinterpret_cast<const double*>(dp), reinterpret_cast<const double*>(dp + hi_at), reinterpret_cast<const int*>(dp + lv_at), 0, (int)cnt,
+                         s->radius, leaf, reinterpret_cast<int*>(dp + off_ub));
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(hp + off_ub, dp + off_ub, sizeof(int) * 2 * cnt, hipMemcpyDeviceToHost, mp->stream));
+      HIP_TRY(hipStreamSynchronize(mp->stream));
+      std::memcpy(ub, hp + off_ub, sizeof(int) * 2 * cnt);
+      if (clk.on) clk.bound += clk.ms_since(t);
+      return LIODOM_OK;
+    };
+    auto exact_fn = [&](const int64_t* index, size_t cnt, int32_t* hits) -> int {
+      const auto t = std::chrono::steady_clock::now();
+      double* h_T = reinterpret_cast<double*>(hp + off_T);
+      for (size_t i = 0; i < cnt; i++) reloc_candidate_matrix(s, centre, index[i], h_T + 12 * i);
+      HIP_TRY(hipMemcpyAsync(dp + off_T, h_T, sizeof(double) * 12 * cnt, hipMemcpyHostToDevice, mp->stream));
+      hipLaunchKernelGGL(k_map_score_poses, dim3((unsigned)((cnt + kRelocWaves - 1) / kRelocWaves)), dim3(kRelocThreads), 0, mp->stream, m, mp->d_occ, mp->occ_cells,
+                         mp->d_in, n_edges, reinterpret_cast<const double*>(dp + off_T), (int)cnt, s->radius, leaf, reinterpret_cast<int*>(dp + off_hits));
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(hp + off_hits, dp + off_hits, sizeof(int) * 2 * cnt, hipMemcpyDeviceToHost, mp->stream));
+      HIP_TRY(hipStreamSynchronize(mp->stream));
+      std::memcpy(hits, hp + off_hits, sizeof(int) * 2 * cnt);
+      if (clk.on) clk.exact += clk.ms_since(t);
+      return LIODOM_OK;
+    };
+    const int32_t max_score = (int32_t)std::min<int64_t>(2 * (int64_t)n_edges, 0x7fffffff);
+    if ((rc = reloc_bnb_search(grid, max_score, batch, bound_fn, exact_fn, &res))) return rc;
+    if (res.best_index < 0 || res.best_index >= n) { g_last_error = "liodom_map_search_pose_bnb: inconsistent result"; return LIODOM_ERR_HIP; }
+  }
+  out->best_index = (int32_t)res.best_index; out->hits_r = res.hits_r; out->hits_0 = res.hits_0; out->n_candidates = (int32_t)n;
+  reloc_candidate_pose(s, res.best_index, out->pose);
+  reloc_candidate_matrix(s, centre, res.best_index, out->T);
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->n_candidates = n; stats->nodes_bounded = res.nodes_bounded; stats->candidates_scored = res.candidates_scored;
+    stats->rounds = (int32_t)std::min<int64_t>(res.rounds, 0x7fffffff); stats->levels_built = levels_built;
+  }
+  if (clk.on) {
+    const double total = clk.ms_since(clk.t0);
+    std::fprintf(stderr, "liodom_map_search_pose_bnb: build %.3f ms, bound %.3f ms, exact %.3f ms, host %.3f ms, total %.3f ms\n", clk.build, clk.bound,
+                 clk.exact, total - clk.build - clk.bound - clk.exact, total);
+  }
   return LIODOM_OK;
 }
 

@@ -20,8 +20,9 @@ constexpr int64_t kRelocCandidatesMax = 1 << 20;
 
 inline bool reloc_finite(double x) { return (x - x) == 0.0; }      // (inf - inf and NaN - NaN are NaN)
 
-// Number of candidates of a valid grid; 0 and *why (optional) set for one liodom_map_search_pose refuses.
-inline int64_t reloc_candidate_count(const liodom_pose_search_t* s, const char** why) {
+// Number of candidates of a valid grid; 0 and *why (optional) set for one liodom_map_search_pose refuses.  `limit`: the most
+// candidates per axis and in all (liodom_map_search_pose_bnb lifts it to kRelocBnbCandidatesMax, reloc_bnb.h).
+inline int64_t reloc_candidate_count(const liodom_pose_search_t* s, const char** why, int64_t limit = kRelocCandidatesMax) {
   const char* dummy;
   if (!why) why = &dummy;
   *why = "";
@@ -40,9 +41,10 @@ inline int64_t reloc_candidate_count(const liodom_pose_search_t* s, const char**
   int64_t n = 1;
   const int32_t half[4] = {s->nx, s->ny, s->nyaw, s->nz};
   for (int a = 0; a < 4; a++) {
-    if (half[a] > kRelocCandidatesMax) { *why = "more than 2^20 candidates"; return 0; }
+    const char* many = limit == kRelocCandidatesMax ? "more than 2^20 candidates" : "more candidates than the call takes";
+    if (half[a] > limit) { *why = many; return 0; }
     n *= 2 * (int64_t)half[a] + 1;
-    if (n > kRelocCandidatesMax) { *why = "more than 2^20 candidates"; return 0; }
+    if (n > limit) { *why = many; return 0; }
   }
   return n;
 }
@@ -76,6 +78,13 @@ inline void reloc_candidate_indices(const liodom_pose_search_t* s, int64_t index
   *iz = (int)index - s->nz;
 }
 
+// the translation of a candidate: what its matrix holds in T[3], T[7], T[11]
+inline void reloc_candidate_translation(const liodom_pose_search_t* s, const RelocCentre& c, int ix, int iy, int iz, double* t) {
+  t[0] = c.t[0] + (ix ? ix * s->step_xy : 0.0);
+  t[1] = c.t[1] + (iy ? iy * s->step_xy : 0.0);
+  t[2] = c.t[2] + (iz ? iz * s->step_z : 0.0);
+}
+
 inline void reloc_candidate_matrix(const liodom_pose_search_t* s, const RelocCentre& c, int64_t index, double* T) {
   int ix, iy, ia, iz;
   reloc_candidate_indices(s, index, &ix, &iy, &ia, &iz);
@@ -86,9 +95,9 @@ inline void reloc_candidate_matrix(const liodom_pose_search_t* s, const RelocCen
     T[4 + j] = sa * c.R[j] + ca * c.R[3 + j];
     T[8 + j] = c.R[6 + j];
   }
-  T[3] = c.t[0] + (ix ? ix * s->step_xy : 0.0);
-  T[7] = c.t[1] + (iy ? iy * s->step_xy : 0.0);
-  T[11] = c.t[2] + (iz ? iz * s->step_z : 0.0);
+  double t[3];
+  reloc_candidate_translation(s, c, ix, iy, iz, t);
+  T[3] = t[0]; T[7] = t[1]; T[11] = t[2];
 }
 
 // every candidate's matrix, in index order: T holds 12 * n doubles, n = reloc_candidate_count(s)

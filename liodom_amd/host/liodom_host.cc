@@ -626,6 +626,16 @@ liodom_pose_search_result_t Map::searchPose(const PointCloud& edges, const liodo
   return out;
 }
 
+liodom_pose_search_result_t Map::searchPoseBnb(const PointCloud& edges, const liodom_pose_search_t& search, int batch, liodom_pose_search_stats_t* stats) {
+  liodom_pose_search_result_t out{};
+  liodom_pose_search_bnb_t opt;
+  liodom_pose_search_bnb_default(&opt);
+  if (batch) opt.batch = batch;
+  check(liodom_map_search_pose_bnb(m_, reinterpret_cast<const float*>(edges.points.data()), (int)edges.points.size(), &search, &opt, &out, stats),
+        "liodom_map_search_pose_bnb");
+  return out;
+}
+
 void LaserOdometer::attachMapper(Map* map, int cells_xy, int cells_z) {
   check(liodom_attach_mapper(eng_->handle(), 0, map ? map->handle() : nullptr, cells_xy, cells_z), "liodom_attach_mapper");
 }

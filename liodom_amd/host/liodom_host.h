@@ -241,6 +241,10 @@ class Map {
   // the map and work on an attached one between scans.
   std::vector<int32_t> scorePoses(const PointCloud& edges, const std::vector<std::array<double, 12>>& poses, int radius = 1);
   liodom_pose_search_result_t searchPose(const PointCloud& edges, const liodom_pose_search_t& search);
+  // searchPoseBnb (liodom_map_search_pose_bnb): searchPose's result for the same grid by branch-and-bound, for grids of up to
+  // 2^31 - 1 candidates; batch 0: the library's default; *stats (optional): what the search did.
+  liodom_pose_search_result_t searchPoseBnb(const PointCloud& edges, const liodom_pose_search_t& search, int batch = 0,
+                                            liodom_pose_search_stats_t* stats = nullptr);
   int numCells();
   liodom_map_t* handle() const { return m_; }
   double xySize() const { return xy_; }
