@@ -5,7 +5,6 @@
 // =============================================================================================
 // grid (kCompactBlocks, streams): every workgroup scans the <= 256 ring counts itself (cheaper than a
 // second launch) and copies its interleaved share of the edges.
-constexpr int kCompactBlocks = 8;
 template <bool kList>
 __device__ __forceinline__ void compact_edges_body(const DevView& v, int s0, int eb, int mirror, int* pre, int* cntr) {
   const int s = stream_of<kList>(v, s0, (int)blockIdx.y);

@@ -16,7 +16,6 @@
 //                 gathers: 8x less fabric traffic than the first version, profiles/r01_c_*).
 // =============================================================================================
 // (kTilePts = 2048, kTileChunks = 32: liodom_sizes.h)
-constexpr int kTileThreads = 512;
 
 // isValidPoint + ring id of one point (feature_extractor.cc:84-102,115-175); 0xFF: dropped.
 __device__ __forceinline__ unsigned char classify_point(const DevView& v, const float4& pt, int i, int H, int height, int width) {
@@ -643,7 +642,6 @@ __global__ __launch_bounds__(kTileThreads) void k_ring_split_fix(DevView v, int 
 // the row's own segment of the ring-sorted copy (ring_start = row * width: fixed, nothing to count first).  Replaces
 // k_classify + k_ring_scatter for these clouds: 36 N bytes of traffic instead of 54 N, no id bytes, no histograms.
 // =============================================================================================
-constexpr int kRowThreads = 512;
 constexpr int kRowRounds = 4;              // columns per thread in flight (rows of up to 2048 points in one sweep)
 template <bool kList = false>
 __global__ __launch_bounds__(kRowThreads) void k_row_compact(DevView v, int s0, const float4* __restrict__ in, size_t in_stride,

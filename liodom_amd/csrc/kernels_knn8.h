@@ -425,7 +425,6 @@ __global__ __launch_bounds__(kKnn8Threads, LIODOM_KNN8_WAVES) void k_knn8(DevVie
 // every cell found, the 64 lists are merged over the wave.  (With a group
 // per query — 27 cells one after the other — the launch took 48 us; as a launch of k_knn8's shape that looked for flagged records,
 // 57 us: 90 000 waves of two dependent loads each.)  The workgroups of a stream walk its list; k_line_gate, the next launch, empties it.
-constexpr int kKnn8ExactBlocks = 4;
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
   v = half_min_u64(v);
   const unsigned long long o = xor32_u64(v);

@@ -135,8 +135,6 @@ __global__ __launch_bounds__(256) void k_window_insert(DevView v, int s0, int eb
 // the saved prediction.  (A waiting workgroup depends only on the solving workgroup of its own stream, which has a
 // lower block index and so was dispatched before it.)
 // =============================================================================================
-constexpr int kRebuildAuxBlocks = 8;      // workgroups for ALLOC (inside k_knn) and for CLEAR (k_lm_solve)
-constexpr int kRebuildAllocBlocks = 32;   // k_rebuild_alloc: the ~8 000 occupied cells of a headline scan in one sweep (it sits between the two solve launches)
 
 // Prefix table of the kept frames (chronological): sbase[0 .. nk], sslot[0 .. nk).  Returns nk; whole workgroup.
 __device__ __forceinline__ int kept_frames_table(const DevView& v, int s, const StreamState& st, int* sbase, int* sslot, int fc_of = -1) {
@@ -520,10 +518,6 @@ __device__ __forceinline__ void rebuild_beside_solve(const DevView& v, int s, St
 // Chain mode: the rebuild's steps as launches of their own on the stream of the kNN passes (light kernels: as extra workgroups of
 // k_lm_solve every one of them owned a whole CU — 256 VGPRs x 8 waves — and could only be placed on a CU that ran nothing else).
 // COUNT + PAD ride on the second kNN pass's launch (k_knn<256, true>: its extra workgroups), ALLOC is k_rebuild_alloc.
-#ifndef LIODOM_REBFIN_THREADS
-#define LIODOM_REBFIN_THREADS LIODOM_LM_THREADS
-#endif
-constexpr int kRebFinThreads = LIODOM_REBFIN_THREADS;
 __global__ __launch_bounds__(kRebFinThreads) void k_rebuild_fin(DevView v, int s0, int eb) {         // APPEND (waits for the solved pose), CLEAR, SCATTER
   __shared__ int sh_cnt[kMaxFrames + 1];
   __shared__ int sh_slot[kMaxFrames];
@@ -710,7 +704,6 @@ __device__ __forceinline__ KeyRun wave_key_runs(bool valid, unsigned long long k
 }
 
 // (kLdsSlots = 8192, kLdsCellsMax = 6144, hash_build_lds_bytes: liodom_sizes.h)
-constexpr int kBuildThreads = 1024;
 constexpr int kBuildUnroll = 4;
 
 // (jc: optional frame cursor of a thread whose m only grows: replaces the binary search by a step)

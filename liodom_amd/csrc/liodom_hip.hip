@@ -13,12 +13,13 @@
 #include <atomic>
 #include <chrono>
 #include <mutex>
+#include <optional>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "liodom_kernels.h"
 #include "handle_plan.h"
+#include "step_plan.h"
 
 using namespace liodom_dev;
 
@@ -38,10 +39,6 @@ thread_local std::string g_last_error;
     }                                                                                         \
   } while (0)
 
-enum KernelId {
-  KID_CLASSIFY = 0, KID_RING_EXTRACT, KID_COMPACT, KID_KNN, KID_LM, KID_HASH_CLEAR,
-  KID_WINDOW_INSERT, KID_HASH_ALLOC, KID_HASH_SCATTER, KID_RING_SCATTER, KID_HASH_BUILD, KID_OTHER
-};
 const char* kKernelNames[LIODOM_NUM_KERNELS] = {
     "k_classify", "k_ring_extract", "k_compact_edges", "k_knn", "k_lm_solve",
     "k_hash_clear", "k_window_insert", "k_hash_alloc", "k_hash_scatter", "k_ring_scatter", "k_hash_build", "other"};
@@ -71,25 +68,18 @@ struct liodom_handle {
   // (mx_x only) and liodom_odometry_step (mx_o only) can therefore run concurrently from two threads.
   std::mutex mx_x, mx_o;
   hipStream_t stream = nullptr;      // odometry side
+  StepState step;                    // the odometry side's state from scan to scan (step_plan.h), under mx_o
+  ExtractState xstep;                // ... and the extraction side's, under mx_x
   hipStream_t stream_k = nullptr;    // overlapped second kNN pass of a scan (kernels_sync.h "Overlapped second kNN pass"): beside the first solve
   bool counted_live = false;         // this handle is part of g_live_handles
-  unsigned int ov_seq = 0;           // launch sequence number its flags carry
   hipEvent_t ev_ov = nullptr;        // recorded on the odometry stream in front of the first overlapped scan after scans that were not
   bool stream_c_shared = false;      // stream_c is stream_k
   bool ov_suppress = false;          // host-fed replay: the host's enqueue work per scan is the limit there, and the overlapped pass costs two more launches
-  bool ov_prev = false;              // the previous scan of this handle was overlapped
   // Chain mode (kernels_sync.h "Chain mode"): the scan's kNN passes and the rebuild on stream_k, the two solves — launches of the
   // solving workgroups alone — on `stream`; the first solve's launch is resident beside the first pass.
   double replay_enq_ns = 0.0, replay_wait_ns = 0.0;      // depth-1 resident replay: host time per scan spent enqueueing / waiting for the previous pose
   long long replay_timed = 0;
-  bool chain_prev = false;           // the previous scan was enqueued in chain mode
-  unsigned int chain_count = 0;      // first-pass workgroups launched in chain mode since the last reset (what knn_done0 counts up to)
-  int verdict_scan = -1;             // scans completed when the host last collected stream 0's pose, and whether that scan's speculative
-  bool verdict_confirmed = false;    // hand-over was confirmed (HostOut::pad, written by finalize_scan)
-  bool chain_fix_pending = false;    // the last chain-mode scan's APPEND may need the repair of k_chain_redo0 (speculative hand-over)
-  bool chain_used = false;           // any scan was: the odometry side's results are complete when stream AND stream_k have drained
   hipEvent_t ev_ch = nullptr;        // at a switch out of chain mode: the odometry stream waits for stream_k
-  int ov_warm = 0;                   // scans enqueued so far, up to kOvWarmScans (the first ones run every kernel of the chain for the first time)
   hipStream_t stream_x = nullptr;    // extraction side (liodom_extract_edges, and the next scan's extraction in the pipelined replay)
   hipStream_t stream_c = nullptr;    // host-fed replay: uploads (a copy engine works beside the extraction kernels of the previous scan)
   hipEvent_t ev_up[3] = {nullptr, nullptr, nullptr};      // staging slot uploaded
@@ -130,7 +120,6 @@ struct liodom_handle {
   hipEvent_t ev_polpin[kEdgePipeBufs] = {nullptr, nullptr, nullptr};
   bool ev_polpin_valid[kEdgePipeBufs] = {false, false, false};
   int pol_pin_next = 0;
-  unsigned int lb_tag = 0;           // launch tag its count words carry
   bool streams_concurrent = true;    // liodom_create's probe: kernels of two streams of this handle ran side by side
   std::atomic<bool> pipe_active{false};        // scans went through the pipeline edge buffers by ticket since the last drain
   std::atomic<bool> replay_live{false};        // scans went through them by the pipelined replay since the last drain (their odometries may not have been collected)
@@ -168,7 +157,6 @@ struct liodom_handle {
   std::vector<liodom_map*> read_maps; // distinct maps with readers; a map's tag is its index + 1 (freed places are null and taken again)
   int4* reader_sel = nullptr;         // [S] device: {tag of the map the stream reads (0: none), cells_xy, cells_z, 0}
   int n_readers = 0;                  // streams with a reader
-  std::vector<int> hb_since;    // hash_incr, per stream: scans since the stream's last k_hash_build (-1: none yet)
   std::vector<EventPair> ev_pool;
   size_t ev_used = 0;
   double k_ms[LIODOM_NUM_KERNELS] = {0};
@@ -186,28 +174,6 @@ int dev_alloc(liodom_handle* h, T** p, size_t count, int memset_value = 0) {
   HIP_TRY(hipMemsetAsync(raw, memset_value, bytes, h->stream));
   *p = static_cast<T*>(raw);
   return LIODOM_OK;
-}
-
-// The odometry side's device results (window, correspondences, pose log, state) are complete when its streams have drained: in
-// chain mode the kNN passes and the rebuild run on stream_k.
-// Speculative hand-over of a chain-mode scan's result (kernels_sync.h): the repair of an APPEND that started from a pose the solve
-// did not end with rides behind the NEXT scan's first pass (k_chain_redo0).  When no such pass follows — the handle leaves chain
-// mode, or the host is about to read the odometry side's results — the repair is enqueued on its own (it waits for the scan's
-// verdict; normally it finds nothing to do).
-void chain_flush(liodom_handle* h) {
-  if (!h->chain_fix_pending) return;
-  h->chain_fix_pending = false;
-  // (the last chain-mode scan's pose has been collected and its record says "confirmed": nothing to repair, no launch — the usual
-  //  case when the host synchronises after a replay)
-  if (h->verdict_scan == h->scans_enqueued[0] && h->verdict_confirmed) return;
-  const int nA = (h->v.edge_cap + 255) / 256;
-  hipLaunchKernelGGL(k_chain_redo0<256>, dim3(nA, 1), dim3(256), 0, h->stream_k, h->v, 0, 0, 0u, 0u, 0u, h->scans_enqueued[0], nA, 0, 1);
-}
-hipError_t sync_odometry(liodom_handle* h) {
-  chain_flush(h);
-  hipError_t e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess && h->chain_used && h->stream_k) e = hipStreamSynchronize(h->stream_k);
-  return e;
 }
 
 int drain_events(liodom_handle* h) {
@@ -248,324 +214,7 @@ struct ProfScope {
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// ---- launch sequences -----------------------------------------------------------------------
-// Feature extraction of `count` streams starting at s0; input scan for stream s0+i at in + i*stride.
-// s0 < 0: of the `count` streams of device-side stream list -s0 - 1 (put_stream_list); input scan of stream s at in + s*stride.
-int launch_extract(liodom_handle* h, hipStream_t q, int eb, int s0, int count, const float4* in, size_t in_stride,
-                   int n, int height, int width, unsigned int wait_odo = 0, int mirror = 0, unsigned int* pub_flag = nullptr, unsigned int* pub_host = nullptr, unsigned int pub_value = 0u) {
-  const DevView& v = h->v;
-  // every kernel comes in two instances (stream_of): rows = streams s0 + row, rows = entries of a stream list
-  auto by_rows = [&](auto launch) { if (s0 < 0) launch(std::true_type{}); else launch(std::false_type{}); };
-  const int tiles = std::max(1, cdiv(n, kTilePts));
-  if (v.lidar_type == 1 && width > 0 && (long long)h->H * width <= (long long)v.max_points) {
-    // organised cloud: ring = row, the split is a per-row compaction (no classify / scatter passes): one pass over the scan
-    ProfScope ps(h, KID_RING_SCATTER, q);
-    by_rows([&](auto L) { hipLaunchKernelGGL((k_row_compact<decltype(L)::value>), dim3(h->H, count), dim3(kRowThreads), 0, q, v, s0, in, in_stride, n, height, width); });
-  } else {
-    if (h->plan.ring_split_lb && !((long long)tiles * count <= h->plan.ring_split_max_wgs && h->plan.ring_split)) {
-      // lock-step batches: one pass, rings at a fixed pitch, tiles sum their predecessors' counts (booked as the scatter)
-      ProfScope ps(h, KID_RING_SCATTER, q);
-      if (++h->lb_tag == 0u) h->lb_tag = 1u;
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split_lb<decltype(L)::value>), dim3(tiles * count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles, h->lb_tag); });
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split_fix<decltype(L)::value>), dim3(1, count), dim3(kTileThreads), ring_split_lb_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width, tiles); });
-    } else if (h->plan.ring_split && (long long)tiles * count <= h->plan.ring_split_max_wgs) {      // (every workgroup resident at once: k_ring_split waits inside the launch)
-      // one pass: classification and scatter in one kernel (booked as the scatter)
-      ProfScope ps(h, KID_RING_SCATTER, q);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_split<decltype(L)::value>), dim3(tiles, count), dim3(kTileThreads), ring_scatter_lds_bytes(h->H), q, v, s0, in, in_stride, n, height, width); });
-    } else {
-    {
-      ProfScope ps(h, KID_CLASSIFY, q);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_classify<decltype(L)::value>), dim3(tiles, count), dim3(kTileThreads), 0, q, v, s0, in, in_stride, n, height, width); });
-    }
-    {
-      ProfScope ps(h, KID_RING_SCATTER, q);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_scatter<decltype(L)::value>), dim3(tiles, count), dim3(kTileThreads), ring_scatter_lds_bytes(h->H), q, v, s0, in, in_stride, n); });
-    }
-    }
-  }
-  {
-    ProfScope ps(h, KID_RING_EXTRACT, q);
-    const int ext = ring_extract_threads(v.scan_regions);
-    // instance by the longest region the expected ring width gives (the last region takes the split's remainder)
-    const int w = h->config.max_width > 0 ? h->config.max_width : std::max(1, h->config.max_points / std::max(1, h->H));
-    const int total = std::max(0, w - 10), sector = total / std::max(1, v.scan_regions);
-    const bool big = total - sector * (v.scan_regions - 1) > kExLPR * kExIPL;
-    const dim3 grid(h->H, count), block(ext);
-    if (ext <= 256) {
-      if (big) by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<256, kExIPLBig, decltype(L)::value>), grid, block, h->plan.ring_lds_bytes, q, v, s0); });
-      else by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<256, kExIPL, decltype(L)::value>), grid, block, h->plan.ring_lds_bytes, q, v, s0); });
-    } else {
-      if (big) by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<1024, kExIPLBig, decltype(L)::value>), grid, block, h->plan.ring_lds_bytes, q, v, s0); });
-      else by_rows([&](auto L) { hipLaunchKernelGGL((k_ring_extract<1024, kExIPL, decltype(L)::value>), grid, block, h->plan.ring_lds_bytes, q, v, s0); });
-    }
-  }
-  {
-    ProfScope ps(h, KID_COMPACT, q);
-    by_rows([&](auto L) { hipLaunchKernelGGL((k_compact_edges<decltype(L)::value>), dim3(kCompactBlocks, count), dim3(256), 0, q, v, s0, eb, wait_odo, mirror, pub_flag, pub_host, pub_value); });
-  }
-  HIP_TRY(hipGetLastError());
-  return LIODOM_OK;
-}
-
-// Odometry on the dense edges already on the device.  If pose_dst != nullptr the poses + infos
-// of the streams are copied to pinned memory right after the solve and pose_event is recorded,
-// so the host can pick them up while the window / hash rebuild still runs.
-// s0 < 0: the `count` streams of device-side stream list -s0 - 1, whose entries the host loops read from `list`.
-int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges, unsigned int signal_odo, const int32_t* list = nullptr);
-
-int launch_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges = 0, unsigned int signal_odo = 0, const int32_t* list = nullptr) {
-  // (a hipGraph replay of this launch sequence was measured slower than the eager launches in rounds 1-2 — the chain is
-  //  bound by its kernels, the host enqueue is hidden behind them, hipGraphLaunch adds start latency — and removed in round 3)
-  const int rc = enqueue_odometry(h, eb, s0, count, wait_edges, signal_odo, list);
-  if (rc) return rc;
-  // results are published by k_lm_solve into host-mapped memory (HostOut)
-  for (int i = 0; i < count; i++) { const int s = list ? list[i] : s0 + i; h->last_eb[s] = eb; h->scans_enqueued[s]++; }
-  return LIODOM_OK;
-}
-
-// The handle's part of the decision to overlap the second kNN pass (ov) and to run a scan in chain mode (chain): the streamed
-// rebuild, flags between the streams, and the GPU to this handle alone — its waiting workgroups and those of a second handle of
-// the process could end up behind each other in a shared hardware queue.  enqueue_odometry adds the scan's own conditions.
-OverlapModes overlap_modes(const liodom_handle* h) { return plan_overlap_modes(h->plan, g_live_handles.load() <= 1); }
-
-int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int wait_edges, unsigned int signal_odo, const int32_t* list) {
-  const DevView& v = h->v;
-  auto stream_at = [&](int i) { return list ? (int)list[i] : s0 + i; };
-  auto by_rows = [&](auto launch) { if (s0 < 0) launch(std::true_type{}); else launch(std::false_type{}); };      // (as in launch_extract)
-  const bool knn_small = h->plan.lockstep;           // 4 queries per workgroup, else 8
-  if (v.use_imu) {
-    ProfScope ps(h, KID_OTHER);
-    by_rows([&](auto L) { hipLaunchKernelGGL((k_imu_override<decltype(L)::value>), dim3(cdiv(count, 64)), dim3(64), 0, h->stream, v, s0, count); });
-  }
-  if (h->n_lagged > 0) {
-    // Lagged mappers: the frame this scan's append will overwrite is set aside before anything of the step runs (one launch for
-    // the step's streams; k_window_stash skips those without a lagged mapper).  A mapping handle runs neither the streamed
-    // rebuild nor chain mode nor the overlapped pass (early_rebuild = 0): the previous scan's append, this launch, the solves, the
-    // map update and this scan's append are all on the odometry stream, in this order.
-    bool any = false;
-    for (int i = 0; i < count; i++) { const int s = stream_at(i); any = any || (h->mappers[s] && h->mapper_opts[s].lag == 1); }
-    if (any) {
-      ProfScope ps(h, KID_OTHER);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_window_stash<decltype(L)::value>), dim3(std::min(16, cdiv(v.edge_cap, 256)), count), dim3(256), 0, h->stream, v, s0, h->lag_on, h->lag_stash, h->lag_stash_n); });
-    }
-  }
-  // early rebuild ("streamed rebuild", kernels_rebuild.h): the four launches of a scan carry extra workgroups that build
-  // the next scan's cell hash in the second table; nothing follows the finalising solve
-  const int map_blocks = cdiv(h->v.map_cap, 256);
-  const bool early = v.early_rebuild != 0;
-  const int nC = cdiv(h->v.edge_cap * std::max(1, h->P - 1), kLmThreads), nP = cdiv(h->v.edge_cap, kLmThreads);
-  // Overlapped second kNN pass (kernels_sync.h): the pass goes to stream_k behind the first solve's launch and waits inside
-  // the kernel; it needs kernels of different streams to run side by side (as the flags of the pipelined replay do) and the
-  // GPU mostly to itself (overlap_modes), and is not used under per-kernel profiling.
-  // (chain mode — only for scans whose edges come from the extraction stream by flag, see below — also overlaps the pass on shapes
-  //  where the four-launch chain cannot: Ouster-128's 704 waiting workgroups beside full-CU rebuild workgroups cost 9 %, in chain
-  //  mode the overlapped pass gains 19 % there)
-  const OverlapModes om = overlap_modes(h);
-  const bool chain_cand = om.chain && wait_edges != 0u;
-  const bool overlap_ok = (om.ov || chain_cand) && !h->profiling && !h->ov_suppress && count == 1;
-  // The first scans of a handle are not overlapped: their launches are the first of every kernel of the chain on this queue
-  // (scratch set-up, code upload), which can hold the odometry stream back for longer than a waiting kernel is willing to
-  // poll.  At a switch to overlapped scans stream_k waits (event) for the odometry stream to have drained, so that its
-  // first polling launch cannot start before everything it depends on has run once.
-  constexpr int kOvWarmScans = 2;
-  const bool overlap = overlap_ok && h->ov_warm >= kOvWarmScans;
-  if (h->ov_warm < kOvWarmScans) h->ov_warm++;
-  unsigned int seq_k = 0u;                           // (0 means "not overlapped" to the kernels)
-  if (overlap) {
-    if (++h->ov_seq == 0u) h->ov_seq = 1u;
-    seq_k = h->ov_seq;
-    if (!h->ov_prev) {
-      HIP_TRY(hipEventRecord(h->ev_ov, h->stream));
-      HIP_TRY(hipStreamWaitEvent(h->stream_k, h->ev_ov, 0));
-    }
-  }
-  // Chain mode: only for scans whose edges come from the extraction stream by flag (the pipelined replay, the ticket API): the
-  // first pass then runs on stream_k, where nothing orders it behind an extraction enqueued on the odometry stream itself.
-  const bool chain = overlap && chain_cand;
-  if (chain != h->chain_prev) {
-    if (chain) {
-      // (stream_k waits for the odometry stream: recorded above — ev_ov — unless the previous scan was overlapped without the chain)
-      if (h->ov_prev) { HIP_TRY(hipEventRecord(h->ev_ov, h->stream)); HIP_TRY(hipStreamWaitEvent(h->stream_k, h->ev_ov, 0)); }
-    } else {
-      chain_flush(h);
-      HIP_TRY(hipEventRecord(h->ev_ch, h->stream_k));
-      HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_ch, 0));
-    }
-  }
-  h->chain_prev = chain;
-  h->ov_prev = overlap;
-  if (chain) {
-    h->chain_used = true;
-    const int scan_no = h->scans_enqueued[s0];
-    h->chain_count += (unsigned int)v.knn_grid;                        // (wraps with the device counter: the kernels compare differences)
-    const unsigned int done_target = h->chain_count;
-    const int gx = (h->v.lm_groups - 1) * 8 + 1;                       // solvers on blocks 0, 8, 16, ... (one XCD); nothing else in the launch
-    const size_t lds = lm_lds_bytes(h->v.edge_cap);
-    // stream_k: first pass | gate (first solve's launch has started; + repair of the previous scan's hand-over: k_chain_redo0) | second pass + COUNT + PAD |
-    //           ALLOC (+ repeat of unconfirmed second-pass workgroups: k_knn_redo) | APPEND + CLEAR + SCATTER
-    // stream:   first solve (resident beside the first pass: waits for its done flags) | finalising solve (waits for the second pass's)
-    const int nCP = cdiv(h->v.edge_cap * std::max(1, h->P - 1), 256) + cdiv(h->v.edge_cap, 256);      // COUNT + PAD workgroups of 256 threads
-    hipLaunchKernelGGL((k_knn<256, false, true>), dim3(v.knn_grid, 1), dim3(256), 0, h->stream_k, v, s0, 0, eb, wait_edges, signal_odo, seq_k, scan_no);
-    if (v.speculate) {      // (speculative hand-over of the previous scan's result not confirmed: rare)
-      const int nA = cdiv(h->v.edge_cap, 256);
-      // (+ 1: the gate in front of the second pass, k_ov_gate's job otherwise)
-      hipLaunchKernelGGL(k_chain_redo0<256>, dim3(nA + v.knn_grid + 1, 1), dim3(256), 0, h->stream_k, v, s0, eb, wait_edges, signal_odo, seq_k, scan_no, nA, 1, h->chain_fix_pending ? 1 : 0);
-    }
-    h->chain_fix_pending = v.speculate != 0;
-    hipLaunchKernelGGL((k_lm_solve<0, true>), dim3(gx, 1), dim3(kLmThreads), lds, h->stream, v, s0, eb, seq_k, done_target);
-    if (!v.speculate) hipLaunchKernelGGL(k_ov_gate, dim3(1), dim3(64), 0, h->stream_k, v, s0, seq_k);
-    hipLaunchKernelGGL((k_knn<256, true>), dim3(v.knn_grid + nCP, 1), dim3(256), 0, h->stream_k, v, s0, 1, eb, 0u, 0u, seq_k, scan_no);
-    // (speculative hand-over not confirmed — rare —: the pass's workgroups once more; the launch's first workgroups are ALLOC)
-    if (v.speculate) hipLaunchKernelGGL(k_knn_redo<256>, dim3(kRebuildAllocBlocks + v.knn_grid, 1), dim3(256), 0, h->stream_k, v, s0, eb, seq_k, scan_no, kRebuildAllocBlocks);
-    hipLaunchKernelGGL((k_lm_solve<1, true>), dim3(gx, 1), dim3(kLmThreads), lds, h->stream, v, s0, eb, seq_k, done_target);
-    // (pose covariance: behind the finalising solve on its stream; the next scan's first solve follows it there, and the next second
-    //  pass — hence the next finalising solve, the next writer of cov_raw — waits for that solve: kernels_cov.h)
-    if (v.cov_raw) hipLaunchKernelGGL(k_pose_cov<>, dim3(count), dim3(64), 0, h->stream, v, s0);
-    if (!v.speculate) hipLaunchKernelGGL(k_rebuild_alloc<>, dim3(kRebuildAllocBlocks, 1), dim3(256), 0, h->stream_k, v, s0);
-    const int nCf = cdiv(h->v.edge_cap * std::max(1, h->P - 1), kRebFinThreads), nPf = cdiv(h->v.edge_cap, kRebFinThreads);
-    hipLaunchKernelGGL(k_rebuild_fin, dim3(nPf + kRebuildAuxBlocks + nCf, 1), dim3(kRebFinThreads), 0, h->stream_k, v, s0, eb);
-    HIP_TRY(hipGetLastError());
-    return LIODOM_OK;
-  }
-  for (int it = 0; it < 2; it++) {
-    {
-      ProfScope ps(h, KID_KNN);
-      const int kx = v.knn_grid + ((early && it == 1 && !seq_k) ? kRebuildAuxBlocks : 0);     // it 1: + ALLOC (overlapped pass: k_rebuild_alloc below)
-      if (knn_small && h->plan.knn8) {
-        // lock-step batches: eight lanes per query (kernels_knn8.h); the workgroups of a stream walk its blocks of 32 queries
-        const dim3 g8(h->plan.knn8_grid, count);
-        if (it == 0) by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8<0, decltype(L)::value>), g8, dim3(kKnn8Threads), 0, h->stream, v, s0, eb); });
-        else by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8<1, decltype(L)::value>), g8, dim3(kKnn8Threads), 0, h->stream, v, s0, eb); });
-        by_rows([&](auto L) { hipLaunchKernelGGL((k_knn8_exact<decltype(L)::value>), dim3(kKnn8ExactBlocks, count), dim3(kKnn8Threads), 0, h->stream, v, s0, it, eb); });      // (the ~1 % of the queries the fast path cannot certify)
-        by_rows([&](auto L) { hipLaunchKernelGGL((k_line_gate<decltype(L)::value>), dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb); });
-      } else if (knn_small) {
-        by_rows([&](auto L) { hipLaunchKernelGGL((k_knn<128, false, false, decltype(L)::value>), dim3(kx, count), dim3(128), 0, h->stream, v, s0, it, eb, wait_edges, signal_odo, 0u, 0); });
-        by_rows([&](auto L) { hipLaunchKernelGGL((k_line_gate<decltype(L)::value>), dim3(cdiv(h->v.knn_blocks * h->v.knn_queries, 256), count), dim3(256), 0, h->stream, v, s0, it, eb); });
-      } else if (it == 1 && seq_k) {
-        hipLaunchKernelGGL(k_ov_gate, dim3(1), dim3(64), 0, h->stream_k, v, s0, seq_k);
-        hipLaunchKernelGGL((k_knn<256, true>), dim3(kx, count), dim3(256), 0, h->stream_k, v, s0, it, eb, 0u, 0u, seq_k, -1);
-        if (v.speculate) hipLaunchKernelGGL(k_knn_redo<256>, dim3(v.knn_grid, count), dim3(256), 0, h->stream_k, v, s0, eb, seq_k, -1, 0);      // (speculative hand-over not confirmed: rare)
-        // ALLOC between the two solve launches, beside the pass's tail
-        hipLaunchKernelGGL(k_rebuild_alloc<>, dim3(kRebuildAllocBlocks, count), dim3(256), 0, h->stream, v, s0);
-      } else {
-        by_rows([&](auto L) { hipLaunchKernelGGL((k_knn<256, false, false, decltype(L)::value>), dim3(kx, count), dim3(256), 0, h->stream, v, s0, it, eb, wait_edges, signal_odo, 0u, 0); });
-      }
-    }
-    {
-      ProfScope ps(h, KID_LM);
-      // it 0: + COUNT, PAD; it 1: + APPEND, CLEAR, SCATTER
-      const int extra = !early ? 0 : (it == 0 ? nC + nP : nP + kRebuildAuxBlocks + nC);
-      const int gx = std::max(h->v.lm_groups + extra, (h->v.lm_groups - 1) * 8 + 1);      // solvers on blocks 0, 8, 16, ... (one XCD)
-      if (it == 0) by_rows([&](auto L) { hipLaunchKernelGGL((k_lm_solve<0, false, decltype(L)::value>), dim3(gx, count), dim3(kLmThreads), lm_lds_bytes(h->v.edge_cap), h->stream, v, s0, eb, seq_k, 0u); });
-      else by_rows([&](auto L) { hipLaunchKernelGGL((k_lm_solve<1, false, decltype(L)::value>), dim3(gx, count), dim3(kLmThreads), lm_lds_bytes(h->v.edge_cap), h->stream, v, s0, eb, seq_k, 0u); });
-    }
-    if (it == 1 && v.cov_raw) {             // pose covariance of the scan, straight behind its finalising solve (kernels_cov.h)
-      ProfScope ps(h, KID_OTHER);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_pose_cov<decltype(L)::value>), dim3(count), dim3(64), 0, h->stream, v, s0); });
-    }
-  }
-  if (v.mapping) {
-    // synchronous replay of the mapping node for the streams with an attached map: updateMap(edges_k,
-    // pose_k), then getLocalMap(pose_k) straight into the stream's received-map buffer.
-    // lag = 1: the map takes the frame that left the window instead (stashed above; world frame already: no transform), then the
-    // optional prune around pose_k, then the same getLocalMap.
-    for (int i = 0; i < count; i++) {
-      const int s = stream_at(i);
-      liodom_map* mp = h->mappers[s];
-      if (!mp) continue;
-      ProfScope ps(h, KID_OTHER);
-      StreamState* st = v.state + s;
-      const liodom_mapper_options_t& mo = h->mapper_opts[s];
-      int rc = mo.lag == 1 ? map_enqueue_update(mp, h->lag_stash + (size_t)s * v.edge_cap, h->lag_stash_n + s, nullptr, h->stream)
-                           : map_enqueue_update(mp, v.edges + ((size_t)eb * v.n_streams + s) * v.edge_cap, &st->n_edges_buf[eb], st->final_odom, h->stream);
-      if (rc) return rc;
-      // (scans_enqueued[s] is this scan's index: launch_odometry counts it when the step has been enqueued)
-      if (mo.prune_period > 0 && (h->scans_enqueued[s] + 1) % mo.prune_period == 0) {
-        rc = map_enqueue_prune(mp, st->final_odom, mo.keep_cells_xy, mo.keep_cells_z, h->stream);
-        if (rc) return rc;
-      }
-      rc = map_enqueue_local(mp, st->final_odom, mo.cells_xy, mo.cells_z, v.recv_pts + (size_t)s * v.recv_cap,
-                             v.recv_cap, &st->n_recv, h->stream, 1);
-      if (rc) return rc;
-    }
-    // map readers: getLocalMap(pose_k) of the step's reader rows, one launch per distinct map (k_map_local_rows plans in LDS and
-    // writes nothing of the map, so the rows share it); nothing else — no stash, no update, no prune.  A reader whose extents
-    // the LDS plan cannot hold takes the two old launches.
-    if (h->n_readers > 0) {
-      ProfScope ps(h, KID_OTHER);
-      for (size_t t = 0; t < h->read_maps.size(); t++) {
-        liodom_map* mp = h->read_maps[t];
-        if (!mp) continue;
-        bool rows = false;
-        for (int i = 0; i < count; i++) {
-          const int s = stream_at(i);
-          if (h->readers[s] != mp) continue;
-          if (h->plan.map_rows && map_rows_fit(mp, h->reader_xy[s], h->reader_z[s])) { rows = true; continue; }
-          StreamState* st = v.state + s;
-          const int rc = map_enqueue_local(mp, st->final_odom, h->reader_xy[s], h->reader_z[s], v.recv_pts + (size_t)s * v.recv_cap, v.recv_cap, &st->n_recv, h->stream, 1);
-          if (rc) return rc;
-        }
-        if (!rows) continue;
-        MapRows r{};
-        r.T = v.state[0].final_odom; r.T_stride = (long long)(sizeof(StreamState) / sizeof(double));
-        r.out = v.recv_pts; r.out_stride = v.recv_cap;
-        r.n_out = &v.state[0].n_recv; r.n_stride = (long long)(sizeof(StreamState) / sizeof(int));
-        r.total = nullptr; r.sel = h->reader_sel; r.tag = (int)t + 1; r.cap = v.recv_cap; r.sticky = 1;
-        r.s0 = s0; r.list = s0 < 0 ? reinterpret_cast<const int*>(v.pipe_flags) + kStreamListBase + (size_t)(-s0 - 1) * (size_t)v.n_streams : nullptr;
-        const dim3 grid(map_rows_grid_x(count, v.recv_cap), count);
-        by_rows([&](auto L) { hipLaunchKernelGGL((k_map_local_rows<decltype(L)::value>), grid, dim3(kMapRowsThreads), 0, h->stream, mp->m, r); });
-      }
-    }
-  }
-  if (early) {
-    // (nothing: the next cell hash is complete when the finalising solve launch ends)
-  } else if (h->plan.lds_hash_build) {
-    ProfScope ps(h, KID_HASH_BUILD);        // window append + LDS-built cell hash, one workgroup per stream
-    // (hash_incr: the new frame is appended to the table of the last rebuild; k_hash_build only works when that says so)
-    // (hash_incr: k_hash_build every kHbPeriod-th scan, k_hash_append — the new frame into the cells of the last rebuild — in between)
-    // (per stream: a single-stream call or a subset step of a lock-step handle steps some of the streams only.  A launch over several streams rebuilds them all
-    //  if any one is due — a rebuild is always exact — so that lock-step batches keep every counter in step.)
-    bool rebuild = !v.hash_incr;
-    for (int i = 0; i < count; i++) rebuild = rebuild || h->hb_since[stream_at(i)] < 0 || h->hb_since[stream_at(i)] >= kHbPeriod - 1;
-    for (int i = 0; i < count; i++) h->hb_since[stream_at(i)] = rebuild ? 0 : h->hb_since[stream_at(i)] + 1;
-    if (!rebuild) by_rows([&](auto L) { hipLaunchKernelGGL((k_hash_append<decltype(L)::value>), dim3(count), dim3(kBuildThreads), 0, h->stream, v, s0, eb); });
-    else by_rows([&](auto L) { hipLaunchKernelGGL((k_hash_build<decltype(L)::value>), dim3(count), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, s0, eb); });
-  } else {
-    {
-      ProfScope ps(h, KID_WINDOW_INSERT);   // window append + cell hash in global memory, map_blocks workgroups per stream
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_window_insert<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0, eb); });
-    }
-    {
-      ProfScope ps(h, KID_HASH_ALLOC);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_hash_alloc<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
-    }
-    {
-      ProfScope ps(h, KID_HASH_SCATTER);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_hash_scatter<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
-    }
-  }
-  if (v.filter_local_map) {     // VoxelGrid(0.4) of the full window (every kernel exits unless the window is full)
-    {
-      ProfScope ps(h, KID_OTHER);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_bbox<decltype(L)::value>), dim3(count), dim3(1024), 0, h->stream, v, s0); });
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_insert<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_alloc<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_scatter<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_voxel_centroid<decltype(L)::value>), dim3(cdiv(h->v.map_cap, 8), count), dim3(256), 0, h->stream, v, s0); });
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_filt_insert<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
-    }
-    {
-      ProfScope ps(h, KID_HASH_ALLOC);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_filt_alloc<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
-    }
-    {
-      ProfScope ps(h, KID_HASH_SCATTER);
-      by_rows([&](auto L) { hipLaunchKernelGGL((k_filt_scatter<decltype(L)::value>), dim3(map_blocks, count), dim3(256), 0, h->stream, v, s0); });
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  return LIODOM_OK;
-}
+#include "liodom_step_host.h"
 
 // Every entry point starts here: the calling thread's current device becomes the handle's (other
 // handles / maps of the process may live on other GPUs, and HIP's current device is per thread).
@@ -713,11 +362,8 @@ int reset_state(liodom_handle* h) {
   }
   h->pf_slot = -1; h->pf_subset = false; h->parity = 0; h->last_eb.assign((size_t)h->S, 0); h->ev_free_valid[0] = h->ev_free_valid[1] = h->ev_free_valid[2] = false;
   h->replay_live.store(false);
-  h->hb_since.assign((size_t)h->S, -1);
   h->ext_seq = h->odo_seq = 0;
-  // the first scans after a reset are not overlapped (as after liodom_create): the first one runs with st.initialized == 0, where
-  // no first solve publishes the pose an overlapped second kNN pass would wait for
-  h->ov_warm = 0; h->ov_prev = false;
+  h->step.reset();
   for (int b = 0; b < kEdgePipeBufs; b++) { h->tk_seq[b] = 0u; h->ev_pin_valid[b] = false; h->ev_polpin_valid[b] = false; }      // outstanding edge tickets are void
   if (h->stream_c && !h->stream_c_shared) HIP_TRY(hipStreamSynchronize(h->stream_c));
   h->x_next = 0; h->odo_pending = 0;
@@ -729,7 +375,7 @@ int reset_state(liodom_handle* h) {
   HIP_TRY(hipMemsetAsync(h->v.redo_sync, 0, sizeof(unsigned int) * 64, h->stream));
   if (h->v.pred_xch) HIP_TRY(hipMemsetAsync(h->v.pred_xch, 0, sizeof(unsigned long long) * (size_t)h->S * kOvReplicas * 512, h->stream));
   HIP_TRY(hipMemsetAsync(h->v.knn_done0, 0, sizeof(unsigned int) * ((size_t)h->S + 64), h->stream));
-  h->chain_prev = false; h->chain_count = 0; h->chain_fix_pending = false; h->verdict_scan = -1; h->replay_enq_ns = 0.0; h->replay_wait_ns = 0.0; h->replay_timed = 0;
+  h->replay_enq_ns = 0.0; h->replay_wait_ns = 0.0; h->replay_timed = 0;
   std::memset(h->host_out, 0, sizeof(HostOut) * 2 * (size_t)h->S);
   if (h->cov_host) {
     std::memset(h->cov_host, 0, sizeof(HostCov) * 2 * (size_t)h->S);
@@ -945,6 +591,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
     v.host_out = static_cast<HostOut*>(dp);
     h->scans_enqueued.assign(S, 0);
+    h->step.bind(S);
     h->last_eb.assign(S, 0);
     h->mappers.assign(S, nullptr); h->mapper_opts.assign(S, liodom_mapper_options_t{2, 1, 0, 0, 0, 0, {0, 0}});
   }
@@ -1115,7 +762,6 @@ static void state_fingerprint(const liodom_handle* h, StateBlobHeader* hd) {
 static int install_stream_state(liodom_handle* h, int stream, const unsigned char* blob, int n_frames, int scan_counter, int n_recv = 0) {
   const DevView& v = h->v;
   const size_t S = (size_t)h->S, s = (size_t)stream;
-  const int map_blocks = cdiv(v.map_cap, 256);
   hipLaunchKernelGGL(k_stream_clear, dim3(64), dim3(kStateThreads), 0, h->stream, v, stream);
   hipLaunchKernelGGL(k_state_unpack, dim3(std::max(1, cdiv(v.map_cap, kStateThreads))), dim3(kStateThreads), 0, h->stream, v, stream, blob);
   // the stream's exchange granules carry tags derived from its frame and scan counts, which start over or jump here
@@ -1128,35 +774,23 @@ static int install_stream_state(liodom_handle* h, int stream, const unsigned cha
     // odometry stream (an uninitialised stream publishes no pose an overlapped pass could wait for; the prediction granules of an
     // imported stream are written by its first scan here); their counters start over with the device's
     HIP_TRY(hipMemsetAsync(v.knn_done0, 0, sizeof(unsigned int) * (S + 64), h->stream));
-    h->ov_warm = 0; h->ov_prev = false; h->chain_prev = false; h->chain_count = 0; h->chain_fix_pending = false; h->verdict_scan = -1;
+    h->step.restart_overlap();
   }
   if (n_frames > 0 || n_recv > 0) {      // (a received map without a frame — a seeded stream before its first scan — is searched too)
-    if (h->plan.lds_hash_build) {
-      hipLaunchKernelGGL(k_hash_build<>, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
-    } else {
-      // (early_rebuild: the three kernels fill the table of parity frame_count & 1, the one the next scan searches; the other one
-      //  and both overflow lists are empty)
-      hipLaunchKernelGGL(k_window_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream, -1);
-      hipLaunchKernelGGL(k_hash_alloc<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_hash_scatter<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-    }
-    if (v.filter_local_map) {     // VoxelGrid(0.4) of a full window (every kernel exits otherwise)
-      hipLaunchKernelGGL(k_voxel_bbox<>, dim3(1), dim3(1024), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_voxel_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_voxel_alloc<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_voxel_scatter<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_voxel_centroid<>, dim3(cdiv(v.map_cap, 8), 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_filt_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_filt_alloc<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-      hipLaunchKernelGGL(k_filt_scatter<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-    }
+    // (the hash step of a scan, always a rebuild, over the installed window: eb -1.  early_rebuild: the three kernels fill the table of
+    //  parity frame_count & 1, the one the next scan searches; the other one and both overflow lists are empty)
+    StepPlan plan;
+    plan_full_rebuild(h->plan, &plan);
+    StepData d;
+    d.s0 = stream; d.count = 1; d.eb = -1;
+    if (const int rc = issue_plan(h, plan, d)) return rc;
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   std::memset(h->host_out + 2 * s, 0, sizeof(HostOut) * 2);
   if (h->cov_host) std::memset(h->cov_host + 2 * s, 0, sizeof(HostCov) * 2);
   h->scans_enqueued[s] = scan_counter;
-  h->hb_since[s] = -1;      // (hash_incr: the stream's next step rebuilds from the whole window)
+  h->step.hb_since[s] = -1;      // (hash_incr: the stream's next step rebuilds from the whole window)
   return LIODOM_OK;
 }
 
@@ -1387,7 +1021,7 @@ static int wait_pose(liodom_handle_t* h, int s0, int count, double* pose_out, li
     if (info) info[i] = r->info;
     if (r->info.status & (LIODOM_STATUS_PIPE_TIMEOUT | LIODOM_STATUS_LM_SYNC_TIMEOUT)) timed_out = true;
     // (speculative hand-over: the record carries the scan's verdict — a confirmed scan needs no repair, chain_flush)
-    if (s == 0) { h->verdict_scan = expect; h->verdict_confirmed = r->pad == 1; }
+    if (s == 0) { h->step.verdict_scan = expect; h->step.verdict_confirmed = r->pad == 1; }
   }
   if (timed_out) {
     // A kernel gave up waiting for another HIP stream of the handle (pipe_wait / ov_wait_*): its workgroups skipped the scan, the
@@ -1816,18 +1450,14 @@ int liodom_extract_edges_device_polar(liodom_handle_t* h, int stream, const void
 // Rebuilds the kNN structure of one stream from window ++ received map without appending a frame.
 static int rebuild_search_structure(liodom_handle* h, int stream) {
   const DevView& v = h->v;
-  const int map_blocks = cdiv(v.map_cap, 256);
   hipLaunchKernelGGL(k_hash_reset, dim3(64), dim3(256), 0, h->stream, v, stream);
   hipLaunchKernelGGL(k_hash_reset_done, dim3(1), dim3(1), 0, h->stream, v, stream);
-  if (h->plan.lds_hash_build) {
-    hipLaunchKernelGGL(k_hash_build<>, dim3(1), dim3(kBuildThreads), hash_build_lds_bytes(), h->stream, v, stream, -1);
-  } else {
-    hipLaunchKernelGGL(k_window_insert<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream, -1);
-    hipLaunchKernelGGL(k_hash_alloc<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-    hipLaunchKernelGGL(k_hash_scatter<>, dim3(map_blocks, 1), dim3(256), 0, h->stream, v, stream);
-  }
-  HIP_TRY(hipGetLastError());
-  return LIODOM_OK;
+  // (a mapping handle: no voxel filter follows the hash step)
+  StepPlan plan;
+  plan_full_rebuild(h->plan, &plan);
+  StepData d;
+  d.s0 = stream; d.count = 1; d.eb = -1;
+  return issue_plan(h, plan, d);
 }
 
 int liodom_set_received_map(liodom_handle_t* h, int stream, const float* xyzi, int64_t n) {
@@ -2063,20 +1693,6 @@ int liodom_process_resident(liodom_handle_t* h, int slot, int64_t n, int height,
   return liodom_process_resident_pipelined(h, slot, -1, n, height, width, poses_out, infos_out);
 }
 
-// One scan of the pipelined replay (both sides locked by the caller).  wait: read the poses back before returning.
-static int replay_one(liodom_handle_t* h, int slot, int next_slot, int64_t n, int height, int width, bool wait,
-                      double* poses_out, liodom_step_info_t* infos_out, const float* next_host = nullptr, int64_t host_stride = 0);
-
-int liodom_process_resident_pipelined(liodom_handle_t* h, int slot, int next_slot, int64_t n, int height,
-                                      int width, double* poses_out, liodom_step_info_t* infos_out) {
-  int rc0 = enter(h);
-  if (rc0) return rc0;
-  if ((rc0 = check_usable(h))) return rc0;
-  SideLocks lk(h, true, true);
-  if ((rc0 = tickets_idle(h))) return rc0;        // (the replay fills the same pipeline edge buffers)
-  return replay_one(h, slot, next_slot, n, height, width, poses_out != nullptr || infos_out != nullptr, poses_out, infos_out);
-}
-
 // ---- subset steps: a lock-step step over a list of streams (liodom_process_resident_subset) ----
 // A strictly ascending list of stream numbers in [0, n_streams).
 static bool stream_list_valid(const liodom_handle* h, const int32_t* streams, int n) {
@@ -2105,92 +1721,6 @@ static int issue_extract_list(liodom_handle* h, int slot, int eb, int n, int hei
   const int rc = put_stream_list(h, extract_queue(h), eb, streams, count);
   if (rc) return rc;
   return issue_extract(h, slot, eb, n, height, width, -eb - 1, count);
-}
-
-int liodom_process_resident_subset(liodom_handle_t* h, int slot, const int32_t* streams, int n_active,
-                                   int next_slot, const int32_t* next_streams, int n_next,
-                                   int64_t n, int height, int width, double* poses_out, liodom_step_info_t* infos_out) {
-  int rc = enter(h);
-  if (rc) return rc;
-  if ((rc = check_usable(h))) return rc;
-  if (!stream_list_valid(h, streams, n_active)) { g_last_error = "liodom_process_resident_subset: streams must be strictly ascending stream indices"; return LIODOM_ERR_INVALID_ARG; }
-  if (next_slot >= 0 && !next_streams) { next_streams = streams; n_next = n_active; }      // (the same streams step again)
-  if (next_slot >= 0 && !stream_list_valid(h, next_streams, n_next)) { g_last_error = "liodom_process_resident_subset: next_streams must be strictly ascending stream indices"; return LIODOM_ERR_INVALID_ARG; }
-  SideLocks lk(h, true, true);
-  if ((rc = tickets_idle(h))) return rc;        // (the pipeline edge buffers, as the replay)
-  const bool wait = poses_out != nullptr || infos_out != nullptr;
-  // every stream now, and every stream (or nothing) ahead: the plain step, launch for launch
-  if (n_active == h->S && (next_slot < 0 || n_next == h->S)) return replay_one(h, slot, next_slot, n, height, width, wait, poses_out, infos_out);
-  if (!h->resident || slot < 0 || slot >= h->n_slots || next_slot >= h->n_slots || n < 0 || n > h->v.max_points) {
-    g_last_error = "bad resident slot"; return LIODOM_ERR_INVALID_ARG;
-  }
-  h->replay_live.store(true);
-  const bool full = n_active == h->S;
-  if (n_active > 0) {
-    const int eb = h->parity;
-    // issued ahead for exactly these streams?  Anything else — another slot, another list, nothing — is extracted now
-    const bool ahead = h->pf_slot == slot && (full ? !h->pf_subset
-                                                   : (h->pf_subset && (int)h->pf_list.size() == n_active && std::equal(streams, streams + n_active, h->pf_list.begin())));
-    if (!ahead) { rc = issue_extract_list(h, slot, eb, (int)n, height, width, streams, n_active); if (rc) return rc; }
-    h->pf_slot = -1; h->pf_subset = false;
-    if (full) {
-      rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb]);
-    } else {
-      // (list kEdgePipeBufs + eb, uploaded on the odometry stream behind the previous odometry of buffer eb)
-      rc = put_stream_list(h, h->stream, kEdgePipeBufs + eb, streams, n_active);
-      if (rc) return rc;
-      rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb], -(kEdgePipeBufs + eb) - 1, n_active, streams);
-    }
-    if (rc) return rc;
-    h->parity = (eb + 1) % kEdgePipeBufs;
-  }
-  h->subset_steps++;
-  if (next_slot >= 0) {
-    // (an extraction issued ahead earlier and not consumed — n_active == 0 — is replaced: same buffer, same HIP stream)
-    if (n_next > 0) { rc = issue_extract_list(h, next_slot, h->parity, (int)n, height, width, next_streams, n_next); if (rc) return rc; }
-    h->pf_slot = next_slot; h->pf_subset = n_next != h->S;
-    h->pf_list.assign(next_streams, next_streams + n_next);
-  }
-  if (wait && n_active > 0) return wait_pose(h, full ? 0 : -1, n_active, poses_out, infos_out, 0, full ? nullptr : streams);
-  return LIODOM_OK;
-}
-
-int liodom_replay_resident(liodom_handle_t* h, int first_slot, int count, int ahead, int depth, int64_t n, int height, int width,
-                           double* poses_out, liodom_step_info_t* infos_out) {
-  int rc0 = enter(h);
-  if (rc0) return rc0;
-  if ((rc0 = check_usable(h))) return rc0;
-  if (count < 0 || first_slot < 0 || depth < 0 || depth > 1) { g_last_error = "bad resident range / depth"; return LIODOM_ERR_INVALID_ARG; }
-  SideLocks lk(h, true, true);
-  if ((rc0 = tickets_idle(h))) return rc0;
-  auto out_p = [&](int i) { return poses_out ? poses_out + (size_t)i * h->S * 7 : nullptr; };
-  auto out_i = [&](int i) { return infos_out ? infos_out + (size_t)i * h->S : nullptr; };
-  const auto t_call = std::chrono::steady_clock::now();
-  h->replay_stamps.clear();
-  h->replay_stamps.reserve((size_t)count);
-  auto stamp = [&]() { h->replay_stamps.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count()); };
-  for (int i = 0; i < count; i++) {
-    const int slot = first_slot + i;
-    const int next = (i + 1 < count || ahead) ? slot + 1 : -1;
-    if (depth == 0) {
-      const int rc = replay_one(h, slot, next, n, height, width, true, out_p(i), out_i(i));
-      if (rc) return rc;
-      continue;
-    }
-    // depth 1: enqueue scan i, then collect the pose of scan i - 1 (its sequence number is one behind the enqueue count)
-    const auto t_a = std::chrono::steady_clock::now();
-    int rc = replay_one(h, slot, next, n, height, width, false, nullptr, nullptr);
-    if (rc) return rc;
-    const auto t_b = std::chrono::steady_clock::now();
-    if (i > 0) { rc = wait_pose(h, 0, h->S, out_p(i - 1), out_i(i - 1), 1); if (rc) return rc; stamp(); }
-    // (where the host's time goes in this loop: liodom_get_modes reports the two averages — the host has one scan's duration to
-    //  enqueue the next scan's launches; if the first number approaches the scan period the GPU starves)
-    h->replay_enq_ns += std::chrono::duration<double, std::nano>(t_b - t_a).count();
-    h->replay_wait_ns += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t_b).count();
-    h->replay_timed++;
-  }
-  if (depth == 1 && count > 0) { const int rc = wait_pose(h, 0, h->S, out_p(count - 1), out_i(count - 1), 0); if (rc) return rc; stamp(); }
-  return LIODOM_OK;
 }
 
 // Host-fed replay: the scan of every stream for resident slot `slot` is copied from host memory on the extraction stream
@@ -2230,34 +1760,128 @@ static int upload_slot_consumed(liodom_handle_t* h, int slot) {      // call rig
   return LIODOM_OK;
 }
 
-static int replay_one(liodom_handle_t* h, int slot, int next_slot, int64_t n, int height, int width, bool wait,
-                      double* poses_out, liodom_step_info_t* infos_out, const float* next_host, int64_t host_stride) {
+// One step of the pipelined replay over resident slots (both sides locked by the caller): the odometry of the `n_active` streams
+// of `streams` on slot `slot`, and, next_slot >= 0, the extraction of the `n_next` streams of `next_streams` issued ahead on the
+// extraction stream (next_host: uploaded first, the host-fed replay).  A list of all h->S streams is the plain lock-step step,
+// launch for launch — the range instances, no list upload — and its pointer is not read.  wait: read the poses back before returning.
+static int step_resident(liodom_handle_t* h, int slot, const int32_t* streams, int n_active, int next_slot, const int32_t* next_streams, int n_next,
+                         int64_t n, int height, int width, bool wait, double* poses_out, liodom_step_info_t* infos_out,
+                         const float* next_host = nullptr, int64_t host_stride = 0) {
   if (!h->resident || slot < 0 || slot >= h->n_slots || next_slot >= h->n_slots || n < 0 || n > h->v.max_points) {
     g_last_error = "bad resident slot"; return LIODOM_ERR_INVALID_ARG;
   }
   // resident layout: [slot][stream][max_points]: one lock-step launch reads a contiguous block
   h->replay_live.store(true);
-  const int eb = h->parity;
+  const bool full = n_active == h->S, next_full = n_next == h->S;
   int rc;
-  if (h->pf_slot != slot || h->pf_subset) {       // extraction not issued ahead (or for some streams only, by a subset step): do it now
-    rc = issue_extract(h, slot, eb, (int)n, height, width);
+  if (n_active > 0) {
+    const int eb = h->parity;
+    // issued ahead for exactly these streams?  Anything else — another slot, another list, nothing — is extracted now
+    const bool ahead = h->pf_slot == slot && (full ? !h->pf_subset
+                                                   : (h->pf_subset && (int)h->pf_list.size() == n_active && std::equal(streams, streams + n_active, h->pf_list.begin())));
+    if (!ahead) { rc = issue_extract_list(h, slot, eb, (int)n, height, width, streams, n_active); if (rc) return rc; }
+    h->pf_slot = -1; h->pf_subset = false;
+    if (full) {
+      rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb]);
+    } else {
+      // (list kEdgePipeBufs + eb, uploaded on the odometry stream behind the previous odometry of buffer eb)
+      rc = put_stream_list(h, h->stream, kEdgePipeBufs + eb, streams, n_active);
+      if (rc) return rc;
+      rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb], -(kEdgePipeBufs + eb) - 1, n_active, streams);
+    }
     if (rc) return rc;
+    h->parity = (eb + 1) % kEdgePipeBufs;
   }
-  h->pf_slot = -1;
-  rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb]);
-  if (rc) return rc;
-  h->parity = (eb + 1) % kEdgePipeBufs;
+  if (!(full && (next_slot < 0 || next_full))) h->subset_steps++;      // (liodom_get_modes: steps that were not the plain step)
   if (next_slot >= 0) {                           // overlap the next scan's (upload and) extraction with this odometry
     if (next_host) { rc = upload_slot_async(h, next_slot, next_host, host_stride, n); if (rc) return rc; }
     // (a gate in front of the next scan's extraction — start it when this scan's first solve starts, so that it runs beside the
     //  solves instead of beside the first kNN pass — was measured: -1.6 %; removed)
-    rc = issue_extract(h, next_slot, h->parity, (int)n, height, width);
-    if (rc) return rc;
+    // (an extraction issued ahead earlier and not consumed — n_active == 0 — is replaced: same buffer, same HIP stream)
+    if (n_next > 0) { rc = issue_extract_list(h, next_slot, h->parity, (int)n, height, width, next_streams, n_next); if (rc) return rc; }
     if (next_host) { rc = upload_slot_consumed(h, next_slot); if (rc) return rc; }
-    h->pf_slot = next_slot; h->pf_subset = false;
+    h->pf_slot = next_slot; h->pf_subset = !next_full;
+    if (!next_full) h->pf_list.assign(next_streams, next_streams + n_next);
   }
-  if (wait) return wait_pose(h, 0, h->S, poses_out, infos_out);
+  if (wait && n_active > 0) return wait_pose(h, full ? 0 : -1, n_active, poses_out, infos_out, 0, full ? nullptr : streams);
   return LIODOM_OK;
+}
+
+// The consumer loop of liodom_replay_resident and liodom_replay_host over `count` scans, scan i stepped by step(i, wait, poses, infos):
+// depth 0 waits inside the step; depth 1 enqueues scan i, then collects the pose of scan i - 1 (its sequence number is one behind
+// the enqueue count).  timed: the resident replay's counters (where the host's time goes in this loop: liodom_get_modes reports the
+// two averages — the host has one scan's duration to enqueue the next scan's launches; if the first number approaches the scan period
+// the GPU starves) and the stamp of every collected pose.
+extern "C++" {      // (a template, inside the C entry points)
+template <class Step>
+static int replay_loop(liodom_handle_t* h, int count, int depth, double* poses_out, liodom_step_info_t* infos_out, bool timed, Step step) {
+  using clock = std::chrono::steady_clock;
+  auto out_p = [&](int i) { return poses_out ? poses_out + (size_t)i * h->S * 7 : nullptr; };
+  auto out_i = [&](int i) { return infos_out ? infos_out + (size_t)i * h->S : nullptr; };
+  const clock::time_point t_call = timed ? clock::now() : clock::time_point();
+  auto stamp = [&]() { if (timed) h->replay_stamps.push_back(std::chrono::duration<double, std::micro>(clock::now() - t_call).count()); };
+  for (int i = 0; i < count; i++) {
+    if (depth == 0) {
+      const int rc = step(i, true, out_p(i), out_i(i));
+      if (rc) return rc;
+      continue;
+    }
+    const clock::time_point t_a = timed ? clock::now() : clock::time_point();
+    int rc = step(i, false, nullptr, nullptr);
+    if (rc) return rc;
+    const clock::time_point t_b = timed ? clock::now() : clock::time_point();
+    if (i > 0) { rc = wait_pose(h, 0, h->S, out_p(i - 1), out_i(i - 1), 1); if (rc) return rc; stamp(); }
+    if (timed) {
+      h->replay_enq_ns += std::chrono::duration<double, std::nano>(t_b - t_a).count();
+      h->replay_wait_ns += std::chrono::duration<double, std::nano>(clock::now() - t_b).count();
+      h->replay_timed++;
+    }
+  }
+  if (depth == 1 && count > 0) { const int rc = wait_pose(h, 0, h->S, out_p(count - 1), out_i(count - 1), 0); if (rc) return rc; stamp(); }
+  return LIODOM_OK;
+}
+}
+
+int liodom_process_resident_pipelined(liodom_handle_t* h, int slot, int next_slot, int64_t n, int height,
+                                      int width, double* poses_out, liodom_step_info_t* infos_out) {
+  int rc0 = enter(h);
+  if (rc0) return rc0;
+  if ((rc0 = check_usable(h))) return rc0;
+  SideLocks lk(h, true, true);
+  if ((rc0 = tickets_idle(h))) return rc0;        // (the replay fills the same pipeline edge buffers)
+  return step_resident(h, slot, nullptr, h->S, next_slot, nullptr, h->S, n, height, width, poses_out != nullptr || infos_out != nullptr, poses_out, infos_out);
+}
+
+int liodom_process_resident_subset(liodom_handle_t* h, int slot, const int32_t* streams, int n_active,
+                                   int next_slot, const int32_t* next_streams, int n_next,
+                                   int64_t n, int height, int width, double* poses_out, liodom_step_info_t* infos_out) {
+  int rc = enter(h);
+  if (rc) return rc;
+  if ((rc = check_usable(h))) return rc;
+  if (!stream_list_valid(h, streams, n_active)) { g_last_error = "liodom_process_resident_subset: streams must be strictly ascending stream indices"; return LIODOM_ERR_INVALID_ARG; }
+  if (next_slot >= 0 && !next_streams) { next_streams = streams; n_next = n_active; }      // (the same streams step again)
+  if (next_slot >= 0 && !stream_list_valid(h, next_streams, n_next)) { g_last_error = "liodom_process_resident_subset: next_streams must be strictly ascending stream indices"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, true, true);
+  if ((rc = tickets_idle(h))) return rc;        // (the pipeline edge buffers, as the replay)
+  const bool wait = poses_out != nullptr || infos_out != nullptr;
+  return step_resident(h, slot, streams, n_active, next_slot, next_streams, n_next, n, height, width, wait, poses_out, infos_out);
+}
+
+int liodom_replay_resident(liodom_handle_t* h, int first_slot, int count, int ahead, int depth, int64_t n, int height, int width,
+                           double* poses_out, liodom_step_info_t* infos_out) {
+  int rc0 = enter(h);
+  if (rc0) return rc0;
+  if ((rc0 = check_usable(h))) return rc0;
+  if (count < 0 || first_slot < 0 || depth < 0 || depth > 1) { g_last_error = "bad resident range / depth"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, true, true);
+  if ((rc0 = tickets_idle(h))) return rc0;
+  h->replay_stamps.clear();
+  h->replay_stamps.reserve((size_t)count);
+  return replay_loop(h, count, depth, poses_out, infos_out, true, [&](int i, bool wait, double* poses, liodom_step_info_t* infos) {
+    const int slot = first_slot + i;
+    const int next = (i + 1 < count || ahead) ? slot + 1 : -1;
+    return step_resident(h, slot, nullptr, h->S, next, nullptr, h->S, n, height, width, wait, poses, infos);
+  });
 }
 
 int liodom_replay_host(liodom_handle_t* h, const float* xyzi_base, int64_t scan_stride_floats, int count, int depth,
@@ -2280,31 +1904,21 @@ int liodom_replay_host(liodom_handle_t* h, const float* xyzi_base, int64_t scan_
   // ALLOC launch on a third stream and made it 133 us.  So not here.
   struct Suppress { liodom_handle* h; ~Suppress() { h->ov_suppress = false; } } suppress{h};
   h->ov_suppress = true;
-  auto out_p = [&](int i) { return poses_out ? poses_out + (size_t)i * h->S * 7 : nullptr; };
-  auto out_i = [&](int i) { return infos_out ? infos_out + (size_t)i * h->S : nullptr; };
   auto src = [&](int i) { return xyzi_base + (size_t)i * (size_t)h->S * (size_t)scan_stride_floats; };
-  for (int i = 0; i < count; i++) {
+  rc = replay_loop(h, count, depth, poses_out, infos_out, false, [&](int i, bool wait, double* poses, liodom_step_info_t* infos) {
     const int slot = i % kRing, next = (i + 1 < count) ? (i + 1) % kRing : -1;
     if (i == 0) {                                 // first scan: upload + extraction now
-      rc = upload_slot_async(h, slot, src(0), scan_stride_floats, n);
-      if (rc) return rc;
-      rc = issue_extract(h, slot, h->parity, (int)n, height, width);
-      if (rc) return rc;
+      int rc1 = upload_slot_async(h, slot, src(0), scan_stride_floats, n);
+      if (rc1) return rc1;
+      rc1 = issue_extract(h, slot, h->parity, (int)n, height, width);
+      if (rc1) return rc1;
       h->pf_slot = slot; h->pf_subset = false;
-      rc = upload_slot_consumed(h, slot);
-      if (rc) return rc;
+      rc1 = upload_slot_consumed(h, slot);
+      if (rc1) return rc1;
     }
-    const float* nh = next >= 0 ? src(i + 1) : nullptr;
-    if (depth == 0) {
-      rc = replay_one(h, slot, next, n, height, width, true, out_p(i), out_i(i), nh, scan_stride_floats);
-      if (rc) return rc;
-      continue;
-    }
-    rc = replay_one(h, slot, next, n, height, width, false, nullptr, nullptr, nh, scan_stride_floats);
-    if (rc) return rc;
-    if (i > 0) { rc = wait_pose(h, 0, h->S, out_p(i - 1), out_i(i - 1), 1); if (rc) return rc; }
-  }
-  if (depth == 1 && count > 0) { rc = wait_pose(h, 0, h->S, out_p(count - 1), out_i(count - 1), 0); if (rc) return rc; }
+    return step_resident(h, slot, nullptr, h->S, next, nullptr, h->S, n, height, width, wait, poses, infos, next >= 0 ? src(i + 1) : nullptr, scan_stride_floats);
+  });
+  if (rc) return rc;
   if (h->stream_c) HIP_TRY(hipStreamSynchronize(h->stream_c));
   for (int b = 0; b < 3; b++) h->ev_xdone_valid[b] = false;
   return drain_pipeline(h);                       // the caller's buffer may be reused / unpinned after the return
@@ -2609,7 +2223,7 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   if (v.knn_done0) (void)hipMemcpy(done_cnt, v.knn_done0, sizeof(done_cnt), hipMemcpyDeviceToHost);
   (void)hipMemcpy(r.spec_stats, reinterpret_cast<const char*>(v.state) + offsetof(StreamState, spec_stats), sizeof(r.spec_stats), hipMemcpyDeviceToHost);
   (void)hipMemcpy(r.hb_stats, reinterpret_cast<const char*>(v.state) + offsetof(StreamState, hb_stats), sizeof(r.hb_stats), hipMemcpyDeviceToHost);
-  r.chain_count = h->chain_count; r.done0 = done_cnt[0]; r.done1 = done_cnt[32];
+  r.chain_count = h->step.chain_count; r.done0 = done_cnt[0]; r.done1 = done_cnt[32];
   if (h->replay_timed) { r.replay_enqueue_us = h->replay_enq_ns / (1e3 * (double)h->replay_timed); r.replay_wait_us = h->replay_wait_ns / (1e3 * (double)h->replay_timed); }
   r.n_lagged = h->n_lagged; r.n_readers = h->n_readers; r.subset_steps = h->subset_steps;
   plan_format_modes(h->plan, r, buf, cap);

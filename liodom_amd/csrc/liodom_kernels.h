@@ -49,7 +49,8 @@ namespace liodom_dev {
 #endif
 constexpr int kWave = 64;
 constexpr uint64_t kEmptyKey = 0xFFFFFFFFFFFFFFFFull;
-// (kLmThreads, kLmGroupsMax, kMaxFrames, kEdgeBufs, kEdgePipeBufs: liodom_sizes.h)
+// (kLmThreads, kLmGroupsMax, kMaxFrames, kEdgeBufs, kEdgePipeBufs, and the launch constants of the kernel files — workgroup sizes,
+//  workgroups per role —: liodom_sizes.h)
 constexpr int kLmEvalThreads = kLmThreads;
 constexpr int kLmCtl = kLmThreads - 64;   // lane 0 of the last wave also runs the trust-region logic; the other waves prepare (compaction, register cache) meanwhile
 constexpr int kKnnGroup = 32;            // lanes cooperating on one query

@@ -28,6 +28,7 @@
 
 #include "liodom_math.h"
 #include "map_state_format.h"
+#include "liodom_sizes.h"      // kMapRowsThreads
 
 namespace liodom_dev {
 
@@ -518,7 +519,6 @@ __global__ __launch_bounds__(256) void k_map_gather(MapView m, float4* out, int 
 // get here with more keys all the same, the plan stops at the cap and raises MAP_STATUS_LOCAL_OVERFLOW.
 // ---------------------------------------------------------------------------------------------
 constexpr int kMapRowsKeysMax = 1024;
-constexpr int kMapRowsThreads = 256;
 constexpr int kMapRowsGridX = 16;       // most workgroups a row is dealt to
 constexpr int kMapRowsGridMax = 2048;   // most workgroups of a launch
 

@@ -1,5 +1,6 @@
-// liodom_sizes.h — the numbers the host's plan of a handle (handle_plan.h) and the kernels must agree on: tile, window and buffer
-// constants and the dynamic-LDS size of every kernel that takes one.  Plain C++ without a HIP include: hipcc takes it through the
+// liodom_sizes.h — the numbers the host's plans (of a handle: handle_plan.h; of a scan's launches: step_plan.h) and the kernels must
+// agree on: tile, window and buffer constants, the launch constants (workgroup sizes, workgroups per role) and the dynamic-LDS size of
+// every kernel that takes one.  Plain C++ without a HIP include: hipcc takes it through the
 // kernel headers, g++ through handle_plan.h.  Each constant sits with the comment of the kernel it belongs to; the kernels
 // themselves are in the kernels_*.h file named beside it.
 #pragma once
@@ -34,6 +35,8 @@ constexpr int kEdgePipeBufs = 3;
 // ---- kernels_extract.h: k_classify / k_ring_scatter / k_ring_split / k_ring_split_lb ----
 constexpr int kTilePts = 2048;
 constexpr int kTileChunks = kTilePts / 64;   // 32
+constexpr int kTileThreads = 512;            // workgroup of the four ring-split kernels
+constexpr int kRowThreads = 512;             // k_row_compact: one workgroup per (row, stream)
 
 LS_HD int ring_scatter_stride(int H) { return H | 1; }
 // LDS: phase A = lane masks [32][Hp] u64 + chunk prefixes [32][Hp] u16; phase B reuses the same
@@ -71,6 +74,9 @@ LS_HD size_t ring_extract_lds_bytes(int slots, int regions) {
   return (b + 15) / 16 * 16;
 }
 
+// ---- kernels_compact.h ----
+constexpr int kCompactBlocks = 8;      // k_compact_edges: grid (kCompactBlocks, streams); every workgroup scans the ring counts itself and copies its interleaved share
+
 // ---- kernels_knn.h / kernels_knn8.h ----
 constexpr int kKnnGridDiv = 2;         // k_knn grid = half of the query blocks the edge capacity allows: a workgroup takes block b and, if the scan has that many edges, b + grid
 constexpr int kG8 = 8;                    // lanes per query
@@ -79,6 +85,7 @@ constexpr int kG8 = 8;                    // lanes per query
 #endif
 constexpr int kKnn8Threads = LIODOM_KNN8_THREADS;      // 4 waves = 32 queries per workgroup (512 threads: the sort below balances better, but the workgroups pack worse — 373 us against 334 for a first pass at 256 streams)
 constexpr int kKnn8Queries = kKnn8Threads / kG8;
+constexpr int kKnn8ExactBlocks = 4;    // k_knn8_exact: workgroups per stream that walk the list of queries the fast path cannot certify (one wave per query)
 
 // ---- kernels_lm.h ----
 // dynamic LDS of k_lm_solve: the index list (the reduction's per-wave sums, sh_wsum, are static: 1 KiB)
@@ -86,7 +93,16 @@ LS_HD size_t lm_lds_bytes(int edge_cap) {
   return (size_t)((edge_cap + 3) & ~3) * sizeof(int);
 }
 
+// ---- kernels_rebuild.h: the streamed rebuild ----
+constexpr int kRebuildAuxBlocks = 8;      // workgroups for ALLOC (inside k_knn) and for CLEAR (k_lm_solve)
+constexpr int kRebuildAllocBlocks = 32;   // k_rebuild_alloc: the ~8 000 occupied cells of a headline scan in one sweep (it sits between the two solve launches)
+#ifndef LIODOM_REBFIN_THREADS
+#define LIODOM_REBFIN_THREADS LIODOM_LM_THREADS
+#endif
+constexpr int kRebFinThreads = LIODOM_REBFIN_THREADS;      // k_rebuild_fin (chain mode: APPEND, CLEAR, SCATTER as a launch of their own)
+
 // ---- kernels_rebuild.h: k_hash_build, k_hash_append ----
+constexpr int kBuildThreads = 1024;
 constexpr int kLdsSlots = 8192;
 constexpr int kLdsCellsMax = 6144;
 LS_HD size_t hash_build_lds_bytes() { return (size_t)kLdsSlots * 16 + 64; }
@@ -96,5 +112,8 @@ LS_HD size_t hash_build_lds_bytes() { return (size_t)kLdsSlots * 16 + 64; }
 constexpr int kHbPeriod = LIODOM_HB_PERIOD;       // scans between two rebuilds from the whole window (<= 8: hb_base)
 constexpr int kHbNewRoom = 96;     // room of a cell that k_hash_append creates (DevView::hb_new_room; kHbSlackMin = 32: hb_slack_min)
 constexpr int kHbSlackMin = 32;
+
+// ---- liodom_map.h: k_map_local_rows ----
+constexpr int kMapRowsThreads = 256;
 
 }  // namespace liodom_dev
