@@ -56,7 +56,11 @@ LD_HD bool valid_point(double x, double y, double z, double min_range, double ma
 }
 
 // Velodyne elevation binning (:127-151).  Returns -1 when the point is dropped.
+// A NaN angle (x = y = z = 0 with min_range 0: atan(0 / 0)) is dropped HERE, before any conversion: the reference converts it to
+// int, which C++ leaves undefined — x86-64 gives INT_MIN (dropped by the range test), gfx950 gives 0 (ring 0, or 32 of 64 lines).
+// The x86 outcome is the one taken ("The ring split on designed clouds").
 LD_HD int velodyne_ring_from_angle(double angle, int scan_lines) {
+  if (angle != angle) return -1;
   int scan_id;
   if (scan_lines == 64) {
     if (angle >= -8.83) scan_id = int((2 - angle) * 3.0 + 0.5);
@@ -77,6 +81,7 @@ LD_HD int velodyne_ring_from_angle(double angle, int scan_lines) {
 // trusts the result when both agree (every branch, truncation and drop test is monotone in the angle; float rounding of these
 // expressions is below 2e-5 degrees, the margin m is 2e-4).
 LD_HD int velodyne_ring_from_angle_f(float angle, int scan_lines) {
+  if (angle != angle) return -1;            // (as above; the fast path never decides a point with a NaN angle, but is not relied on)
   int scan_id;
   if (scan_lines == 64) {
     if (angle >= -8.83f) scan_id = (int)((2.0f - angle) * 3.0f + 0.5f);

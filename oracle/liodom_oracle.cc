@@ -89,6 +89,9 @@ inline bool is_valid_point(const orc_params_t& p, double x, double y, double z, 
 inline int velodyne_ring(const orc_params_t& p, double z, double distance) {
   int scan_id = -1;
   double angle = std::atan(z / distance) * 180 / M_PI;                                 // :128
+  // x = y = z = 0 with min_range 0: a NaN angle, which the reference converts to int (undefined in C++; INT_MIN on x86-64, so the
+  // tests below drop the point).  Stated here, so that the answer does not depend on the compiler.
+  if (std::isnan(angle)) return -1;
   if (p.scan_lines == 64) {                                                            // :130
     if (angle >= -8.83) scan_id = int((2 - angle) * 3.0 + 0.5);                        // :131-132
     else scan_id = p.scan_lines / 2 + int((-8.83 - angle) * 2.0 + 0.5);                // :134
