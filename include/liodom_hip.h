@@ -597,6 +597,55 @@ int liodom_attach_map_reader(liodom_handle_t* h, int stream, liodom_map_t* m, in
 int liodom_seed_stream(liodom_handle_t* h, int stream, const double* pose /*[7]*/);
 int liodom_map_get_local_batch(liodom_map_t* m, const double* T /*n x 12*/, int n, int cells_xy, int cells_z, float* xyzi,
                                int64_t cap_per_row, int64_t* n_points /*[n]*/);
+/* ---- knowing that a reader is lost: per-scan map-hit records (no counterpart in the reference; DESIGN.md §3 "Knowing that a
+ * reader is lost").  liodom_step_info_t counts matches against window ++ received map: a stream that slides
+ * along its own window keeps them high while it leaves the map.  These records hold, per scan and from the device, the two counts
+ * the relocaliser ranks by, taken at the pose the scan returned.  Everything is opt-in: a handle that never calls
+ * liodom_set_map_hits allocates and launches what it always did.
+ *
+ *   liodom_set_map_hits     radius 0 | 1 switches the records of one stream on (or changes the radius), -1 switches them off.
+ *       mapping = 1 handles only (else LIODOM_ERR_UNSUPPORTED).  The call takes both sides of the handle and waits for its HIP
+ *       streams, like liodom_attach_map_reader; LIODOM_ERR_BUSY while edge tickets are outstanding; a bad stream or radius is
+ *       LIODOM_ERR_INVALID_ARG with the handle untouched.  The first enabling call allocates the log: pose_log_capacity records
+ *       of 128 bytes per stream, indexed like the pose log.  While it is on, the stream gets one record for every scan that gets
+ *       a pose-log entry (scans at or beyond pose_log_capacity are not logged; a stream that sits a subset step out gets none
+ *       for that step).  The setting survives liodom_reset, liodom_reset_stream, liodom_seed_stream and
+ *       liodom_import_stream_state, which move the log index exactly as they move the pose-log index.  liodom_get_modes reports
+ *       map_hits=<streams with it on> when that is not 0.
+ *   the record              edges = scan k's edge cloud as it lies in the handle's edge buffer (sensor frame: what the stream's
+ *       mapper would be given), T = the stream's final pose of scan k as the 3 x 4 matrix the device holds, copied into the
+ *       record.  hits_r, hits_0 are what liodom_map_score_poses(map, edges_k, n_edges, rec.T, 1, radius) returns: same probes,
+ *       keys, leaf test and finiteness rules.  Nothing of the map is written.  The occupancy is kept between scans while the
+ *       map does not change: every call and every enqueue that can change the map's cells (liodom_map_update, _prune, _evict,
+ *       _merge_state, _import_state, _reset, a writing mapper's step) invalidates it, and the next step that needs it builds it
+ *       again, on the handle's stream.  It has a row for each of the map's max_cells cells (4 bytes per 32 leaves each),
+ *       allocated when hits are first on for a stream that reads the map, never inside a step.
+ *       A stream without a reader — none attached, or a WRITING mapper (liodom_attach_mapper[_ex]) — gets LIODOM_HIT_NO_READER
+ *       records with zero counts and n_edges 0: counting against a map that changes every scan is out of scope.
+ *   liodom_get_map_hit_log  records first .. first + count - 1 of a stream, with the range rules and the synchronisation of
+ *       liodom_get_pose_log; LIODOM_ERR_UNSUPPORTED on a handle that never switched the records on.  Entries no scan has
+ *       written have flags 0.  (An un-synchronised per-scan wait, as liodom_wait_pose_covariance is for its record, does not exist.)
+ *   liodom_map_hit_rows     the kernel's public form: row i probes its own cloud, edges_xyzi + 4 * i * edge_stride_points with
+ *       n_edges[i] points, under T + 12 i; hits[2 i], hits[2 i + 1] = hits_r, hits_0.  Works on detached and attached maps.
+ *       Limits, argument rules, threading rule, read-only guarantee and error codes are those of liodom_map_score_poses:
+ *       n <= 2^20, 0 <= n_edges[i] <= edge_stride_points <= max_update_points, radius 0 | 1.  n = 0, or an n_edges that is 0
+ *       everywhere: LIODOM_OK with zero counts.  It rebuilds the occupancy on every call, as liodom_map_score_poses does. */
+typedef struct liodom_map_hit_t {
+  int32_t scan_index;      /* = liodom_step_info_t.scan_index of the same scan */
+  uint32_t flags;          /* LIODOM_HIT_* */
+  int32_t n_edges;         /* edges of the scan that were probed */
+  int32_t hits_r, hits_0;  /* as liodom_map_score_poses defines them */
+  int32_t radius;          /* 0 | 1 */
+  int32_t reserved[2];
+  double T[12];            /* the matrix the counts were taken under: the stream's final pose of this scan, 3 x 4 row-major */
+} liodom_map_hit_t;        /* 128 bytes */
+#define LIODOM_HIT_VALID 1u      /* a reader was attached and the scan was counted */
+#define LIODOM_HIT_NO_READER 2u  /* no reader on the stream at this scan: counts 0 */
+#define LIODOM_HIT_NO_SOLVE 4u   /* first scan of an unseeded stream: counted under the initial pose (may accompany VALID) */
+int liodom_set_map_hits(liodom_handle_t* h, int stream, int radius /* -1 off, 0, 1 */);
+int liodom_get_map_hit_log(liodom_handle_t* h, int stream, int first, int count, liodom_map_hit_t* out);
+int liodom_map_hit_rows(liodom_map_t* m, const float* edges_xyzi, int64_t edge_stride_points, const int32_t* n_edges /*[n]*/,
+                        const double* T /*n x 12*/, int n, int radius /*0 | 1*/, int32_t* hits /*n x 2: hits_r, hits_0*/);
 /* Sticky LIODOM_MAP_* bits raised by the device since creation. */
 int liodom_map_status(liodom_map_t* m, uint32_t* status);
 

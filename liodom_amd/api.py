@@ -14,7 +14,7 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
                                                   "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
-                                                  "kernels_reloc_bnb.h", "reloc_bnb.h",
+                                                  "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h",
                                                   "liodom_sizes.h", "handle_plan.h", "step_plan.h", "liodom_step_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -179,6 +179,44 @@ class PoseSearchStats(C.Structure):
     """liodom_pose_search_stats_t: what a liodom_map_search_pose_bnb call did."""
     _fields_ = [("n_candidates", C.c_int64), ("nodes_bounded", C.c_int64), ("candidates_scored", C.c_int64),
                 ("rounds", C.c_int32), ("levels_built", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class MapHit(C.Structure):
+    """liodom_map_hit_t: one scan's map-hit record (liodom_set_map_hits)."""
+    _fields_ = [("scan_index", C.c_int32), ("flags", C.c_uint32), ("n_edges", C.c_int32), ("hits_r", C.c_int32), ("hits_0", C.c_int32),
+                ("radius", C.c_int32), ("reserved", C.c_int32 * 2), ("T", C.c_double * 12)]
+
+
+MAP_HIT_DTYPE = np.dtype([("scan_index", "<i4"), ("flags", "<u4"), ("n_edges", "<i4"), ("hits_r", "<i4"), ("hits_0", "<i4"), ("radius", "<i4"),
+                          ("reserved", "<i4", (2,)), ("T", "<f8", (3, 4))])
+HIT_VALID, HIT_NO_READER, HIT_NO_SOLVE = 1, 2, 4
+TRACKING, LOST = "TRACKING", "LOST"
+
+
+class TrackPolicy:
+    """When a map reader counts as lost: the rules of liodom_amd/csrc/track_policy.h, restated (tests/test_track_policy.py holds the
+    two equal).  feed() takes one hit record and answers TRACKING or LOST: LOST at the lost_after-th consecutive valid scan whose
+    fraction (hits_r + hits_0) / (2 n_edges) is below min_fraction (n_edges = 0 counts as below; a record without HIT_VALID changes
+    nothing); the streak starts over with LOST."""
+
+    def __init__(self, min_fraction, lost_after=3):
+        self.min_fraction, self.lost_after, self.below = float(min_fraction), int(lost_after), 0
+
+    @staticmethod
+    def fraction(hits_r, hits_0, n_edges):
+        return (float(hits_r) + float(hits_0)) / (2.0 * float(n_edges)) if n_edges > 0 else 0.0
+
+    def feed(self, hits_r, hits_0, n_edges, flags):
+        if not (int(flags) & HIT_VALID):
+            return TRACKING
+        if n_edges > 0 and self.fraction(hits_r, hits_0, n_edges) >= self.min_fraction:
+            self.below = 0
+            return TRACKING
+        self.below += 1
+        if self.below < max(1, self.lost_after):
+            return TRACKING
+        self.below = 0
+        return LOST
 
 
 class EdgeTicket(C.Structure):
@@ -555,6 +593,12 @@ def load():
     L.liodom_map_score_poses.restype = C.c_int
     L.liodom_map_score_poses.argtypes = [vp, fp, C.c_int, dp, C.c_int, C.c_int, ip]
     L.liodom_pose_search_default.argtypes = [C.POINTER(PoseSearch)]
+    L.liodom_set_map_hits.restype = C.c_int
+    L.liodom_set_map_hits.argtypes = [vp, C.c_int, C.c_int]
+    L.liodom_get_map_hit_log.restype = C.c_int
+    L.liodom_get_map_hit_log.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    L.liodom_map_hit_rows.restype = C.c_int
+    L.liodom_map_hit_rows.argtypes = [vp, fp, C.c_int64, ip, dp, C.c_int, C.c_int, ip]
     L.liodom_map_search_pose.restype = C.c_int
     L.liodom_map_search_pose.argtypes = [vp, fp, C.c_int, C.POINTER(PoseSearch), C.POINTER(PoseSearchResult), dp, ip]
     L.liodom_pose_search_bnb_default.argtypes = [C.POINTER(PoseSearchBnb)]
@@ -664,6 +708,7 @@ EXPORTED_SYMBOLS = [
     "liodom_attach_map_reader", "liodom_seed_stream", "liodom_map_get_local_batch",
     "liodom_map_score_poses", "liodom_pose_search_default", "liodom_map_search_pose",
     "liodom_pose_search_bnb_default", "liodom_map_bound_nodes", "liodom_map_search_pose_bnb",
+    "liodom_set_map_hits", "liodom_get_map_hit_log", "liodom_map_hit_rows",
 ]
 
 
@@ -1149,6 +1194,39 @@ class Liodom:
         self.seed_stream(pose, stream=stream)
         return dict(pose=pose, hits_r=last["hits_r"], hits_0=last["hits_0"], n_edges=int(edges.shape[0]), fraction=fraction, levels=found)
 
+    def set_map_hits(self, radius, stream=0):
+        """Per-scan map-hit records for `stream` (liodom_set_map_hits): radius 0 or 1 switches them on, -1 off."""
+        self._check(self.L.liodom_set_map_hits(self.h, int(stream), int(radius)))
+
+    def map_hits(self, first, count, stream=0):
+        """Hit records of scans first .. first + count - 1 of `stream` (liodom_get_map_hit_log) as a structured array
+        (MAP_HIT_DTYPE: scan_index, flags, n_edges, hits_r, hits_0, radius, reserved, T [3, 4])."""
+        out = np.zeros(max(int(count), 1), MAP_HIT_DTYPE)
+        self._check(self.L.liodom_get_map_hit_log(self.h, int(stream), int(first), int(count), out.ctypes.data_as(C.c_void_p)))
+        return out[:max(int(count), 0)]
+
+    def localize_scan(self, map, scan, height, width, stamp, policy, levels, stream=0):
+        """process_scan with the "lost" policy and the recovery on top: the scan's hit record (set_map_hits must be on for the
+        stream) is fed to `policy` (a TrackPolicy, kept by the caller from scan to scan); on LOST the stream is relocalised
+        (relocalize with policy.min_fraction, `levels` as there) around the pose of the last scan whose fraction was
+        >= policy.min_fraction — this scan's pose if there has been none — and, if that seeds the stream, the SAME scan is
+        processed again.  Returns dict(pose, info, hit, state, relocalized): pose / info / hit (a MAP_HIT_DTYPE record) of the scan
+        as it was last processed, state = what the policy answered for its first processing, relocalized = the result of
+        relocalize (None: not lost, or nothing good enough was found and the stream goes on as it was)."""
+        pose, info = self.process_scan(scan, height, width, stamp=stamp, stream=stream)
+        hit = self.map_hits(info.scan_index, 1, stream=stream)[0].copy()
+        state = policy.feed(hit["hits_r"], hit["hits_0"], hit["n_edges"], hit["flags"])
+        good = getattr(policy, "last_good_pose", None)
+        found = None
+        if state == LOST:
+            found = self.relocalize(map, scan, height, width, pose if good is None else good, levels, min_fraction=policy.min_fraction, stream=stream)
+            if found is not None:
+                pose, info = self.process_scan(scan, height, width, stamp=stamp, stream=stream)
+                hit = self.map_hits(info.scan_index, 1, stream=stream)[0].copy()
+        if (int(hit["flags"]) & HIT_VALID) and hit["n_edges"] > 0 and policy.fraction(hit["hits_r"], hit["hits_0"], hit["n_edges"]) >= policy.min_fraction:
+            policy.last_good_pose = np.array(pose, dtype=np.float64)
+        return dict(pose=pose, info=info, hit=hit, state=state, relocalized=found)
+
     def local_map(self, stream=0):
         cap = self.edge_cap * int(self.params.local_map_size) + (max(int(self.config.recv_capacity), 262144) if self.params.mapping else 0)
         w = np.zeros((cap, 4), np.float32)
@@ -1283,6 +1361,24 @@ class Map:
         hits = np.zeros((T.shape[0], 2), np.int32)
         self._chk(self._L.liodom_map_score_poses(self.h, _fp(e), e.shape[0], _dp(T), T.shape[0], int(radius), _ip(hits)))
         return hits
+
+    def hit_rows(self, edges_list, T, radius=1):
+        """hits_r, hits_0 of n rows, each its own edge cloud under its own pose (liodom_map_hit_rows): edges_list = n arrays [E_i, 4],
+        T = [n, 3, 4] (or [n, 12]) -> int32 [n, 2].  Row i equals score_poses(edges_list[i], T[i], radius)[0].  Read-only on the map."""
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(-1, 12)
+        clouds = [np.ascontiguousarray(e, dtype=np.float32).reshape(-1, 4) for e in edges_list]
+        n = T.shape[0]
+        if len(clouds) != n:
+            raise ValueError("hit_rows: one edge cloud per pose")
+        counts = np.array([c.shape[0] for c in clouds], np.int32).reshape(-1)
+        stride = int(counts.max()) if n else 0
+        packed = np.zeros((max(n, 1), max(stride, 1), 4), np.float32)
+        for i, c in enumerate(clouds):
+            packed[i, :c.shape[0]] = c
+        hits = np.zeros((max(n, 1), 2), np.int32)
+        self._chk(self._L.liodom_map_hit_rows(self.h, _fp(packed), max(stride, 1) if n else 0, _ip(np.ascontiguousarray(counts) if n else np.zeros(1, np.int32)),
+                                              _dp(T if n else np.zeros(12)), n, int(radius), _ip(hits)))
+        return hits[:n]
 
     def search_pose(self, edges, centre, want_T=False, want_hits=False, **grid):
         """Scores the candidate grid around centre = [qx qy qz qw tx ty tz] (liodom_map_search_pose; grid keywords as

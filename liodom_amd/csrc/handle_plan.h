@@ -397,7 +397,7 @@ struct ModesRuntime {
   int hb_stats[4] = {0, 0, 0, 0}, spec_stats[4] = {0, 0, 0, 0};
   unsigned int chain_count = 0, done0 = 0, done1 = 0;
   double replay_enqueue_us = 0.0, replay_wait_us = 0.0;
-  int n_lagged = 0, n_readers = 0;
+  int n_lagged = 0, n_readers = 0, n_hits = 0;
   long long subset_steps = 0;
 };
 
@@ -421,6 +421,7 @@ inline void plan_format_modes(const HandlePlan& p, const ModesRuntime& r, char* 
   if (p.pose_covariance) { char* t = tail(&room); snprintf(t, room, " pose_cov=1"); }
   if (r.n_lagged > 0) { char* t = tail(&room); snprintf(t, room, " mapper_lag=%d", r.n_lagged); }      // streams with a lagged mapper (liodom_attach_mapper_ex); their steps run on the odometry stream alone, as every mapping handle's
   if (r.n_readers > 0) { char* t = tail(&room); snprintf(t, room, " map_readers=%d map_rows=%d", r.n_readers, p.map_rows ? 1 : 0); }     // streams that read a map they never write (liodom_attach_map_reader)
+  if (r.n_hits > 0) { char* t = tail(&room); snprintf(t, room, " map_hits=%d", r.n_hits); }      // streams with per-scan hit records on (liodom_set_map_hits)
   { char* t = tail(&room); snprintf(t, room, " subset_steps=%lld", r.subset_steps); }      // (steps liodom_process_resident_subset ran over a stream list, i.e. did not hand to the plain step)
 }
 

@@ -157,6 +157,11 @@ struct liodom_handle {
   std::vector<liodom_map*> read_maps; // distinct maps with readers; a map's tag is its index + 1 (freed places are null and taken again)
   int4* reader_sel = nullptr;         // [S] device: {tag of the map the stream reads (0: none), cells_xy, cells_z, 0}
   int n_readers = 0;                  // streams with a reader
+  // per-scan map-hit records (liodom_set_map_hits; all null / empty until the first enabling call)
+  liodom_map_hit_t* hit_log = nullptr;   // [S][pose_log_cap] device, indexed like pose_log
+  int* hit_radius = nullptr;          // [S] device: -1 off, else the radius the stream's scans are counted with
+  std::vector<int> hit_radius_h;      // ... and the host's copy
+  int n_hits = 0;                     // streams with hits on
   std::vector<EventPair> ev_pool;
   size_t ev_used = 0;
   double k_ms[LIODOM_NUM_KERNELS] = {0};
@@ -1589,6 +1594,7 @@ int liodom_attach_map_reader(liodom_handle_t* h, int stream, liodom_map_t* m, in
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->readers.assign((size_t)h->S, nullptr); h->reader_xy.assign((size_t)h->S, 0); h->reader_z.assign((size_t)h->S, 0);
   }
+  if (h->n_hits > 0 && h->hit_radius_h[(size_t)stream] >= 0 && (rc = map_keep_occ(m))) return rc;      // (hit records: the kept occupancy, sized once)
   // (attach first, detach second: a stream that re-attaches the map it reads keeps the map on the handle's stream throughout)
   if ((rc = map_attachment(h, m, +1, true))) return rc;
   if ((rc = detach_stream_map(h, stream))) return rc;
@@ -1602,6 +1608,43 @@ int liodom_attach_map_reader(liodom_handle_t* h, int stream, liodom_map_t* m, in
   h->n_readers++;
   const int4 sel = make_int4((int)t + 1, cells_xy, cells_z, 0);
   HIP_TRY(hipMemcpy(h->reader_sel + stream, &sel, sizeof(sel), hipMemcpyHostToDevice));
+  return LIODOM_OK;
+}
+
+static_assert(sizeof(liodom_map_hit_t) == liodom_dev::kMapHitRecordBytes, "k_map_hit_rows writes the record as eight 16-byte stores");
+int liodom_set_map_hits(liodom_handle_t* h, int stream, int radius) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if (!h->v.mapping) { g_last_error = "liodom_set_map_hits: the handle was created with mapping = 0"; return LIODOM_ERR_UNSUPPORTED; }
+  if (radius < -1 || radius > 1) { g_last_error = "liodom_set_map_hits: radius is -1 (off), 0 or 1"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, true, true);
+  if ((rc = state_quiesce(h))) return rc;
+  if (!h->hit_log) {
+    if (radius < 0) return LIODOM_OK;      // never on: nothing to switch off
+    // the log and the per-stream radius, from the first enabling call on
+    if ((rc = dev_alloc(h, &h->hit_log, (size_t)h->S * (size_t)h->v.pose_log_cap))) return rc;
+    if ((rc = dev_alloc(h, &h->hit_radius, (size_t)h->S, 0xff))) return rc;      // (all -1)
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->hit_radius_h.assign((size_t)h->S, -1);
+  }
+  liodom_map* rd = h->readers.empty() ? nullptr : h->readers[(size_t)stream];
+  if (radius >= 0 && rd && (rc = map_keep_occ(rd))) return rc;
+  int& cur = h->hit_radius_h[(size_t)stream];
+  h->n_hits += (radius >= 0 ? 1 : 0) - (cur >= 0 ? 1 : 0);
+  cur = radius;
+  HIP_TRY(hipMemcpy(h->hit_radius + stream, &radius, sizeof(int), hipMemcpyHostToDevice));
+  return LIODOM_OK;
+}
+
+int liodom_get_map_hit_log(liodom_handle_t* h, int stream, int first, int count, liodom_map_hit_t* out) {
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if (!h->hit_log) { g_last_error = "liodom_get_map_hit_log: liodom_set_map_hits has never been switched on for this handle"; return LIODOM_ERR_UNSUPPORTED; }
+  if (first < 0 || count < 0 || first + count > h->v.pose_log_cap) { g_last_error = "pose log range"; return LIODOM_ERR_INVALID_ARG; }
+  SideLocks lk(h, true, false);
+  HIP_TRY(sync_odometry(h));
+  if (out && count)
+    HIP_TRY(hipMemcpy(out, h->hit_log + (size_t)stream * h->v.pose_log_cap + first, sizeof(liodom_map_hit_t) * (size_t)count, hipMemcpyDeviceToHost));
   return LIODOM_OK;
 }
 
@@ -2225,7 +2268,7 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   (void)hipMemcpy(r.hb_stats, reinterpret_cast<const char*>(v.state) + offsetof(StreamState, hb_stats), sizeof(r.hb_stats), hipMemcpyDeviceToHost);
   r.chain_count = h->step.chain_count; r.done0 = done_cnt[0]; r.done1 = done_cnt[32];
   if (h->replay_timed) { r.replay_enqueue_us = h->replay_enq_ns / (1e3 * (double)h->replay_timed); r.replay_wait_us = h->replay_wait_ns / (1e3 * (double)h->replay_timed); }
-  r.n_lagged = h->n_lagged; r.n_readers = h->n_readers; r.subset_steps = h->subset_steps;
+  r.n_lagged = h->n_lagged; r.n_readers = h->n_readers; r.subset_steps = h->subset_steps; r.n_hits = h->n_hits;
   plan_format_modes(h->plan, r, buf, cap);
   return LIODOM_OK;
 }

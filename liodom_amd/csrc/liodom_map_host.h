@@ -27,6 +27,10 @@ struct liodom_map {
   size_t batch_bytes = 0;
   unsigned int* d_occ = nullptr;     // liodom_map_score_poses / _search_pose: leaf occupancy [occ_cells][words] (the first call allocates it for
   int occ_cells = 0;                 // the cells the map holds then, a map that has grown since regrows it)
+  // the kept occupancy of the per-scan hit records (liodom_set_map_hits): every entry point and enqueue that can change the cells
+  // bumps `gen`; d_occ holds the occupancy of the map as it was at generation occ_gen (0: of none).  Host-side, under the caller's
+  // threading rule for the map.
+  unsigned long long gen = 1, occ_gen = 0;
   unsigned long long* d_blocks = nullptr;   // liodom_map_search_pose_bnb / _bound_nodes: the block tables of the levels a call uses (the
   size_t blocks_entries = 0;               // first call allocates them, a call that needs more regrows them)
   unsigned char* h_pin = nullptr;          // liodom_map_search_pose_bnb: pinned host staging of a round's nodes, candidates and counts
@@ -107,6 +111,7 @@ int map_build(liodom_map* mp, const liodom_map_config_t* c, hipStream_t stream) 
 int map_enqueue_update(liodom_map* mp, const float4* d_pts, const int* d_n, const double* d_T, hipStream_t q) {
   using namespace liodom_dev;
   const MapView& m = mp->m;
+  mp->gen++;
   const int xb_old = (m.cell_cap + 255) / 256, xb_new = (m.upd_cap + 255) / 256;
   const int xb = std::max(xb_old, xb_new);
   if (d_T) hipLaunchKernelGGL(k_map_assign<true>, dim3(1), dim3(1024), 0, q, m, d_pts, d_n, d_T);
@@ -223,6 +228,7 @@ int map_ensure_prune(liodom_map* mp) {
 int map_enqueue_prune(liodom_map* mp, const double* d_T, int keep_xy, int keep_z, hipStream_t q) {
   using namespace liodom_dev;
   const MapView& m = mp->m;
+  mp->gen++;
   const int clear_blocks = std::min(64, (m.ctable + kMapPruneThreads - 1) / kMapPruneThreads);
   hipLaunchKernelGGL(k_map_prune_plan, dim3(1 + clear_blocks), dim3(kMapPruneThreads), 0, q, m, d_T, keep_xy, keep_z, mp->d_prune);
   hipLaunchKernelGGL(k_map_prune_move, dim3(std::min(16, (m.cell_cap + 255) / 256), std::min(m.max_cells, 256)), dim3(256), 0, q, m, mp->d_prune);
@@ -270,6 +276,7 @@ int map_install_state(liodom_map* mp, const unsigned char* blob, const liodom_de
   using namespace liodom_dev;
   const MapView& m = mp->m;
   const int n_cells = hd ? hd->n_cells : 0, n_points = hd ? (int)hd->n_points : 0;
+  mp->gen++;
   if (n_cells > 0) {
     // everything that can fail comes before the map is touched
     int rc = map_ensure_head(mp);
@@ -302,6 +309,7 @@ int map_ensure_occ(liodom_map* mp, int n_cells) {
   if (mp->d_occ && mp->occ_cells >= n_cells) return LIODOM_OK;
   HIP_TRY(hipStreamSynchronize(mp->stream));
   if (mp->d_occ) { (void)hipFree(mp->d_occ); mp->d_occ = nullptr; mp->occ_cells = 0; }
+  mp->occ_gen = 0;
   HIP_TRY(hipMalloc(reinterpret_cast<void**>(&mp->d_occ), sizeof(unsigned int) * std::max<size_t>((size_t)n_cells * (size_t)mp->m.words, 4)));
   mp->occ_cells = n_cells;
   return LIODOM_OK;
@@ -338,6 +346,7 @@ int map_score(liodom_map* mp, const float* edges, int n_edges, const double* T, 
     hipLaunchKernelGGL(k_map_occ_clear, dim3((unsigned)std::min<size_t>(2048, (n16 + 255) / 256)), dim3(256), 0, mp->stream, m, mp->d_occ, mp->occ_cells);
     hipLaunchKernelGGL(k_map_occ_build, dim3(std::min(16, (m.cell_cap + 255) / 256), std::min(n_cells, 256)), dim3(256), 0, mp->stream, m, mp->d_occ, mp->occ_cells);
     tm.stop();
+    mp->occ_gen = mp->gen;      // (what the step path's hit records would build: it need not build it again)
   }
   {
     MapStateTimer tm(mp->stream, "liodom_map_score_poses score");
@@ -382,6 +391,30 @@ int map_build_occ(liodom_map* mp, int n_cells) {
   hipLaunchKernelGGL(k_map_occ_clear, dim3((unsigned)std::min<size_t>(2048, (n16 + 255) / 256)), dim3(256), 0, mp->stream, m, mp->d_occ, mp->occ_cells);
   hipLaunchKernelGGL(k_map_occ_build, dim3(std::min(16, (m.cell_cap + 255) / 256), std::min(n_cells, 256)), dim3(256), 0, mp->stream, m, mp->d_occ, mp->occ_cells);
   HIP_TRY(hipGetLastError());
+  mp->occ_gen = mp->gen;
+  return LIODOM_OK;
+}
+
+// ---- per-scan hit records (kernels_map_hits.h) ----
+// The kept occupancy: d_occ with a row for each of max_cells cells, so that no step ever has to regrow it (a synchronising
+// re-allocation); called when a stream that reads the map has its hits switched on, never from a step.
+int map_keep_occ(liodom_map* mp) { return map_ensure_occ(mp, mp->m.max_cells); }
+
+// The occupancy of the map as it is now on `q`, without asking the device how many cells it holds (the two kernels clamp to
+// n_cells themselves): enqueued only if a cell may have changed since d_occ was last built.  map_keep_occ has run.
+// LIODOM_MAP_STATE_TIMING=1 reports each build on stderr, so a build can be counted.
+int map_refresh_occ(liodom_map* mp, hipStream_t q) {
+  using namespace liodom_dev;
+  if (mp->occ_cells < mp->m.max_cells) { const int rc = map_keep_occ(mp); if (rc) return rc; }      // (never on the documented paths)
+  if (mp->occ_gen == mp->gen) return LIODOM_OK;
+  const MapView& m = mp->m;
+  const size_t n16 = ((size_t)mp->occ_cells * (size_t)m.words + 3) / 4;
+  MapStateTimer tm(q, "liodom map_hits occupancy");
+  hipLaunchKernelGGL(k_map_occ_clear, dim3((unsigned)std::min<size_t>(2048, (n16 + 255) / 256)), dim3(256), 0, q, m, mp->d_occ, mp->occ_cells);
+  hipLaunchKernelGGL(k_map_occ_build, dim3(std::min(16, (m.cell_cap + 255) / 256), std::min(mp->occ_cells, 256)), dim3(256), 0, q, m, mp->d_occ, mp->occ_cells);
+  tm.stop();
+  HIP_TRY(hipGetLastError());
+  mp->occ_gen = mp->gen;
   return LIODOM_OK;
 }
 
@@ -748,6 +781,7 @@ int liodom_map_merge_state(liodom_map_t* mp, const void* blob, int64_t bytes, in
     g_last_error = "liodom_map_merge_state: not enough free cells for the blob's cells (max_cells)"; return LIODOM_ERR_CAPACITY;
   }
   if (info.n_taken > 0 || hd.status) {
+    mp->gen++;
     const int xb = std::min(16, (m.cell_cap + 255) / 256), yb = std::min(n_cells, 256);
     hipLaunchKernelGGL(k_map_merge, dim3(xb, yb), dim3(256), 0, mp->stream, m, mp->d_head, mp->d_out, n_cells, n_points, d_info, d_rank, (int)hd.status);
     HIP_TRY(hipGetLastError());
@@ -767,6 +801,50 @@ int liodom_map_score_poses(liodom_map_t* mp, const float* edges_xyzi, int n_edge
   }
   if (n == 0) return LIODOM_OK;
   return map_score(mp, edges_xyzi, n_edges, T, n, radius, hits, nullptr);
+}
+
+int liodom_map_hit_rows(liodom_map_t* mp, const float* edges_xyzi, int64_t edge_stride_points, const int32_t* n_edges, const double* T, int n, int radius,
+                        int32_t* hits) {
+  using namespace liodom_dev;
+  if (!mp || n < 0 || n > kRelocCandidatesMax || (n > 0 && (!n_edges || !T || !hits)) || (radius != 0 && radius != 1) || edge_stride_points < 0) {
+    g_last_error = "liodom_map_hit_rows: null map, counts, poses or hits, a count that is negative or above 2^20, a negative stride, or a radius that is not 0 or 1";
+    return LIODOM_ERR_INVALID_ARG;
+  }
+  if (edge_stride_points > mp->cfg.max_update_points) { g_last_error = "liodom_map_hit_rows: a row stride above the map's max_update_points"; return LIODOM_ERR_INVALID_ARG; }
+  bool any = false;
+  for (int i = 0; i < n; i++) {
+    if (n_edges[i] < 0 || n_edges[i] > edge_stride_points) { g_last_error = "liodom_map_hit_rows: a row's edge count is negative or above the row stride"; return LIODOM_ERR_INVALID_ARG; }
+    any = any || n_edges[i] > 0;
+  }
+  if (any && !edges_xyzi) { g_last_error = "liodom_map_hit_rows: null edges"; return LIODOM_ERR_INVALID_ARG; }
+  if (n == 0) return LIODOM_OK;
+  if (!any) { std::memset(hits, 0, sizeof(int32_t) * 2 * (size_t)n); return LIODOM_OK; }
+  HIP_TRY(hipSetDevice(mp->device));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  MapState st;
+  HIP_TRY(hipMemcpy(&st, mp->m.st, sizeof(st), hipMemcpyDeviceToHost));
+  const int n_cells = std::max(0, std::min(st.n_cells, mp->m.max_cells));
+  // staging: the rows' clouds back to back at the caller's stride, then the poses, the edge counts and the counts
+  const size_t e_bytes = sizeof(float4) * (size_t)n * (size_t)edge_stride_points, t_bytes = sizeof(double) * 12 * (size_t)n, c_bytes = sizeof(int) * (size_t)n;
+  const size_t t_off = (e_bytes + 15) / 16 * 16, c_off = t_off + t_bytes, h_off = (c_off + c_bytes + 7) / 8 * 8;
+  int rc = map_ensure_occ(mp, n_cells);
+  if (rc || (rc = map_ensure_batch(mp, h_off + sizeof(int) * 2 * (size_t)n))) return rc;
+  float4* d_edges = reinterpret_cast<float4*>(mp->d_batch);
+  double* d_T = reinterpret_cast<double*>(mp->d_batch + t_off);
+  int* d_cnt = reinterpret_cast<int*>(mp->d_batch + c_off);
+  int* d_hits = reinterpret_cast<int*>(mp->d_batch + h_off);
+  HIP_TRY(hipMemcpyAsync(d_edges, edges_xyzi, e_bytes, hipMemcpyHostToDevice, mp->stream));
+  HIP_TRY(hipMemcpyAsync(d_T, T, t_bytes, hipMemcpyHostToDevice, mp->stream));
+  HIP_TRY(hipMemcpyAsync(d_cnt, n_edges, c_bytes, hipMemcpyHostToDevice, mp->stream));
+  if (n_cells > 0 && (rc = map_build_occ(mp, n_cells))) return rc;
+  MapHitRows r{};
+  r.edges = d_edges; r.edge_stride = edge_stride_points; r.n_edges = d_cnt; r.n_stride = 1; r.T = d_T; r.T_stride = 12;
+  r.edge_cap = (int)edge_stride_points; r.radius = radius; r.hits = d_hits;
+  hipLaunchKernelGGL(k_map_hit_rows<false>, dim3((unsigned)n), dim3(kMapHitThreads), 0, mp->stream, mp->m, mp->d_occ, mp->occ_cells, (float)mp->cfg.resolution, r);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(hits, d_hits, sizeof(int) * 2 * (size_t)n, hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));      // (the staged clouds, poses and counts are the caller's memory)
+  return LIODOM_OK;
 }
 
 void liodom_pose_search_default(liodom_pose_search_t* s) {

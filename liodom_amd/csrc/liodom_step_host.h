@@ -122,6 +122,38 @@ int issue_plan(liodom_handle* h, const StepPlan& plan, const StepData& d) {
             else hipLaunchKernelGGL((k_map_local_rows<false>), grid, dim3(kMapRowsThreads), 0, h->stream, mp->m, r);
           }
         }
+        // per-scan hit records (liodom_set_map_hits): the step's rows with hits on, counted at final_odom against the occupancy
+        // of the map they read — one k_map_hit_rows launch per distinct map, in front of it the occupancy's two launches only if
+        // the map may have changed since it was built — and one launch for the rows without a reader (NO_READER records).
+        if (h->n_hits > 0) {
+          ProfScope ps(h, KID_OTHER);
+          MapHitRows r{};
+          r.edges = v.edges + (size_t)eb * v.n_streams * v.edge_cap; r.edge_stride = v.edge_cap;
+          r.n_edges = &v.state[0].n_edges_buf[eb]; r.n_stride = (long long)(sizeof(StreamState) / sizeof(int));
+          r.T = v.state[0].final_odom; r.T_stride = (long long)(sizeof(StreamState) / sizeof(double));
+          r.edge_cap = v.edge_cap; r.log = reinterpret_cast<uint4*>(h->hit_log); r.log_cap = v.pose_log_cap;
+          r.scan_no = &v.state[0].scan_counter; r.raw = &v.state[0].append_raw;
+          r.radius_of = h->hit_radius; r.sel = h->reader_sel; r.s0 = s0;
+          r.list = s0 < 0 ? reinterpret_cast<const int*>(v.pipe_flags) + kStreamListBase + (size_t)(-s0 - 1) * (size_t)v.n_streams : nullptr;
+          auto reads = [&](int s) { return h->readers.empty() ? nullptr : h->readers[s]; };
+          for (size_t t = 0; t <= h->read_maps.size(); t++) {      // (the last turn: tag 0, the rows without a reader)
+            liodom_map* mp = t < h->read_maps.size() ? h->read_maps[t] : nullptr;
+            if (t < h->read_maps.size() && !mp) continue;
+            bool any = false;
+            for (int i = 0; i < count && !any; i++) {
+              const int s = d.list ? (int)d.list[i] : s0 + i;
+              any = h->hit_radius_h[s] >= 0 && reads(s) == mp;
+            }
+            if (!any) continue;
+            if (mp) { const int rc = map_refresh_occ(mp, h->stream); if (rc) return rc; }
+            r.tag = mp ? (int)t + 1 : 0;
+            const MapView none{};
+            if (s0 < 0) hipLaunchKernelGGL((k_map_hit_rows<true>), dim3(count), dim3(kMapHitThreads), 0, h->stream, mp ? mp->m : none, mp ? mp->d_occ : nullptr,
+                                           mp ? mp->occ_cells : 0, mp ? (float)mp->cfg.resolution : 0.f, r);
+            else hipLaunchKernelGGL((k_map_hit_rows<false>), dim3(count), dim3(kMapHitThreads), 0, h->stream, mp ? mp->m : none, mp ? mp->d_occ : nullptr,
+                                    mp ? mp->occ_cells : 0, mp ? (float)mp->cfg.resolution : 0.f, r);
+          }
+        }
         break;
       }
       case SK_HASH_APPEND: LAUNCH_ROWS(k_hash_append, (), v, s0, eb); break;

@@ -91,6 +91,12 @@ void Stats::stopFrame(const Clock::time_point& stop) {
     frame_times_.push_back((double)std::chrono::duration_cast<std::chrono::milliseconds>(stop - start).count());
   }
 }
+void Stats::dropLastScan() {
+  if (!poses_.empty()) { poses_.pop_back(); n_poses_.fetch_sub(1, std::memory_order_release); }
+  if (!laser_odom_.empty()) laser_odom_.pop_back();
+  if (!frame_times_.empty()) frame_times_.pop_back();
+  if (!num_of_features_.empty()) num_of_features_.pop_back();
+}
 void Stats::clear() { n_poses_ = 0; poses_.clear(); feat_extr_.clear(); laser_odom_.clear(); frame_times_.clear(); num_of_features_.clear(); }
 
 // File formats of Stats::writeResults (stats.cc:73-132): poses.txt = KITTI rows of the top 3x4 of
@@ -586,6 +592,14 @@ void LaserOdometer::seed(const Pose& pose) {
   // (it solves), so the rate watchdog runs from it on
   prev_odom_ = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
   prev_stamp_ = 0.0; published_ = false; init_ = true; last_scan_ = -1;
+}
+
+void LaserOdometer::setMapHits(int radius) { check(liodom_set_map_hits(eng_->handle(), 0, radius), "liodom_set_map_hits"); }
+
+liodom_map_hit_t LaserOdometer::mapHit(int scan_index) {
+  liodom_map_hit_t rec{};
+  check(liodom_get_map_hit_log(eng_->handle(), 0, scan_index, 1, &rec), "liodom_get_map_hit_log");
+  return rec;
 }
 
 std::vector<PointCloud> Map::getLocalBatch(const std::vector<std::array<double, 12>>& poses, int cells_xy, int cells_z) {

@@ -82,6 +82,9 @@ class Stats {
   void stopFrame(const Clock::time_point& stop);                                                // :60
   void writeResults(const std::string& dir);                                                    // :73-132
   void clear();
+  // takes the last fused scan's entries back (pose, odometry time, frame time, feature count): a scan that is processed again after
+  // a relocalisation keeps one row in the result files
+  void dropLastScan();
   size_t numPoses();
  private:
   std::vector<std::array<double, 12>> poses_;
@@ -320,6 +323,11 @@ class LaserOdometer {
   // seed: the next scan is the first and solves from `pose`; with a map attached the odometer receives its local map there.
   void attachMapReader(Map* map, int cells_xy = 2, int cells_z = 1);
   void seed(const Pose& pose);
+  // Knowing that a reader is lost (liodom_set_map_hits / liodom_get_map_hit_log; no counterpart in the reference).  setMapHits:
+  // radius 0 | 1 gives every scan a hit record against the attached reader's map, -1 switches them off.  mapHit: the record of scan
+  // `scan_index` (liodom_step_info_t::scan_index of the scan); liodom_amd/csrc/track_policy.h says what to make of it.
+  void setMapHits(int radius);
+  liodom_map_hit_t mapHit(int scan_index);
   // One pass of the loop body of LaserOdometer::operator() (laser_odometry.cc:107-267).
   Pose process(const PointCloud& feats, double stamp, liodom_step_info_t* info = nullptr);
   // The same on an edge cloud the extractor left on the device (Features::ticket)

@@ -17,6 +17,13 @@
 // attached read-only (LaserOdometer::attachMapReader: it is never written), seed_pose=qx,qy,qz,qw,tx,ty,tz places the first scan
 // in it (LaserOdometer::seed; default: the identity) and every scan solves against window ++ local map.  Not with mapper_lag,
 // map_prune_period or map_pager, which write.
+// map_hits=FILE (with localize=1) switches the per-scan hit records on (LaserOdometer::setMapHits, hit_radius=0|1, default 1) and
+// writes one line per scan: scan_index hits_r hits_0 n_edges.  relocalize_below=FRACTION adds the recovery (track_policy.h with
+// lost_after=N, default 3): when the policy answers LOST, the scan's edges (FeatureExtractor::lastEdges) are searched in the map around the pose of the last scan
+// whose fraction was >= FRACTION (this scan's pose if there was none) — one branch-and-bound level of +-reloc_window=METRES
+// (default 10) at 0.4 m and +-pi at 0.02 rad, then the fine level (0.1 m, 0.005 rad, +-4 steps) — and, if the best pose's fraction
+// is >= FRACTION, the odometer is seeded there and the SAME scan processed again: the result files and FILE keep one row per scan,
+// the last processing's, and the run prints "relocalized at scan K".  Fused per-scan path only.
 // threads=true runs the reference's own structure instead of the fused per-scan call: the clouds are
 // pushed into SharedData (lidarClb), a FeatureExtractor thread and a LaserOdometer thread work side by
 // side on the same handle (src/liodom_node.cc:89-91) and hand edge clouds over through the queue — the clouds stay on the
@@ -26,6 +33,7 @@
 // first=K+1 starts from such a file at scan K+1: the result files of the two runs, one behind the other, are those of one run
 // (last=K stops after scan K).  Fused per-scan path only (not with threads=true).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <dirent.h>
 #include <fstream>
@@ -34,6 +42,7 @@
 #include <thread>
 
 #include "liodom_host.h"
+#include "../csrc/track_policy.h"
 
 int main(int argc, char** argv) {
   if (argc < 3) { std::fprintf(stderr, "usage: %s <scan_dir> <out_dir/> [name=value ...]\n", argv[0]); return 2; }
@@ -78,8 +87,17 @@ int main(int argc, char** argv) {
     std::unique_ptr<liodom::MapPager> pager;
     std::string map_state_in, map_state_out, map_pager, seed_pose;
     bool localize = false;
+    std::string map_hits;
+    int hit_radius = 1;
+    liodom_dev::TrackPolicy policy{-1.0, 3};      // relocalize_below < 0: no recovery
+    double reloc_window = 10.0;
     for (const std::string& a : kv) {
       if (a == "localize=1" || a == "localize=true") localize = true;
+      if (a.rfind("map_hits=", 0) == 0) map_hits = a.substr(9);
+      if (a.rfind("hit_radius=", 0) == 0) hit_radius = std::stoi(a.substr(11));
+      if (a.rfind("relocalize_below=", 0) == 0) policy.min_fraction = std::stod(a.substr(17));
+      if (a.rfind("lost_after=", 0) == 0) policy.lost_after = std::stoi(a.substr(11));
+      if (a.rfind("reloc_window=", 0) == 0) reloc_window = std::stod(a.substr(13));
       if (a.rfind("seed_pose=", 0) == 0) seed_pose = a.substr(10);
       if (a.rfind("map_state_in=", 0) == 0) map_state_in = a.substr(13);
       if (a.rfind("map_state_out=", 0) == 0) map_state_out = a.substr(14);
@@ -91,6 +109,12 @@ int main(int argc, char** argv) {
     }
     if (localize && (!params->mapping_ || map_state_in.empty())) { std::fprintf(stderr, "liodom_replay: localize=1 needs mapping=true map_state_in=FILE\n"); return 2; }
     if (!seed_pose.empty() && !localize) { std::fprintf(stderr, "liodom_replay: seed_pose needs localize=1\n"); return 2; }
+    const bool recover = policy.min_fraction >= 0.0;
+    if ((!map_hits.empty() || recover) && !localize) { std::fprintf(stderr, "liodom_replay: map_hits / relocalize_below need localize=1 (a map that is read)\n"); return 2; }
+    if (recover && map_hits.empty()) { std::fprintf(stderr, "liodom_replay: relocalize_below needs map_hits=FILE\n"); return 2; }
+    if ((hit_radius != 0 && hit_radius != 1) || !(reloc_window >= 0.0) || (recover && !(policy.min_fraction <= 1.0))) {
+      std::fprintf(stderr, "liodom_replay: hit_radius is 0 or 1, reloc_window >= 0, relocalize_below in 0 .. 1\n"); return 2;
+    }
     if (params->mapping_) {
       double xy = 40.0, z = 50.0, res = 0.4;      // liodom_mapping_node.cc:115-134
       liodom_mapper_options_t mo;
@@ -122,6 +146,7 @@ int main(int argc, char** argv) {
         }
         odometer.attachMapReader(mapper.get(), mo.cells_xy, mo.cells_z);
         odometer.seed(sp);
+        if (!map_hits.empty()) odometer.setMapHits(hit_radius);
       } else {
         odometer.attachMapper(mapper.get(), mo);
       }
@@ -165,7 +190,8 @@ int main(int argc, char** argv) {
         if (a.rfind("last=", 0) == 0) has_last = true;
       }
       const char* bad = nullptr;
-      if (want_threads && pager) bad = "map_pager works on the fused per-scan path only, not with threads=true";
+      if (want_threads && !map_hits.empty()) bad = "map_hits / relocalize_below work on the fused per-scan path only, not with threads=true";
+      else if (want_threads && pager) bad = "map_pager works on the fused per-scan path only, not with threads=true";
       else if (want_threads && (!save_state.empty() || !load_state.empty() || save_at >= 0 || has_first || has_last))
         bad = "save_state / load_state / save_at / first / last work on the fused per-scan path only, not with threads=true";
       else if (save_state.empty() != (save_at < 0)) bad = "save_state=FILE and save_at=K go together";
@@ -225,9 +251,48 @@ int main(int argc, char** argv) {
                   msgs.size(), secs, (double)msgs.size() / secs, host_handoff ? "host" : "device", poll_us);
       if (msgs.size() != clouds.size()) { std::fprintf(stderr, "liodom_replay: %zu of %zu scans processed\n", msgs.size(), clouds.size()); return 1; }
     }
+    std::ofstream hits_log;
+    if (!map_hits.empty()) hits_log.open(map_hits);
+    liodom_dev::TrackState track;
+    liodom::Pose last_good;
+    bool have_good = false;
+    liodom::FeatureExtractor reloc_extractor(eng);
     for (size_t i = (size_t)std::max(0l, first); (long)i <= last && !threads; i++) {
       liodom_step_info_t info;
       liodom::Pose p = odometer.processScan(clouds[i], 0.1 * (double)i, &info);
+      if (!map_hits.empty()) {
+        liodom_map_hit_t hit = odometer.mapHit(info.scan_index);
+        if (recover && liodom_dev::track_feed(policy, &track, hit.hits_r, hit.hits_0, hit.n_edges, hit.flags) == liodom_dev::TRACK_LOST) {
+          liodom::PointCloud edges;
+          reloc_extractor.lastEdges(edges);      // (the scan's edges as they lie in the handle: what the record was counted on)
+          const liodom::Pose& c = have_good ? last_good : p;
+          liodom_pose_search_t s;
+          liodom_pose_search_default(&s);
+          for (int j = 0; j < 4; j++) s.centre[j] = c.q[j];
+          for (int j = 0; j < 3; j++) s.centre[4 + j] = c.t[j];
+          s.step_xy = 0.4; s.step_yaw = 0.02; s.nx = s.ny = (int)std::ceil(reloc_window / 0.4); s.nyaw = (int)std::ceil(M_PI / 0.02); s.radius = 1;
+          liodom_pose_search_result_t found = mapper->searchPoseBnb(edges, s);
+          for (int j = 0; j < 7; j++) s.centre[j] = found.pose[j];
+          s.step_xy = 0.1; s.step_yaw = 0.005; s.nx = s.ny = s.nyaw = 4;
+          found = mapper->searchPose(edges, s);
+          if (!liodom_dev::track_below(policy, found.hits_r, found.hits_0, (int32_t)edges.size())) {
+            liodom::Pose sp;
+            for (int j = 0; j < 4; j++) sp.q[j] = found.pose[j];
+            for (int j = 0; j < 3; j++) sp.t[j] = found.pose[4 + j];
+            odometer.seed(sp);
+            liodom::Stats::getInstance()->dropLastScan();
+            p = odometer.processScan(clouds[i], 0.1 * (double)i, &info);
+            hit = odometer.mapHit(info.scan_index);
+            std::printf("relocalized at scan %zu: fraction %.3f at %.3f %.3f %.3f\n", i, liodom_dev::track_fraction(found.hits_r, found.hits_0, (int32_t)edges.size()),
+                        found.pose[4], found.pose[5], found.pose[6]);
+          } else {
+            std::printf("lost at scan %zu: nothing good enough within the window (best fraction %.3f)\n", i,
+                        liodom_dev::track_fraction(found.hits_r, found.hits_0, (int32_t)edges.size()));
+          }
+        }
+        if ((hit.flags & LIODOM_HIT_VALID) && !liodom_dev::track_below(policy, hit.hits_r, hit.hits_0, hit.n_edges)) { last_good = p; have_good = true; }
+        hits_log << hit.scan_index << ' ' << hit.hits_r << ' ' << hit.hits_0 << ' ' << hit.n_edges << '\n';
+      }
       const liodom::OdometryMsg msg = odometer.publishOdom(0.1 * (double)i, p);      // ~odom / ~twist numbers
       odom_log << msg.stamp;
       for (double v : msg.orientation) odom_log << ' ' << v;
