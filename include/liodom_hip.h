@@ -316,7 +316,10 @@ int liodom_extract_edges_device_polar(liodom_handle_t* h, int stream, const void
 int liodom_set_received_map(liodom_handle_t* h, int stream, const float* xyzi, int64_t n);
 /* imuClb -> SharedData::setLastIMUOri (src/liodom_node.cc:66-70): latest IMU orientation [x y z w].
  * With use_imu = 1 the roll and pitch of every predicted pose are replaced by the IMU's before the
- * solve (src/laser_odometry.cc:152-183).  Identity until first set. */
+ * solve (src/laser_odometry.cc:152-183).  Identity until first set.  The quaternion need not be
+ * normalised (tf's setRotation divides |q|^2 out; q and -q are the same orientation), but a non-finite
+ * component or a norm whose square is 0 — tf would divide by it and every later pose of the stream would
+ * be NaN — is LIODOM_ERR_INVALID_ARG: the stored orientation and the stream stay as they were. */
 int liodom_set_imu_orientation(liodom_handle_t* h, int stream, const double* q_xyzw);
 /* laser_to_base_ (TF lookup at src/laser_odometry.cc:110-119): 3 x 4 row-major, identity by default.
  * It enters the IMU override only; poses are returned in the laser frame (odom_). */

@@ -284,6 +284,24 @@ def parse_stream_state(blob):
     return out
 
 
+def patch_stream_state(blob, **fields):
+    """A copy of a stream-state blob with poses of its record replaced (pure Python): odom, prev_odom, final_odom (3 x 4 or 12),
+    param_q (4), param_t (3), imu_q (4; sets has_imu).  Counters, window and fingerprint stay, so liodom_import_stream_state takes
+    the result on the handle the blob came from.  For tests and tools that start a stream from a chosen pose state."""
+    b = bytearray(bytes(blob))
+    parse_stream_state(b)          # (raises on anything that is not a blob)
+    where = dict(odom=(0, 12), prev_odom=(96, 12), final_odom=(192, 12), param_q=(288, 4), param_t=(320, 3), imu_q=(384, 4))
+    for name, value in fields.items():
+        off, n = where[name]       # KeyError: not a patchable field
+        a = np.ascontiguousarray(value, dtype="<f8").reshape(-1)
+        if a.shape[0] != n:
+            raise ValueError("%s takes %d doubles" % (name, n))
+        b[STATE_HEADER_BYTES + off:STATE_HEADER_BYTES + off + 8 * n] = a.tobytes()
+        if name == "imu_q":
+            b[STATE_HEADER_BYTES + 376:STATE_HEADER_BYTES + 380] = np.array([1], "<i4").tobytes()
+    return bytes(b)
+
+
 # ---- map-state blob (liodom_map_export_state; layout in csrc/map_state_format.h and DESIGN.md §3) ----
 MAP_STATE_MAGIC = b"LIODOMMP"
 MAP_STATE_VERSION = 1

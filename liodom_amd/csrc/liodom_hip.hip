@@ -1485,6 +1485,16 @@ int liodom_set_imu_orientation(liodom_handle_t* h, int stream, const double* q_x
   int rc = check_stream(h, stream);
   if (rc) return rc;
   if (!q_xyzw) return LIODOM_ERR_INVALID_ARG;
+  // what would poison the stream is refused before anything is touched (liodom_seed_stream's rule for its pose): tf's setRotation
+  // divides by |q|^2, so a zero or non-finite quaternion makes the prediction — and every pose after it — NaN, with no status bit.
+  // A non-unit quaternion is fine: tf divides the norm out.
+  double nn = 0.0;
+  for (int i = 0; i < 4; i++) {
+    if (!std::isfinite(q_xyzw[i])) { g_last_error = "liodom_set_imu_orientation: non-finite quaternion"; return LIODOM_ERR_INVALID_ARG; }
+    nn += q_xyzw[i] * q_xyzw[i];
+  }
+  // (|q|^2 as tf forms it: a norm so small or so large that it underflows to 0 or overflows counts as zero / non-finite)
+  if (!(nn > 0.0) || !std::isfinite(nn) || !std::isfinite(2.0 / nn)) { g_last_error = "liodom_set_imu_orientation: quaternion of zero norm"; return LIODOM_ERR_INVALID_ARG; }
   SideLocks lk(h, true, false);
   // pageable-memory async copies are staged by the runtime before the call returns
   HIP_TRY(hipMemcpyAsync(h->v.imu_q + (size_t)stream * 4, q_xyzw, sizeof(double) * 4, hipMemcpyHostToDevice, h->stream));

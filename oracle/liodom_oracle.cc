@@ -1436,6 +1436,14 @@ void orc_odom_get_state(void* h, double* odom12, double* prev12) {
   std::memcpy(odom12, o->odom.m, sizeof(double) * 12);
   std::memcpy(prev12, o->prev_odom.m, sizeof(double) * 12);
 }
+// Starts the odometer from a designed state (tests/designed_poses.py): odom_ and prev_odom_ as given, init_ as given; the window,
+// the IMU orientation and laser_to_base keep what they have.  The next step() then runs :148-195 and the end of the scan from it.
+void orc_odom_set_state(void* h, const double* odom12, const double* prev12, int initialised) {
+  Odometer* o = static_cast<Odometer*>(h);
+  std::memcpy(o->odom.m, odom12, sizeof(double) * 12);
+  std::memcpy(o->prev_odom.m, prev12, sizeof(double) * 12);
+  o->init = initialised != 0;
+}
 
 // --- unit-level entry points ---------------------------------------------------------------
 void orc_knn5(const float* map_xyzi, int64_t m, const float* q_xyzi, int64_t nq, int mode,

@@ -111,6 +111,7 @@ def lib():
         L.orc_odom_get_window.argtypes = [C.c_void_p, fp, C.c_int64]
         L.orc_odom_set_received_map.argtypes = [C.c_void_p, fp, C.c_int64]
         L.orc_odom_get_state.argtypes = [C.c_void_p, dp, dp]
+        L.orc_odom_set_state.argtypes = [C.c_void_p, dp, dp, C.c_int]
         L.orc_odom_get_received_map.restype = C.c_int64
         L.orc_odom_get_received_map.argtypes = [C.c_void_p, fp, C.c_int64]
         L.orc_odom_map_total.restype = C.c_int64
@@ -277,6 +278,12 @@ class Odometer:
         b = np.zeros(12)
         lib().orc_odom_get_state(self.h, _dp(a), _dp(b))
         return a.reshape(3, 4), b.reshape(3, 4)
+
+    def set_state(self, odom34, prev34, initialised=True):
+        """Starts the next step from a designed (odom_, prev_odom_); the window, IMU orientation and mounting stay."""
+        a = np.ascontiguousarray(odom34, dtype=np.float64).reshape(12)
+        b = np.ascontiguousarray(prev34, dtype=np.float64).reshape(12)
+        lib().orc_odom_set_state(self.h, _dp(a), _dp(b), int(bool(initialised)))
 
 
 class Map:

@@ -39,6 +39,39 @@ void hc_predict(const double* odom, const double* prev, double* pred) {
   iso_mul(inv, odom, rel);
   iso_mul(odom, rel, pred);
 }
+void hc_quat_from_pose(const double* T12, int rotation_mode, double* q) { quat_from_pose(T12, rotation_mode, q); }
+// predict_next's algebra (kernels_lm.h; the kernel's own function is __device__): the prediction, its quaternion, its translation
+void hc_predict_next(const double* T, const double* prev, int rotation_mode, double* out19) {
+  double inv[12], rel[12], pred[12];
+  iso_inverse(prev, inv);
+  iso_mul(inv, T, rel);
+  iso_mul(T, rel, pred);
+  for (int i = 0; i < 12; i++) out19[i] = pred[i];
+  quat_from_pose(pred, rotation_mode, out19 + 12);
+  out19[16] = pred[3]; out19[17] = pred[7]; out19[18] = pred[11];
+}
+// One scan without correspondences, in the order the kernels run it on a stream's state (odom = the prediction made when the
+// previous scan finished, prev = the previous final pose, param_q / param_t = the solve's start point): k_imu_override, two solves
+// that change nothing, iso_from_qt, finalize_scan's quat_from_pose and predict_next.  State updated in place; final12 and pose7
+// (quaternion, translation: pose_out and the pose log) are what the scan returns.
+void hc_scan_no_match(double* odom, double* prev, double* param_q, double* param_t, const double* imu_q, const double* l2b,
+                      int rotation_mode, int use_imu, double* final12, double* pose7) {
+  if (use_imu) {
+    double out[12];
+    imu_override(odom, imu_q, l2b, rotation_mode, out);
+    for (int i = 0; i < 12; i++) odom[i] = out[i];
+    quat_from_pose(out, rotation_mode, param_q);
+    param_t[0] = out[3]; param_t[1] = out[7]; param_t[2] = out[11];
+  }
+  iso_from_qt(param_q, param_t, final12);
+  quat_from_pose(final12, rotation_mode, pose7);
+  pose7[4] = final12[3]; pose7[5] = final12[7]; pose7[6] = final12[11];
+  double p19[19];
+  hc_predict_next(final12, prev, rotation_mode, p19);
+  for (int i = 0; i < 12; i++) { prev[i] = final12[i]; odom[i] = p19[i]; }
+  for (int i = 0; i < 4; i++) param_q[i] = p19[12 + i];
+  for (int i = 0; i < 3; i++) param_t[i] = p19[16 + i];
+}
 // accumulator (29 doubles) over n blocks of 9 doubles (p, a, b) at pose (q, t)
 void hc_accumulate(const double* blocks9, int n, const double* q, const double* t, double min_d,
                    double max_d, double* acc) {
