@@ -815,6 +815,78 @@ int liodom_map_search_pose_bnb(liodom_map_t* m, const float* edges_xyzi, int n_e
                                const liodom_pose_search_bnb_t* opt /*NULL: defaults*/, liodom_pose_search_result_t* out,
                                liodom_pose_search_stats_t* stats /*optional*/);
 
+/* ---- finding the place: a database of binary polar descriptors (no counterpart in the reference; DESIGN.md §3 "Finding the
+ * place", INTEGRATION.md §7 "Relocalising without a guess").  Every search above needs a pose to search around; a liodom_places_t
+ * answers "near which key frame was this scan taken?" without one.  It is an object of its own: it touches no handle and no map,
+ * has a HIP stream and a mutex of its own, and every call synchronises that stream before it returns.
+ *
+ * A place is one descriptor of a key frame's edge cloud IN THE SENSOR FRAME, plus the pose the key frame was taken at and a caller
+ * tag.  The descriptor has W = n_rings * n_layers 64-bit words, 1 <= W <= 64; bit `sector` of word ring * n_layers + layer is set
+ * iff a point of the cloud falls into that bin.  There are always 64 sectors: a sector is a bit and a yaw shift is a rotate.
+ * All arithmetic is float32, no fused multiply-add.  Tables, made in double and rounded to float once (they travel in the blob):
+ *   C_i, S_i = float(cos(i pi / 32)), float(sin(i pi / 32)), i = 1 .. 15;  R2_i = float((i r_max / n_rings)^2), i = 1 .. n_rings;
+ *   Z_i = float(z_min + i (z_max - z_min) / n_layers), i = 0 .. n_layers.
+ * A point (x, y, z) with a non-finite coordinate sets nothing.  j = #{i : |y| C_i >= |x| S_i}; the sector is j for x >= 0, y >= 0;
+ * 31 - j for x < 0, y >= 0; 32 + j for x < 0, y < 0; 63 - j for x >= 0, y < 0 (-0 is not below 0).  r2 = x x + y y (two
+ * multiplies, one add); ring = #{i : r2 >= R2_i}, and ring == n_rings sets nothing.  z < Z_0 sets nothing; layer = #{i >= 1 :
+ * z >= Z_i}, and layer == n_layers sets nothing.
+ * Distance of a query q and a place k: d(s) = sum over the words of popcount(rotl64(q[w], s) ^ k[w]), s = 0 .. 63; the place's
+ * distance is the smallest d(s), its shift the lowest such s.  Places rank by (distance, index), lowest first.  The pose of a match
+ * is place_pose o Rz(shift * 2 pi / 64), composed in double, the place's quaternion normalised as liodom_seed_stream does: a
+ * query taken at the place's position with its heading turned by +a about z matches at shift = a / (2 pi / 64).
+ * The descriptor has no roll or pitch term and no height term: it assumes a sensor that is level to within what a vehicle does
+ * and mounted at the height the key frames were taken with.
+ *
+ *   liodom_place_geometry_default   16 rings, 4 layers, r_max 80 m, z from -4 to 12 m.
+ *   liodom_places_create      max_places 1 .. 2^20, max_edges 1 .. 2^24 (points of one cloud); on the calling thread's current device.
+ *   liodom_places_describe    desc_out[i * W ..] = the descriptor of row i (the cloud at edges_xyzi + 4 * i * edge_stride_points floats,
+ *       n_edges[i] points), bits_out[i] (optional) = its popcount.
+ *   liodom_places_add         describes one cloud and appends it with its pose [qx qy qz qw tx ty tz] and tag; *index (optional) =
+ *       its index.  A full database: LIODOM_ERR_CAPACITY, database untouched.
+ *   liodom_places_query       describes n rows and writes the k best places of each to out[i * k ..], best first; rows beyond the
+ *       number of places have index -1 and every other field 0.  bits_query[i] (optional) = popcount of row i's descriptor.
+ *   liodom_places_query_desc  the same for n descriptors the caller holds (n x W words).
+ *   liodom_places_state_size / _export_state / _import_state   the database as one blob (layout: liodom_amd/csrc/
+ *       place_state_format.h): magic "LIODOMPL", version, the geometry and its tables, then per place descriptor, bit count, tag and
+ *       pose.  Export with cap too small: LIODOM_ERR_CAPACITY, *bytes = the size needed, nothing written.  Import validates on the
+ *       host before anything is launched: truncation, bad magic / version, W outside 1 .. 64, sizes that do not add up, tables
+ *       that are not the geometry's, a bit count that is not its descriptor's popcount, a pose liodom_places_add would refuse, or a
+ *       geometry that differs in any bit from the database's: LIODOM_ERR_INVALID_ARG; more places than max_places:
+ *       LIODOM_ERR_CAPACITY.  On any error the database is untouched.
+ *   liodom_places_reset       no places; capacities and allocations are kept.
+ * Limits: 1 <= k <= 16, n <= 2^20.  LIODOM_ERR_INVALID_ARG, with nothing computed: a null where one is required, a negative count
+ * or stride, k out of range, n_edges[i] > edge_stride_points or > max_edges, a non-finite pose or | |q| - 1 | > 1e-6.
+ * Non-finite edges are no error.  n = 0, or a database without places: LIODOM_OK (index -1 rows). */
+typedef struct liodom_places liodom_places_t;
+typedef struct liodom_place_geometry_t {
+  int32_t n_rings, n_layers;
+  double r_max, z_min, z_max;
+  int64_t reserved;
+} liodom_place_geometry_t;     /* 40 bytes */
+typedef struct liodom_place_match_t {
+  int32_t index;               /* of the place, -1: none */
+  int32_t distance, shift;     /* Hamming distance at the best yaw shift; the lowest such shift, 0 .. 63 */
+  int32_t bits_place;          /* popcount of the place's descriptor */
+  int64_t id;                  /* the place's tag */
+  double pose[7];              /* place_pose o Rz(shift * 2 pi / 64): what liodom_seed_stream or a search centre takes */
+  double place_pose[7];        /* as given to liodom_places_add */
+} liodom_place_match_t;        /* 136 bytes */
+void liodom_place_geometry_default(liodom_place_geometry_t* g);
+int liodom_places_create(const liodom_place_geometry_t* geom, int max_places, int max_edges, liodom_places_t** out);
+void liodom_places_destroy(liodom_places_t* db);
+int liodom_places_count(liodom_places_t* db, int32_t* count);
+int liodom_places_reset(liodom_places_t* db);
+int liodom_places_describe(liodom_places_t* db, const float* edges_xyzi, int64_t edge_stride_points, const int32_t* n_edges /*[n]*/, int n,
+                           uint64_t* desc_out /*n x W*/, int32_t* bits_out /*optional, [n]*/);
+int liodom_places_add(liodom_places_t* db, const float* edges_xyzi, int n_edges, const double* pose /*[7]*/, int64_t id,
+                      int32_t* index /*optional*/);
+int liodom_places_query(liodom_places_t* db, const float* edges_xyzi, int64_t edge_stride_points, const int32_t* n_edges /*[n]*/, int n,
+                        int k, liodom_place_match_t* out /*n x k*/, int32_t* bits_query /*optional, [n]*/);
+int liodom_places_query_desc(liodom_places_t* db, const uint64_t* desc /*n x W*/, int n, int k, liodom_place_match_t* out /*n x k*/);
+int liodom_places_state_size(liodom_places_t* db, int64_t* bytes);
+int liodom_places_export_state(liodom_places_t* db, void* blob, int64_t cap, int64_t* bytes);
+int liodom_places_import_state(liodom_places_t* db, const void* blob, int64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
                                                   "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h",
+                                                  "kernels_places.h", "liodom_places_host.h", "place_state_format.h",
                                                   "liodom_sizes.h", "handle_plan.h", "step_plan.h", "liodom_step_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -217,6 +218,164 @@ class TrackPolicy:
             return TRACKING
         self.below = 0
         return LOST
+
+
+class PlaceGeometry(C.Structure):
+    """liodom_place_geometry_t: the five numbers of a place descriptor (include/liodom_hip.h)."""
+    _fields_ = [("n_rings", C.c_int32), ("n_layers", C.c_int32), ("r_max", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double),
+                ("reserved", C.c_int64)]
+
+
+class PlaceMatch(C.Structure):
+    """liodom_place_match_t: one of the K best places of a query."""
+    _fields_ = [("index", C.c_int32), ("distance", C.c_int32), ("shift", C.c_int32), ("bits_place", C.c_int32), ("id", C.c_int64),
+                ("pose", C.c_double * 7), ("place_pose", C.c_double * 7)]
+
+
+PLACE_MATCH_DTYPE = np.dtype([("index", "<i4"), ("distance", "<i4"), ("shift", "<i4"), ("bits_place", "<i4"), ("id", "<i8"),
+                              ("pose", "<f8", (7,)), ("place_pose", "<f8", (7,))])
+
+
+class PlacePolicy:
+    """When a scan becomes a key frame of a place database: the rules of liodom_amd/csrc/place_policy.h, restated
+    (tests/test_place_policy.py holds the two equal).  feed(pose7) answers True — and remembers the pose — for the first finite pose
+    and for one that has moved from the last key frame's by >= min_dist metres or by a rotation >= min_yaw radians."""
+
+    def __init__(self, min_dist, min_yaw=float("inf")):
+        self.min_dist, self.min_yaw, self.last = float(min_dist), float(min_yaw), None
+
+    @staticmethod
+    def dist(a, b):
+        import math
+        dx, dy, dz = a[4] - b[4], a[5] - b[5], a[6] - b[6]
+        return math.sqrt(dx * dx + dy * dy + dz * dz)
+
+    @staticmethod
+    def angle(a, b):
+        import math
+        na = math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + a[3] * a[3])
+        nb = math.sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2] + b[3] * b[3])
+        dot = abs(a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]) / (na * nb)
+        return 2.0 * math.acos(dot if dot < 1.0 else 1.0)
+
+    def feed(self, pose7):
+        import math
+        p = [float(v) for v in np.asarray(pose7, np.float64).reshape(7)]
+        if not all(math.isfinite(v) for v in p) or not (p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3] > 0.0):
+            return False
+        if self.last is not None and not (self.dist(p, self.last) >= self.min_dist) and not (self.angle(p, self.last) >= self.min_yaw):
+            return False
+        self.last = p
+        return True
+
+
+# ---- place-state blob (liodom_places_export_state; layout in csrc/place_state_format.h and DESIGN.md §3) ----
+PLACE_STATE_MAGIC = b"LIODOMPL"
+PLACE_STATE_VERSION = 1
+PLACE_STATE_HEADER_BYTES = 64
+PLACE_TABLES_BYTES = 656
+PLACE_RECORD_BYTES = 72
+PLACE_RECORD_DTYPE = np.dtype([("id", "<i8"), ("bits", "<i4"), ("reserved", "<i4"), ("pose", "<f8", (7,))])
+
+
+def place_geometry(n_rings=16, n_layers=4, r_max=80.0, z_min=-4.0, z_max=12.0):
+    """The five numbers as a tuple (the defaults are liodom_place_geometry_default's)."""
+    return (int(n_rings), int(n_layers), float(r_max), float(z_min), float(z_max))
+
+
+def place_tables(geom):
+    """The descriptor's tables as place_state_format.h makes them (double, rounded to float once): dict(C, S (15,), R2 (n_rings,),
+    Z (n_layers + 1,)) of float32."""
+    import math
+    n_rings, n_layers, r_max, z_min, z_max = place_geometry(*geom)
+    if not (1 <= n_rings and 1 <= n_layers and n_rings * n_layers <= 64 and math.isfinite(r_max) and math.isfinite(z_min) and
+            math.isfinite(z_max) and r_max > 0.0 and z_min < z_max):
+        raise ValueError("not a place geometry: 1 <= n_rings * n_layers <= 64, r_max > 0, z_min < z_max, all finite")
+    return dict(C=np.array([math.cos(i * math.pi / 32.0) for i in range(1, 16)], np.float64).astype(np.float32),
+                S=np.array([math.sin(i * math.pi / 32.0) for i in range(1, 16)], np.float64).astype(np.float32),
+                R2=np.array([(i * r_max / n_rings) * (i * r_max / n_rings) for i in range(1, n_rings + 1)], np.float64).astype(np.float32),
+                Z=np.array([z_min + i * (z_max - z_min) / n_layers for i in range(n_layers + 1)], np.float64).astype(np.float32))
+
+
+def _place_tables_bytes(geom):
+    t = place_tables(geom)
+    raw = np.zeros(PLACE_TABLES_BYTES // 4, "<f4")
+    raw[0:15], raw[16:31] = t["C"], t["S"]
+    raw[32:32 + len(t["R2"])] = t["R2"]
+    raw[96:96 + len(t["Z"])] = t["Z"]
+    return raw.tobytes()
+
+
+def build_place_state(geom, desc, ids, poses, bits=None):
+    """Writes a place-state blob: geom = the five numbers, desc [n, W] uint64, ids (n,), poses [n, 7]; bits (n,) defaults to the
+    descriptors' popcounts.  The writer the tests fill a database with that needs no describe kernel."""
+    g = place_geometry(*geom)
+    W = g[0] * g[1]
+    tables = _place_tables_bytes(g)
+    desc = np.ascontiguousarray(desc, dtype="<u8").reshape(-1, W)
+    n = desc.shape[0]
+    rec = np.zeros(n, PLACE_RECORD_DTYPE)
+    rec["id"] = np.asarray(ids, np.int64).reshape(n)
+    rec["pose"] = np.asarray(poses, np.float64).reshape(n, 7)
+    rec["bits"] = np.bitwise_count(desc).sum(axis=1) if bits is None else np.asarray(bits, np.int32).reshape(n)
+    total = PLACE_STATE_HEADER_BYTES + PLACE_TABLES_BYTES + (8 * W + PLACE_RECORD_BYTES) * n
+    blob = b"".join([PLACE_STATE_MAGIC, np.array([PLACE_STATE_VERSION, PLACE_STATE_HEADER_BYTES], "<u4").tobytes(),
+                     np.array([total], "<u8").tobytes(), np.array(g[:2], "<i4").tobytes(), np.array(g[2:], "<f8").tobytes(),
+                     np.array([n, 0], "<i4").tobytes(), tables, desc.tobytes(), rec.tobytes()])
+    assert len(blob) == total
+    return blob
+
+
+def parse_place_state(blob, geom=None):
+    """A place-state blob as a dict (pure Python: no library, no GPU).  Keys: version, total_bytes, geometry (the five numbers),
+    tables (as place_tables), count, desc [n, W] uint64, bits, ids, poses [n, 7].  Raises ValueError on everything the library's
+    place_state_validate rejects as malformed, and — with geom — on a geometry that differs in any bit."""
+    b = bytes(blob)
+    if len(b) < PLACE_STATE_HEADER_BYTES:
+        raise ValueError("place-state blob truncated (%d bytes)" % len(b))
+    if b[:8] != PLACE_STATE_MAGIC:
+        raise ValueError("not a place-state blob (bad magic)")
+    version, header_bytes = (int(x) for x in np.frombuffer(b, "<u4", 2, 8))
+    total = int(np.frombuffer(b, "<u8", 1, 16)[0])
+    if version != PLACE_STATE_VERSION or header_bytes != PLACE_STATE_HEADER_BYTES:
+        raise ValueError("place-state blob of version %d (this code reads %d)" % (version, PLACE_STATE_VERSION))
+    if total != len(b):
+        raise ValueError("place-state blob says %d bytes, has %d" % (total, len(b)))
+    if len(b) < PLACE_STATE_HEADER_BYTES + PLACE_TABLES_BYTES:
+        raise ValueError("place-state blob truncated (%d bytes)" % len(b))
+    n_rings, n_layers = (int(x) for x in np.frombuffer(b, "<i4", 2, 24))
+    r_max, z_min, z_max = (float(x) for x in np.frombuffer(b, "<f8", 3, 32))
+    count, reserved = (int(x) for x in np.frombuffer(b, "<i4", 2, 56))
+    g = (n_rings, n_layers, r_max, z_min, z_max)
+    if n_rings > 64 or n_layers > 64:
+        raise ValueError("place-state blob: not a geometry")
+    try:
+        tables = _place_tables_bytes(g)
+    except ValueError:
+        raise ValueError("place-state blob: not a geometry")
+    if reserved != 0:
+        raise ValueError("place-state blob: reserved header word is not 0")
+    W = n_rings * n_layers
+    rest = len(b) - PLACE_STATE_HEADER_BYTES - PLACE_TABLES_BYTES
+    if count < 0 or rest != (8 * W + PLACE_RECORD_BYTES) * count:
+        raise ValueError("place-state blob: sizes do not add up")
+    if b[PLACE_STATE_HEADER_BYTES:PLACE_STATE_HEADER_BYTES + PLACE_TABLES_BYTES] != tables:
+        raise ValueError("place-state blob: the tables are not the ones its geometry gives")
+    if geom is not None and (np.array(place_geometry(*geom)[:2], "<i4").tobytes() + np.array(place_geometry(*geom)[2:], "<f8").tobytes()) != b[24:56]:
+        raise ValueError("place-state blob comes from a database with another geometry")
+    off = PLACE_STATE_HEADER_BYTES + PLACE_TABLES_BYTES
+    desc = np.frombuffer(b, "<u8", W * count, off).reshape(count, W).copy()
+    rec = np.frombuffer(b, PLACE_RECORD_DTYPE, count, off + 8 * W * count).copy()
+    if not np.array_equal(rec["bits"], np.bitwise_count(desc).sum(axis=1).astype(np.int32)):
+        raise ValueError("place-state blob: a bit count is not the popcount of its descriptor")
+    if (rec["reserved"] != 0).any():
+        raise ValueError("place-state blob: reserved record word is not 0")
+    with np.errstate(all="ignore"):
+        norm = np.sqrt((rec["pose"][:, :4] ** 2).sum(axis=1))
+        if not (np.isfinite(rec["pose"]).all() and (np.abs(norm - 1.0) <= 1e-6).all()):
+            raise ValueError("place-state blob: a pose is non-finite or its quaternion is not normalised")
+    return dict(version=version, total_bytes=total, geometry=g, tables=place_tables(g), count=count, desc=desc, bits=rec["bits"].copy(),
+                ids=rec["id"].copy(), poses=rec["pose"].copy())
 
 
 class EdgeTicket(C.Structure):
@@ -678,6 +837,31 @@ def load():
     L.liodom_scan_buffer_polar.argtypes = [vp, C.c_int, C.POINTER(vp), i64p]
     L.liodom_extract_edges_device_polar.restype = C.c_int
     L.liodom_extract_edges_device_polar.argtypes = [vp, C.c_int, vp, tp]
+    u64p = C.POINTER(C.c_uint64)
+    L.liodom_place_geometry_default.restype = None
+    L.liodom_place_geometry_default.argtypes = [C.POINTER(PlaceGeometry)]
+    L.liodom_places_create.restype = C.c_int
+    L.liodom_places_create.argtypes = [C.POINTER(PlaceGeometry), C.c_int, C.c_int, C.POINTER(vp)]
+    L.liodom_places_destroy.restype = None
+    L.liodom_places_destroy.argtypes = [vp]
+    L.liodom_places_count.restype = C.c_int
+    L.liodom_places_count.argtypes = [vp, ip]
+    L.liodom_places_reset.restype = C.c_int
+    L.liodom_places_reset.argtypes = [vp]
+    L.liodom_places_describe.restype = C.c_int
+    L.liodom_places_describe.argtypes = [vp, fp, C.c_int64, ip, C.c_int, u64p, ip]
+    L.liodom_places_add.restype = C.c_int
+    L.liodom_places_add.argtypes = [vp, fp, C.c_int, dp, C.c_int64, ip]
+    L.liodom_places_query.restype = C.c_int
+    L.liodom_places_query.argtypes = [vp, fp, C.c_int64, ip, C.c_int, C.c_int, vp, ip]
+    L.liodom_places_query_desc.restype = C.c_int
+    L.liodom_places_query_desc.argtypes = [vp, u64p, C.c_int, C.c_int, vp]
+    L.liodom_places_state_size.restype = C.c_int
+    L.liodom_places_state_size.argtypes = [vp, i64p]
+    L.liodom_places_export_state.restype = C.c_int
+    L.liodom_places_export_state.argtypes = [vp, vp, C.c_int64, i64p]
+    L.liodom_places_import_state.restype = C.c_int
+    L.liodom_places_import_state.argtypes = [vp, vp, C.c_int64]
     _lib = L
     return L
 
@@ -727,6 +911,9 @@ EXPORTED_SYMBOLS = [
     "liodom_map_score_poses", "liodom_pose_search_default", "liodom_map_search_pose",
     "liodom_pose_search_bnb_default", "liodom_map_bound_nodes", "liodom_map_search_pose_bnb",
     "liodom_set_map_hits", "liodom_get_map_hit_log", "liodom_map_hit_rows",
+    "liodom_place_geometry_default", "liodom_places_create", "liodom_places_destroy", "liodom_places_count", "liodom_places_reset",
+    "liodom_places_describe", "liodom_places_add", "liodom_places_query", "liodom_places_query_desc",
+    "liodom_places_state_size", "liodom_places_export_state", "liodom_places_import_state",
 ]
 
 
@@ -1197,12 +1384,7 @@ class Liodom:
         dict(pose, hits_r, hits_0, n_edges, fraction, levels=[each level's result]) comes back: process the SAME scan next.  Otherwise
         None, and the stream is as it was but for the edges extract_edges left in it."""
         edges = self.extract_edges(scan, height, width, stream=stream)["edges"]
-        pose, found = np.array(centre, dtype=np.float64).reshape(7), []
-        for grid in levels:
-            grid = dict(grid)
-            bnb, batch = grid.pop("bnb", False), grid.pop("batch", 0)
-            found.append(map.search_pose_bnb(edges, pose, batch=batch, **grid) if bnb else map.search_pose(edges, pose, **grid))
-            pose = found[-1]["pose"]
+        pose, found = self._search_levels(map, edges, centre, levels)
         if not found or edges.shape[0] == 0:
             return None
         last = found[-1]
@@ -1211,6 +1393,57 @@ class Liodom:
             return None
         self.seed_stream(pose, stream=stream)
         return dict(pose=pose, hits_r=last["hits_r"], hits_0=last["hits_0"], n_edges=int(edges.shape[0]), fraction=fraction, levels=found)
+
+    @staticmethod
+    def _search_levels(map, edges, centre, levels):
+        """The levels of relocalize: each a grid (Map.search_pose, or Map.search_pose_bnb with bnb=True) around the one before's
+        best, the first around `centre` -> (the last level's pose, [each level's result])."""
+        pose, found = np.array(centre, dtype=np.float64).reshape(7), []
+        for grid in levels:
+            grid = dict(grid)
+            bnb, batch = grid.pop("bnb", False), grid.pop("batch", 0)
+            found.append(map.search_pose_bnb(edges, pose, batch=batch, **grid) if bnb else map.search_pose(edges, pose, **grid))
+            pose = found[-1]["pose"]
+        return pose, found
+
+    def add_place(self, places, pose, id=0, stream=0):
+        """Makes the scan just processed a place: its edge cloud (get_edges: the sensor frame) goes to places.add with `pose` =
+        [qx qy qz qw tx ty tz] — the pose that scan ended with — and the tag `id`.  Returns the place's index."""
+        return places.add(self.get_edges(stream=stream)["edges"], pose, id)
+
+    def relocalize_global(self, map, places, scan, height, width, k, levels, min_fraction=0.5, pager=None, stream=0):
+        """relocalize without a guess: the scan's edges (extract_edges, once) are looked up in `places` (Places.query, the k best),
+        and `levels` (as relocalize's) run around the pose of every match in turn; with a `pager` (MapPager of `map`), pager.step at
+        the match's pose comes first, so that the map holds the cells around it.  The match whose last level scores highest wins
+        (ties go to the better rank).  If its score / (2 * n_edges) >= min_fraction the stream is seeded with the searched pose
+        (with a pager: after a pager.step there) and dict(pose, hits_r, hits_0, n_edges, fraction, levels, match, rank, matches)
+        comes back: process the SAME scan next.  Otherwise — also for an empty database — None, and the stream is as it was but for
+        the edges extract_edges left in it.  A host loop over existing calls: nothing is scored here."""
+        edges = self.extract_edges(scan, height, width, stream=stream)["edges"]
+        if edges.shape[0] == 0 or not levels:
+            return None
+        matches = places.query([edges], k)[0]
+        best = None
+        for rank, m in enumerate(matches):
+            if m["index"] < 0:
+                break
+            if pager is not None:
+                pager.step(pose_T34(m["pose"]))
+            pose, found = self._search_levels(map, edges, m["pose"], levels)
+            score = found[-1]["hits_r"] + found[-1]["hits_0"]
+            if best is None or score > best[0]:
+                best = (score, rank, m, pose, found)
+        if best is None:
+            return None
+        score, rank, m, pose, found = best
+        fraction = score / (2.0 * edges.shape[0])
+        if not fraction >= min_fraction:
+            return None
+        if pager is not None:
+            pager.step(pose_T34(pose))
+        self.seed_stream(pose, stream=stream)
+        return dict(pose=pose, hits_r=found[-1]["hits_r"], hits_0=found[-1]["hits_0"], n_edges=int(edges.shape[0]), fraction=fraction,
+                    levels=found, match=m, rank=rank, matches=matches)
 
     def set_map_hits(self, radius, stream=0):
         """Per-scan map-hit records for `stream` (liodom_set_map_hits): radius 0 or 1 switches them on, -1 off."""
@@ -1523,3 +1756,127 @@ class Map:
         """The map as it was created: no cells, status 0; capacities and allocations kept (liodom_map_reset).  ERR_BUSY while
         attached."""
         self._chk(self._L.liodom_map_reset(self.h))
+
+
+def pose_T34(pose7):
+    """[qx qy qz qw tx ty tz] as a 3 x 4 matrix, the quaternion normalised in double first (as liodom_seed_stream does)."""
+    p = np.asarray(pose7, np.float64).reshape(7)
+    qx, qy, qz, qw = p[:4] / np.sqrt(np.sum(p[:4] * p[:4]))
+    R = np.array([[1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw)],
+                  [2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw)],
+                  [2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)]])
+    return np.ascontiguousarray(np.concatenate([R, p[4:].reshape(3, 1)], axis=1))
+
+
+class Places:
+    """liodom_places_t: a device-resident set of places — one binary polar descriptor per key frame's edge cloud (sensor frame),
+    with the key frame's pose and a tag — and the K nearest places of a query cloud, with the yaw offset each matches at
+    (include/liodom_hip.h "finding the place").  Touches no handle and no map."""
+
+    def __init__(self, max_places=4096, max_edges=16384, **geom):
+        L = load()
+        g = PlaceGeometry()
+        L.liodom_place_geometry_default(C.byref(g))
+        for k, v in geom.items():
+            if k not in ("n_rings", "n_layers", "r_max", "z_min", "z_max"):
+                raise KeyError(k)
+            setattr(g, k, v)
+        self.h = C.c_void_p()
+        self._L = L
+        self._chk(L.liodom_places_create(C.byref(g), int(max_places), int(max_edges), C.byref(self.h)))
+        self.geometry = (int(g.n_rings), int(g.n_layers), float(g.r_max), float(g.z_min), float(g.z_max))
+        self.words = int(g.n_rings) * int(g.n_layers)
+        self.max_places, self.max_edges = int(max_places), int(max_edges)
+
+    def _chk(self, rc):
+        if rc != 0:
+            e = LiodomError("liodom_places error %d: %s" % (rc, (self._L.liodom_last_error() or b"").decode()))
+            e.code = rc      # LIODOM_ERR_* (ERR_INVALID_ARG, ERR_CAPACITY, ...)
+            raise e
+
+    def close(self):
+        if self.h:
+            self._L.liodom_places_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _rows(edges_list):
+        """n clouds [E_i, 4] packed at one stride -> (packed [n, stride, 4], counts (n,), stride)."""
+        clouds = [np.ascontiguousarray(e, dtype=np.float32).reshape(-1, 4) for e in edges_list]
+        counts = np.array([c.shape[0] for c in clouds], np.int32).reshape(-1)
+        stride = int(counts.max()) if len(clouds) else 0
+        packed = np.zeros((max(len(clouds), 1), max(stride, 1), 4), np.float32)
+        for i, c in enumerate(clouds):
+            packed[i, :c.shape[0]] = c
+        return packed, (counts if len(clouds) else np.zeros(1, np.int32)), (max(stride, 1) if len(clouds) else 0)
+
+    def count(self):
+        n = C.c_int32()
+        self._chk(self._L.liodom_places_count(self.h, C.byref(n)))
+        return n.value
+
+    def reset(self):
+        """No places; capacities and allocations are kept (liodom_places_reset)."""
+        self._chk(self._L.liodom_places_reset(self.h))
+
+    def describe(self, edges_list):
+        """The descriptors of n edge clouds (liodom_places_describe) -> (desc [n, W] uint64, bits (n,) int32)."""
+        packed, counts, stride = self._rows(edges_list)
+        n = len(edges_list)
+        desc, bits = np.zeros((max(n, 1), self.words), np.uint64), np.zeros(max(n, 1), np.int32)
+        self._chk(self._L.liodom_places_describe(self.h, _fp(packed), stride, _ip(counts), n, desc.ctypes.data_as(C.POINTER(C.c_uint64)), _ip(bits)))
+        return desc[:n], bits[:n]
+
+    def add(self, edges, pose7, id=0):
+        """Describes one edge cloud (sensor frame) and appends it as a place taken at pose7 = [qx qy qz qw tx ty tz] with the tag
+        `id` (liodom_places_add) -> its index.  LiodomError with .code ERR_CAPACITY when the database is full (untouched)."""
+        e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
+        p = np.ascontiguousarray(pose7, dtype=np.float64).reshape(7)
+        idx = C.c_int32(-1)
+        self._chk(self._L.liodom_places_add(self.h, _fp(e), e.shape[0], _dp(p), int(id), C.byref(idx)))
+        return idx.value
+
+    def query(self, edges_list, k=1, want_bits=False):
+        """The k best places of each of n edge clouds (liodom_places_query) -> a structured array [n, k] (PLACE_MATCH_DTYPE: index,
+        distance, shift, bits_place, id, pose [7], place_pose [7]; index -1 beyond the number of places), best first; with
+        want_bits also the popcounts of the queries' descriptors (n,)."""
+        packed, counts, stride = self._rows(edges_list)
+        n = len(edges_list)
+        out = np.zeros((max(n, 1), max(int(k), 1)), PLACE_MATCH_DTYPE)
+        bits = np.zeros(max(n, 1), np.int32)
+        self._chk(self._L.liodom_places_query(self.h, _fp(packed), stride, _ip(counts), n, int(k), out.ctypes.data_as(C.c_void_p),
+                                              _ip(bits) if want_bits else None))
+        return (out[:n], bits[:n]) if want_bits else out[:n]
+
+    def query_desc(self, desc, k=1):
+        """The k best places of each of n descriptors [n, W] uint64 (liodom_places_query_desc) -> as query."""
+        d = np.ascontiguousarray(desc, dtype=np.uint64).reshape(-1, self.words)
+        n = d.shape[0]
+        out = np.zeros((max(n, 1), max(int(k), 1)), PLACE_MATCH_DTYPE)
+        self._chk(self._L.liodom_places_query_desc(self.h, d.ctypes.data_as(C.POINTER(C.c_uint64)), n, int(k), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
+
+    def state_size(self):
+        n = C.c_int64()
+        self._chk(self._L.liodom_places_state_size(self.h, C.byref(n)))
+        return n.value
+
+    def export_state(self):
+        """The database as one blob (liodom_places_export_state; parse_place_state reads it)."""
+        cap = self.state_size()
+        buf = (C.c_ubyte * cap)()
+        n = C.c_int64()
+        self._chk(self._L.liodom_places_export_state(self.h, buf, cap, C.byref(n)))
+        return bytes(memoryview(buf)[:n.value])
+
+    def import_state(self, blob):
+        """Makes the database what `blob` says (liodom_places_import_state): any database of the same geometry will do, whatever its
+        capacity.  LiodomError with .code ERR_INVALID_ARG / ERR_CAPACITY (database untouched)."""
+        b = bytes(blob)
+        self._chk(self._L.liodom_places_import_state(self.h, b, len(b)))

@@ -2310,3 +2310,5 @@ int liodom_device_info(liodom_handle_t* h, char* name, int name_cap, int* comput
 }
 
 }  // extern "C"
+
+#include "liodom_places_host.h"

@@ -1,6 +1,7 @@
 #include "liodom_host.h"
 #include "../csrc/liodom_math.h"   // odom_message: the same header the kernels use
 #include "../csrc/map_state_cells.h"   // blobs of paged-out cells, taken apart and put together
+#include "../csrc/place_policy.h"      // when a scan becomes a key frame of a PlaceDb
 
 #include <algorithm>
 #include <cmath>
@@ -479,6 +480,57 @@ std::vector<int32_t> Map::mergeState(const std::vector<uint8_t>& blob) {
   std::vector<int32_t> taken((size_t)std::max<int64_t>(0, std::min<int64_t>(n_cells, ((int64_t)blob.size() - 64) / 32)));
   check(liodom_map_merge_state(m_, blob.data(), (int64_t)blob.size(), taken.empty() ? nullptr : taken.data(), nullptr), "liodom_map_merge_state");
   return taken;
+}
+
+PlaceDb::PlaceDb(int max_places, int max_edges, const liodom_place_geometry_t* geom) {
+  liodom_place_geometry_t g;
+  liodom_place_geometry_default(&g);
+  check(liodom_places_create(geom ? geom : &g, max_places, max_edges, &db_), "liodom_places_create");
+}
+PlaceDb::~PlaceDb() { liodom_places_destroy(db_); }
+
+int PlaceDb::add(const PointCloud& edges, const Pose& pose, int64_t id) {
+  const double p[7] = {pose.q[0], pose.q[1], pose.q[2], pose.q[3], pose.t[0], pose.t[1], pose.t[2]};
+  int32_t index = -1;
+  check(liodom_places_add(db_, reinterpret_cast<const float*>(edges.points.data()), (int)edges.size(), p, id, &index), "liodom_places_add");
+  return index;
+}
+
+int PlaceDb::addIfKeyFrame(const PointCloud& edges, const Pose& pose, int64_t id, double min_dist, double min_yaw) {
+  const double p[7] = {pose.q[0], pose.q[1], pose.q[2], pose.q[3], pose.t[0], pose.t[1], pose.t[2]};
+  liodom_dev::PlacePolicyState s;
+  s.has = has_key_;
+  std::memcpy(s.last, last_key_, sizeof(last_key_));
+  if (!liodom_dev::place_policy_feed(liodom_dev::PlacePolicy{min_dist, min_yaw}, &s, p)) return -1;
+  const int index = add(edges, pose, id);      // (throws: the last key frame stays)
+  has_key_ = true;
+  std::memcpy(last_key_, p, sizeof(last_key_));
+  return index;
+}
+
+std::vector<liodom_place_match_t> PlaceDb::query(const PointCloud& edges, int k) {
+  std::vector<liodom_place_match_t> out((size_t)std::max(k, 0));
+  const int32_t n = (int32_t)edges.size();
+  check(liodom_places_query(db_, reinterpret_cast<const float*>(edges.points.data()), (int64_t)n, &n, 1, k, out.data(), nullptr), "liodom_places_query");
+  return out;
+}
+
+int PlaceDb::count() {
+  int32_t n = 0;
+  check(liodom_places_count(db_, &n), "liodom_places_count");
+  return n;
+}
+void PlaceDb::reset() { check(liodom_places_reset(db_), "liodom_places_reset"); }
+
+std::vector<uint8_t> PlaceDb::exportState() {
+  int64_t bytes = 0;
+  check(liodom_places_state_size(db_, &bytes), "liodom_places_state_size");
+  std::vector<uint8_t> blob((size_t)bytes);
+  check(liodom_places_export_state(db_, blob.data(), bytes, &bytes), "liodom_places_export_state");
+  return blob;
+}
+void PlaceDb::importState(const std::vector<uint8_t>& blob) {
+  check(liodom_places_import_state(db_, blob.data(), (int64_t)blob.size()), "liodom_places_import_state");
 }
 
 MapPager::MapPager(Map* map, int keep_xy, int keep_z, int load_xy, int load_z)

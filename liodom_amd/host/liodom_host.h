@@ -285,6 +285,30 @@ class MapPager {
   std::map<std::array<int32_t, 3>, std::list<Cell>::iterator> index_;
 };
 
+// A place database (liodom_places_*; no counterpart in the reference): key frames' edge clouds in the sensor frame as binary polar
+// descriptors, and the K nearest places of a query cloud with the yaw offset each matches at (include/liodom_hip.h "finding the
+// place").  An object of its own: no Engine, no Map.  addIfKeyFrame applies the distance policy of csrc/place_policy.h.
+class PlaceDb {
+ public:
+  PlaceDb(int max_places, int max_edges, const liodom_place_geometry_t* geom = nullptr);      // null: the default geometry
+  ~PlaceDb();
+  PlaceDb(const PlaceDb&) = delete;
+  PlaceDb& operator=(const PlaceDb&) = delete;
+  int add(const PointCloud& edges, const Pose& pose, int64_t id = 0);                          // the new place's index
+  // add(), if `pose` has moved min_dist metres or min_yaw radians from the last key frame's (the first pose always has): the index, or -1
+  int addIfKeyFrame(const PointCloud& edges, const Pose& pose, int64_t id, double min_dist, double min_yaw);
+  std::vector<liodom_place_match_t> query(const PointCloud& edges, int k);                     // best first; index -1 beyond the places
+  int count();
+  void reset();
+  std::vector<uint8_t> exportState();
+  void importState(const std::vector<uint8_t>& blob);
+  liodom_places_t* handle() const { return db_; }
+ private:
+  liodom_places_t* db_ = nullptr;
+  bool has_key_ = false;
+  double last_key_[7] = {0, 0, 0, 1, 0, 0, 0};
+};
+
 // The numbers LaserOdometer::publishOdom puts into nav_msgs/Odometry, geometry_msgs/TwistStamped
 // and the fixed_frame -> base_frame TF (laser_odometry.cc:395-446).
 struct OdometryMsg {
