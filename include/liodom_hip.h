@@ -887,6 +887,91 @@ int liodom_places_state_size(liodom_places_t* db, int64_t* bytes);
 int liodom_places_export_state(liodom_places_t* db, void* blob, int64_t cap, int64_t* bytes);
 int liodom_places_import_state(liodom_places_t* db, const void* blob, int64_t bytes);
 
+/* ---- closing loops: a pose graph over key frames, optimised on the device (no counterpart in the reference; DESIGN.md §3
+ * "Closing loops", INTEGRATION.md §7 "Correcting a revisit").  A liodom_graph_t is an object of its own: it touches no handle and
+ * no map, has a HIP stream and a mutex of its own, and every call synchronises that stream before it returns.
+ *
+ * A node is a pose X = (q, t), world <- frame, [qx qy qz qw tx ty tz]; it is free or fixed.  An edge (i, j, Z, Omega) says
+ * "X_i^-1 o X_j was measured as Z, with information Omega (6 x 6, row-major)".  Its error: D = Z^-1 o X_i^-1 o X_j = (q_d, t_d),
+ * e = [s vec(q_d); t_d], s = +1 for w_d >= 0, else -1 (the rotation part is the half angle: the rotation angle is 2 |vec|, as in
+ * liodom_pose_cov_t).  The cost is chi2 = sum over the edges of e^T Omega e.  A node moves by delta = (d, dt):
+ * q <- [sin|d| d/|d|, cos|d|] (x) q (left multiplication, world frame), t <- t + dt — the parameterisation of the scan solver.
+ * With J the exact derivative of the stacked e by the stacked delta at 0: gradient g = J^T Omega e, H = J^T Omega J, and one
+ * Levenberg-Marquardt step solves (H + lambda diag H) delta = -g by preconditioned conjugate gradients (6 x 6 blocks in the
+ * coordinates of the chain of edges (n - 1, n), block-Jacobi where there is none: DESIGN.md §3 "Closing loops").  A fixed
+ * node has delta = 0: its rows and columns drop out.  A free node without edges stays where it is (its block counts as the
+ * identity).  All arithmetic is double; sums run in an order that depends on the graph alone (no atomics), so equal graphs give
+ * equal bytes.  Quaternions are divided by their norm when they are taken in.
+ *
+ *   liodom_graph_create       1 <= max_nodes <= 65 536, 1 <= max_edges <= 262 144; on the calling thread's current device.  Device
+ *       memory is taken here, about 1.3 KiB per edge and 1 KiB per node of capacity.  The solve is one launch of one workgroup
+ *       per step, and nothing but max_pcg_iterations bounds how long it runs: about 60 us per iteration up to 1 024 nodes,
+ *       1.5 ms at 16 384 (MI355X), so a step of a graph of that size can take seconds and one at full capacity minutes.
+ *   liodom_graph_reset        no nodes, no edges; capacities and allocations are kept.
+ *   liodom_graph_count        *n_nodes, *n_edges (either optional).
+ *   liodom_graph_add_nodes    appends n poses (n x 7); fixed[k] != 0 (optional, NULL: all free) fixes node k.  *first (optional) =
+ *       the index of the first one; indices count up from 0 in the order of adding.
+ *   liodom_graph_add_edges    appends n edge records.  kind is the caller's (0 odometry, 1 loop by convention; nothing reads it);
+ *       reserved must be 0.
+ *   liodom_graph_set_fixed / _get_poses / _set_poses   nodes first .. first + n - 1.
+ *   liodom_graph_get_edges    edges first .. first + n - 1, as stored (Z's quaternion normalised).
+ *   liodom_graph_linearize    at the current poses: chi2_per_edge[n_edges], gradient[6 n_nodes] (0 for fixed nodes),
+ *       diag[n_nodes x 36] (each node's 6 x 6 block of H, row-major; also for fixed nodes).  Every output is optional.
+ *   liodom_graph_multiply     y = (H + lambda diag H) x at the current poses, x and y 6 n_nodes each; rows of fixed nodes are 0
+ *       and their x is not read; a free node without edges: y = x.
+ *   liodom_graph_options_default   max_iterations 20, max_pcg_iterations 0 (= 6 x free nodes, at most 65 536), pcg_tolerance 1e-8
+ *       (on |r| / |g|), gradient_tolerance 1e-9 (on max |g|), cost_tolerance 1e-10 (on the relative decrease of chi2).
+ *   liodom_graph_optimize     Levenberg-Marquardt from lambda = 1e-4.  A step is accepted iff chi2 decreases: lambda <-
+ *       max(lambda / 10, 1e-12); otherwise lambda <- 10 lambda and the poses stay.  Ends (report->termination) with max |g| <=
+ *       gradient_tolerance, a relative decrease of an accepted step <= cost_tolerance, after max_iterations steps tried, with
+ *       lambda > 1e12, or with a breakdown of the conjugate gradients (p^T H p <= 0, or a diagonal block that is not positive
+ *       definite: an information matrix that is not).  The poses are those of the last accepted step.  opt NULL: the defaults;
+ *       report optional.  A graph without a fixed node: LIODOM_ERR_INVALID_ARG.  A graph without a free node or without an edge
+ *       returns at once (LIODOM_GRAPH_TERM_GRADIENT, 0 iterations).
+ * LIODOM_ERR_INVALID_ARG, graph untouched: a null where one is required, a negative count, a range beyond the nodes or edges, a
+ * non-finite pose or Z, | |q| - 1 | > 1e-6, an edge with i == j or an index that is no node, reserved != 0, an Omega with a
+ * non-finite entry or one that is not symmetric bit for bit, options out of range (a negative count or tolerance, or a NaN).
+ * LIODOM_ERR_CAPACITY, graph untouched: more nodes than max_nodes or more edges than max_edges. */
+typedef struct liodom_graph liodom_graph_t;
+typedef struct liodom_graph_edge_t {
+  int32_t i, j, kind, reserved;
+  double z[7];
+  double info[36];
+} liodom_graph_edge_t;         /* 360 bytes */
+typedef struct liodom_graph_options_t {
+  int32_t max_iterations, max_pcg_iterations;
+  double pcg_tolerance, gradient_tolerance, cost_tolerance;
+} liodom_graph_options_t;      /* 32 bytes */
+#define LIODOM_GRAPH_TERM_GRADIENT 0
+#define LIODOM_GRAPH_TERM_COST 1
+#define LIODOM_GRAPH_TERM_MAX_ITERATIONS 2
+#define LIODOM_GRAPH_TERM_LAMBDA 3
+#define LIODOM_GRAPH_TERM_BREAKDOWN 4
+typedef struct liodom_graph_report_t {
+  double initial_cost, final_cost;   /* chi2 at the poses the call found and at those it left */
+  double max_gradient;               /* max |g| at the poses it left */
+  double final_lambda;
+  int32_t iterations;                /* steps tried */
+  int32_t accepted_steps;
+  int32_t pcg_iterations;            /* over all steps */
+  int32_t termination;               /* LIODOM_GRAPH_TERM_* */
+} liodom_graph_report_t;       /* 48 bytes */
+int liodom_graph_create(int max_nodes, int max_edges, liodom_graph_t** out);
+void liodom_graph_destroy(liodom_graph_t* g);
+int liodom_graph_reset(liodom_graph_t* g);
+int liodom_graph_count(liodom_graph_t* g, int32_t* n_nodes, int32_t* n_edges);
+int liodom_graph_add_nodes(liodom_graph_t* g, const double* poses /*n x 7*/, const int32_t* fixed /*optional, [n]*/, int n,
+                           int32_t* first /*optional*/);
+int liodom_graph_add_edges(liodom_graph_t* g, const liodom_graph_edge_t* edges, int n);
+int liodom_graph_set_fixed(liodom_graph_t* g, int first, int n, const int32_t* fixed);
+int liodom_graph_get_poses(liodom_graph_t* g, int first, int n, double* poses /*n x 7*/);
+int liodom_graph_set_poses(liodom_graph_t* g, int first, int n, const double* poses /*n x 7*/);
+int liodom_graph_get_edges(liodom_graph_t* g, int first, int n, liodom_graph_edge_t* edges);
+int liodom_graph_linearize(liodom_graph_t* g, double* chi2_per_edge, double* gradient, double* diag);
+int liodom_graph_multiply(liodom_graph_t* g, double lambda, const double* x, double* y);
+void liodom_graph_options_default(liodom_graph_options_t* opt);
+int liodom_graph_optimize(liodom_graph_t* g, const liodom_graph_options_t* opt, liodom_graph_report_t* report);
+
 #ifdef __cplusplus
 }
 #endif

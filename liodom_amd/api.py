@@ -16,6 +16,7 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
                                                   "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h",
                                                   "kernels_places.h", "liodom_places_host.h", "place_state_format.h",
+                                                  "kernels_graph.h", "liodom_graph_host.h", "graph_csr.h",
                                                   "liodom_sizes.h", "handle_plan.h", "step_plan.h", "liodom_step_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -234,6 +235,27 @@ class PlaceMatch(C.Structure):
 
 PLACE_MATCH_DTYPE = np.dtype([("index", "<i4"), ("distance", "<i4"), ("shift", "<i4"), ("bits_place", "<i4"), ("id", "<i8"),
                               ("pose", "<f8", (7,)), ("place_pose", "<f8", (7,))])
+
+
+class GraphEdge(C.Structure):
+    """liodom_graph_edge_t: "X_i^-1 o X_j was measured as z, with information info" (include/liodom_hip.h "closing loops")."""
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32), ("z", C.c_double * 7), ("info", C.c_double * 36)]
+
+
+GRAPH_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("kind", "<i4"), ("reserved", "<i4"), ("z", "<f8", (7,)), ("info", "<f8", (6, 6))])
+GRAPH_TERMINATIONS = ("gradient", "cost", "max_iterations", "lambda", "breakdown")      # LIODOM_GRAPH_TERM_*
+
+
+class GraphOptions(C.Structure):
+    """liodom_graph_options_t."""
+    _fields_ = [("max_iterations", C.c_int32), ("max_pcg_iterations", C.c_int32), ("pcg_tolerance", C.c_double),
+                ("gradient_tolerance", C.c_double), ("cost_tolerance", C.c_double)]
+
+
+class GraphReport(C.Structure):
+    """liodom_graph_report_t."""
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("max_gradient", C.c_double), ("final_lambda", C.c_double),
+                ("iterations", C.c_int32), ("accepted_steps", C.c_int32), ("pcg_iterations", C.c_int32), ("termination", C.c_int32)]
 
 
 class PlacePolicy:
@@ -862,6 +884,34 @@ def load():
     L.liodom_places_export_state.argtypes = [vp, vp, C.c_int64, i64p]
     L.liodom_places_import_state.restype = C.c_int
     L.liodom_places_import_state.argtypes = [vp, vp, C.c_int64]
+    L.liodom_graph_create.restype = C.c_int
+    L.liodom_graph_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
+    L.liodom_graph_destroy.restype = None
+    L.liodom_graph_destroy.argtypes = [vp]
+    L.liodom_graph_reset.restype = C.c_int
+    L.liodom_graph_reset.argtypes = [vp]
+    L.liodom_graph_count.restype = C.c_int
+    L.liodom_graph_count.argtypes = [vp, ip, ip]
+    L.liodom_graph_add_nodes.restype = C.c_int
+    L.liodom_graph_add_nodes.argtypes = [vp, dp, ip, C.c_int, ip]
+    L.liodom_graph_add_edges.restype = C.c_int
+    L.liodom_graph_add_edges.argtypes = [vp, vp, C.c_int]
+    L.liodom_graph_set_fixed.restype = C.c_int
+    L.liodom_graph_set_fixed.argtypes = [vp, C.c_int, C.c_int, ip]
+    L.liodom_graph_get_poses.restype = C.c_int
+    L.liodom_graph_get_poses.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.liodom_graph_set_poses.restype = C.c_int
+    L.liodom_graph_set_poses.argtypes = [vp, C.c_int, C.c_int, dp]
+    L.liodom_graph_get_edges.restype = C.c_int
+    L.liodom_graph_get_edges.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.liodom_graph_linearize.restype = C.c_int
+    L.liodom_graph_linearize.argtypes = [vp, dp, dp, dp]
+    L.liodom_graph_multiply.restype = C.c_int
+    L.liodom_graph_multiply.argtypes = [vp, C.c_double, dp, dp]
+    L.liodom_graph_options_default.restype = None
+    L.liodom_graph_options_default.argtypes = [C.POINTER(GraphOptions)]
+    L.liodom_graph_optimize.restype = C.c_int
+    L.liodom_graph_optimize.argtypes = [vp, C.POINTER(GraphOptions), C.POINTER(GraphReport)]
     _lib = L
     return L
 
@@ -914,6 +964,9 @@ EXPORTED_SYMBOLS = [
     "liodom_place_geometry_default", "liodom_places_create", "liodom_places_destroy", "liodom_places_count", "liodom_places_reset",
     "liodom_places_describe", "liodom_places_add", "liodom_places_query", "liodom_places_query_desc",
     "liodom_places_state_size", "liodom_places_export_state", "liodom_places_import_state",
+    "liodom_graph_create", "liodom_graph_destroy", "liodom_graph_reset", "liodom_graph_count", "liodom_graph_add_nodes",
+    "liodom_graph_add_edges", "liodom_graph_set_fixed", "liodom_graph_get_poses", "liodom_graph_set_poses", "liodom_graph_get_edges",
+    "liodom_graph_linearize", "liodom_graph_multiply", "liodom_graph_options_default", "liodom_graph_optimize",
 ]
 
 
@@ -1880,3 +1933,122 @@ class Places:
         capacity.  LiodomError with .code ERR_INVALID_ARG / ERR_CAPACITY (database untouched)."""
         b = bytes(blob)
         self._chk(self._L.liodom_places_import_state(self.h, b, len(b)))
+
+
+def make_graph_options(**kw):
+    """GraphOptions with the defaults of liodom_graph_options_default (20 steps, PCG to 1e-8 in at most 6 x free nodes iterations,
+    gradient tolerance 1e-9, cost tolerance 1e-10)."""
+    o = GraphOptions()
+    load().liodom_graph_options_default(C.byref(o))
+    for k, v in kw.items():
+        if k not in ("max_iterations", "max_pcg_iterations", "pcg_tolerance", "gradient_tolerance", "cost_tolerance"):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
+
+
+def graph_edges(i, j, z, info, kind=0):
+    """n edge records (GRAPH_EDGE_DTYPE) from i (n,), j (n,), z [n, 7] and info [n, 6, 6] or one [6, 6] for all."""
+    i = np.asarray(i, np.int32).reshape(-1)
+    out = np.zeros(i.shape[0], GRAPH_EDGE_DTYPE)
+    out["i"], out["j"], out["kind"] = i, np.asarray(j, np.int32).reshape(-1), kind
+    out["z"] = np.asarray(z, np.float64).reshape(-1, 7)
+    out["info"] = np.asarray(info, np.float64).reshape((-1, 6, 6))
+    return out
+
+
+class PoseGraph:
+    """liodom_graph_t: a pose graph over key frames — nodes [qx qy qz qw tx ty tz], free or fixed, and edges "X_i^-1 o X_j was
+    measured as z with information info" — linearised and optimised on the device (include/liodom_hip.h "closing loops").
+    Touches no handle and no map."""
+
+    def __init__(self, max_nodes=4096, max_edges=16384):
+        self._L = load()
+        self.h = C.c_void_p()
+        self._chk(self._L.liodom_graph_create(int(max_nodes), int(max_edges), C.byref(self.h)))
+        self.max_nodes, self.max_edges = int(max_nodes), int(max_edges)
+
+    def _chk(self, rc):
+        if rc != 0:
+            e = LiodomError("liodom_graph error %d: %s" % (rc, (self._L.liodom_last_error() or b"").decode()))
+            e.code = rc
+            raise e
+
+    def close(self):
+        if self.h:
+            self._L.liodom_graph_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        self._chk(self._L.liodom_graph_reset(self.h))
+
+    def count(self):
+        """(nodes, edges)."""
+        n, e = C.c_int32(), C.c_int32()
+        self._chk(self._L.liodom_graph_count(self.h, C.byref(n), C.byref(e)))
+        return n.value, e.value
+
+    def add_nodes(self, poses, fixed=None):
+        """Appends poses [n, 7] (fixed: n flags, None: all free) -> the index of the first."""
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        f = None if fixed is None else np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.int32)
+        if f is not None and f.shape[0] != p.shape[0]:
+            raise ValueError("one fixed flag per pose")
+        first = C.c_int32(-1)
+        self._chk(self._L.liodom_graph_add_nodes(self.h, _dp(p), None if f is None else _ip(f), p.shape[0], C.byref(first)))
+        return first.value
+
+    def add_edges(self, edges):
+        """Appends edge records (GRAPH_EDGE_DTYPE; graph_edges makes them)."""
+        e = np.ascontiguousarray(edges, dtype=GRAPH_EDGE_DTYPE).reshape(-1)
+        self._chk(self._L.liodom_graph_add_edges(self.h, e.ctypes.data_as(C.c_void_p), e.shape[0]))
+
+    def set_fixed(self, first, fixed):
+        f = np.ascontiguousarray(np.asarray(fixed).reshape(-1) != 0, dtype=np.int32)
+        self._chk(self._L.liodom_graph_set_fixed(self.h, int(first), f.shape[0], _ip(f)))
+
+    def poses(self, first=0, n=None):
+        n = self.count()[0] - int(first) if n is None else int(n)
+        out = np.zeros((max(n, 1), 7), np.float64)
+        self._chk(self._L.liodom_graph_get_poses(self.h, int(first), n, _dp(out)))
+        return out[:n]
+
+    def set_poses(self, first, poses):
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        self._chk(self._L.liodom_graph_set_poses(self.h, int(first), p.shape[0], _dp(p)))
+
+    def edges(self, first=0, n=None):
+        n = self.count()[1] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 1), GRAPH_EDGE_DTYPE)
+        self._chk(self._L.liodom_graph_get_edges(self.h, int(first), n, out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
+
+    def linearize(self):
+        """At the current poses -> (chi2 per edge (E,), gradient [N, 6] (0 for fixed nodes), diagonal blocks [N, 6, 6])."""
+        N, E = self.count()
+        chi2, g, D = np.zeros(max(E, 1)), np.zeros((max(N, 1), 6)), np.zeros((max(N, 1), 6, 6))
+        self._chk(self._L.liodom_graph_linearize(self.h, _dp(chi2), _dp(g), _dp(D)))
+        return chi2[:E], g[:N], D[:N]
+
+    def multiply(self, x, lam=0.0):
+        """(H + lam diag H) x at the current poses, x [N, 6] -> [N, 6]; rows and columns of fixed nodes dropped."""
+        N = self.count()[0]
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(N, 6)
+        y = np.zeros((max(N, 1), 6))
+        self._chk(self._L.liodom_graph_multiply(self.h, float(lam), _dp(x) if N else None, _dp(y)))
+        return y[:N]
+
+    def optimize(self, **options):
+        """Levenberg-Marquardt with the conjugate gradients on the device (liodom_graph_optimize; keywords: make_graph_options)
+        -> a dict of the report, termination as one of GRAPH_TERMINATIONS."""
+        o, r = make_graph_options(**options), GraphReport()
+        self._chk(self._L.liodom_graph_optimize(self.h, C.byref(o), C.byref(r)))
+        d = {k: getattr(r, k) for k, _ in GraphReport._fields_}
+        d["termination"] = GRAPH_TERMINATIONS[r.termination]
+        return d

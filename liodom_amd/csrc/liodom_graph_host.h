@@ -1,0 +1,415 @@
+// Host side of the pose graph (C-ABI liodom_graph_* of include/liodom_hip.h).  Included by liodom_hip.hip (same translation unit:
+// shares HIP_TRY / g_last_error).  A graph touches no handle and no map: it has a HIP stream and a mutex of its own, and every call
+// synchronises that stream before it returns.
+//
+// The graph lives on the host (poses, fixed flags, edge records): that copy is what the calls read and write, and what an error
+// leaves untouched.  The device copy and the CSR are made again, before the next launch, whenever the host copy has changed.
+// The Levenberg-Marquardt loop runs here around the launches; per step tried: k_graph_gather, k_graph_pcg, k_graph_retract,
+// k_graph_cost, k_graph_sum, and after an accepted one k_graph_linearize, k_graph_sum — whatever the number of PCG iterations.
+#pragma once
+#include <mutex>
+#include <vector>
+
+#include "graph_csr.h"
+#include "kernels_graph.h"
+
+struct liodom_graph {
+  int max_nodes = 0, max_edges = 0, device = 0;
+  hipStream_t stream = nullptr;
+  std::mutex mx;
+  std::vector<void*> allocs;
+  // the graph
+  std::vector<double> poses;                  // [n][7]
+  std::vector<int32_t> fixed;                 // [n]
+  std::vector<liodom_graph_edge_t> edges;
+  bool uploaded = false;                      // the device holds this graph (poses in d_poses) and its CSR
+  bool linearized = false;                    // ... and its linearisation (per-edge blocks, D, g; Minv for d_lambda)
+  // device
+  double *d_poses = nullptr, *d_cand = nullptr, *d_z = nullptr, *d_info = nullptr;
+  int *d_fixed = nullptr, *d_parent = nullptr, *d_ei = nullptr, *d_ej = nullptr, *d_offsets = nullptr, *d_entries = nullptr, *d_bad = nullptr;
+  double *d_chi2 = nullptr, *d_gi = nullptr, *d_gj = nullptr, *d_Hii = nullptr, *d_Hij = nullptr, *d_Hjj = nullptr;
+  double *d_g = nullptr, *d_D = nullptr, *d_Minv = nullptr;
+  double *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_zv = nullptr, *d_Ap = nullptr, *d_in = nullptr, *d_sum = nullptr;
+  liodom_dev::GraphPcgStatus* d_status = nullptr;
+};
+
+namespace {
+
+void graph_free(liodom_graph* g) {
+  if (!g) return;
+  hipSetDevice(g->device);
+  if (g->stream) { hipStreamSynchronize(g->stream); hipStreamDestroy(g->stream); }
+  for (void* p : g->allocs) hipFree(p);
+  delete g;
+}
+
+template <typename T>
+int graph_alloc(liodom_graph* g, T** ptr, size_t count) {
+  void* raw = nullptr;
+  HIP_TRY(hipMalloc(&raw, sizeof(T) * std::max<size_t>(count, 1)));
+  g->allocs.push_back(raw);
+  *ptr = static_cast<T*>(raw);
+  return LIODOM_OK;
+}
+
+inline unsigned graph_blocks(int n) { return (unsigned)std::max(1, (n + liodom_dev::kGraphThreads - 1) / liodom_dev::kGraphThreads); }
+
+// the device copy of the graph and its CSR
+int graph_upload(liodom_graph* g) {
+  if (g->uploaded) return LIODOM_OK;
+  const int N = (int)g->fixed.size(), E = (int)g->edges.size();
+  std::vector<int32_t> ei((size_t)E), ej((size_t)E), offsets, entries;
+  std::vector<double> z(7 * (size_t)E), info(36 * (size_t)E);
+  for (int e = 0; e < E; e++) {
+    const liodom_graph_edge_t& ed = g->edges[(size_t)e];
+    ei[(size_t)e] = ed.i; ej[(size_t)e] = ed.j;
+    std::memcpy(&z[7 * (size_t)e], ed.z, sizeof(ed.z));
+    std::memcpy(&info[36 * (size_t)e], ed.info, sizeof(ed.info));
+  }
+  if (!liodom_dev::graph_build_csr(ei.data(), ej.data(), E, N, &offsets, &entries)) {
+    g_last_error = "liodom_graph: an edge names a node that does not exist"; return LIODOM_ERR_INVALID_ARG;      // (checked when it was added)
+  }
+  // the chain the preconditioner works along (kernels_graph.h): a free node n hangs on the first edge (n - 1, n)
+  std::vector<int32_t> parent((size_t)N, -1);
+  for (int e = E - 1; e >= 0; e--) {
+    if (ej[(size_t)e] == ei[(size_t)e] + 1 && !g->fixed[(size_t)ej[(size_t)e]]) parent[(size_t)ej[(size_t)e]] = e;
+  }
+  g->linearized = false;
+  if (N) {
+    HIP_TRY(hipMemcpyAsync(g->d_parent, parent.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->d_poses, g->poses.data(), sizeof(double) * 7 * (size_t)N, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->d_fixed, g->fixed.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, g->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(g->d_offsets, offsets.data(), sizeof(int) * ((size_t)N + 1), hipMemcpyHostToDevice, g->stream));
+  if (E) {
+    HIP_TRY(hipMemcpyAsync(g->d_ei, ei.data(), sizeof(int) * (size_t)E, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->d_ej, ej.data(), sizeof(int) * (size_t)E, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->d_entries, entries.data(), sizeof(int) * 2 * (size_t)E, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->d_z, z.data(), sizeof(double) * z.size(), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->d_info, info.data(), sizeof(double) * info.size(), hipMemcpyHostToDevice, g->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));          // (the staging vectors are this function's)
+  g->uploaded = true;
+  return LIODOM_OK;
+}
+
+// per-edge quantities at d_poses, and *cost = their chi2 summed (enqueued and waited for)
+int graph_linearize(liodom_graph* g, double* cost) {
+  using namespace liodom_dev;
+  const int E = (int)g->edges.size();
+  if (E) {
+    hipLaunchKernelGGL(k_graph_linearize, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, (long long)g->max_edges, g->d_poses,
+                       g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_chi2, g->d_gi, g->d_gj, g->d_Hii, g->d_Hij, g->d_Hjj);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_graph_sum, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, E, g->d_chi2, g->d_sum);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(cost, g->d_sum, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  return LIODOM_OK;
+}
+
+int graph_gather(liodom_graph* g, double lambda) {
+  using namespace liodom_dev;
+  const int N = (int)g->fixed.size();
+  HIP_TRY(hipMemsetAsync(g->d_bad, 0, sizeof(int), g->stream));
+  hipLaunchKernelGGL(k_graph_gather, dim3(graph_blocks(N)), dim3(kGraphThreads), 0, g->stream, N, (long long)g->max_nodes, (long long)g->max_edges,
+                     lambda, g->d_fixed, g->d_parent, g->d_offsets, g->d_entries, g->d_gi, g->d_gj, g->d_Hii, g->d_Hjj, g->d_g, g->d_D, g->d_Minv, g->d_bad);
+  HIP_TRY(hipGetLastError());
+  return LIODOM_OK;
+}
+
+// upload + linearise + gather at lambda 0, if the device does not hold them
+int graph_prepare(liodom_graph* g) {
+  int rc;
+  if ((rc = graph_upload(g))) return rc;
+  if (g->linearized) return LIODOM_OK;
+  double cost = 0.0;
+  if ((rc = graph_linearize(g, &cost))) return rc;
+  if ((rc = graph_gather(g, 0.0))) return rc;
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  g->linearized = true;
+  return LIODOM_OK;
+}
+
+int graph_check_range(const liodom_graph* g, int first, int n, size_t have, const void* ptr, const char* who) {
+  if (!g || first < 0 || n < 0 || (size_t)first + (size_t)n > have || (n > 0 && !ptr)) {
+    g_last_error = std::string(who) + ": null argument, a negative count, or a range beyond what the graph holds"; return LIODOM_ERR_INVALID_ARG;
+  }
+  return LIODOM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int liodom_graph_create(int max_nodes, int max_edges, liodom_graph_t** out) {
+  using namespace liodom_dev;
+  if (!out) { g_last_error = "liodom_graph_create: null argument"; return LIODOM_ERR_INVALID_ARG; }
+  *out = nullptr;
+  if (max_nodes < 1 || max_nodes > kGraphMaxNodes || max_edges < 1 || max_edges > kGraphMaxEdges) {
+    g_last_error = "liodom_graph_create: max_nodes outside 1 .. 65536 or max_edges outside 1 .. 262144"; return LIODOM_ERR_INVALID_ARG;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    g_last_error = "liodom_graph_create: no HIP device available (this library has no CPU fallback)";
+    return LIODOM_ERR_NO_DEVICE;
+  }
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  liodom_graph* g = new liodom_graph();
+  g->max_nodes = max_nodes; g->max_edges = max_edges; g->device = dev;
+  auto build = [&]() -> int {
+    HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    const size_t N = (size_t)max_nodes, E = (size_t)max_edges;
+    int rc;
+    if ((rc = graph_alloc(g, &g->d_poses, 7 * N)) || (rc = graph_alloc(g, &g->d_cand, 7 * N)) || (rc = graph_alloc(g, &g->d_fixed, N)) || (rc = graph_alloc(g, &g->d_parent, N)) ||
+        (rc = graph_alloc(g, &g->d_offsets, N + 1)) || (rc = graph_alloc(g, &g->d_ei, E)) || (rc = graph_alloc(g, &g->d_ej, E)) ||
+        (rc = graph_alloc(g, &g->d_entries, 2 * E)) || (rc = graph_alloc(g, &g->d_z, 7 * E)) || (rc = graph_alloc(g, &g->d_info, 36 * E)) ||
+        (rc = graph_alloc(g, &g->d_chi2, E)) || (rc = graph_alloc(g, &g->d_gi, 6 * E)) || (rc = graph_alloc(g, &g->d_gj, 6 * E)) ||
+        (rc = graph_alloc(g, &g->d_Hii, 36 * E)) || (rc = graph_alloc(g, &g->d_Hij, 36 * E)) || (rc = graph_alloc(g, &g->d_Hjj, 36 * E)) ||
+        (rc = graph_alloc(g, &g->d_g, 6 * N)) || (rc = graph_alloc(g, &g->d_D, 36 * N)) || (rc = graph_alloc(g, &g->d_Minv, 36 * N)) ||
+        (rc = graph_alloc(g, &g->d_x, 6 * N)) || (rc = graph_alloc(g, &g->d_r, 6 * N)) || (rc = graph_alloc(g, &g->d_p, 6 * N)) ||
+        (rc = graph_alloc(g, &g->d_zv, 6 * N)) || (rc = graph_alloc(g, &g->d_Ap, 6 * N)) || (rc = graph_alloc(g, &g->d_in, 6 * N)) ||
+        (rc = graph_alloc(g, &g->d_sum, 1)) || (rc = graph_alloc(g, &g->d_bad, 1)) || (rc = graph_alloc(g, &g->d_status, 1)))
+      return rc;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return LIODOM_OK;
+  };
+  const int rc = build();
+  if (rc != LIODOM_OK) { graph_free(g); return rc; }
+  *out = g;
+  return LIODOM_OK;
+}
+
+void liodom_graph_destroy(liodom_graph_t* g) { graph_free(g); }
+
+int liodom_graph_reset(liodom_graph_t* g) {
+  if (!g) { g_last_error = "liodom_graph_reset: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  g->poses.clear(); g->fixed.clear(); g->edges.clear();
+  g->uploaded = false; g->linearized = false;
+  return LIODOM_OK;
+}
+
+int liodom_graph_count(liodom_graph_t* g, int32_t* n_nodes, int32_t* n_edges) {
+  if (!g) { g_last_error = "liodom_graph_count: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (n_nodes) *n_nodes = (int32_t)g->fixed.size();
+  if (n_edges) *n_edges = (int32_t)g->edges.size();
+  return LIODOM_OK;
+}
+
+int liodom_graph_add_nodes(liodom_graph_t* g, const double* poses, const int32_t* fixed, int n, int32_t* first) {
+  if (!g || n < 0 || (n > 0 && !poses)) { g_last_error = "liodom_graph_add_nodes: null graph or poses, or a negative count"; return LIODOM_ERR_INVALID_ARG; }
+  for (int k = 0; k < n; k++) {
+    if (const char* why = liodom_dev::graph_pose_refusal(poses + 7 * (size_t)k)) { g_last_error = std::string("liodom_graph_add_nodes: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (g->fixed.size() + (size_t)n > (size_t)g->max_nodes) { g_last_error = "liodom_graph_add_nodes: more nodes than max_nodes"; return LIODOM_ERR_CAPACITY; }
+  if (first) *first = (int32_t)g->fixed.size();
+  if (n == 0) return LIODOM_OK;
+  const size_t at = g->fixed.size();
+  g->poses.resize(7 * (at + (size_t)n));
+  g->fixed.resize(at + (size_t)n);
+  for (int k = 0; k < n; k++) {
+    liodom_dev::graph_pose_normalised(poses + 7 * (size_t)k, &g->poses[7 * (at + (size_t)k)]);
+    g->fixed[at + (size_t)k] = (fixed && fixed[k]) ? 1 : 0;
+  }
+  g->uploaded = false;
+  return LIODOM_OK;
+}
+
+int liodom_graph_add_edges(liodom_graph_t* g, const liodom_graph_edge_t* edges, int n) {
+  if (!g || n < 0 || (n > 0 && !edges)) { g_last_error = "liodom_graph_add_edges: null graph or edges, or a negative count"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  const int N = (int)g->fixed.size();
+  for (int k = 0; k < n; k++) {
+    const char* why = edges[k].reserved != 0 ? "an edge's reserved field is not 0" : liodom_dev::graph_edge_refusal(edges[k].i, edges[k].j, edges[k].z, edges[k].info, N);
+    if (why) { g_last_error = std::string("liodom_graph_add_edges: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  }
+  if (g->edges.size() + (size_t)n > (size_t)g->max_edges) { g_last_error = "liodom_graph_add_edges: more edges than max_edges"; return LIODOM_ERR_CAPACITY; }
+  if (n == 0) return LIODOM_OK;
+  g->edges.reserve(g->edges.size() + (size_t)n);
+  for (int k = 0; k < n; k++) {
+    liodom_graph_edge_t ed = edges[k];
+    liodom_dev::graph_pose_normalised(edges[k].z, ed.z);
+    g->edges.push_back(ed);
+  }
+  g->uploaded = false;
+  return LIODOM_OK;
+}
+
+int liodom_graph_set_fixed(liodom_graph_t* g, int first, int n, const int32_t* fixed) {
+  if (!g) { g_last_error = "liodom_graph_set_fixed: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (int rc = graph_check_range(g, first, n, g->fixed.size(), fixed, "liodom_graph_set_fixed")) return rc;
+  for (int k = 0; k < n; k++) g->fixed[(size_t)first + (size_t)k] = fixed[k] ? 1 : 0;
+  if (n) g->uploaded = false;
+  return LIODOM_OK;
+}
+
+int liodom_graph_get_poses(liodom_graph_t* g, int first, int n, double* poses) {
+  if (!g) { g_last_error = "liodom_graph_get_poses: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (int rc = graph_check_range(g, first, n, g->fixed.size(), poses, "liodom_graph_get_poses")) return rc;
+  if (n) std::memcpy(poses, &g->poses[7 * (size_t)first], sizeof(double) * 7 * (size_t)n);
+  return LIODOM_OK;
+}
+
+int liodom_graph_set_poses(liodom_graph_t* g, int first, int n, const double* poses) {
+  if (!g) { g_last_error = "liodom_graph_set_poses: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (int rc = graph_check_range(g, first, n, g->fixed.size(), poses, "liodom_graph_set_poses")) return rc;
+  for (int k = 0; k < n; k++) {
+    if (const char* why = liodom_dev::graph_pose_refusal(poses + 7 * (size_t)k)) { g_last_error = std::string("liodom_graph_set_poses: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  }
+  for (int k = 0; k < n; k++) liodom_dev::graph_pose_normalised(poses + 7 * (size_t)k, &g->poses[7 * ((size_t)first + (size_t)k)]);
+  if (n) g->uploaded = false;
+  return LIODOM_OK;
+}
+
+int liodom_graph_get_edges(liodom_graph_t* g, int first, int n, liodom_graph_edge_t* edges) {
+  if (!g) { g_last_error = "liodom_graph_get_edges: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (int rc = graph_check_range(g, first, n, g->edges.size(), edges, "liodom_graph_get_edges")) return rc;
+  if (n) std::memcpy(edges, &g->edges[(size_t)first], sizeof(liodom_graph_edge_t) * (size_t)n);
+  return LIODOM_OK;
+}
+
+int liodom_graph_linearize(liodom_graph_t* g, double* chi2_per_edge, double* gradient, double* diag) {
+  if (!g) { g_last_error = "liodom_graph_linearize: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  HIP_TRY(hipSetDevice(g->device));
+  if (int rc = graph_prepare(g)) return rc;
+  const size_t N = g->fixed.size(), E = g->edges.size();
+  std::vector<double> D;
+  if (chi2_per_edge && E) HIP_TRY(hipMemcpyAsync(chi2_per_edge, g->d_chi2, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
+  if (gradient && N) HIP_TRY(hipMemcpyAsync(gradient, g->d_g, sizeof(double) * 6 * N, hipMemcpyDeviceToHost, g->stream));
+  if (diag && N) {
+    D.resize(36 * N);
+    HIP_TRY(hipMemcpy2DAsync(D.data(), sizeof(double) * N, g->d_D, sizeof(double) * (size_t)g->max_nodes, sizeof(double) * N, 36, hipMemcpyDeviceToHost, g->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  if (diag && N) {
+    for (size_t n = 0; n < N; n++)
+      for (size_t k = 0; k < 36; k++) diag[36 * n + k] = D[k * N + n];          // the device keeps the blocks component-major
+  }
+  return LIODOM_OK;
+}
+
+int liodom_graph_multiply(liodom_graph_t* g, double lambda, const double* x, double* y) {
+  using namespace liodom_dev;
+  if (!g) { g_last_error = "liodom_graph_multiply: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  const int N = (int)g->fixed.size();
+  if (N > 0 && (!x || !y)) { g_last_error = "liodom_graph_multiply: null x or y"; return LIODOM_ERR_INVALID_ARG; }
+  if (!(lambda >= 0.0) || !std::isfinite(lambda)) { g_last_error = "liodom_graph_multiply: lambda is negative or not finite"; return LIODOM_ERR_INVALID_ARG; }
+  if (N == 0) return LIODOM_OK;
+  HIP_TRY(hipSetDevice(g->device));
+  if (int rc = graph_prepare(g)) return rc;
+  HIP_TRY(hipMemcpyAsync(g->d_in, x, sizeof(double) * 6 * (size_t)N, hipMemcpyHostToDevice, g->stream));
+  hipLaunchKernelGGL(k_graph_multiply, dim3(graph_blocks(N)), dim3(kGraphThreads), 0, g->stream, N, (long long)g->max_nodes, (long long)g->max_edges,
+                     lambda, g->d_fixed, g->d_offsets, g->d_entries, g->d_ei, g->d_ej, g->d_D, g->d_Hij, g->d_in, g->d_Ap);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(y, g->d_Ap, sizeof(double) * 6 * (size_t)N, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  return LIODOM_OK;
+}
+
+void liodom_graph_options_default(liodom_graph_options_t* opt) {
+  if (!opt) return;
+  opt->max_iterations = 20; opt->max_pcg_iterations = 0;
+  opt->pcg_tolerance = 1e-8; opt->gradient_tolerance = 1e-9; opt->cost_tolerance = 1e-10;
+}
+
+int liodom_graph_optimize(liodom_graph_t* g, const liodom_graph_options_t* opt_in, liodom_graph_report_t* report) {
+  using namespace liodom_dev;
+  if (!g) { g_last_error = "liodom_graph_optimize: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  liodom_graph_options_t opt;
+  liodom_graph_options_default(&opt);
+  if (opt_in) opt = *opt_in;
+  if (opt.max_iterations < 0 || opt.max_pcg_iterations < 0 || !(opt.pcg_tolerance >= 0.0) || !(opt.gradient_tolerance >= 0.0) || !(opt.cost_tolerance >= 0.0)) {
+    g_last_error = "liodom_graph_optimize: an option is negative or not a number"; return LIODOM_ERR_INVALID_ARG;
+  }
+  std::lock_guard<std::mutex> lk(g->mx);
+  const int N = (int)g->fixed.size(), E = (int)g->edges.size();
+  int n_free = 0;
+  for (int n = 0; n < N; n++) n_free += g->fixed[(size_t)n] ? 0 : 1;
+  if (n_free == N) { g_last_error = "liodom_graph_optimize: the graph has no fixed node"; return LIODOM_ERR_INVALID_ARG; }
+  liodom_graph_report_t rep;
+  std::memset(&rep, 0, sizeof(rep));
+  rep.final_lambda = 1e-4;
+  rep.termination = LIODOM_GRAPH_TERM_GRADIENT;
+  HIP_TRY(hipSetDevice(g->device));
+  int rc;
+  if ((rc = graph_upload(g))) return rc;
+  double cost = 0.0;
+  if ((rc = graph_linearize(g, &cost))) return rc;
+  g->linearized = false;                              // (Minv is about to be made for another lambda)
+  rep.initial_cost = rep.final_cost = cost;
+  if (n_free == 0 || E == 0) { if (report) *report = rep; return LIODOM_OK; }
+  const int max_pcg = opt.max_pcg_iterations > 0 ? opt.max_pcg_iterations : std::min(6 * n_free, 65536);
+  double lambda = 1e-4;
+  bool moved = false;                                 // d_poses differs from the host's poses
+  // from here on an error must leave the host copy as it is and the device copy marked stale
+  auto run = [&]() -> int {
+    int pending = -1;                                 // the termination found; one more launch reports max |g| at the poses left
+    while (true) {
+      const int pcg_its = (pending >= 0 || rep.iterations >= opt.max_iterations) ? 0 : max_pcg;
+      if ((rc = graph_gather(g, lambda))) return rc;
+      hipLaunchKernelGGL(k_graph_pcg, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, N, (long long)g->max_nodes, (long long)g->max_edges, lambda,
+                         pcg_its, opt.pcg_tolerance, opt.gradient_tolerance, g->d_fixed, g->d_parent, g->d_poses, g->d_offsets, g->d_entries, g->d_ei, g->d_ej,
+                         g->d_g, g->d_D, g->d_Minv, g->d_Hij, g->d_bad, g->d_x, g->d_r, g->d_p, g->d_zv, g->d_Ap, g->d_status);
+      HIP_TRY(hipGetLastError());
+      GraphPcgStatus st;
+      HIP_TRY(hipMemcpyAsync(&st, g->d_status, sizeof(st), hipMemcpyDeviceToHost, g->stream));
+      HIP_TRY(hipStreamSynchronize(g->stream));
+      rep.max_gradient = st.gmax;
+      if (pending >= 0) { rep.termination = pending; return LIODOM_OK; }
+      if (st.flag == GRAPH_PCG_GRADIENT) { rep.termination = LIODOM_GRAPH_TERM_GRADIENT; return LIODOM_OK; }
+      if (rep.iterations >= opt.max_iterations) { rep.termination = LIODOM_GRAPH_TERM_MAX_ITERATIONS; return LIODOM_OK; }      // (that launch solved nothing)
+      if (st.flag == GRAPH_PCG_BREAKDOWN) { rep.pcg_iterations += st.iterations; rep.termination = LIODOM_GRAPH_TERM_BREAKDOWN; return LIODOM_OK; }
+      rep.pcg_iterations += st.iterations;
+      rep.iterations++;
+      hipLaunchKernelGGL(k_graph_retract, dim3(graph_blocks(N)), dim3(kGraphThreads), 0, g->stream, N, g->d_poses, g->d_fixed, g->d_x, g->d_cand);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_graph_cost, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, g->d_cand, g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_chi2);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_graph_sum, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, E, g->d_chi2, g->d_sum);
+      HIP_TRY(hipGetLastError());
+      double cand = 0.0;
+      HIP_TRY(hipMemcpyAsync(&cand, g->d_sum, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+      HIP_TRY(hipStreamSynchronize(g->stream));
+      if (cand < cost) {                              // (false for a NaN)
+        std::swap(g->d_poses, g->d_cand);
+        moved = true;
+        rep.accepted_steps++;
+        const double decrease = cost != 0.0 ? (cost - cand) / std::fabs(cost) : 0.0;      // (an indefinite Omega can make chi2 negative)
+        lambda = std::max(lambda / 10.0, 1e-12);
+        rep.final_lambda = lambda;
+        if ((rc = graph_linearize(g, &cost))) return rc;          // (the same edges summed in the same order: equal to cand)
+        rep.final_cost = cost;
+        if (decrease <= opt.cost_tolerance) pending = LIODOM_GRAPH_TERM_COST;
+      } else {
+        lambda *= 10.0;
+        rep.final_lambda = lambda;
+        if (lambda > 1e12) { rep.termination = LIODOM_GRAPH_TERM_LAMBDA; return LIODOM_OK; }
+      }
+    }
+  };
+  rc = run();
+  std::vector<double> out;
+  if (rc == LIODOM_OK && moved) {
+    out.resize(7 * (size_t)N);
+    hipError_t e = hipMemcpyAsync(out.data(), g->d_poses, sizeof(double) * out.size(), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    if (e != hipSuccess) { g_last_error = std::string("liodom_graph_optimize: download failed: ") + hipGetErrorString(e); rc = LIODOM_ERR_HIP; }
+  }
+  if (rc != LIODOM_OK) { g->uploaded = false; g->linearized = false; return rc; }
+  if (moved) g->poses.swap(out);
+  if (report) *report = rep;
+  return LIODOM_OK;
+}
+
+}  // extern "C"

@@ -2312,3 +2312,4 @@ int liodom_device_info(liodom_handle_t* h, char* name, int name_cap, int* comput
 }  // extern "C"
 
 #include "liodom_places_host.h"
+#include "liodom_graph_host.h"

@@ -1087,4 +1087,162 @@ LD_HD int lm_update(LmState& st, const double* acc) {
   return lm_propose(st);
 }
 
+// ---------------------------------------------------------------------------------------
+// Pose graph (kernels_graph.h; contract: include/liodom_hip.h "closing loops").  No counterpart in the reference.  Strict FP64,
+// no contraction.  A pose is X = (q, t), world <- frame, [qx qy qz qw tx ty tz], q of unit norm.  An edge (i, j, Z, Omega) says
+// "X_i^-1 o X_j was measured as Z".  D = Z^-1 o X_i^-1 o X_j = (q_d, t_d) with
+//   q_d = conj(q_z) (x) conj(q_i) (x) q_j,   t_d = R_z^T (R_i^T (t_j - t_i) - t_z),
+// and the error is e = [s vec(q_d); t_d], s = +1 for w_d >= 0, else -1: the rotation part is the half-angle quantity of the
+// solver's tangent.  A node moves by delta = (d, dt): q <- [sin|d| d/|d|, cos|d|] (x) q, t <- t + dt (quat_plus).  At delta = 0
+// the factor is [d, 1] to first order, and R <- (I + 2 [d]x) R, so with a = conj(q_z) (x) conj(q_i), u = t_j - t_i,
+// W = R_z^T R_i^T and Q[:, k] = s vec(a (x) [e_k, 0] (x) q_j):
+//   A = de/d(delta_i) = [[-Q, 0], [2 W [u]x, -W]],      B = de/d(delta_j) = [[Q, 0], [0, W]]        (6 x 6, row-major)
+// — exact derivatives, no small-angle shortcut: e is linear in each of (d, 1) and dt at delta = 0.
+// tests/graph_model.py restates all of it in NumPy; tests/test_graph_math_host.py holds this file to it.
+// ---------------------------------------------------------------------------------------
+LD_HD void pg_quat_mul(const double* a, const double* b, double* o) {          // a (x) b
+  o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
+  o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
+  o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
+  o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
+}
+LD_HD void pg_rot3(const double* q, double* R /*9, row-major*/) {              // Eigen::Quaterniond::toRotationMatrix
+  const double x = q[0], y = q[1], z = q[2], w = q[3];
+  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w;
+  const double txx = tx * x, txy = ty * x, txz = tz * x;
+  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
+  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
+}
+// e[6] of one edge; with A and B non-null also the two Jacobians (36 each, row-major)
+LD_HD void graph_edge_error(const double* Xi, const double* Xj, const double* Z, double* e, double* A, double* B) {
+  double Ri[9], Rz[9];
+  pg_rot3(Xi, Ri);
+  pg_rot3(Z, Rz);
+  const double u[3] = {Xj[4] - Xi[4], Xj[5] - Xi[5], Xj[6] - Xi[6]};
+  double m[3];
+  LD_UNROLL
+  for (int r = 0; r < 3; r++) m[r] = (Ri[r] * u[0] + Ri[3 + r] * u[1] + Ri[6 + r] * u[2]) - Z[4 + r];      // R_i^T u - t_z
+  const double ci[4] = {-Xi[0], -Xi[1], -Xi[2], Xi[3]}, cz[4] = {-Z[0], -Z[1], -Z[2], Z[3]};
+  double a[4], qd[4];
+  pg_quat_mul(cz, ci, a);
+  pg_quat_mul(a, Xj, qd);
+  const double s = qd[3] >= 0.0 ? 1.0 : -1.0;
+  LD_UNROLL
+  for (int r = 0; r < 3; r++) {
+    e[r] = s * qd[r];
+    e[3 + r] = Rz[r] * m[0] + Rz[3 + r] * m[1] + Rz[6 + r] * m[2];                                         // R_z^T m
+  }
+  if (!A || !B) return;
+  double W[9];                                                                                             // R_z^T R_i^T
+  LD_UNROLL
+  for (int r = 0; r < 3; r++) {
+    LD_UNROLL
+    for (int c = 0; c < 3; c++) W[r * 3 + c] = Rz[r] * Ri[c * 3] + Rz[3 + r] * Ri[c * 3 + 1] + Rz[6 + r] * Ri[c * 3 + 2];
+  }
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) { A[i] = 0.0; B[i] = 0.0; }
+  LD_UNROLL
+  for (int k = 0; k < 3; k++) {
+    const double ek[4] = {k == 0 ? 1.0 : 0.0, k == 1 ? 1.0 : 0.0, k == 2 ? 1.0 : 0.0, 0.0};
+    double c[4], d[4];
+    pg_quat_mul(a, ek, c);
+    pg_quat_mul(c, Xj, d);
+    LD_UNROLL
+    for (int r = 0; r < 3; r++) { B[r * 6 + k] = s * d[r]; A[r * 6 + k] = -(s * d[r]); }
+  }
+  // 2 W [u]x, column k = 2 W (e_k-th column of [u]x);  [u]x = [[0, -u2, u1], [u2, 0, -u0], [-u1, u0, 0]]
+  const double ux[9] = {0.0, -u[2], u[1], u[2], 0.0, -u[0], -u[1], u[0], 0.0};
+  LD_UNROLL
+  for (int r = 0; r < 3; r++) {
+    LD_UNROLL
+    for (int c = 0; c < 3; c++) {
+      A[(3 + r) * 6 + c] = 2.0 * (W[r * 3] * ux[c] + W[r * 3 + 1] * ux[3 + c] + W[r * 3 + 2] * ux[6 + c]);
+      A[(3 + r) * 6 + 3 + c] = -W[r * 3 + c];
+      B[(3 + r) * 6 + 3 + c] = W[r * 3 + c];
+    }
+  }
+}
+// e^T Omega e (Omega 6 x 6 row-major, summed row by row)
+LD_HD double graph_edge_chi2(const double* e, const double* Om) {
+  double chi2 = 0.0;
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {
+    double s = 0.0;
+    LD_UNROLL
+    for (int c = 0; c < 6; c++) s += Om[r * 6 + c] * e[c];
+    chi2 += e[r] * s;
+  }
+  return chi2;
+}
+// What one edge gives the normal equations: chi2, gi = A^T Omega e, gj = B^T Omega e (6 each), Hii = A^T Omega A, Hij = A^T
+// Omega B, Hjj = B^T Omega B (36 each, row-major; the two diagonal blocks computed as an upper triangle and mirrored).  Entry k
+// of an output lies at out[k * stride]: the kernel writes component-major arrays, a host caller passes stride 1.
+LD_HD void graph_edge_blocks(const double* e, const double* A, const double* B, const double* Om, long long stride, double* chi2,
+                             double* gi, double* gj, double* Hii, double* Hij, double* Hjj) {
+  double Oe[6], OA[36], OB[36];
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {
+    double s = 0.0;
+    LD_UNROLL
+    for (int c = 0; c < 6; c++) s += Om[r * 6 + c] * e[c];
+    Oe[r] = s;
+    LD_UNROLL
+    for (int k = 0; k < 6; k++) {
+      double sa = 0.0, sb = 0.0;
+      LD_UNROLL
+      for (int c = 0; c < 6; c++) { sa += Om[r * 6 + c] * A[c * 6 + k]; sb += Om[r * 6 + c] * B[c * 6 + k]; }
+      OA[r * 6 + k] = sa; OB[r * 6 + k] = sb;
+    }
+  }
+  double x2 = 0.0;
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) x2 += e[r] * Oe[r];
+  *chi2 = x2;
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {
+    double si = 0.0, sj = 0.0;
+    LD_UNROLL
+    for (int k = 0; k < 6; k++) { si += A[k * 6 + r] * Oe[k]; sj += B[k * 6 + r] * Oe[k]; }
+    gi[r * stride] = si; gj[r * stride] = sj;
+    LD_UNROLL
+    for (int c = 0; c < 6; c++) {
+      double sij = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 6; k++) sij += A[k * 6 + r] * OB[k * 6 + c];
+      Hij[(r * 6 + c) * stride] = sij;
+      if (c >= r) {
+        double sii = 0.0, sjj = 0.0;
+        LD_UNROLL
+        for (int k = 0; k < 6; k++) { sii += A[k * 6 + r] * OA[k * 6 + c]; sjj += B[k * 6 + r] * OB[k * 6 + c]; }
+        Hii[(r * 6 + c) * stride] = sii; Hii[(c * 6 + r) * stride] = sii;
+        Hjj[(r * 6 + c) * stride] = sjj; Hjj[(c * 6 + r) * stride] = sjj;
+      }
+    }
+  }
+}
+// X (+) delta: the retraction above, the quaternion brought back to unit norm
+LD_HD void graph_retract(const double* X, const double* delta, double* out) {
+  double q[4];
+  quat_plus(X, delta, q);
+  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  LD_UNROLL
+  for (int k = 0; k < 4; k++) out[k] = q[k] / n;
+  LD_UNROLL
+  for (int k = 0; k < 3; k++) out[4 + k] = X[4 + k] + delta[3 + k];
+}
+// The inverse of D + lambda diag(D) (D 6 x 6 row-major, its upper triangle read); false, inv36 untouched, where that is not
+// positive definite
+LD_HD bool graph_damped_inverse(const double* D36, double lambda, double* inv36) {
+  double H21[21];
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) {
+    LD_UNROLL
+    for (int j = i; j < 6; j++) H21[h_idx(i, j)] = (i == j) ? D36[i * 6 + i] + lambda * D36[i * 6 + i] : D36[i * 6 + j];
+  }
+  return spd_inverse6(H21, inv36);
+}
+
 }  // namespace liodom_dev

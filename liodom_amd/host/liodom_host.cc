@@ -533,6 +533,75 @@ void PlaceDb::importState(const std::vector<uint8_t>& blob) {
   check(liodom_places_import_state(db_, blob.data(), (int64_t)blob.size()), "liodom_places_import_state");
 }
 
+PoseGraph::PoseGraph(int max_nodes, int max_edges) { check(liodom_graph_create(max_nodes, max_edges, &g_), "liodom_graph_create"); }
+PoseGraph::~PoseGraph() { liodom_graph_destroy(g_); }
+
+int PoseGraph::addNode(const Pose& pose, bool fixed) {
+  const double p[7] = {pose.q[0], pose.q[1], pose.q[2], pose.q[3], pose.t[0], pose.t[1], pose.t[2]};
+  const int32_t f = fixed ? 1 : 0;
+  int32_t first = -1;
+  check(liodom_graph_add_nodes(g_, p, &f, 1, &first), "liodom_graph_add_nodes");
+  return first;
+}
+void PoseGraph::addEdge(int i, int j, const Pose& z, const std::array<double, 36>& info, int kind) {
+  liodom_graph_edge_t e;
+  std::memset(&e, 0, sizeof(e));
+  e.i = i; e.j = j; e.kind = kind;
+  const double p[7] = {z.q[0], z.q[1], z.q[2], z.q[3], z.t[0], z.t[1], z.t[2]};
+  std::memcpy(e.z, p, sizeof(p));
+  std::memcpy(e.info, info.data(), sizeof(e.info));
+  check(liodom_graph_add_edges(g_, &e, 1), "liodom_graph_add_edges");
+}
+void PoseGraph::addEdges(const std::vector<liodom_graph_edge_t>& edges) {
+  check(liodom_graph_add_edges(g_, edges.data(), (int)edges.size()), "liodom_graph_add_edges");
+}
+void PoseGraph::setFixed(int node, bool fixed) {
+  const int32_t f = fixed ? 1 : 0;
+  check(liodom_graph_set_fixed(g_, node, 1, &f), "liodom_graph_set_fixed");
+}
+int PoseGraph::nodes() {
+  int32_t n = 0;
+  check(liodom_graph_count(g_, &n, nullptr), "liodom_graph_count");
+  return n;
+}
+int PoseGraph::edges() {
+  int32_t n = 0;
+  check(liodom_graph_count(g_, nullptr, &n), "liodom_graph_count");
+  return n;
+}
+Pose PoseGraph::pose(int node) {
+  double p[7];
+  check(liodom_graph_get_poses(g_, node, 1, p), "liodom_graph_get_poses");
+  Pose out;
+  for (int k = 0; k < 4; k++) out.q[k] = p[k];
+  for (int k = 0; k < 3; k++) out.t[k] = p[4 + k];
+  return out;
+}
+void PoseGraph::setPose(int node, const Pose& pose) {
+  const double p[7] = {pose.q[0], pose.q[1], pose.q[2], pose.q[3], pose.t[0], pose.t[1], pose.t[2]};
+  check(liodom_graph_set_poses(g_, node, 1, p), "liodom_graph_set_poses");
+}
+void PoseGraph::reset() { check(liodom_graph_reset(g_), "liodom_graph_reset"); }
+void PoseGraph::linearize(std::vector<double>* chi2, std::vector<double>* gradient, std::vector<double>* diag) {
+  int32_t n = 0, e = 0;
+  check(liodom_graph_count(g_, &n, &e), "liodom_graph_count");
+  if (chi2) chi2->assign((size_t)e, 0.0);
+  if (gradient) gradient->assign(6 * (size_t)n, 0.0);
+  if (diag) diag->assign(36 * (size_t)n, 0.0);
+  check(liodom_graph_linearize(g_, chi2 ? chi2->data() : nullptr, gradient ? gradient->data() : nullptr, diag ? diag->data() : nullptr), "liodom_graph_linearize");
+}
+std::vector<double> PoseGraph::multiply(const std::vector<double>& x, double lambda) {
+  if (x.size() != 6 * (size_t)nodes()) throw std::invalid_argument("PoseGraph::multiply: x needs 6 entries per node");
+  std::vector<double> y(x.size(), 0.0);
+  check(liodom_graph_multiply(g_, lambda, x.data(), y.data()), "liodom_graph_multiply");
+  return y;
+}
+liodom_graph_report_t PoseGraph::optimize(const liodom_graph_options_t* options) {
+  liodom_graph_report_t rep;
+  check(liodom_graph_optimize(g_, options, &rep), "liodom_graph_optimize");
+  return rep;
+}
+
 MapPager::MapPager(Map* map, int keep_xy, int keep_z, int load_xy, int load_z)
     : map_(map), keep_xy_(keep_xy), keep_z_(keep_z), load_xy_(load_xy), load_z_(load_z) {
   if (!map || load_xy < 0 || load_z < 0 || keep_xy < load_xy || keep_z < load_z) throw std::invalid_argument("MapPager: needs keep >= load >= 0 on both axes");

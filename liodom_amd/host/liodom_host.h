@@ -309,6 +309,33 @@ class PlaceDb {
   double last_key_[7] = {0, 0, 0, 1, 0, 0, 0};
 };
 
+// A pose graph over key frames (liodom_graph_*; no counterpart in the reference): nodes, edges "X_i^-1 o X_j was measured as Z
+// with information Omega", and their optimisation on the device (include/liodom_hip.h "closing loops").  An object of its own: no
+// Engine, no Map.  The loop that feeds and applies it is Python's (liodom_amd/loop.py); this is the thin class.
+class PoseGraph {
+ public:
+  PoseGraph(int max_nodes, int max_edges);
+  ~PoseGraph();
+  PoseGraph(const PoseGraph&) = delete;
+  PoseGraph& operator=(const PoseGraph&) = delete;
+  int addNode(const Pose& pose, bool fixed = false);                                            // the new node's index
+  void addEdge(int i, int j, const Pose& z, const std::array<double, 36>& info, int kind = 0);
+  void addEdges(const std::vector<liodom_graph_edge_t>& edges);
+  void setFixed(int node, bool fixed);
+  int nodes();
+  int edges();
+  Pose pose(int node);
+  void setPose(int node, const Pose& pose);
+  void reset();
+  // chi2 per edge, gradient [6 N], diagonal blocks [N x 36] at the current poses; null: not wanted
+  void linearize(std::vector<double>* chi2, std::vector<double>* gradient, std::vector<double>* diag);
+  std::vector<double> multiply(const std::vector<double>& x, double lambda = 0.0);              // (H + lambda diag H) x
+  liodom_graph_report_t optimize(const liodom_graph_options_t* options = nullptr);              // null: the defaults
+  liodom_graph_t* handle() const { return g_; }
+ private:
+  liodom_graph_t* g_ = nullptr;
+};
+
 // The numbers LaserOdometer::publishOdom puts into nav_msgs/Odometry, geometry_msgs/TwistStamped
 // and the fixed_frame -> base_frame TF (laser_odometry.cc:395-446).
 struct OdometryMsg {

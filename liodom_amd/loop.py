@@ -1,0 +1,153 @@
+"""LoopCloser: key frames, their pose graph, and the correction of a detected revisit.
+
+A host loop over existing calls, as MapPager is: PlacePolicy picks the key frames, a Places database finds the key frame a new one
+was taken near, Map.search_pose measures the pose in the map, a PoseGraph holds the key frames with their odometry and loop edges,
+and close() optimises it and applies the result — the map is rebuilt from the key frames' clouds at the corrected poses, the poses
+in the place database are rewritten, the stream is seeded again.  Nothing is computed here but pose compositions.
+
+What close() cannot do: scans that were no key frames are not in the rebuilt map (their clouds are not kept); a loop measurement
+is as fine as the last search level's step; every loop edge is believed (no robust loss).
+"""
+import math
+
+import numpy as np
+
+from . import api
+
+ODOMETRY_INFO = np.diag([400.0, 400.0, 400.0, 100.0, 100.0, 100.0])     # half-angle rotation first, then translation [1 / m^2]
+LOOP_INFO = np.diag([400.0, 400.0, 400.0, 100.0, 100.0, 100.0])
+
+
+def _qmul(a, b):
+    ax, ay, az, aw = a
+    bx, by, bz, bw = b
+    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by + ay * bw + az * bx - ax * bz,
+                     aw * bz + az * bw + ax * by - ay * bx, aw * bw - ax * bx - ay * by - az * bz])
+
+
+def _pose(p):
+    p = np.array(p, np.float64).reshape(7)
+    p[:4] /= math.sqrt(float(np.sum(p[:4] * p[:4])))
+    return p
+
+
+def compose(X, Y):
+    """X o Y of two poses [qx qy qz qw tx ty tz]."""
+    X, Y = _pose(X), _pose(Y)
+    return np.concatenate([_qmul(X[:4], Y[:4]), api.pose_T34(X)[:, :3] @ Y[4:] + X[4:]])
+
+
+def inverse(X):
+    X = _pose(X)
+    return np.concatenate([[-X[0], -X[1], -X[2], X[3]], -(api.pose_T34(X)[:, :3].T @ X[4:])])
+
+
+def between(Xi, Xj):
+    """X_i^-1 o X_j: what an edge (i, j) of the graph measures."""
+    return compose(inverse(Xi), Xj)
+
+
+class LoopCloser:
+    """LoopCloser(map, places, levels, ...): feed(pose, edges) per scan, close() when loops have been found.
+
+    map, places   the Map the loop measurements are searched in and the Places database of the key frames
+    levels        the grids of Map.search_pose, coarse to fine, run around a match's pose (as Liodom.relocalize's)
+    graph         a PoseGraph (made here with max_nodes / max_edges if None)
+    min_dist, min_yaw   the key-frame policy (PlacePolicy)
+    min_gap       a key frame enters `places` only when min_gap newer key frames exist: a query never returns the recent past
+    k             matches asked of the database per key frame
+    min_fraction  a match becomes a loop edge if its last level scores (hits_r + hits_0) / (2 n_edges) >= min_fraction
+    odometry_info, loop_info   the information matrices (6 x 6, half-angle rotation first) of the two kinds of edge
+    max_update_points          points per Map.update call of the rebuild
+
+    `places` must be this LoopCloser's alone: empty when it is handed in, and filled by feed() only — a place's tag is its key
+    frame's node index, and close() rewrites the poses by it (it raises ValueError, before anything is changed, if the database
+    holds anything else).
+
+    feed returns dict(key_frame, node, loops): loops = [dict(place, node, fraction, pose, match)] of the edges added.
+    key_poses: the key frames' poses as fed (after close(): as corrected); clouds: their edge clouds (sensor frame)."""
+
+    def __init__(self, map, places, levels, graph=None, min_dist=4.0, min_yaw=float("inf"), min_gap=10, k=3, min_fraction=0.5,
+                 odometry_info=ODOMETRY_INFO, loop_info=LOOP_INFO, max_update_points=65536, max_nodes=4096, max_edges=16384):
+        if min_gap < 1 or k < 1:
+            raise ValueError("LoopCloser: needs min_gap >= 1 and k >= 1")
+        self.map, self.places, self.levels = map, places, list(levels)
+        self.graph = api.PoseGraph(max_nodes, max_edges) if graph is None else graph
+        self.policy = api.PlacePolicy(min_dist, min_yaw)
+        self.min_gap, self.k, self.min_fraction = int(min_gap), int(k), float(min_fraction)
+        self.odometry_info = np.array(odometry_info, np.float64).reshape(6, 6)
+        self.loop_info = np.array(loop_info, np.float64).reshape(6, 6)
+        self.max_update_points = int(max_update_points)
+        self.key_poses, self.clouds = [], []
+        self.inserted = 0                # key frames 0 .. inserted - 1 are in `places`
+        self.loops = []                  # (place node, node) of every loop edge
+        self.last_pose = None            # the last pose fed, key frame or not
+
+    def feed(self, pose, edges):
+        pose = _pose(pose)
+        self.last_pose = pose
+        if not self.policy.feed(pose):
+            return dict(key_frame=False, node=None, loops=[])
+        edges = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
+        node = self.graph.add_nodes(pose[None], [1 if not self.key_poses else 0])
+        if self.key_poses:
+            self.graph.add_edges(api.graph_edges([node - 1], [node], [between(self.key_poses[-1], pose)], self.odometry_info, kind=0))
+        self.key_poses.append(pose)
+        self.clouds.append(edges.copy())
+        # lagged insertion: only key frames with min_gap newer ones behind them are places
+        while self.inserted + self.min_gap <= node:
+            self.places.add(self.clouds[self.inserted], self.key_poses[self.inserted], id=self.inserted)
+            self.inserted += 1
+        loops = []
+        if self.inserted > 0 and edges.shape[0] > 0 and self.levels:
+            seen = set()
+            for m in self.places.query([edges], self.k)[0]:
+                place = int(m["id"])
+                if m["index"] < 0 or place in seen:
+                    continue
+                seen.add(place)
+                found, results = api.Liodom._search_levels(self.map, edges, m["pose"], self.levels)
+                fraction = (results[-1]["hits_r"] + results[-1]["hits_0"]) / (2.0 * edges.shape[0])
+                if not fraction >= self.min_fraction:
+                    continue
+                self.graph.add_edges(api.graph_edges([place], [node], [between(m["place_pose"], found)], self.loop_info, kind=1))
+                self.loops.append((place, node))
+                loops.append(dict(place=place, node=node, fraction=fraction, pose=np.array(found, np.float64), match=m))
+        return dict(key_frame=True, node=node, loops=loops)
+
+    def close(self, handle=None, stream=0, reader_cells=None, **options):
+        """Optimises the graph (the first key frame is fixed; **options: make_graph_options) and applies the result:
+          map      reset and rebuilt from the key frames' clouds at the corrected poses; with reader_cells = (cells_xy, cells_z) the
+                   handle's stream is detached from it before (attach_mapper(None)) and attached as its reader again after
+          places   the poses of the database rewritten (export_state -> parse_place_state -> build_place_state -> import_state)
+          stream   with a handle: seeded (seed_stream) at the corrected pose of the last scan fed — the last key frame's corrected
+                   pose composed with the odometry since
+        Returns dict(report, before [K, 7], after [K, 7], pose = the corrected current pose)."""
+        if not self.key_poses:
+            raise ValueError("LoopCloser.close: no key frame yet")
+        before = np.stack(self.key_poses)
+        st = api.parse_place_state(self.places.export_state()) if self.inserted else None
+        if (st["count"] if st else self.places.count()) != self.inserted or (st and list(st["ids"]) != list(range(self.inserted))):
+            raise ValueError("LoopCloser.close: the place database holds places that feed() did not add")
+        report = self.graph.optimize(**options)
+        after = self.graph.poses()
+        current = compose(after[-1], between(before[-1], self.last_pose))
+        if handle is not None and reader_cells is not None:
+            handle.attach_mapper(None, stream=stream)
+        self.map.reset()
+        chunk = max(1, min(self.max_update_points, int(getattr(self.map, "max_update_points", self.max_update_points))))
+        for cloud, pose in zip(self.clouds, after):
+            T = api.pose_T34(pose)
+            for at in range(0, cloud.shape[0], chunk):
+                self.map.update(cloud[at:at + chunk], T)
+        if handle is not None and reader_cells is not None:
+            handle.attach_map_reader(self.map, reader_cells[0], reader_cells[1], stream=stream)
+        if self.inserted:
+            poses = np.stack([after[int(i)] for i in st["ids"]])
+            self.places.import_state(api.build_place_state(st["geometry"], st["desc"], st["ids"], poses, st["bits"]))
+        if handle is not None:
+            handle.seed_stream(current, stream=stream)
+        self.key_poses = [p.copy() for p in after]
+        self.last_pose = current
+        self.policy.last = [float(v) for v in after[-1]]
+        return dict(report=report, before=before, after=after, pose=current)
