@@ -907,14 +907,15 @@ int liodom_places_import_state(liodom_places_t* db, const void* blob, int64_t by
  *       memory is taken here, about 1.3 KiB per edge and 1 KiB per node of capacity.  The solve is one launch of one workgroup
  *       per step, and nothing but max_pcg_iterations bounds how long it runs: about 60 us per iteration up to 1 024 nodes,
  *       1.5 ms at 16 384 (MI355X), so a step of a graph of that size can take seconds and one at full capacity minutes.
- *   liodom_graph_reset        no nodes, no edges; capacities and allocations are kept.
+ *   liodom_graph_reset        no nodes, no edges; capacities and allocations are kept, and so is the table of losses
+ *       (liodom_graph_set_loss): it is a setting of the graph, like its capacities.
  *   liodom_graph_count        *n_nodes, *n_edges (either optional).
  *   liodom_graph_add_nodes    appends n poses (n x 7); fixed[k] != 0 (optional, NULL: all free) fixes node k.  *first (optional) =
  *       the index of the first one; indices count up from 0 in the order of adding.
- *   liodom_graph_add_edges    appends n edge records.  kind is the caller's (0 odometry, 1 loop by convention; nothing reads it);
- *       reserved must be 0.
+ *   liodom_graph_add_edges    appends n edge records.  kind is the caller's (0 odometry, 1 loop by convention; it selects the
+ *       edge's loss, see "robust losses" below, and nothing else reads it); reserved must be 0.  An edge is active when added.
  *   liodom_graph_set_fixed / _get_poses / _set_poses   nodes first .. first + n - 1.
- *   liodom_graph_get_edges    edges first .. first + n - 1, as stored (Z's quaternion normalised).
+ *   liodom_graph_get_edges    edges first .. first + n - 1, as stored (Z's quaternion normalised), inactive ones too.
  *   liodom_graph_linearize    at the current poses: chi2_per_edge[n_edges], gradient[6 n_nodes] (0 for fixed nodes),
  *       diag[n_nodes x 36] (each node's 6 x 6 block of H, row-major; also for fixed nodes).  Every output is optional.
  *   liodom_graph_multiply     y = (H + lambda diag H) x at the current poses, x and y 6 n_nodes each; rows of fixed nodes are 0
@@ -928,9 +929,35 @@ int liodom_places_import_state(liodom_places_t* db, const void* blob, int64_t by
  *       definite: an information matrix that is not).  The poses are those of the last accepted step.  opt NULL: the defaults;
  *       report optional.  A graph without a fixed node: LIODOM_ERR_INVALID_ARG.  A graph without a free node or without an edge
  *       returns at once (LIODOM_GRAPH_TERM_GRADIENT, 0 iterations).
+ *
+ * Robust losses and switched-off edges (all opt-in: a graph on which none of these calls is made computes what it did before
+ * they existed, byte for byte).  With s = e^T Omega e of an edge, a loss rho with scale c > 0 replaces s in the cost, and
+ * w = rho'(s) weights the edge in g and H (first-order IRLS: no second-order term).  Every rho is concave in s, so the weighted
+ * quadratic lies above the cost and touches it at the current poses: a large enough lambda always finds a decrease, and the
+ * accept / reject rule of liodom_graph_optimize stays sound.
+ *     LIODOM_GRAPH_LOSS_NONE 0            rho = s                                       w = 1
+ *     LIODOM_GRAPH_LOSS_HUBER 1           rho = s if s <= c^2, else 2 c sqrt(s) - c^2   w = 1 if s <= c^2, else c / sqrt(s)
+ *     LIODOM_GRAPH_LOSS_CAUCHY 2          rho = c^2 log1p(s / c^2)                      w = 1 / (1 + s / c^2)
+ *     LIODOM_GRAPH_LOSS_GEMAN_MCCLURE 3   rho = s c^2 / (c^2 + s)                       w = (c^2 / (c^2 + s))^2
+ * c is in units of sqrt(chi2): it must exceed what honest drift produces on a true edge, or a true edge is down-weighted with
+ * the false ones (DESIGN.md §3 "Closing loops" has a designed graph on which Geman-McClure with c = 3 rejects every true loop).
+ *   liodom_graph_set_loss / _get_loss   the graph keeps a table of (loss, scale) over kind 0 .. 15, all NONE at first; an edge
+ *       whose kind is outside 0 .. 15 is always quadratic.  The scale is not read for NONE (it is then stored and returned as
+ *       0).  _get_loss: either output optional.  liodom_graph_reset keeps the table.
+ *   liodom_graph_set_edge_active / _get_edge_active   edges first .. first + n - 1, active[k] != 0: active.  An inactive edge
+ *       gives nothing to the cost, g, H, a node's degree or the preconditioner's chain: a free node whose edges are all inactive
+ *       is a node without edges (identity block, it stays where it is), and a node hangs on an edge (n - 1, n) only if that edge
+ *       is active.
+ *   liodom_graph_edge_weights   rho[n_edges] and weight[n_edges] at the current poses, either optional; both 0 for an inactive edge.
+ *   liodom_graph_linearize    chi2_per_edge stays the raw s, for inactive edges too; gradient and diag are the weighted ones.
+ *   liodom_graph_multiply     uses the weighted blocks.
+ *   liodom_graph_optimize     the cost is the sum of rho over the active edges — in the accept test, initial_cost, final_cost
+ *       and cost_tolerance —, max_gradient is that of the weighted g, and "without an edge" above reads "without an active edge".
+ * Sums stay in an order that depends on the graph alone: equal graphs with equal settings give equal bytes.
  * LIODOM_ERR_INVALID_ARG, graph untouched: a null where one is required, a negative count, a range beyond the nodes or edges, a
  * non-finite pose or Z, | |q| - 1 | > 1e-6, an edge with i == j or an index that is no node, reserved != 0, an Omega with a
- * non-finite entry or one that is not symmetric bit for bit, options out of range (a negative count or tolerance, or a NaN).
+ * non-finite entry or one that is not symmetric bit for bit, options out of range (a negative count or tolerance, or a NaN),
+ * a loss kind outside 0 .. 15, an unknown loss, a scale that is not finite and > 0 (with a loss other than NONE).
  * LIODOM_ERR_CAPACITY, graph untouched: more nodes than max_nodes or more edges than max_edges. */
 typedef struct liodom_graph liodom_graph_t;
 typedef struct liodom_graph_edge_t {
@@ -947,8 +974,12 @@ typedef struct liodom_graph_options_t {
 #define LIODOM_GRAPH_TERM_MAX_ITERATIONS 2
 #define LIODOM_GRAPH_TERM_LAMBDA 3
 #define LIODOM_GRAPH_TERM_BREAKDOWN 4
+#define LIODOM_GRAPH_LOSS_NONE 0
+#define LIODOM_GRAPH_LOSS_HUBER 1
+#define LIODOM_GRAPH_LOSS_CAUCHY 2
+#define LIODOM_GRAPH_LOSS_GEMAN_MCCLURE 3
 typedef struct liodom_graph_report_t {
-  double initial_cost, final_cost;   /* chi2 at the poses the call found and at those it left */
+  double initial_cost, final_cost;   /* chi2 (with a loss: the sum of rho) at the poses the call found and at those it left */
   double max_gradient;               /* max |g| at the poses it left */
   double final_lambda;
   int32_t iterations;                /* steps tried */
@@ -971,6 +1002,11 @@ int liodom_graph_linearize(liodom_graph_t* g, double* chi2_per_edge, double* gra
 int liodom_graph_multiply(liodom_graph_t* g, double lambda, const double* x, double* y);
 void liodom_graph_options_default(liodom_graph_options_t* opt);
 int liodom_graph_optimize(liodom_graph_t* g, const liodom_graph_options_t* opt, liodom_graph_report_t* report);
+int liodom_graph_set_loss(liodom_graph_t* g, int kind, int loss, double scale);
+int liodom_graph_get_loss(liodom_graph_t* g, int kind, int32_t* loss /*optional*/, double* scale /*optional*/);
+int liodom_graph_set_edge_active(liodom_graph_t* g, int first, int n, const int32_t* active);
+int liodom_graph_get_edge_active(liodom_graph_t* g, int first, int n, int32_t* active);
+int liodom_graph_edge_weights(liodom_graph_t* g, double* rho /*optional, [n_edges]*/, double* weight /*optional, [n_edges]*/);
 
 #ifdef __cplusplus
 }

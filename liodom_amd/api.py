@@ -912,6 +912,16 @@ def load():
     L.liodom_graph_options_default.argtypes = [C.POINTER(GraphOptions)]
     L.liodom_graph_optimize.restype = C.c_int
     L.liodom_graph_optimize.argtypes = [vp, C.POINTER(GraphOptions), C.POINTER(GraphReport)]
+    L.liodom_graph_set_loss.restype = C.c_int
+    L.liodom_graph_set_loss.argtypes = [vp, C.c_int, C.c_int, C.c_double]
+    L.liodom_graph_get_loss.restype = C.c_int
+    L.liodom_graph_get_loss.argtypes = [vp, C.c_int, ip, dp]
+    L.liodom_graph_set_edge_active.restype = C.c_int
+    L.liodom_graph_set_edge_active.argtypes = [vp, C.c_int, C.c_int, ip]
+    L.liodom_graph_get_edge_active.restype = C.c_int
+    L.liodom_graph_get_edge_active.argtypes = [vp, C.c_int, C.c_int, ip]
+    L.liodom_graph_edge_weights.restype = C.c_int
+    L.liodom_graph_edge_weights.argtypes = [vp, dp, dp]
     _lib = L
     return L
 
@@ -967,6 +977,8 @@ EXPORTED_SYMBOLS = [
     "liodom_graph_create", "liodom_graph_destroy", "liodom_graph_reset", "liodom_graph_count", "liodom_graph_add_nodes",
     "liodom_graph_add_edges", "liodom_graph_set_fixed", "liodom_graph_get_poses", "liodom_graph_set_poses", "liodom_graph_get_edges",
     "liodom_graph_linearize", "liodom_graph_multiply", "liodom_graph_options_default", "liodom_graph_optimize",
+    "liodom_graph_set_loss", "liodom_graph_get_loss", "liodom_graph_set_edge_active", "liodom_graph_get_edge_active",
+    "liodom_graph_edge_weights",
 ]
 
 
@@ -1957,6 +1969,9 @@ def graph_edges(i, j, z, info, kind=0):
     return out
 
 
+GRAPH_LOSSES = ("none", "huber", "cauchy", "geman_mcclure")      # LIODOM_GRAPH_LOSS_*
+
+
 class PoseGraph:
     """liodom_graph_t: a pose graph over key frames — nodes [qx qy qz qw tx ty tz], free or fixed, and edges "X_i^-1 o X_j was
     measured as z with information info" — linearised and optimised on the device (include/liodom_hip.h "closing loops").
@@ -2052,3 +2067,38 @@ class PoseGraph:
         d = {k: getattr(r, k) for k, _ in GraphReport._fields_}
         d["termination"] = GRAPH_TERMINATIONS[r.termination]
         return d
+
+    def set_loss(self, kind, loss, scale=1.0):
+        """The robust loss of the edges of `kind` (0 .. 15): loss one of GRAPH_LOSSES or its number, scale c > 0 in units of
+        sqrt(chi2) (liodom_graph_set_loss).  reset() keeps it."""
+        if isinstance(loss, str):
+            if loss not in GRAPH_LOSSES:
+                raise ValueError("unknown loss %r (one of %s)" % (loss, ", ".join(GRAPH_LOSSES)))
+            loss = GRAPH_LOSSES.index(loss)
+        self._chk(self._L.liodom_graph_set_loss(self.h, int(kind), int(loss), float(scale)))
+
+    def loss(self, kind):
+        """(name, scale) of the loss set on `kind`; the scale of "none" is 0."""
+        l, c = C.c_int32(), C.c_double()
+        self._chk(self._L.liodom_graph_get_loss(self.h, int(kind), C.byref(l), C.byref(c)))
+        return GRAPH_LOSSES[l.value], c.value
+
+    def set_edge_active(self, first, active):
+        """Switches edges first .. first + len(active) - 1 on (true) or off: an inactive edge stays in edges() and gives nothing
+        to the cost, the gradient, H, a node's degree or the preconditioner's chain."""
+        a = np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, dtype=np.int32)
+        self._chk(self._L.liodom_graph_set_edge_active(self.h, int(first), a.shape[0], _ip(a)))
+
+    def edge_active(self, first=0, n=None):
+        n = self.count()[1] - int(first) if n is None else int(n)
+        out = np.zeros(max(n, 1), np.int32)
+        self._chk(self._L.liodom_graph_get_edge_active(self.h, int(first), n, _ip(out)))
+        return out[:n] != 0
+
+    def edge_weights(self):
+        """At the current poses -> (rho (E,), weight (E,)): the loss of each edge's chi2 and its derivative, the factor on the
+        edge in the gradient and H; both 0 for an inactive edge."""
+        E = self.count()[1]
+        rho, w = np.zeros(max(E, 1)), np.zeros(max(E, 1))
+        self._chk(self._L.liodom_graph_edge_weights(self.h, _dp(rho), _dp(w)))
+        return rho[:E], w[:E]

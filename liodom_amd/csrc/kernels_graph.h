@@ -11,6 +11,8 @@
 //                       preconditioner is block-Jacobi in the coordinates of the odometry chain ("the preconditioner" below).
 //   k_graph_multiply    y = (H + lambda diag H) x by node rows, the row code of k_graph_pcg as a launch of its own
 //   k_graph_retract / k_graph_cost / k_graph_sum   the candidate poses, their chi2 per edge, and a sum in a fixed order
+//   k_graph_linearize_robust / k_graph_cost_robust   the same two with a robust loss per edge and edges that are switched off (at
+//                       the end of this file); launched only where a graph asks for either
 //
 // Fixed nodes: delta = 0; their rows and columns drop out (gradient 0, inverse block 0, skipped as a neighbour).  A free node
 // without edges: its block counts as the identity, its gradient is 0, it stays where it is.
@@ -497,6 +499,63 @@ __global__ __launch_bounds__(kGraphPcgThreads) void k_graph_sum(int n, const dou
   for (int i = (int)threadIdx.x; i < n; i += kGraphPcgThreads) s[0] += in[i];
   graph_block_sum<1>(s, sh);
   if (threadIdx.x == 0) *out = s[0];
+}
+
+
+// The robust instances (a loss on some edge's kind, or an edge switched off; the host launches k_graph_linearize and k_graph_cost
+// otherwise: they are what they were before a loss existed, and these two stand after every other kernel so that nothing before
+// them moves in the code object).  code[e] is the edge's loss (kGraphLoss*) or kGraphLossInactive, scale[e] its
+// c; the host derives both from the graph's table and flags.  Per edge: the raw s = e^T Omega e in chi2, rho(s) and w = rho'(s);
+// w multiplies the finished entries of the five blocks at the store (graph_edge_blocks_t), so code 0 — or w = 1 — gives the
+// quadratic kernel's bytes.  An inactive edge: s, rho = w = 0, and nothing else — no node's list names it, its blocks are never read.
+__global__ __launch_bounds__(kGraphThreads) void k_graph_linearize_robust(int n_edges, long long edge_cap, const double* __restrict__ poses,
+                                                                          const int* __restrict__ ei, const int* __restrict__ ej,
+                                                                          const double* __restrict__ z, const double* __restrict__ info,
+                                                                          const int* __restrict__ code, const double* __restrict__ scale,
+                                                                          double* __restrict__ chi2, double* __restrict__ rho,
+                                                                          double* __restrict__ w, double* __restrict__ gi,
+                                                                          double* __restrict__ gj, double* __restrict__ Hii,
+                                                                          double* __restrict__ Hij, double* __restrict__ Hjj) {
+  const int e = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
+  if (e >= n_edges) return;
+  double Xi[7], Xj[7], Z[7], Om[36], err[6], A[36], B[36];
+  const double* pi = poses + 7ll * ei[e];
+  const double* pj = poses + 7ll * ej[e];
+#pragma unroll
+  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * e + k]; }
+#pragma unroll
+  for (int k = 0; k < 36; k++) Om[k] = info[36ll * e + k];
+  const int ce = code[e];
+  if (ce == kGraphLossInactive) {
+    graph_edge_error(Xi, Xj, Z, err, nullptr, nullptr);
+    chi2[e] = graph_edge_chi2(err, Om);
+    rho[e] = 0.0; w[e] = 0.0;
+    return;
+  }
+  graph_edge_error(Xi, Xj, Z, err, A, B);
+  graph_edge_blocks_t<true>(err, A, B, Om, edge_cap, ce, scale[e], chi2 + e, rho + e, w + e, gi + e, gj + e, Hii + e, Hij + e, Hjj + e);
+}
+
+__global__ __launch_bounds__(kGraphThreads) void k_graph_cost_robust(int n_edges, const double* __restrict__ poses, const int* __restrict__ ei,
+                                                                     const int* __restrict__ ej, const double* __restrict__ z,
+                                                                     const double* __restrict__ info, const int* __restrict__ code,
+                                                                     const double* __restrict__ scale, double* __restrict__ chi2,
+                                                                     double* __restrict__ rho, double* __restrict__ w) {
+  const int e = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
+  if (e >= n_edges) return;
+  double Xi[7], Xj[7], Z[7], Om[36], err[6];
+  const double* pi = poses + 7ll * ei[e];
+  const double* pj = poses + 7ll * ej[e];
+#pragma unroll
+  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * e + k]; }
+#pragma unroll
+  for (int k = 0; k < 36; k++) Om[k] = info[36ll * e + k];
+  graph_edge_error(Xi, Xj, Z, err, nullptr, nullptr);
+  const double s = graph_edge_chi2(err, Om);
+  const int ce = code[e];
+  double r = 0.0, wt = 0.0;
+  if (ce != kGraphLossInactive) graph_loss(ce, scale[e], s, &r, &wt);
+  chi2[e] = s; rho[e] = r; w[e] = wt;
 }
 
 }  // namespace liodom_dev

@@ -6,6 +6,11 @@
 // leaves untouched.  The device copy and the CSR are made again, before the next launch, whenever the host copy has changed.
 // The Levenberg-Marquardt loop runs here around the launches; per step tried: k_graph_gather, k_graph_pcg, k_graph_retract,
 // k_graph_cost, k_graph_sum, and after an accepted one k_graph_linearize, k_graph_sum — whatever the number of PCG iterations.
+//
+// Robust losses and switched-off edges: the table of losses per kind and the active flags are part of the host copy.  At upload
+// every edge gets a code (its kind's loss, or "inactive") and a scale, and the CSR and the chain are made of the active edges.
+// If every code is 0 the quadratic kernels run, as they did before a loss existed; otherwise their robust twins, which also
+// write rho and w per edge, and the cost that is summed is rho.
 #pragma once
 #include <mutex>
 #include <vector>
@@ -22,6 +27,11 @@ struct liodom_graph {
   std::vector<double> poses;                  // [n][7]
   std::vector<int32_t> fixed;                 // [n]
   std::vector<liodom_graph_edge_t> edges;
+  std::vector<int32_t> active;                // [n_edges]
+  int32_t loss[liodom_dev::kGraphLossKinds] = {};        // per edge kind 0 .. 15; kept by reset
+  double loss_scale[liodom_dev::kGraphLossKinds] = {};
+  bool robust = false;                        // (made at upload) some edge's code is not 0: the robust kernels run
+  int n_active = 0;                           // (made at upload)
   bool uploaded = false;                      // the device holds this graph (poses in d_poses) and its CSR
   bool linearized = false;                    // ... and its linearisation (per-edge blocks, D, g; Minv for d_lambda)
   // device
@@ -29,6 +39,8 @@ struct liodom_graph {
   int *d_fixed = nullptr, *d_parent = nullptr, *d_ei = nullptr, *d_ej = nullptr, *d_offsets = nullptr, *d_entries = nullptr, *d_bad = nullptr;
   double *d_chi2 = nullptr, *d_gi = nullptr, *d_gj = nullptr, *d_Hii = nullptr, *d_Hij = nullptr, *d_Hjj = nullptr;
   double *d_g = nullptr, *d_D = nullptr, *d_Minv = nullptr;
+  int* d_code = nullptr;
+  double *d_scale = nullptr, *d_rho = nullptr, *d_w = nullptr;
   double *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_zv = nullptr, *d_Ap = nullptr, *d_in = nullptr, *d_sum = nullptr;
   liodom_dev::GraphPcgStatus* d_status = nullptr;
 };
@@ -58,23 +70,28 @@ inline unsigned graph_blocks(int n) { return (unsigned)std::max(1, (n + liodom_d
 int graph_upload(liodom_graph* g) {
   if (g->uploaded) return LIODOM_OK;
   const int N = (int)g->fixed.size(), E = (int)g->edges.size();
-  std::vector<int32_t> ei((size_t)E), ej((size_t)E), offsets, entries;
-  std::vector<double> z(7 * (size_t)E), info(36 * (size_t)E);
+  std::vector<int32_t> ei((size_t)E), ej((size_t)E), offsets, entries, parent, code((size_t)E);
+  std::vector<double> z(7 * (size_t)E), info(36 * (size_t)E), scale((size_t)E);
+  bool robust = false;
+  int n_active = 0;
   for (int e = 0; e < E; e++) {
     const liodom_graph_edge_t& ed = g->edges[(size_t)e];
     ei[(size_t)e] = ed.i; ej[(size_t)e] = ed.j;
     std::memcpy(&z[7 * (size_t)e], ed.z, sizeof(ed.z));
     std::memcpy(&info[36 * (size_t)e], ed.info, sizeof(ed.info));
+    const bool has_loss = ed.kind >= 0 && ed.kind < liodom_dev::kGraphLossKinds;      // (any other kind is quadratic)
+    code[(size_t)e] = !g->active[(size_t)e] ? liodom_dev::kGraphLossInactive : has_loss ? g->loss[ed.kind] : liodom_dev::kGraphLossNone;
+    scale[(size_t)e] = has_loss && g->loss[ed.kind] != liodom_dev::kGraphLossNone ? g->loss_scale[ed.kind] : 1.0;
+    robust = robust || code[(size_t)e] != liodom_dev::kGraphLossNone;
+    n_active += g->active[(size_t)e] ? 1 : 0;
   }
-  if (!liodom_dev::graph_build_csr(ei.data(), ej.data(), E, N, &offsets, &entries)) {
+  if (!liodom_dev::graph_build_csr(ei.data(), ej.data(), E, N, &offsets, &entries, g->active.data())) {
     g_last_error = "liodom_graph: an edge names a node that does not exist"; return LIODOM_ERR_INVALID_ARG;      // (checked when it was added)
   }
-  // the chain the preconditioner works along (kernels_graph.h): a free node n hangs on the first edge (n - 1, n)
-  std::vector<int32_t> parent((size_t)N, -1);
-  for (int e = E - 1; e >= 0; e--) {
-    if (ej[(size_t)e] == ei[(size_t)e] + 1 && !g->fixed[(size_t)ej[(size_t)e]]) parent[(size_t)ej[(size_t)e]] = e;
-  }
+  // the chain the preconditioner works along (kernels_graph.h): a free node n hangs on the first active edge (n - 1, n)
+  liodom_dev::graph_chain_parents(ei.data(), ej.data(), E, g->fixed.data(), N, g->active.data(), &parent);
   g->linearized = false;
+  g->robust = robust; g->n_active = n_active;
   if (N) {
     HIP_TRY(hipMemcpyAsync(g->d_parent, parent.data(), sizeof(int) * (size_t)N, hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipMemcpyAsync(g->d_poses, g->poses.data(), sizeof(double) * 7 * (size_t)N, hipMemcpyHostToDevice, g->stream));
@@ -84,7 +101,11 @@ int graph_upload(liodom_graph* g) {
   if (E) {
     HIP_TRY(hipMemcpyAsync(g->d_ei, ei.data(), sizeof(int) * (size_t)E, hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipMemcpyAsync(g->d_ej, ej.data(), sizeof(int) * (size_t)E, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(g->d_entries, entries.data(), sizeof(int) * 2 * (size_t)E, hipMemcpyHostToDevice, g->stream));
+    if (!entries.empty()) HIP_TRY(hipMemcpyAsync(g->d_entries, entries.data(), sizeof(int) * entries.size(), hipMemcpyHostToDevice, g->stream));
+    if (robust) {
+      HIP_TRY(hipMemcpyAsync(g->d_code, code.data(), sizeof(int) * (size_t)E, hipMemcpyHostToDevice, g->stream));
+      HIP_TRY(hipMemcpyAsync(g->d_scale, scale.data(), sizeof(double) * (size_t)E, hipMemcpyHostToDevice, g->stream));
+    }
     HIP_TRY(hipMemcpyAsync(g->d_z, z.data(), sizeof(double) * z.size(), hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipMemcpyAsync(g->d_info, info.data(), sizeof(double) * info.size(), hipMemcpyHostToDevice, g->stream));
   }
@@ -93,16 +114,22 @@ int graph_upload(liodom_graph* g) {
   return LIODOM_OK;
 }
 
-// per-edge quantities at d_poses, and *cost = their chi2 summed (enqueued and waited for)
+// per-edge quantities at d_poses, and *cost = their chi2 — with a loss or an edge switched off: their rho — summed (enqueued and
+// waited for)
 int graph_linearize(liodom_graph* g, double* cost) {
   using namespace liodom_dev;
   const int E = (int)g->edges.size();
-  if (E) {
+  if (E && g->robust) {
+    hipLaunchKernelGGL(k_graph_linearize_robust, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, (long long)g->max_edges, g->d_poses,
+                       g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_code, g->d_scale, g->d_chi2, g->d_rho, g->d_w, g->d_gi, g->d_gj, g->d_Hii,
+                       g->d_Hij, g->d_Hjj);
+    HIP_TRY(hipGetLastError());
+  } else if (E) {
     hipLaunchKernelGGL(k_graph_linearize, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, (long long)g->max_edges, g->d_poses,
                        g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_chi2, g->d_gi, g->d_gj, g->d_Hii, g->d_Hij, g->d_Hjj);
     HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_graph_sum, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, E, g->d_chi2, g->d_sum);
+  hipLaunchKernelGGL(k_graph_sum, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, E, g->robust ? g->d_rho : g->d_chi2, g->d_sum);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(cost, g->d_sum, sizeof(double), hipMemcpyDeviceToHost, g->stream));
   HIP_TRY(hipStreamSynchronize(g->stream));
@@ -171,6 +198,7 @@ int liodom_graph_create(int max_nodes, int max_edges, liodom_graph_t** out) {
         (rc = graph_alloc(g, &g->d_g, 6 * N)) || (rc = graph_alloc(g, &g->d_D, 36 * N)) || (rc = graph_alloc(g, &g->d_Minv, 36 * N)) ||
         (rc = graph_alloc(g, &g->d_x, 6 * N)) || (rc = graph_alloc(g, &g->d_r, 6 * N)) || (rc = graph_alloc(g, &g->d_p, 6 * N)) ||
         (rc = graph_alloc(g, &g->d_zv, 6 * N)) || (rc = graph_alloc(g, &g->d_Ap, 6 * N)) || (rc = graph_alloc(g, &g->d_in, 6 * N)) ||
+        (rc = graph_alloc(g, &g->d_code, E)) || (rc = graph_alloc(g, &g->d_scale, E)) || (rc = graph_alloc(g, &g->d_rho, E)) || (rc = graph_alloc(g, &g->d_w, E)) ||
         (rc = graph_alloc(g, &g->d_sum, 1)) || (rc = graph_alloc(g, &g->d_bad, 1)) || (rc = graph_alloc(g, &g->d_status, 1)))
       return rc;
     HIP_TRY(hipStreamSynchronize(g->stream));
@@ -187,7 +215,7 @@ void liodom_graph_destroy(liodom_graph_t* g) { graph_free(g); }
 int liodom_graph_reset(liodom_graph_t* g) {
   if (!g) { g_last_error = "liodom_graph_reset: null graph"; return LIODOM_ERR_INVALID_ARG; }
   std::lock_guard<std::mutex> lk(g->mx);
-  g->poses.clear(); g->fixed.clear(); g->edges.clear();
+  g->poses.clear(); g->fixed.clear(); g->edges.clear(); g->active.clear();        // (the loss table is a setting: it stays)
   g->uploaded = false; g->linearized = false;
   return LIODOM_OK;
 }
@@ -236,6 +264,7 @@ int liodom_graph_add_edges(liodom_graph_t* g, const liodom_graph_edge_t* edges, 
     liodom_dev::graph_pose_normalised(edges[k].z, ed.z);
     g->edges.push_back(ed);
   }
+  g->active.resize(g->edges.size(), 1);
   g->uploaded = false;
   return LIODOM_OK;
 }
@@ -317,6 +346,65 @@ int liodom_graph_multiply(liodom_graph_t* g, double lambda, const double* x, dou
   return LIODOM_OK;
 }
 
+int liodom_graph_set_loss(liodom_graph_t* g, int kind, int loss, double scale) {
+  using namespace liodom_dev;
+  if (!g) { g_last_error = "liodom_graph_set_loss: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  if (kind < 0 || kind >= kGraphLossKinds) { g_last_error = "liodom_graph_set_loss: kind outside 0 .. 15"; return LIODOM_ERR_INVALID_ARG; }
+  if (loss < kGraphLossNone || loss > kGraphLossGemanMcClure) { g_last_error = "liodom_graph_set_loss: unknown loss"; return LIODOM_ERR_INVALID_ARG; }
+  if (loss != kGraphLossNone && (!std::isfinite(scale) || !(scale > 0.0))) {
+    g_last_error = "liodom_graph_set_loss: the scale is not finite and > 0"; return LIODOM_ERR_INVALID_ARG;
+  }
+  std::lock_guard<std::mutex> lk(g->mx);
+  g->loss[kind] = loss;
+  g->loss_scale[kind] = loss == kGraphLossNone ? 0.0 : scale;
+  g->uploaded = false;
+  return LIODOM_OK;
+}
+
+int liodom_graph_get_loss(liodom_graph_t* g, int kind, int32_t* loss, double* scale) {
+  if (!g) { g_last_error = "liodom_graph_get_loss: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  if (kind < 0 || kind >= liodom_dev::kGraphLossKinds) { g_last_error = "liodom_graph_get_loss: kind outside 0 .. 15"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (loss) *loss = g->loss[kind];
+  if (scale) *scale = g->loss_scale[kind];
+  return LIODOM_OK;
+}
+
+int liodom_graph_set_edge_active(liodom_graph_t* g, int first, int n, const int32_t* active) {
+  if (!g) { g_last_error = "liodom_graph_set_edge_active: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (int rc = graph_check_range(g, first, n, g->edges.size(), active, "liodom_graph_set_edge_active")) return rc;
+  for (int k = 0; k < n; k++) g->active[(size_t)first + (size_t)k] = active[k] ? 1 : 0;
+  if (n) g->uploaded = false;
+  return LIODOM_OK;
+}
+
+int liodom_graph_get_edge_active(liodom_graph_t* g, int first, int n, int32_t* active) {
+  if (!g) { g_last_error = "liodom_graph_get_edge_active: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (int rc = graph_check_range(g, first, n, g->edges.size(), active, "liodom_graph_get_edge_active")) return rc;
+  if (n) std::memcpy(active, &g->active[(size_t)first], sizeof(int32_t) * (size_t)n);
+  return LIODOM_OK;
+}
+
+int liodom_graph_edge_weights(liodom_graph_t* g, double* rho, double* weight) {
+  if (!g) { g_last_error = "liodom_graph_edge_weights: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  const size_t E = g->edges.size();
+  if (E == 0 || (!rho && !weight)) return LIODOM_OK;
+  HIP_TRY(hipSetDevice(g->device));
+  if (int rc = graph_prepare(g)) return rc;
+  if (g->robust) {
+    if (rho) HIP_TRY(hipMemcpyAsync(rho, g->d_rho, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
+    if (weight) HIP_TRY(hipMemcpyAsync(weight, g->d_w, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
+  } else {                                            // quadratic, every edge active: rho = chi2, w = 1
+    if (rho) HIP_TRY(hipMemcpyAsync(rho, g->d_chi2, sizeof(double) * E, hipMemcpyDeviceToHost, g->stream));
+    if (weight) for (size_t e = 0; e < E; e++) weight[e] = 1.0;
+  }
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  return LIODOM_OK;
+}
+
 void liodom_graph_options_default(liodom_graph_options_t* opt) {
   if (!opt) return;
   opt->max_iterations = 20; opt->max_pcg_iterations = 0;
@@ -348,7 +436,7 @@ int liodom_graph_optimize(liodom_graph_t* g, const liodom_graph_options_t* opt_i
   if ((rc = graph_linearize(g, &cost))) return rc;
   g->linearized = false;                              // (Minv is about to be made for another lambda)
   rep.initial_cost = rep.final_cost = cost;
-  if (n_free == 0 || E == 0) { if (report) *report = rep; return LIODOM_OK; }
+  if (n_free == 0 || g->n_active == 0) { if (report) *report = rep; return LIODOM_OK; }
   const int max_pcg = opt.max_pcg_iterations > 0 ? opt.max_pcg_iterations : std::min(6 * n_free, 65536);
   double lambda = 1e-4;
   bool moved = false;                                 // d_poses differs from the host's poses
@@ -374,9 +462,14 @@ int liodom_graph_optimize(liodom_graph_t* g, const liodom_graph_options_t* opt_i
       rep.iterations++;
       hipLaunchKernelGGL(k_graph_retract, dim3(graph_blocks(N)), dim3(kGraphThreads), 0, g->stream, N, g->d_poses, g->d_fixed, g->d_x, g->d_cand);
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_graph_cost, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, g->d_cand, g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_chi2);
+      if (g->robust) {
+        hipLaunchKernelGGL(k_graph_cost_robust, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, g->d_cand, g->d_ei, g->d_ej, g->d_z, g->d_info,
+                           g->d_code, g->d_scale, g->d_chi2, g->d_rho, g->d_w);
+      } else {
+        hipLaunchKernelGGL(k_graph_cost, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, g->d_cand, g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_chi2);
+      }
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_graph_sum, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, E, g->d_chi2, g->d_sum);
+      hipLaunchKernelGGL(k_graph_sum, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, E, g->robust ? g->d_rho : g->d_chi2, g->d_sum);
       HIP_TRY(hipGetLastError());
       double cand = 0.0;
       HIP_TRY(hipMemcpyAsync(&cand, g->d_sum, sizeof(double), hipMemcpyDeviceToHost, g->stream));

@@ -1177,11 +1177,45 @@ LD_HD double graph_edge_chi2(const double* e, const double* Om) {
   }
   return chi2;
 }
+// A robust loss on s = e^T Omega e with scale c > 0: *rho replaces s in the cost, *w = rho'(s) weights the edge in g and H
+// (include/liodom_hip.h "closing loops" has the table).  Every rho is concave in s with rho(0) = 0 and rho' <= 1, so rho <= s
+// and 0 <= w <= 1; both are enforced after rounding.  An unknown loss, and s <= 0 (an indefinite Omega; a NaN goes through), are
+// quadratic.  c^2 is never formed — it overflows at c = 1e150 —: Huber compares sqrt(s) with c, the other two take u = s / c^2
+// as (s / c) / c and the weight c^2 / (c^2 + s) as 1 / (1 + u); Cauchy's c^2 log1p(u) is c (c log1p(u)), and s itself where
+// u < 2^-54 (log1p(u) = u (1 - u / 2 + ...) there: s is the correctly rounded value, also where u has underflowed to 0).
+// Rounding errors, u = 2^-53, L = the error of log1p in ulp (sqrt is correctly rounded): rho 2 u (Huber), (2 + L) u (Cauchy),
+// 2.5 u (Geman-McClure); w 1 u, 2 u, 4.5 u.  tests/test_graph_loss_host.py derives and checks them.
+constexpr int kGraphLossNone = 0, kGraphLossHuber = 1, kGraphLossCauchy = 2, kGraphLossGemanMcClure = 3;
+constexpr int kGraphLossInactive = -1;      // the per-edge code of an edge that is switched off (kernels_graph.h)
+LD_HD void graph_loss(int loss, double c, double s, double* rho, double* w) {
+  double r = s, wt = 1.0;
+  if (s > 0.0) {
+    if (loss == kGraphLossHuber) {
+      const double root = sqrt(s);
+      if (root > c) { r = c * (2.0 * root - c); wt = c / root; }
+    } else if (loss == kGraphLossCauchy) {
+      const double u = (s / c) / c;
+      if (u >= 5.5511151231257827e-17) r = c * (c * log1p(u));
+      wt = 1.0 / (1.0 + u);
+    } else if (loss == kGraphLossGemanMcClure) {
+      const double u = (s / c) / c;
+      const double q = 1.0 / (1.0 + u);
+      r = s * q; wt = q * q;
+    }
+    if (r > s) r = s;
+    if (wt > 1.0) wt = 1.0;
+  }
+  *rho = r; *w = wt;
+}
 // What one edge gives the normal equations: chi2, gi = A^T Omega e, gj = B^T Omega e (6 each), Hii = A^T Omega A, Hij = A^T
 // Omega B, Hjj = B^T Omega B (36 each, row-major; the two diagonal blocks computed as an upper triangle and mirrored).  Entry k
 // of an output lies at out[k * stride]: the kernel writes component-major arrays, a host caller passes stride 1.
-LD_HD void graph_edge_blocks(const double* e, const double* A, const double* B, const double* Om, long long stride, double* chi2,
-                             double* gi, double* gj, double* Hii, double* Hij, double* Hjj) {
+// ROBUST: *rho and *w = graph_loss(loss, scale, chi2), and w multiplies every FINISHED entry of gi, gj, Hii, Hij, Hjj as it is
+// stored — first-order IRLS, no second-order term; w = 1 stores the quadratic instance's bytes.  *chi2 stays the raw e^T Omega e.
+template <bool ROBUST>
+LD_HD void graph_edge_blocks_t(const double* e, const double* A, const double* B, const double* Om, long long stride, int loss,
+                               double scale, double* chi2, double* rho, double* w, double* gi, double* gj, double* Hii, double* Hij,
+                               double* Hjj) {
   double Oe[6], OA[36], OB[36];
   LD_UNROLL
   for (int r = 0; r < 6; r++) {
@@ -1201,27 +1235,40 @@ LD_HD void graph_edge_blocks(const double* e, const double* A, const double* B, 
   LD_UNROLL
   for (int r = 0; r < 6; r++) x2 += e[r] * Oe[r];
   *chi2 = x2;
+  double wt = 1.0;
+  if (ROBUST) {
+    double r;
+    graph_loss(loss, scale, x2, &r, &wt);
+    *rho = r; *w = wt;
+  }
   LD_UNROLL
   for (int r = 0; r < 6; r++) {
     double si = 0.0, sj = 0.0;
     LD_UNROLL
     for (int k = 0; k < 6; k++) { si += A[k * 6 + r] * Oe[k]; sj += B[k * 6 + r] * Oe[k]; }
+    if (ROBUST) { si *= wt; sj *= wt; }
     gi[r * stride] = si; gj[r * stride] = sj;
     LD_UNROLL
     for (int c = 0; c < 6; c++) {
       double sij = 0.0;
       LD_UNROLL
       for (int k = 0; k < 6; k++) sij += A[k * 6 + r] * OB[k * 6 + c];
+      if (ROBUST) sij *= wt;
       Hij[(r * 6 + c) * stride] = sij;
       if (c >= r) {
         double sii = 0.0, sjj = 0.0;
         LD_UNROLL
         for (int k = 0; k < 6; k++) { sii += A[k * 6 + r] * OA[k * 6 + c]; sjj += B[k * 6 + r] * OB[k * 6 + c]; }
+        if (ROBUST) { sii *= wt; sjj *= wt; }
         Hii[(r * 6 + c) * stride] = sii; Hii[(c * 6 + r) * stride] = sii;
         Hjj[(r * 6 + c) * stride] = sjj; Hjj[(c * 6 + r) * stride] = sjj;
       }
     }
   }
+}
+LD_HD void graph_edge_blocks(const double* e, const double* A, const double* B, const double* Om, long long stride, double* chi2,
+                             double* gi, double* gj, double* Hii, double* Hij, double* Hjj) {
+  graph_edge_blocks_t<false>(e, A, B, Om, stride, 0, 0.0, chi2, nullptr, nullptr, gi, gj, Hii, Hij, Hjj);
 }
 // X (+) delta: the retraction above, the quaternion brought back to unit norm
 LD_HD void graph_retract(const double* X, const double* delta, double* out) {

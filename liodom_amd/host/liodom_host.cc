@@ -601,6 +601,31 @@ liodom_graph_report_t PoseGraph::optimize(const liodom_graph_options_t* options)
   check(liodom_graph_optimize(g_, options, &rep), "liodom_graph_optimize");
   return rep;
 }
+void PoseGraph::setLoss(int kind, int loss, double scale) { check(liodom_graph_set_loss(g_, kind, loss, scale), "liodom_graph_set_loss"); }
+std::pair<int, double> PoseGraph::loss(int kind) {
+  int32_t l = 0;
+  double c = 0.0;
+  check(liodom_graph_get_loss(g_, kind, &l, &c), "liodom_graph_get_loss");
+  return {(int)l, c};
+}
+void PoseGraph::setEdgeActive(int first, const std::vector<bool>& active) {
+  std::vector<int32_t> a(active.size());
+  for (size_t k = 0; k < active.size(); k++) a[k] = active[k] ? 1 : 0;
+  check(liodom_graph_set_edge_active(g_, first, (int)a.size(), a.data()), "liodom_graph_set_edge_active");
+}
+std::vector<bool> PoseGraph::edgeActive() {
+  std::vector<int32_t> a((size_t)edges() + 1, 0);
+  check(liodom_graph_get_edge_active(g_, 0, (int)a.size() - 1, a.data()), "liodom_graph_get_edge_active");
+  std::vector<bool> out(a.size() - 1);
+  for (size_t k = 0; k < out.size(); k++) out[k] = a[k] != 0;
+  return out;
+}
+void PoseGraph::edgeWeights(std::vector<double>* rho, std::vector<double>* weight) {
+  const size_t e = (size_t)edges();
+  if (rho) rho->assign(e, 0.0);
+  if (weight) weight->assign(e, 0.0);
+  check(liodom_graph_edge_weights(g_, rho ? rho->data() : nullptr, weight ? weight->data() : nullptr), "liodom_graph_edge_weights");
+}
 
 MapPager::MapPager(Map* map, int keep_xy, int keep_z, int load_xy, int load_z)
     : map_(map), keep_xy_(keep_xy), keep_z_(keep_z), load_xy_(load_xy), load_z_(load_z) {

@@ -331,6 +331,12 @@ class PoseGraph {
   void linearize(std::vector<double>* chi2, std::vector<double>* gradient, std::vector<double>* diag);
   std::vector<double> multiply(const std::vector<double>& x, double lambda = 0.0);              // (H + lambda diag H) x
   liodom_graph_report_t optimize(const liodom_graph_options_t* options = nullptr);              // null: the defaults
+  // robust losses and switched-off edges (include/liodom_hip.h "robust losses"): loss one of LIODOM_GRAPH_LOSS_*, per edge kind 0 .. 15
+  void setLoss(int kind, int loss, double scale = 1.0);
+  std::pair<int, double> loss(int kind);                                                        // (loss, scale)
+  void setEdgeActive(int first, const std::vector<bool>& active);                               // edges first .. first + size - 1
+  std::vector<bool> edgeActive();
+  void edgeWeights(std::vector<double>* rho, std::vector<double>* weight);                      // per edge; null: not wanted
   liodom_graph_t* handle() const { return g_; }
  private:
   liodom_graph_t* g_ = nullptr;

@@ -5,8 +5,17 @@ was taken near, Map.search_pose measures the pose in the map, a PoseGraph holds 
 and close() optimises it and applies the result — the map is rebuilt from the key frames' clouds at the corrected poses, the poses
 in the place database are rewritten, the stream is seeded again.  Nothing is computed here but pose compositions.
 
+A false loop edge — the descriptor has no roll, pitch or height term, and a site with repeated structure will produce one — bends
+the whole graph under the plain quadratic cost.  close(loss=(name, scale), reject_below=r) is the answer to that: a first solve
+with a robust loss on the loop edges (kind 1), the loop edges whose weight collapsed below r switched off, and a second, plain
+quadratic solve over the survivors from the robust result, which takes the robust loss's bias off them.
+
 What close() cannot do: scans that were no key frames are not in the rebuilt map (their clouds are not kept); a loop measurement
-is as fine as the last search level's step; every loop edge is believed (no robust loss).
+is as fine as the last search level's step.  The robust solve is only as good as its scale, which is in units of sqrt(chi2) of
+a loop edge: it has to exceed what honest drift puts on a TRUE loop edge at the dead-reckoned poses, or the true edges are
+down-weighted with the false one and the solve settles in the wrong minimum (DESIGN.md §3 "Closing loops" has a ring of 8 key
+frames on which Geman-McClure with scale 3 rejects every true loop and scale 5 does not).  And it rejects by consensus: where
+false loop edges agree with each other and outnumber the true ones, they win.
 """
 import math
 
@@ -80,7 +89,8 @@ class LoopCloser:
         self.max_update_points = int(max_update_points)
         self.key_poses, self.clouds = [], []
         self.inserted = 0                # key frames 0 .. inserted - 1 are in `places`
-        self.loops = []                  # (place node, node) of every loop edge
+        self.loops = []                  # (place node, node) of every active loop edge, in the graph's edge order
+        self.rejected = []               # (place node, node, weight) of the loop edges close() has switched off
         self.last_pose = None            # the last pose fed, key frame or not
 
     def feed(self, pose, edges):
@@ -115,21 +125,79 @@ class LoopCloser:
                 loops.append(dict(place=place, node=node, fraction=fraction, pose=np.array(found, np.float64), match=m))
         return dict(key_frame=True, node=node, loops=loops)
 
-    def close(self, handle=None, stream=0, reader_cells=None, **options):
+    def add_loop(self, place, node, Z, info=None):
+        """A loop edge from another source — a surveyed tie, a user's hint, a test —: "X_place^-1 o X_node was measured as Z", the
+        edge feed() would add (kind 1, info None: loop_info).  place and node are key frames' node indices, place < node."""
+        place, node = int(place), int(node)
+        if not (0 <= place < node < len(self.key_poses)):
+            raise ValueError("LoopCloser.add_loop: place and node must be key frames with place < node")
+        info = self.loop_info if info is None else np.array(info, np.float64).reshape(6, 6)
+        self.graph.add_edges(api.graph_edges([place], [node], [_pose(Z)], info, kind=1))
+        self.loops.append((place, node))
+
+    def _loop_edges(self):
+        """Edge indices of the active loop edges: one per entry of self.loops, in its order."""
+        ed, act = self.graph.edges(), self.graph.edge_active()
+        idx = [e for e in range(ed.shape[0]) if int(ed["kind"][e]) == 1 and act[e]]
+        if [(int(ed["i"][e]), int(ed["j"][e])) for e in idx] != [tuple(l) for l in self.loops]:
+            raise ValueError("LoopCloser.close: the graph's loop edges are not the ones feed() and add_loop() added")
+        return idx
+
+    def close(self, handle=None, stream=0, reader_cells=None, loss=None, reject_below=None, **options):
         """Optimises the graph (the first key frame is fixed; **options: make_graph_options) and applies the result:
           map      reset and rebuilt from the key frames' clouds at the corrected poses; with reader_cells = (cells_xy, cells_z) the
                    handle's stream is detached from it before (attach_mapper(None)) and attached as its reader again after
           places   the poses of the database rewritten (export_state -> parse_place_state -> build_place_state -> import_state)
           stream   with a handle: seeded (seed_stream) at the corrected pose of the last scan fed — the last key frame's corrected
                    pose composed with the odometry since
-        Returns dict(report, before [K, 7], after [K, 7], pose = the corrected current pose)."""
+        Returns dict(report, before [K, 7], after [K, 7], pose = the corrected current pose).
+
+        loss = (name, scale): the solve runs with that robust loss (api.GRAPH_LOSSES) on the loop edges — kind 1; the odometry
+        edges, kind 0, are never touched — and kind 1 is set back to "none" whatever happens.  The return gains robust_report (=
+        report) and weights, the loop edges' weights in the order of self.loops.
+        reject_below = r (needs loss): after the robust solve every loop edge with weight < r is switched off (it stays in the
+        graph's edges, inactive), and the graph is optimised again from the robust result with the plain quadratic cost; that
+        second result is what is applied, and `report` is its report.  The return gains rejected = [(place, node, weight)],
+        kept = [(place, node, weight)] and applied = True; self.loops keeps the survivors, self.rejected accumulates.  If EVERY
+        loop edge is rejected nothing is applied and nothing is switched off: the map, the places, the stream, self.loops and
+        the graph — its poses are set back — stay as they were, and the return is dict(applied=False, rejected, kept=[],
+        robust_report, report=None, before, after=before, pose=the last pose fed)."""
+        if reject_below is not None and loss is None:
+            raise ValueError("LoopCloser.close: reject_below needs a loss")
         if not self.key_poses:
             raise ValueError("LoopCloser.close: no key frame yet")
         before = np.stack(self.key_poses)
         st = api.parse_place_state(self.places.export_state()) if self.inserted else None
         if (st["count"] if st else self.places.count()) != self.inserted or (st and list(st["ids"]) != list(range(self.inserted))):
             raise ValueError("LoopCloser.close: the place database holds places that feed() did not add")
-        report = self.graph.optimize(**options)
+        extra = {}
+        if loss is None:
+            report = self.graph.optimize(**options)
+        else:
+            idx = self._loop_edges()
+            start = self.graph.poses()
+            self.graph.set_loss(1, loss[0], loss[1])
+            try:
+                report = self.graph.optimize(**options)
+                weights = self.graph.edge_weights()[1][idx] if idx else np.zeros(0)
+            finally:
+                self.graph.set_loss(1, "none")
+            extra = dict(robust_report=report, weights=weights)
+            if reject_below is not None:
+                both = [(l[0], l[1], float(w)) for l, w in zip(self.loops, weights)]
+                rejected = [b for b in both if b[2] < reject_below]
+                kept = [b for b in both if not b[2] < reject_below]
+                if rejected and not kept:
+                    self.graph.set_poses(0, start)
+                    return dict(applied=False, rejected=rejected, kept=[], robust_report=report, weights=weights, report=None,
+                                before=before, after=before.copy(), pose=self.last_pose.copy())
+                for e, b in zip(idx, both):
+                    if b[2] < reject_below:
+                        self.graph.set_edge_active(e, [0])
+                self.loops = [(b[0], b[1]) for b in kept]
+                self.rejected += rejected
+                report = self.graph.optimize(**options)
+                extra.update(rejected=rejected, kept=kept, applied=True)
         after = self.graph.poses()
         current = compose(after[-1], between(before[-1], self.last_pose))
         if handle is not None and reader_cells is not None:
@@ -150,4 +218,4 @@ class LoopCloser:
         self.key_poses = [p.copy() for p in after]
         self.last_pose = current
         self.policy.last = [float(v) for v in after[-1]]
-        return dict(report=report, before=before, after=after, pose=current)
+        return dict(report=report, before=before, after=after, pose=current, **extra)
