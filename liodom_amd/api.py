@@ -12,7 +12,7 @@ _HASH = _LIB + ".srchash"
 _BUILD_INFO = {"rebuilt": None, "source_hash": None}
 _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kernels.h", "kernels_extract.h", "kernels_sync.h",
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
-                                                  "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
+                                                  "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "stream_state_format.h", "pose7.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
                                                   "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h",
                                                   "kernels_places.h", "liodom_places_host.h", "place_state_format.h",
@@ -412,7 +412,7 @@ ERR_BUSY = -6
 ERR_NEEDS_SYNC = -7
 
 
-# ---- stream-state blob (liodom_export_stream_state; layout in csrc/kernels_state.h and DESIGN.md §3) ----
+# ---- stream-state blob (liodom_export_stream_state; layout in csrc/stream_state_format.h and DESIGN.md §3) ----
 STATE_MAGIC = b"LIODOMST"
 STATE_VERSION = 1
 STATE_HEADER_BYTES = 64

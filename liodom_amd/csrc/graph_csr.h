@@ -2,7 +2,7 @@
 // node -> incident (edge, side) lists its node-parallel kernels sum over.
 // Plain C++, no HIP include: tests/graph_csr_main.cc and tests/graph_csr_active_main.cc compile it for the host alone under sanitizers; liodom_graph_host.h uses it.
 //
-// An edge is (i, j, Z, Omega): nodes i != j, both in 0 .. n_nodes - 1; Z = [qx qy qz qw tx ty tz], finite, | |q| - 1 | <= 1e-6;
+// An edge is (i, j, Z, Omega): nodes i != j, both in 0 .. n_nodes - 1; Z = [qx qy qz qw tx ty tz] as pose7.h takes it;
 // Omega 6 x 6 row-major, finite, symmetric bit for bit.  The lists are a CSR: the pairs of node n are entries offsets[n] ..
 // offsets[n + 1] - 1, each edge * 2 + side (side 0: n is the edge's i; 1: its j), in ascending edge order — so a sum over them
 // depends on the graph alone.  An edge can be switched off (liodom_graph_set_edge_active): the lists and the preconditioner's
@@ -14,6 +14,8 @@
 
 #include <vector>
 
+#include "pose7.h"
+
 namespace liodom_dev {
 
 constexpr int kGraphMaxNodes = 65536;
@@ -22,10 +24,8 @@ constexpr int kGraphLossKinds = 16;           // a graph keeps a loss per edge k
 
 // 0: fine; otherwise why not (static text)
 inline const char* graph_pose_refusal(const double* pose) {
-  for (int k = 0; k < 7; k++) if (!isfinite(pose[k])) return "a pose has a non-finite number";
-  const double n = sqrt(pose[0] * pose[0] + pose[1] * pose[1] + pose[2] * pose[2] + pose[3] * pose[3]);
-  if (!(fabs(n - 1.0) <= 1e-6)) return "a pose's quaternion is not normalised (| |q| - 1 | > 1e-6)";
-  return nullptr;
+  const Pose7Verdict v = pose7_check(pose);
+  return v == kPose7Ok ? nullptr : v == kPose7NonFinite ? "a pose has a non-finite number" : "a pose's quaternion is not normalised (" POSE7_RULE ")";
 }
 inline const char* graph_edge_refusal(int32_t i, int32_t j, const double* z, const double* info, int n_nodes) {
   if (i < 0 || j < 0 || i >= n_nodes || j >= n_nodes) return "an edge names a node that does not exist";
@@ -39,11 +39,7 @@ inline const char* graph_edge_refusal(int32_t i, int32_t j, const double* z, con
   return nullptr;
 }
 // pose with its quaternion divided by its norm (after graph_pose_refusal has passed)
-inline void graph_pose_normalised(const double* pose, double* out) {
-  const double n = sqrt(pose[0] * pose[0] + pose[1] * pose[1] + pose[2] * pose[2] + pose[3] * pose[3]);
-  for (int k = 0; k < 4; k++) out[k] = pose[k] / n;
-  for (int k = 4; k < 7; k++) out[k] = pose[k];
-}
+inline void graph_pose_normalised(const double* pose, double* out) { pose7_normalised(pose, out); }
 
 // The CSR of n_edges edges over n_nodes nodes.  false (outputs unspecified) if an index is out of range.  active (optional,
 // [n_edges]; null: every edge): an edge whose flag is 0 is left out — it is in no node's list, so it adds nothing to a node's

@@ -1,48 +1,8 @@
-// kernels_state.h — a stream's odometry state as one contiguous blob: k_state_pack / k_state_unpack, and the per-stream clear
-// behind liodom_reset_stream / liodom_import_stream_state.
+// kernels_state.h — a stream's odometry state as one contiguous blob (layout in stream_state_format.h): k_state_pack /
+// k_state_unpack, and the per-stream clear behind liodom_reset_stream / liodom_import_stream_state.
 // Part of liodom_kernels.h (included there, inside namespace liodom_dev, behind kernels_cov.h; not a standalone header).
 // None of this is on the per-scan path: a handle that never calls the four stream-state entry points launches none of these
 // kernels and allocates nothing for them.
-// =============================================================================================
-// Blob layout (little endian; every part starts on a 16-byte boundary; DESIGN.md §3 has the same table):
-//   [0, 64)      StateBlobHeader   magic "LIODOMST", version, total size, fingerprint of what must match on import
-//   [64, 480)    StateBlobRecord   poses, counters and flags, sizes of the parts that follow, last IMU orientation
-//   [480, ...)   int32 count[round_up(local_map_size, 4)]   points of window frame j, OLDEST FIRST (LocalMapManager order);
-//                                  entries behind n_frames are 0
-//   then         float4 points[n_points]   the frames back to back, oldest first: the order of liodom_get_window
-//   then         float4 recv[n_recv]       (mapping = 1) the last received ~map cloud
-// The blob holds the stream's LOGICAL state only.  What a handle derives from it — cell hash, filtered local map, kNN saves — and
-// what only tunes a code path — spec_*, hb_* — does not travel: liodom_import_stream_state rebuilds the former for whichever
-// variant the importing handle runs and starts the latter afresh.
-// =============================================================================================
-constexpr unsigned int kStateBlobVersion = 1u;
-constexpr int kStateHeaderBytes = 64;
-struct StateBlobHeader {
-  char magic[8];                 // "LIODOMST"
-  uint32_t version;              // kStateBlobVersion
-  uint32_t header_bytes;         // 64
-  uint64_t total_bytes;          // of the whole blob
-  uint32_t local_map_size, mapping, filter_local_map, use_imu, pose_rotation_mode, lm_apply_step_on_ftol;      // the fingerprint
-  uint32_t reserved[4];
-};
-struct StateBlobRecord {
-  double odom[12], prev_odom[12], final_odom[12], param_q[4], param_t[3];      // as in StreamState
-  int32_t initialized, append_raw, frame_count, n_frames, scan_counter;
-  uint32_t status;               // the sticky LIODOM_STATUS_* bits
-  int32_t n_points;              // window points = sum of the frame counts
-  int32_t n_recv;                // points of the received ~map cloud (0 unless mapping)
-  int32_t has_imu, pad;          // imu_q is meaningful (use_imu handles)
-  double imu_q[4];               // last IMU orientation [x y z w]
-};
-static_assert(sizeof(StateBlobHeader) == kStateHeaderBytes, "blob header is 64 bytes");
-static_assert(sizeof(StateBlobRecord) == 416, "blob record is 416 bytes");
-constexpr int kStateCountsOffset = kStateHeaderBytes + (int)sizeof(StateBlobRecord);      // 480
-__host__ __device__ __forceinline__ int state_counts_bytes(int P) { return 4 * ((P + 3) / 4 * 4); }
-__host__ __device__ __forceinline__ size_t state_points_offset(int P) { return (size_t)kStateCountsOffset + (size_t)state_counts_bytes(P); }
-__host__ __device__ __forceinline__ size_t state_blob_bytes(int P, long long n_points, long long n_recv) {
-  return state_points_offset(P) + 16 * (size_t)(n_points + n_recv);
-}
-
 constexpr int kStateThreads = 256;
 
 // Gathers stream s into `blob` (device memory, 16-byte aligned, state_blob_bytes(P, P * edge_cap, recv_cap) bytes): the record and

@@ -730,7 +730,7 @@ int liodom_reset(liodom_handle_t* h) {
   return reset_state(h);
 }
 
-// ---- streams with a life of their own: per-stream reset, export and import of the odometry state (kernels_state.h) ----
+// ---- streams with a life of their own: per-stream reset, export and import of the odometry state (kernels_state.h, stream_state_format.h) ----
 // None of these calls is on the per-scan path; each takes both sides, refuses while edge tickets are outstanding, and waits for
 // every HIP stream of the handle (a pending chain-mode repair included) before it touches anything.
 static size_t state_max_bytes(const liodom_handle* h) {
@@ -756,9 +756,11 @@ static int ensure_state_stage(liodom_handle* h) {
   h->state_stage = static_cast<unsigned char*>(dp);
   return LIODOM_OK;
 }
-static void state_fingerprint(const liodom_handle* h, StateBlobHeader* hd) {
-  hd->local_map_size = (uint32_t)h->P; hd->mapping = h->params.mapping ? 1u : 0u; hd->filter_local_map = h->params.filter_local_map ? 1u : 0u;
-  hd->use_imu = h->params.use_imu ? 1u : 0u; hd->pose_rotation_mode = (uint32_t)h->v.rotation_mode; hd->lm_apply_step_on_ftol = h->v.apply_on_ftol ? 1u : 0u;
+static StateBlobHeader state_fingerprint(const liodom_handle* h) {
+  StateBlobHeader hd = {};
+  hd.local_map_size = (uint32_t)h->P; hd.mapping = h->params.mapping ? 1u : 0u; hd.filter_local_map = h->params.filter_local_map ? 1u : 0u;
+  hd.use_imu = h->params.use_imu ? 1u : 0u; hd.pose_rotation_mode = (uint32_t)h->v.rotation_mode; hd.lm_apply_step_on_ftol = h->v.apply_on_ftol ? 1u : 0u;
+  return hd;
 }
 // Everything of stream `stream` but its edge buffers becomes what `blob` (device staging; null: a stream that never ran) says, and
 // the structure its next scan searches is rebuilt from the window for the variant this handle runs.  Streams are idle (state_quiesce).
@@ -833,8 +835,7 @@ int liodom_export_stream_state(liodom_handle_t* h, int stream, void* blob, int64
   HIP_TRY(hipMemcpyAsync(h->state_stage_host, h->state_stage, prefix, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   StateBlobRecord rec;
-  std::memcpy(&rec, h->state_stage_host + kStateHeaderBytes, sizeof(rec));
-  if (rec.n_points < 0 || rec.n_points > (long long)h->P * v.edge_cap || rec.n_recv < 0 || rec.n_recv > v.recv_cap) {
+  if (!state_packed_record(h->state_stage_host, h->P, v.edge_cap, v.recv_cap, &rec)) {
     g_last_error = "liodom_export_stream_state: inconsistent stream state"; return LIODOM_ERR_HIP;
   }
   const size_t need = state_blob_bytes(h->P, rec.n_points, rec.n_recv);
@@ -844,11 +845,7 @@ int liodom_export_stream_state(liodom_handle_t* h, int stream, void* blob, int64
     HIP_TRY(hipMemcpyAsync(h->state_stage_host + prefix, h->state_stage + prefix, need - prefix, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
-  StateBlobHeader hd;
-  std::memset(&hd, 0, sizeof(hd));
-  std::memcpy(hd.magic, "LIODOMST", 8);
-  hd.version = kStateBlobVersion; hd.header_bytes = (uint32_t)kStateHeaderBytes; hd.total_bytes = (uint64_t)need;
-  state_fingerprint(h, &hd);
+  const StateBlobHeader hd = state_header(state_fingerprint(h), (uint64_t)need);
   std::memcpy(blob, &hd, sizeof(hd));
   std::memcpy(static_cast<unsigned char*>(blob) + kStateHeaderBytes, h->state_stage_host + kStateHeaderBytes, need - (size_t)kStateHeaderBytes);
   return LIODOM_OK;
@@ -862,42 +859,13 @@ int liodom_import_stream_state(liodom_handle_t* h, int stream, const void* blob,
   SideLocks lk(h, true, true);
   if ((rc = state_quiesce(h))) return rc;
   // every rejection comes before the handle is touched
-  const int P = h->P;
-  const unsigned char* b = static_cast<const unsigned char*>(blob);
-  if (bytes < (int64_t)state_points_offset(P)) { g_last_error = "liodom_import_stream_state: blob truncated"; return LIODOM_ERR_INVALID_ARG; }
-  StateBlobHeader hd, mine;
-  std::memcpy(&hd, b, sizeof(hd));
-  if (std::memcmp(hd.magic, "LIODOMST", 8) != 0 || hd.version != kStateBlobVersion || hd.header_bytes != (uint32_t)kStateHeaderBytes ||
-      hd.total_bytes != (uint64_t)bytes) {
-    g_last_error = "liodom_import_stream_state: not a stream-state blob of this version and size"; return LIODOM_ERR_INVALID_ARG;
-  }
-  std::memset(&mine, 0, sizeof(mine));
-  state_fingerprint(h, &mine);
-  if (hd.local_map_size != mine.local_map_size || hd.mapping != mine.mapping || hd.filter_local_map != mine.filter_local_map ||
-      hd.use_imu != mine.use_imu || hd.pose_rotation_mode != mine.pose_rotation_mode || hd.lm_apply_step_on_ftol != mine.lm_apply_step_on_ftol) {
-    g_last_error = "liodom_import_stream_state: the blob comes from a handle with other parameters (local_map_size, mapping, filter_local_map, "
-                   "use_imu, pose_rotation_mode, lm_apply_step_on_ftol must match)";
-    return LIODOM_ERR_INVALID_ARG;
-  }
+  const char* why;
   StateBlobRecord rec;
-  std::memcpy(&rec, b + kStateHeaderBytes, sizeof(rec));
-  const int nf_want = rec.frame_count < P ? rec.frame_count : P;
-  if (rec.frame_count < 0 || rec.n_frames != nf_want || rec.scan_counter != rec.frame_count || rec.n_points < 0 || rec.n_recv < 0 ||
-      (rec.n_recv > 0 && !h->v.mapping) || (rec.initialized != 0 && rec.initialized != 1) || (rec.append_raw != 0 && rec.append_raw != 1) ||
-      (uint64_t)state_blob_bytes(P, rec.n_points, rec.n_recv) != hd.total_bytes) {
-    g_last_error = "liodom_import_stream_state: inconsistent state record"; return LIODOM_ERR_INVALID_ARG;
+  if ((rc = stream_state_validate(blob, bytes, state_fingerprint(h), h->v.mapping, h->v.edge_cap, h->v.recv_cap, &why, &rec))) {
+    g_last_error = std::string("liodom_import_stream_state: ") + why; return rc;
   }
-  const int32_t* cnt = reinterpret_cast<const int32_t*>(b + kStateCountsOffset);
-  long long sum = 0;
-  for (int j = 0; j < state_counts_bytes(P) / 4; j++) {
-    if (cnt[j] < 0 || (j >= rec.n_frames && cnt[j] != 0)) { g_last_error = "liodom_import_stream_state: bad frame count"; return LIODOM_ERR_INVALID_ARG; }
-    if (cnt[j] > h->v.edge_cap) { g_last_error = "liodom_import_stream_state: a frame is larger than the handle's edge capacity"; return LIODOM_ERR_CAPACITY; }
-    sum += cnt[j];
-  }
-  if (sum != rec.n_points) { g_last_error = "liodom_import_stream_state: frame counts do not add up"; return LIODOM_ERR_INVALID_ARG; }
-  if (rec.n_recv > h->v.recv_cap) { g_last_error = "liodom_import_stream_state: received map larger than recv_capacity"; return LIODOM_ERR_CAPACITY; }
   if ((rc = ensure_state_stage(h))) return rc;
-  std::memcpy(h->state_stage_host, b, (size_t)bytes);
+  std::memcpy(h->state_stage_host, blob, (size_t)bytes);
   HIP_TRY(hipMemcpyAsync(h->state_stage, h->state_stage_host, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
   return install_stream_state(h, stream, h->state_stage, rec.n_frames, rec.scan_counter, rec.n_recv);
 }
@@ -915,30 +883,18 @@ int liodom_seed_stream(liodom_handle_t* h, int stream, const double* pose) {
   if ((rc = check_usable(h))) return rc;
   if (!h->v.mapping) { g_last_error = "liodom_seed_stream: the handle was created with mapping = 0"; return LIODOM_ERR_UNSUPPORTED; }
   if (!pose) { g_last_error = "liodom_seed_stream: null pose"; return LIODOM_ERR_INVALID_ARG; }
-  double nn = 0.0;
-  for (int i = 0; i < 7; i++) if (!std::isfinite(pose[i])) { g_last_error = "liodom_seed_stream: non-finite pose"; return LIODOM_ERR_INVALID_ARG; }
-  for (int i = 0; i < 4; i++) nn += pose[i] * pose[i];
-  const double norm = std::sqrt(nn);
-  if (!(std::fabs(norm - 1.0) <= 1e-6)) { g_last_error = "liodom_seed_stream: the quaternion is not normalised (| |q| - 1 | > 1e-6)"; return LIODOM_ERR_INVALID_ARG; }
+  if (const Pose7Verdict bad = pose7_check(pose)) {
+    g_last_error = bad == kPose7NonFinite ? "liodom_seed_stream: non-finite pose" : "liodom_seed_stream: the quaternion is not normalised (" POSE7_RULE ")";
+    return LIODOM_ERR_INVALID_ARG;
+  }
   SideLocks lk(h, true, true);
   if ((rc = state_quiesce(h))) return rc;
   if ((rc = ensure_state_stage(h))) return rc;
-  // the seed: quaternion normalised in double, the matrix by iso_from_qt — what the first scan's queries are transformed with and
-  // what its solve starts from, with no arithmetic in between (a zero-velocity prediction)
-  StateBlobRecord rec;
-  std::memset(&rec, 0, sizeof(rec));
-  for (int i = 0; i < 4; i++) rec.param_q[i] = pose[i] / norm;
-  for (int i = 0; i < 3; i++) rec.param_t[i] = pose[4 + i];
-  iso_from_qt(rec.param_q, rec.param_t, rec.odom);
-  std::memcpy(rec.prev_odom, rec.odom, sizeof(rec.odom));
-  std::memcpy(rec.final_odom, rec.odom, sizeof(rec.odom));
-  rec.initialized = 1;
-  rec.imu_q[3] = 1.0;
-  const int P = h->P;
-  const size_t prefix = state_points_offset(P);
+  const StateBlobRecord rec = state_seed_record(pose);
+  const size_t prefix = state_points_offset(h->P);
   // the received map: getLocalMap(T(pose)) of the stream's attachment, planned and gathered straight into the staging blob's
   // received-map section (the window is empty: it follows the counts); its size is read before anything of the stream is touched
-  int cxy = 0, cz = 0;
+  int cxy = 0, cz = 0, n_recv = 0;
   if (liodom_map* mp = stream_map(h, stream, &cxy, &cz)) {
     HIP_TRY(hipMemcpyAsync(mp->d_T, rec.odom, sizeof(double) * 12, hipMemcpyHostToDevice, h->stream));
     if ((rc = map_enqueue_local(mp, mp->d_T, cxy, cz, reinterpret_cast<float4*>(h->state_stage + prefix), h->v.recv_cap, mp->d_out_n, h->stream, 0))) return rc;
@@ -946,12 +902,11 @@ int liodom_seed_stream(liodom_handle_t* h, int stream, const double* pose) {
     HIP_TRY(hipMemcpyAsync(&ms, mp->m.st, sizeof(ms), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (ms.n_result > h->v.recv_cap) { g_last_error = "liodom_seed_stream: the local map at the seed is larger than recv_capacity"; return LIODOM_ERR_CAPACITY; }
-    rec.n_recv = ms.n_result < 0 ? 0 : ms.n_result;
+    n_recv = ms.n_result < 0 ? 0 : ms.n_result;
   }
-  std::memset(h->state_stage_host, 0, prefix);
-  std::memcpy(h->state_stage_host + kStateHeaderBytes, &rec, sizeof(rec));
+  state_seed_prefix(rec, n_recv, h->P, h->state_stage_host);
   HIP_TRY(hipMemcpyAsync(h->state_stage, h->state_stage_host, prefix, hipMemcpyHostToDevice, h->stream));
-  return install_stream_state(h, stream, h->state_stage, 0, 0, rec.n_recv);
+  return install_stream_state(h, stream, h->state_stage, 0, 0, n_recv);
 }
 
 static int copy_edges_out(liodom_handle_t* h, int stream, int eb, hipStream_t q, float* edges_xyzi, int32_t* edge_ring,

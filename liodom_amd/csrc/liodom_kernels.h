@@ -24,7 +24,7 @@
 //   k_imu_override    A8     use_imu: roll / pitch of the prediction from the IMU (:152-183)
 //   k_pose_cov               (pose_covariance = 1) covariance + eigen-decomposition of the finalising solve's H, one wave per stream
 //   k_state_pack / k_state_unpack / k_stream_clear   a stream's odometry state as one blob (liodom_export_stream_state /
-//                            liodom_import_stream_state / liodom_reset_stream; kernels_state.h): never on the per-scan path
+//                            liodom_import_stream_state / liodom_reset_stream; kernels_state.h, layout in stream_state_format.h): never on the per-scan path
 //   k_window_stash           (lagged mapper, liodom_attach_mapper_ex; kernels_mapper.h) the frame a scan's append overwrites, set aside for the map
 //   (liodom_map.h)    A12-A14 the mapping node's Map: updateMap / getLocalMap / getMap; pruning
 //
@@ -37,6 +37,7 @@
 #include "../../include/liodom_hip.h"
 #include "liodom_math.h"
 #include "liodom_sizes.h"
+#include "stream_state_format.h"
 #include "wave_ops.h"
 
 namespace liodom_dev {

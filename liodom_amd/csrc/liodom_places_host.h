@@ -236,7 +236,7 @@ int liodom_places_add(liodom_places_t* db, const float* edges_xyzi, int n_edges,
   using namespace liodom_dev;
   if (!db || !pose || n_edges < 0 || (n_edges > 0 && !edges_xyzi)) { g_last_error = "liodom_places_add: null database, pose or edges, or a negative count"; return LIODOM_ERR_INVALID_ARG; }
   if (n_edges > db->max_edges) { g_last_error = "liodom_places_add: more edges than max_edges"; return LIODOM_ERR_INVALID_ARG; }
-  if (!place_pose_ok(pose)) { g_last_error = "liodom_places_add: non-finite pose, or the quaternion is not normalised (| |q| - 1 | > 1e-6)"; return LIODOM_ERR_INVALID_ARG; }
+  if (pose7_check(pose) != kPose7Ok) { g_last_error = "liodom_places_add: non-finite pose, or the quaternion is not normalised (" POSE7_RULE ")"; return LIODOM_ERR_INVALID_ARG; }
   std::lock_guard<std::mutex> lk(db->mx);
   if (db->count >= db->max_places) { g_last_error = "liodom_places_add: the database holds max_places places"; return LIODOM_ERR_CAPACITY; }
   HIP_TRY(hipSetDevice(db->device));

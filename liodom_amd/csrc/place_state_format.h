@@ -17,6 +17,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "pose7.h"
+
 #ifndef LIODOM_OK
 #define LIODOM_OK 0
 #endif
@@ -89,14 +91,6 @@ inline void place_make_tables(int n_rings, int n_layers, double r_max, double z_
   for (int i = 0; i <= n_layers; i++) t->z[i] = (float)(z_min + (double)i * (z_max - z_min) / (double)n_layers);
 }
 
-// A pose as liodom_seed_stream takes it: seven finite numbers, | |q| - 1 | <= 1e-6.
-inline bool place_pose_ok(const double* pose) {
-  double nn = 0.0;
-  for (int i = 0; i < 7; i++) if (!isfinite(pose[i])) return false;
-  for (int i = 0; i < 4; i++) nn += pose[i] * pose[i];
-  return fabs(sqrt(nn) - 1.0) <= 1e-6;
-}
-
 inline int place_popcount64(uint64_t v) {
   int n = 0;
   for (; v; v &= v - 1) n++;
@@ -159,7 +153,7 @@ inline int place_state_validate(const void* blob, int64_t bytes, const int32_t* 
     }
     if (r.bits != bits) { *why = "place-state blob: a bit count is not the popcount of its descriptor"; return LIODOM_ERR_INVALID_ARG; }
     if (r.reserved != 0) { *why = "place-state blob: reserved record word is not 0"; return LIODOM_ERR_INVALID_ARG; }
-    if (!place_pose_ok(r.pose)) { *why = "place-state blob: a pose is non-finite or its quaternion is not normalised"; return LIODOM_ERR_INVALID_ARG; }
+    if (pose7_check(r.pose) != kPose7Ok) { *why = "place-state blob: a pose is non-finite or its quaternion is not normalised"; return LIODOM_ERR_INVALID_ARG; }
   }
   if (max_places >= 0 && (int64_t)hd.count > max_places) { *why = "place-state blob holds more places than max_places"; return LIODOM_ERR_CAPACITY; }
   return LIODOM_OK;
@@ -168,9 +162,7 @@ inline int place_state_validate(const void* blob, int64_t bytes, const int32_t* 
 // The pose a match stands for: place_pose o Rz(shift * 2 pi / 64), in double: the place's quaternion normalised as
 // liodom_seed_stream normalises a seed, times (0, 0, sin(a / 2), cos(a / 2)); the translation is the place's.
 inline void place_match_pose(const double* place_pose, int shift, double* out) {
-  double nn = 0.0;
-  for (int i = 0; i < 4; i++) nn += place_pose[i] * place_pose[i];
-  const double norm = sqrt(nn);
+  const double norm = pose7_norm(place_pose);
   const double ax = place_pose[0] / norm, ay = place_pose[1] / norm, az = place_pose[2] / norm, aw = place_pose[3] / norm;
   const double a = (double)shift * (2.0 * kPlacePi / 64.0);
   const double bz = sin(a / 2.0), bw = cos(a / 2.0);

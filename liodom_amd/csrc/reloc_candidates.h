@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/liodom_hip.h"
+#include "pose7.h"
 
 namespace liodom_dev {
 
@@ -29,10 +30,9 @@ inline int64_t reloc_candidate_count(const liodom_pose_search_t* s, const char**
   if (!s) { *why = "null search"; return 0; }
   if (s->radius != 0 && s->radius != 1) { *why = "radius is not 0 or 1"; return 0; }
   if (s->nx < 0 || s->ny < 0 || s->nz < 0 || s->nyaw < 0) { *why = "negative half count"; return 0; }
-  for (int i = 0; i < 7; i++) if (!reloc_finite(s->centre[i])) { *why = "non-finite centre"; return 0; }
-  double nn = 0.0;
-  for (int i = 0; i < 4; i++) nn += s->centre[i] * s->centre[i];
-  if (!(fabs(sqrt(nn) - 1.0) <= 1e-6)) { *why = "the centre's quaternion is not normalised (| |q| - 1 | > 1e-6)"; return 0; }
+  if (const Pose7Verdict v = pose7_check(s->centre)) {
+    *why = v == kPose7NonFinite ? "non-finite centre" : "the centre's quaternion is not normalised (" POSE7_RULE ")"; return 0;
+  }
   // a step is read only where its half count is > 0
   if (((s->nx > 0 || s->ny > 0) && !(s->step_xy > 0.0 && reloc_finite(s->step_xy))) || (s->nz > 0 && !(s->step_z > 0.0 && reloc_finite(s->step_z))) ||
       (s->nyaw > 0 && !(s->step_yaw > 0.0 && reloc_finite(s->step_yaw)))) {
@@ -53,11 +53,10 @@ struct RelocCentre { double q[4], t[3], R[9]; };
 
 inline RelocCentre reloc_centre(const liodom_pose_search_t* s) {
   RelocCentre c;
-  double nn = 0.0;
-  for (int i = 0; i < 4; i++) nn += s->centre[i] * s->centre[i];
-  const double norm = sqrt(nn);
-  for (int i = 0; i < 4; i++) c.q[i] = s->centre[i] / norm;
-  for (int i = 0; i < 3; i++) c.t[i] = s->centre[4 + i];
+  double p[7];
+  pose7_normalised(s->centre, p);
+  for (int i = 0; i < 4; i++) c.q[i] = p[i];
+  for (int i = 0; i < 3; i++) c.t[i] = p[4 + i];
   const double x = c.q[0], y = c.q[1], z = c.q[2], w = c.q[3];      // iso_from_qt
   const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
   const double twx = tx * w, twy = ty * w, twz = tz * w;
@@ -115,9 +114,7 @@ inline void reloc_candidate_pose(const liodom_pose_search_t* s, int64_t index, d
   const double sz = ia ? sin(h) : 0.0, cw = ia ? cos(h) : 1.0;      // qz = (0, 0, sz, cw)
   const double bx = c.q[0], by = c.q[1], bz = c.q[2], bw = c.q[3];
   double q[4] = {cw * bx - sz * by, cw * by + sz * bx, cw * bz + sz * bw, cw * bw - sz * bz};
-  double nn = 0.0;
-  for (int i = 0; i < 4; i++) nn += q[i] * q[i];
-  const double norm = sqrt(nn);
+  const double norm = pose7_norm(q);
   for (int i = 0; i < 4; i++) pose[i] = q[i] / norm;
   pose[4] = c.t[0] + (ix ? ix * s->step_xy : 0.0);
   pose[5] = c.t[1] + (iy ? iy * s->step_xy : 0.0);

@@ -1,5 +1,5 @@
 """Streams with a life of their own: liodom_reset_stream, liodom_export_stream_state, liodom_import_stream_state
-(include/liodom_hip.h, csrc/kernels_state.h) on one-stream, few-stream (streamed rebuild) and lock-step (LDS-built table, k_knn8,
+(include/liodom_hip.h, csrc/kernels_state.h, layout in csrc/stream_state_format.h) on one-stream, few-stream (streamed rebuild) and lock-step (LDS-built table, k_knn8,
 incremental cell hash) handles.
 
   1. one stream of a handle is reset while the others go on: the others are bit-identical to the run without the reset, the reset

@@ -1,19 +1,26 @@
-"""The stream-state blob of liodom_export_stream_state (layout: csrc/kernels_state.h): api.parse_stream_state on a
-blob assembled here from the documented layout, and the four entry points in the header and in the cross-compiled library.
-CPU only; no compute calls."""
+"""The stream-state blob of liodom_export_stream_state (layout: csrc/stream_state_format.h): api.parse_stream_state
+on a blob assembled here from the documented layout, the four entry points in the header and in the cross-compiled library, and
+stream_state_validate as a stand-alone host program (tests/stream_state_validate_main.cc), built plain and under AddressSanitizer +
+UBSan and run as a program: every named case of stream_state_cases.py, every prefix and every flipped byte of header, record and
+counts.  CPU only; no compute calls, nothing sanitized is loaded into Python."""
 import ctypes as C
 import os
 import re
+import shutil
 import struct
+import subprocess
 
 import numpy as np
 import pytest
 
 import liodom_amd as la
 from liodom_amd import api
+import stream_state_cases as ssc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["liodom_reset_stream", "liodom_stream_state_size", "liodom_export_stream_state", "liodom_import_stream_state"]
+SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+_EXE = {}
 
 
 def assemble(P=5, frame_count=7, counts=(3, 1, 0, 2, 4), n_recv=0, mapping=0, use_imu=1, magic=b"LIODOMST", version=1, total=None):
@@ -90,3 +97,77 @@ def test_entry_points_are_declared_and_exported():
     for name in SYMBOLS:
         assert hasattr(L, name), "missing export: " + name
     assert all(hasattr(la.Liodom, m) for m in ("reset_stream", "export_stream_state", "import_stream_state"))
+    for src in ("stream_state_format.h", "pose7.h"):               # a change to either rebuilds the library
+        assert os.path.join(ROOT, "liodom_amd", "csrc", src) in api._SRC
+
+
+# ---- the validator as a program of its own ---------------------------------------------------------------------------------------
+def good_blobs():
+    """(good blob, the handle that takes it): local_map_size 5 (three padding entries behind the counts) and 8 (none), a mapping
+    blob with a received map, and a stream whose window is not full yet.  Capacities somewhat above what the blob needs."""
+    out = []
+    for kw in (dict(), dict(P=8, frame_count=11, counts=(3, 1, 0, 2, 4, 1, 5, 2)), dict(n_recv=3, mapping=1), dict(frame_count=4, counts=(3, 1, 2, 4))):
+        blob = assemble(**kw)[0]
+        mapping = kw.get("mapping", 0)
+        out.append((blob, ssc.Taker(ssc.fingerprint_of(blob), bool(mapping), 6, 4 if mapping else 0)))
+    return out
+
+
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
+def exe(request, tmp_path_factory):
+    cxx = shutil.which("g++")
+    assert cxx, "g++ is needed to build the validator program"
+    if request.param not in _EXE:
+        out = str(tmp_path_factory.mktemp("stream_state") / ("validate_" + request.param))
+        flags = ["-O2"] if request.param == "plain" else ["-O1", "-g"] + SAN
+        r = subprocess.run([cxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off"] + flags +
+                           ["-I", os.path.join(ROOT, "liodom_amd", "csrc"), "-o", out, os.path.join(ROOT, "tests", "stream_state_validate_main.cc")],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        _EXE[request.param] = out
+    return _EXE[request.param]
+
+
+def _args(path, taker):
+    return [str(path)] + [str(x) for x in taker.fingerprint] + [str(int(taker.mapping)), str(taker.edge_cap), str(taker.recv_cap)]
+
+
+def test_validator_judges_every_named_case(exe, tmp_path):
+    seen = set()
+    for g, (good, taker) in enumerate(good_blobs()):
+        for i, c in enumerate(ssc.cases(good, taker)):
+            path = tmp_path / ("%d_%d.blob" % (g, i))
+            path.write_bytes(c.blob)
+            r = subprocess.run([exe, "judge"] + _args(path, c.taker), capture_output=True, text=True, timeout=60)
+            assert r.returncode == 0 and not r.stderr, (c.name, r.stdout, r.stderr)
+            code, _, why = r.stdout.strip().partition(" ")
+            assert int(code) == c.code, (g, c.name, r.stdout)
+            assert (why != "") == (c.code != ssc.OK), (g, c.name, r.stdout)
+            seen.add(c.name)
+    # every case the list can make has been made by one of the good blobs
+    assert {"a count in a padding entry, the sum kept", "count 1 above edge_cap, count 3 negative", "n_recv 1, sizes consistent, mapping off",
+            "n_recv equal to recv_cap", "recv_cap one below n_recv", "n_recv above recv_cap and a wrong sum"} <= seen, sorted(seen)
+
+
+def test_validator_sweeps_prefixes_and_flipped_bytes(exe, tmp_path):
+    for g, (good, taker) in enumerate(good_blobs()):
+        path = tmp_path / ("good_%d.blob" % g)
+        path.write_bytes(good)
+        r = subprocess.run([exe, "sweep"] + _args(path, taker), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and not r.stderr, r.stdout + r.stderr
+        m = re.fullmatch(r"stream_state_validate: (\d+) cases, (\d+) flipped bytes refused, 0 failures", r.stdout.strip())
+        head = 480 + 4 * ((taker.fingerprint[0] + 3) // 4 * 4)
+        assert m and int(m.group(1)) == len(good) + 4 + head, r.stdout
+        # what a flipped byte cannot break: reserved header words (16), the record's 47 doubles, status, has_imu and pad
+        assert int(m.group(2)) == head - 16 - 8 * 47 - 12, r.stdout
+
+
+def test_parse_accepts_every_accepted_case():
+    n = 0
+    for good, taker in good_blobs():
+        for c in ssc.cases(good, taker):
+            if c.code == ssc.OK:
+                st = api.parse_stream_state(c.blob)
+                assert st["total_bytes"] == len(c.blob) and st["local_map_size"] == taker.fingerprint[0], c.name
+                n += 1
+    assert n >= 19
