@@ -20,6 +20,7 @@
 #include "liodom_kernels.h"
 #include "handle_plan.h"
 #include "step_plan.h"
+#include "edge_pipe.h"
 
 using namespace liodom_dev;
 
@@ -52,9 +53,6 @@ struct EventPair { hipEvent_t a, b; int kid; };
 std::atomic<int> g_live_handles{0};      // handles alive in this process (the overlapped second kNN pass is for a GPU one handle has to itself)
 
 struct liodom_handle {
-  liodom_handle() {
-    for (int b = 0; b < kEdgePipeBufs; b++) { ev_free_valid[b] = false; eb_reader[b] = 0u; tk_seq[b] = 0u; }
-  }
   liodom_params_t params;
   liodom_config_t config;
   HandlePlan plan;                   // what liodom_create decided: code paths, capacities (handle_plan.h); safe mode is the only later change
@@ -84,30 +82,20 @@ struct liodom_handle {
   hipStream_t stream_c = nullptr;    // host-fed replay: uploads (a copy engine works beside the extraction kernels of the previous scan)
   hipEvent_t ev_up[3] = {nullptr, nullptr, nullptr};      // staging slot uploaded
   hipEvent_t ev_xdone[3] = {nullptr, nullptr, nullptr};   // extraction that read the staging slot has been issued (recorded on the extraction stream)
-  bool ev_xdone_valid[3] = {false, false, false};
   hipEvent_t ev_edges[kEdgePipeBufs] = {nullptr, nullptr, nullptr};   // edge buffer b written
   hipEvent_t ev_free[kEdgePipeBufs] = {nullptr, nullptr, nullptr};    // odometry finished reading edge buffer b
-  std::atomic<bool> ev_free_valid[kEdgePipeBufs];      // (written by the odometry side, read by the extraction side)
-  int parity = 0;                    // edge buffer of the next scan to enter odometry
-  // pipelined replay without cross-stream events (pipe_flags in DevView; events remain for handles with >= 16 streams and as the fallback):
-  unsigned int ext_seq = 0, odo_seq = 0;                 // extractions issued / odometries enqueued through the pipelined replay
-  unsigned int eb_seq[kEdgePipeBufs] = {0, 0, 0};        // sequence number of the extraction last issued into buffer b
-  std::atomic<unsigned int> eb_reader[kEdgePipeBufs];    // number of the odometry that last read buffer b (0: none to wait for); written by the odometry side
-  // Device-resident hand-off of the two-thread binding (liodom_extract_edges_device on the extraction side fills pipeline buffer
-  // x_next and returns a ticket; liodom_odometry_step_device on the odometry side consumes it): the element of the reference's
-  // feature queue (shared_data.cc:64-89) without the cloud leaving HBM.
-  std::atomic<unsigned int> tk_seq[kEdgePipeBufs];       // 0: slot free, else the sequence number of the extraction it holds; freed by the odometry side
-                                                         // when the pose of that scan has been collected (its odometry has completed)
-  int x_next = 0;                                        // slot of the next liodom_extract_edges_device (extraction side)
-  int odo_fifo[2] = {0, 0}, odo_pending = 0;             // odometry side: slots of the submitted, not yet collected scans (oldest first)
+  // Who may use the three pipeline edge buffers, and what a launch into one has to wait for (edge_pipe.h): the pipelined replay
+  // (flags in device memory, pipe_flags in DevView; events for handles with >= 16 streams and as the fallback) and the device-resident
+  // hand-off of the two-thread binding (liodom_extract_edges_device on the extraction side fills a buffer and returns a ticket,
+  // liodom_odometry_step_device on the odometry side consumes it: the element of the reference's feature queue,
+  // shared_data.cc:64-89, without the cloud leaving HBM).
+  EdgePipe pipe;
   float4* host_edges = nullptr;      // host-mapped mirror of the dense edges of pipeline buffers 0..2 (one-stream handles; DevView::host_edges)
   int4* host_edges_meta = nullptr;
   unsigned int* host_edges_hdr = nullptr;
-  float4* pin_ring = nullptr;        // page-locked scan staging ring [kEdgePipeBufs][max_points]: liodom_scan_buffer hands slots out, pageable scans are copied through it
+  StagingRing pin;                   // page-locked scan staging ring [kEdgePipeBufs][max_points] (hipHostMalloc: pin.base): liodom_scan_buffer hands slots out, pageable scans are copied through it
   std::vector<double> replay_stamps;  // (debug) host time, us since the call began, at which every pose of the last liodom_replay_resident call was collected
   hipEvent_t ev_pin[kEdgePipeBufs] = {nullptr, nullptr, nullptr};     // the upload out of staging slot r has completed
-  bool ev_pin_valid[kEdgePipeBufs] = {false, false, false};
-  int pin_next = 0;
   // Polar scans (liodom_set_polar_geometry; nothing below exists on a handle that never sets one): the geometry's tables on the
   // device, three compact staging slots the blobs are uploaded into (taken in turn), and the page-locked blob ring of the ticket
   // path (liodom_scan_buffer_polar) with the events that tell when an upload has left a ring slot.
@@ -116,17 +104,10 @@ struct liodom_handle {
   void* pol_tables = nullptr;        // device: float4 beam[H], float2 enc[T]
   unsigned char* pol_stage = nullptr;     // device: [kEdgePipeBufs][blob_bytes]
   int pol_stage_next = 0;
-  unsigned char* pol_pin = nullptr;       // host, page-locked: [kEdgePipeBufs][blob_bytes]
+  StagingRing pol_pin;                    // host, page-locked: [kEdgePipeBufs][blob_bytes]
   hipEvent_t ev_polpin[kEdgePipeBufs] = {nullptr, nullptr, nullptr};
-  bool ev_polpin_valid[kEdgePipeBufs] = {false, false, false};
-  int pol_pin_next = 0;
   bool streams_concurrent = true;    // liodom_create's probe: kernels of two streams of this handle ran side by side
-  std::atomic<bool> pipe_active{false};        // scans went through the pipeline edge buffers by ticket since the last drain
-  std::atomic<bool> replay_live{false};        // scans went through them by the pipelined replay since the last drain (their odometries may not have been collected)
   std::atomic<bool> fallback_pending{false};   // a kernel of this handle gave up an in-kernel wait (LIODOM_STATUS_PIPE_TIMEOUT): liodom_reset() switches to events
-  int pf_slot = -1;                  // resident slot whose extraction has been issued ahead
-  bool pf_subset = false;            // ... for the streams of pf_list only (liodom_process_resident_subset); false: for every stream
-  std::vector<int32_t> pf_list;
   long long subset_steps = 0;        // steps that ran over a stream list (liodom_get_modes)
   std::vector<int> last_eb;          // per stream: edge buffer of the stream's most recent scan that entered odometry (inspection)
   hipEvent_t pose_event = nullptr;
@@ -263,18 +244,15 @@ hipStream_t extract_queue(liodom_handle* h) { return h->profiling ? h->stream : 
 // The plain (non-pipelined) entry points run everything on h->stream with edge buffer 0; make
 // sure no extraction issued ahead by the pipelined replay is still in flight.
 int tickets_idle(liodom_handle* h) {      // the plain entry points use pipeline edge buffer 0 themselves
-  for (int b = 0; b < kEdgePipeBufs; b++) {
-    if (h->tk_seq[b].load() != 0u) { g_last_error = "edge tickets of liodom_extract_edges_device are outstanding: consume them with liodom_odometry_step_device first"; return LIODOM_ERR_BUSY; }
-  }
-  return LIODOM_OK;
+  if (h->pipe.tickets_idle()) return LIODOM_OK;
+  g_last_error = "edge tickets of liodom_extract_edges_device are outstanding: consume them with liodom_odometry_step_device first";
+  return LIODOM_ERR_BUSY;
 }
 int drain_pipeline(liodom_handle* h) {
-  const bool replayed = h->replay_live.exchange(false);
-  if (h->pf_slot >= 0 || h->parity != 0 || h->pipe_active.exchange(false) || replayed) {
+  if (h->pipe.needs_drain()) {
     HIP_TRY(hipStreamSynchronize(h->stream_x));
     HIP_TRY(sync_odometry(h));
-    h->pf_slot = -1; h->pf_subset = false; h->parity = 0; h->ev_free_valid[0] = h->ev_free_valid[1] = h->ev_free_valid[2] = false;
-    for (int b = 0; b < kEdgePipeBufs; b++) h->eb_reader[b] = 0;      // (everything has completed: nothing to wait for)
+    h->pipe.drained();
   }
   return LIODOM_OK;
 }
@@ -288,7 +266,7 @@ int enqueue_pipeline_odometry(liodom_handle* h, int eb, unsigned int wait_seq, i
   if (h->plan.use_flags) {
     // no cross-stream events (they cost ~11 us of idle odometry stream per scan, with the host far ahead as well): the
     // first kNN launch waits for the extraction's flag and signals that the previous odometry has completed
-    const unsigned int m = ++h->odo_seq == 0 ? ++h->odo_seq : h->odo_seq;
+    const unsigned int m = h->pipe.odometry_numbered();
     if (h->plan.flag_gate) {
       if (s0 < 0) hipLaunchKernelGGL(k_pipe_gate<true>, dim3(1), dim3(64), 0, h->stream, h->v, s0, eb, wait_seq, m - 1u);
       else hipLaunchKernelGGL(k_pipe_gate<>, dim3(1), dim3(64), 0, h->stream, h->v, s0, eb, wait_seq, m - 1u);
@@ -297,13 +275,13 @@ int enqueue_pipeline_odometry(liodom_handle* h, int eb, unsigned int wait_seq, i
       rc = launch_odometry(h, eb, s0, count, wait_seq, m - 1u, list);
     }
     if (rc) return rc;
-    h->eb_reader[eb] = m;
+    h->pipe.odometry_reads(eb, m);
   } else {
     HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_edges[eb], 0));
     rc = launch_odometry(h, eb, s0, count, 0u, 0u, list);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(h->ev_free[eb], h->stream));
-    h->ev_free_valid[eb] = true;
+    h->pipe.odometry_recorded(eb);
   }
   return LIODOM_OK;
 }
@@ -319,12 +297,11 @@ int issue_extract(liodom_handle* h, int slot, int eb, int n, int height, int wid
   if (h->plan.use_flags) {
     // dependencies through flags in device memory (pipe_wait): the buffer's last reader must have
     // completed before k_compact_edges rewrites it; the last workgroup of k_compact_edges sets the flag of this extraction
-    h->eb_seq[eb] = ++h->ext_seq;
-    if (h->ext_seq == 0) h->eb_seq[eb] = ++h->ext_seq;      // (0 means "nothing to wait for")
-    return launch_extract(h, q, eb, s0, count, in, (size_t)h->v.max_points, n, height, width, h->eb_reader[eb], 0,
-                          h->v.pipe_flags + eb, nullptr, h->eb_seq[eb]);
+    const unsigned int seq = h->pipe.extract_numbered(eb);
+    return launch_extract(h, q, eb, s0, count, in, (size_t)h->v.max_points, n, height, width, h->pipe.eb_reader[eb], 0,
+                          h->v.pipe_flags + eb, nullptr, seq);
   }
-  if (h->ev_free_valid[eb]) HIP_TRY(hipStreamWaitEvent(q, h->ev_free[eb], 0));
+  if (h->pipe.ev_free_valid[eb]) HIP_TRY(hipStreamWaitEvent(q, h->ev_free[eb], 0));
   int rc = launch_extract(h, q, eb, s0, count, in, (size_t)h->v.max_points, n, height, width);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
@@ -365,15 +342,12 @@ int reset_state(liodom_handle* h) {
     hipLaunchKernelGGL(k_init_cells, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->v);
     HIP_TRY(hipGetLastError());
   }
-  h->pf_slot = -1; h->pf_subset = false; h->parity = 0; h->last_eb.assign((size_t)h->S, 0); h->ev_free_valid[0] = h->ev_free_valid[1] = h->ev_free_valid[2] = false;
-  h->replay_live.store(false);
-  h->ext_seq = h->odo_seq = 0;
+  h->last_eb.assign((size_t)h->S, 0);
   h->step.reset();
-  for (int b = 0; b < kEdgePipeBufs; b++) { h->tk_seq[b] = 0u; h->ev_pin_valid[b] = false; h->ev_polpin_valid[b] = false; }      // outstanding edge tickets are void
   if (h->stream_c && !h->stream_c_shared) HIP_TRY(hipStreamSynchronize(h->stream_c));
-  h->x_next = 0; h->odo_pending = 0;
+  h->pipe.reset();      // outstanding edge tickets are void
+  h->pin.uploads_left(); h->pol_pin.uploads_left();
   if (h->host_edges_hdr) std::memset(h->host_edges_hdr, 0, sizeof(unsigned int) * 2 * kEdgePipeBufs);
-  for (int b = 0; b < kEdgePipeBufs; b++) { h->eb_seq[b] = 0; h->eb_reader[b] = 0; }
   HIP_TRY(hipMemsetAsync(h->v.pipe_flags, 0, sizeof(unsigned int) * (kEdgePipeBufs + 1), h->stream));
   HIP_TRY(hipMemsetAsync(h->v.lm_xch, 0, sizeof(unsigned long long) * (size_t)h->S * 2 * kLmGroupsMax * 64, h->stream));
   HIP_TRY(hipMemsetAsync(h->v.pose_xch, 0, sizeof(unsigned long long) * (size_t)h->S * 64, h->stream));
@@ -706,10 +680,10 @@ void liodom_destroy(liodom_handle_t* h) {
   if (h->host_edges) hipHostFree(h->host_edges);
   if (h->host_edges_meta) hipHostFree(h->host_edges_meta);
   if (h->host_edges_hdr) hipHostFree(h->host_edges_hdr);
-  if (h->pin_ring) hipHostFree(h->pin_ring);
+  if (h->pin.base) hipHostFree(h->pin.base);
   if (h->pol_tables) hipFree(h->pol_tables);
   if (h->pol_stage) hipFree(h->pol_stage);
-  if (h->pol_pin) hipHostFree(h->pol_pin);
+  if (h->pol_pin.base) hipHostFree(h->pol_pin.base);
   for (int b = 0; b < kEdgePipeBufs; b++) { if (h->ev_polpin[b]) hipEventDestroy(h->ev_polpin[b]); }
   if (h->state_stage_host) hipHostFree(h->state_stage_host);
   for (int b = 0; b < kEdgePipeBufs; b++) { if (h->ev_pin[b]) hipEventDestroy(h->ev_pin[b]); }
@@ -764,8 +738,8 @@ static StateBlobHeader state_fingerprint(const liodom_handle* h) {
 }
 // Everything of stream `stream` but its edge buffers becomes what `blob` (device staging; null: a stream that never ran) says, and
 // the structure its next scan searches is rebuilt from the window for the variant this handle runs.  Streams are idle (state_quiesce).
-// Left alone: the handle-wide pipeline state (pf_slot, parity, edge buffers, eb_seq / eb_reader, ext_seq / odo_seq, pipe_flags):
-// an extraction issued ahead stays valid for every stream.
+// Left alone: the handle-wide pipeline state (EdgePipe, edge_pipe.h; the edge buffers and pipe_flags on the device): an extraction
+// issued ahead stays valid for every stream.
 static int install_stream_state(liodom_handle* h, int stream, const unsigned char* blob, int n_frames, int scan_counter, int n_recv = 0) {
   const DevView& v = h->v;
   const size_t S = (size_t)h->S, s = (size_t)stream;
@@ -1021,11 +995,52 @@ int liodom_odometry_step(liodom_handle_t* h, int stream, const float* edges_xyzi
 }
 
 // ---- device-resident hand-off between the two sides (the reference's feature queue without the cloud leaving HBM) ----
+// The HIP half of a page-locked staging ring (StagingRing, edge_pipe.h; ev: its three events), for XYZI scans (h->pin) and for polar
+// blobs (h->pol_pin) alike.  Extraction side (mx_x held).
+// The upload that last read slot r (three scans ago) must have left it.
+static int ring_slot_wait(StagingRing& ring, hipEvent_t* ev, int r) {
+  if (ring.valid[r]) { HIP_TRY(hipEventSynchronize(ev[r])); ring.valid[r] = false; }
+  return LIODOM_OK;
+}
+// liodom_scan_buffer*: the slot the caller assembles the next scan in.
+static int ring_hand_out(StagingRing& ring, hipEvent_t* ev, void** out) {
+  if (int rc = ring_slot_wait(ring, ev, ring.next)) return rc;
+  *out = ring.slot(ring.next);
+  return LIODOM_OK;
+}
+// Where the upload of `bytes` at *src starts from.  An upload is asynchronous when it starts from page-locked memory: a slot of the
+// ring itself (liodom_scan_buffer*), or a buffer the caller registered (liodom_pin_host_buffer) — which must stay untouched until
+// liodom_wait_edges / liodom_odometry_step_device of the ticket has returned.  A pageable source is copied through the ring (*src
+// then points into it).  *used: the ring slot the upload reads, -1 for a registered buffer; ring_uploaded takes it.
+static int ring_source(StagingRing& ring, hipEvent_t* ev, const void** src, size_t bytes, int* used) {
+  const int own = ring.owns(*src);
+  bool pinned = own >= 0;
+  if (!pinned) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, *src) == hipSuccess) pinned = attr.type == hipMemoryTypeHost;
+    else (void)hipGetLastError();                    // (unregistered pageable memory: not an error)
+  }
+  *used = ring.source_slot(own, pinned);
+  if (!pinned) {
+    if (int rc = ring_slot_wait(ring, ev, *used)) return rc;
+    std::memcpy(ring.slot(*used), *src, bytes);
+    *src = ring.slot(*used);
+  }
+  return LIODOM_OK;
+}
+// The upload has been enqueued on q: the ring slot it reads may be refilled once it has left it.
+static int ring_uploaded(StagingRing& ring, hipEvent_t* ev, int used, hipStream_t q) {
+  if (used < 0) return LIODOM_OK;
+  HIP_TRY(hipEventRecord(ev[used], q));
+  ring.upload_recorded(used);
+  return LIODOM_OK;
+}
+
 static int ensure_pin_ring(liodom_handle* h) {
-  if (h->pin_ring) return LIODOM_OK;
+  if (h->pin.base) return LIODOM_OK;
   void* p = nullptr;
   HIP_TRY(hipHostMalloc(&p, sizeof(float4) * (size_t)kEdgePipeBufs * (size_t)h->v.max_points, hipHostMallocDefault));
-  h->pin_ring = static_cast<float4*>(p);
+  h->pin.bind(p, sizeof(float4) * (size_t)h->v.max_points);
   for (int b = 0; b < kEdgePipeBufs; b++) HIP_TRY(hipEventCreateWithFlags(&h->ev_pin[b], hipEventDisableTiming));
   return LIODOM_OK;
 }
@@ -1037,45 +1052,40 @@ int liodom_scan_buffer(liodom_handle_t* h, int stream, float** xyzi, int64_t* ca
   if (h->S != 1) { g_last_error = "liodom_scan_buffer: one-stream handles only"; return LIODOM_ERR_UNSUPPORTED; }
   SideLocks lk(h, false, true);
   if ((rc = ensure_pin_ring(h))) return rc;
-  const int r = h->pin_next;
-  // the upload that last read this slot (three scans ago) must have left it
-  if (h->ev_pin_valid[r]) { HIP_TRY(hipEventSynchronize(h->ev_pin[r])); h->ev_pin_valid[r] = false; }
-  *xyzi = reinterpret_cast<float*>(h->pin_ring + (size_t)r * h->v.max_points);
+  if ((rc = ring_hand_out(h->pin, h->ev_pin, reinterpret_cast<void**>(xyzi)))) return rc;
   if (capacity_points) *capacity_points = h->v.max_points;
   return LIODOM_OK;
 }
 
 // The two ends of liodom_extract_edges_device that its polar form shares.  Extraction side (mx_x held).
-// Is the hand-off slot of the next extraction free?
+// Is the hand-off slot of the next extraction free?  (EdgePipe::ticket_slot says why each refusal is what it is.)
 static int ticket_slot_free(liodom_handle* h) {
-  if (h->pf_slot >= 0) { g_last_error = "edge extraction by ticket: a pipelined replay of this handle has an extraction issued ahead: call liodom_sync() first"; return LIODOM_ERR_NEEDS_SYNC; }
-  // The pipelined replay uses the same three edge buffers (h->parity) and may have odometries in flight that nobody has collected
-  // (liodom_process_resident_pipelined without read-back): this extraction would rewrite a buffer under them (wait_odo = 0 below
-  // relies on the ticket discipline: a slot is refilled only after its pose has been collected).
-  if (h->replay_live.load()) { g_last_error = "edge extraction by ticket: scans of a pipelined replay (liodom_process_resident / liodom_replay_*) are still in the edge buffers: call liodom_sync() first"; return LIODOM_ERR_NEEDS_SYNC; }      // (not BUSY: a caller that keeps the cloud and retries would spin forever)
-  if (h->tk_seq[h->x_next].load() != 0u) {
-    g_last_error = "edge extraction by ticket: all hand-off slots hold edge clouds no liodom_odometry_step_device has taken yet";
-    return LIODOM_ERR_BUSY;
+  switch (h->pipe.ticket_slot()) {
+    case kSlotFree: return LIODOM_OK;
+    case kSlotExtractionAhead:
+      g_last_error = "edge extraction by ticket: a pipelined replay of this handle has an extraction issued ahead: call liodom_sync() first";
+      return LIODOM_ERR_NEEDS_SYNC;
+    case kSlotReplayLive:      // (not BUSY: a caller that keeps the cloud and retries would spin forever)
+      g_last_error = "edge extraction by ticket: scans of a pipelined replay (liodom_process_resident / liodom_replay_*) are still in the edge buffers: call liodom_sync() first";
+      return LIODOM_ERR_NEEDS_SYNC;
+    case kSlotsFull: break;
   }
-  return LIODOM_OK;
+  g_last_error = "edge extraction by ticket: all hand-off slots hold edge clouds no liodom_odometry_step_device has taken yet";
+  return LIODOM_ERR_BUSY;
 }
 // The extraction of the cloud at `in` (device, its upload or projection enqueued on q) into the free hand-off slot, and its ticket.
 static int ticket_extract(liodom_handle* h, hipStream_t q, int stream, const float4* in, int n, int height, int width, liodom_edge_ticket_t* ticket) {
-  const int eb = h->x_next;
-  unsigned int seq = ++h->ext_seq;
-  if (seq == 0u) seq = ++h->ext_seq;                 // (0 means "nothing to wait for")
+  const EdgeTicketDraft t = h->pipe.ticket_draft();
+  const int eb = t.slot;
   unsigned int* host_seq = h->v.host_edges_hdr ? h->v.host_edges_hdr + eb : nullptr;
   // (the slot is free: the odometry that last read buffer eb has been collected, i.e. has completed — no wait on the device,
   //  which would depend on when the other thread submits its next scan)
   unsigned int* const dev_flag = h->plan.use_flags ? h->v.pipe_flags + eb : (unsigned int*)nullptr;
-  int rc = launch_extract(h, q, eb, stream, 1, in, 0, n, height, width, 0u, 1, dev_flag, host_seq, seq);
+  int rc = launch_extract(h, q, eb, stream, 1, in, 0, n, height, width, 0u, 1, dev_flag, host_seq, t.seq);
   if (rc) return rc;
   if (!h->plan.use_flags) HIP_TRY(hipEventRecord(h->ev_edges[eb], q));
-  h->eb_seq[eb] = seq;
-  h->pipe_active.store(true);
-  h->tk_seq[eb].store(seq);
-  h->x_next = (eb + 1) % kEdgePipeBufs;
-  ticket->seq = seq; ticket->slot = eb; ticket->stream = stream; ticket->reserved = 0;
+  h->pipe.ticket_issued(t);
+  ticket->seq = t.seq; ticket->slot = eb; ticket->stream = stream; ticket->reserved = 0;
   return LIODOM_OK;
 }
 
@@ -1092,31 +1102,12 @@ int liodom_extract_edges_device(liodom_handle_t* h, int stream, const float* xyz
   hipStream_t q = extract_queue(h);
   float4* in = h->stage_in + (size_t)stream * h->v.max_points;
   if (n) {
-    // The scan's upload is asynchronous when it starts from page-locked memory: a slot of the handle's own ring
-    // (liodom_scan_buffer), or a buffer the caller registered (liodom_pin_host_buffer) — which must stay untouched until
-    // liodom_wait_edges / liodom_odometry_step_device of this ticket has returned.  A pageable scan is copied through the ring.
     if ((rc = ensure_pin_ring(h))) return rc;
-    const char* lo = reinterpret_cast<const char*>(h->pin_ring);
-    const char* hi = lo + sizeof(float4) * (size_t)kEdgePipeBufs * (size_t)h->v.max_points;
-    const char* src = reinterpret_cast<const char*>(xyzi);
-    bool own = src >= lo && src < hi, pinned = own;
-    if (!own) {
-      hipPointerAttribute_t attr;
-      if (hipPointerGetAttributes(&attr, xyzi) == hipSuccess) pinned = attr.type == hipMemoryTypeHost;
-      else (void)hipGetLastError();                  // (unregistered pageable memory: not an error)
-    }
-    const int r = own ? (int)((src - lo) / (sizeof(float4) * (size_t)h->v.max_points)) : h->pin_next;
-    if (!pinned) {
-      if (h->ev_pin_valid[r]) { HIP_TRY(hipEventSynchronize(h->ev_pin[r])); h->ev_pin_valid[r] = false; }
-      std::memcpy(h->pin_ring + (size_t)r * h->v.max_points, xyzi, sizeof(float4) * (size_t)n);
-      xyzi = reinterpret_cast<const float*>(h->pin_ring + (size_t)r * h->v.max_points);
-    }
-    HIP_TRY(hipMemcpyAsync(in, xyzi, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, q));
-    if (own || !pinned) {                            // the page-locked ring slot may be refilled once this upload has left it
-      HIP_TRY(hipEventRecord(h->ev_pin[r], q));
-      h->ev_pin_valid[r] = true;
-      h->pin_next = (r + 1) % kEdgePipeBufs;
-    }
+    const void* src = xyzi;
+    int used = -1;
+    if ((rc = ring_source(h->pin, h->ev_pin, &src, sizeof(float4) * (size_t)n, &used))) return rc;
+    HIP_TRY(hipMemcpyAsync(in, src, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, q));
+    if ((rc = ring_uploaded(h->pin, h->ev_pin, used, q))) return rc;
   }
   return ticket_extract(h, q, stream, in, (int)n, height, width, ticket);
 }
@@ -1165,16 +1156,19 @@ int liodom_odometry_submit_device(liodom_handle_t* h, const liodom_edge_ticket_t
   const int eb = ticket->slot;
   if (h->S != 1 || eb < 0 || eb >= kEdgePipeBufs) { g_last_error = "liodom_odometry_submit_device: bad ticket"; return LIODOM_ERR_INVALID_ARG; }
   SideLocks lk(h, true, false);                      // odometry side only: safe beside a concurrent liodom_extract_edges_device
-  if (ticket->seq == 0u || h->tk_seq[eb].load() != ticket->seq) {
-    g_last_error = "liodom_odometry_submit_device: stale or unknown ticket (already consumed, or voided by liodom_reset)";
-    return LIODOM_ERR_INVALID_ARG;
+  switch (h->pipe.submit_check(ticket->seq, eb)) {
+    case kSubmitOk: break;
+    case kSubmitStale:
+      g_last_error = "liodom_odometry_submit_device: stale or unknown ticket (already consumed, or voided by liodom_reset)";
+      return LIODOM_ERR_INVALID_ARG;
+    case kSubmitAlready: g_last_error = "liodom_odometry_submit_device: ticket already submitted"; return LIODOM_ERR_INVALID_ARG;
+    case kSubmitTwoInFlight:
+      g_last_error = "liodom_odometry_submit_device: two scans are in flight: collect a pose first (liodom_odometry_collect)";
+      return LIODOM_ERR_BUSY;
   }
-  for (int i = 0; i < h->odo_pending; i++) if (h->odo_fifo[i] == eb) { g_last_error = "liodom_odometry_submit_device: ticket already submitted"; return LIODOM_ERR_INVALID_ARG; }
-  if (h->odo_pending >= 2) { g_last_error = "liodom_odometry_submit_device: two scans are in flight: collect a pose first (liodom_odometry_collect)"; return LIODOM_ERR_BUSY; }
   rc = enqueue_pipeline_odometry(h, eb, ticket->seq);
   if (rc) return rc;
-  h->pipe_active.store(true);
-  h->odo_fifo[h->odo_pending++] = eb;
+  h->pipe.submitted(eb);
   return LIODOM_OK;
 }
 
@@ -1182,22 +1176,34 @@ int liodom_odometry_collect(liodom_handle_t* h, int stream, double* pose_out, li
   int rc = check_stream(h, stream);
   if (rc) return rc;
   SideLocks lk(h, true, false);
-  if (h->odo_pending <= 0) { g_last_error = "liodom_odometry_collect: no scan has been submitted"; return LIODOM_ERR_INVALID_ARG; }
-  rc = wait_pose(h, stream, 1, pose_out, info, h->odo_pending - 1);      // the oldest of the (at most two) scans in flight
-  const int eb = h->odo_fifo[0];
-  h->odo_fifo[0] = h->odo_fifo[1];
-  h->odo_pending--;
-  h->tk_seq[eb].store(0u);                           // its odometry has completed: the slot may be refilled
+  const int lag = h->pipe.collect_lag();
+  if (lag < 0) { g_last_error = "liodom_odometry_collect: no scan has been submitted"; return LIODOM_ERR_INVALID_ARG; }
+  rc = wait_pose(h, stream, 1, pose_out, info, lag);      // the oldest of the (at most two) scans in flight
+  h->pipe.collected();
   return rc;
 }
 
 int liodom_odometry_step_device(liodom_handle_t* h, const liodom_edge_ticket_t* ticket, double stamp, double* pose_out,
                                 liodom_step_info_t* info) {
   if (!h || !ticket) return LIODOM_ERR_INVALID_ARG;
-  if (h->odo_pending != 0) { g_last_error = "liodom_odometry_step_device: a submitted scan has not been collected (liodom_odometry_collect)"; return LIODOM_ERR_BUSY; }
+  if (h->pipe.odo_pending != 0) { g_last_error = "liodom_odometry_step_device: a submitted scan has not been collected (liodom_odometry_collect)"; return LIODOM_ERR_BUSY; }
   const int rc = liodom_odometry_submit_device(h, ticket, stamp);
   if (rc) return rc;
   return liodom_odometry_collect(h, ticket->stream, pose_out, info);
+}
+
+// liodom_process_scan and its polar form.  Both take the two sides — they use the extraction scratch on the odometry stream — and
+// start with scan_alone; once the cloud is on its way into the stream's staging block on the odometry stream, scan_tail does the rest.
+static int scan_alone(liodom_handle* h) {
+  if (int rc = tickets_idle(h)) return rc;
+  return drain_pipeline(h);           // nothing issued ahead on the extraction stream may still use that scratch
+}
+static int scan_tail(liodom_handle* h, int stream, int n, int height, int width, double* pose_out, liodom_step_info_t* info) {
+  int rc = launch_extract(h, h->stream, 0, stream, 1, h->stage_in + (size_t)stream * h->v.max_points, 0, n, height, width);
+  if (rc) return rc;
+  rc = launch_odometry(h, 0, stream, 1);
+  if (rc) return rc;
+  return wait_pose(h, stream, 1, pose_out, info);
 }
 
 int liodom_process_scan(liodom_handle_t* h, int stream, const float* xyzi, int64_t n, int height,
@@ -1207,17 +1213,10 @@ int liodom_process_scan(liodom_handle_t* h, int stream, const float* xyzi, int64
   if (rc) return rc;
   if ((rc = check_usable(h))) return rc;
   if (n < 0 || n > h->v.max_points || (n > 0 && !xyzi)) { g_last_error = "bad point count"; return LIODOM_ERR_CAPACITY; }
-  SideLocks lk(h, true, true);        // uses the extraction scratch on the odometry stream
-  if ((rc = tickets_idle(h))) return rc;
-  rc = drain_pipeline(h);             // nothing issued ahead on the extraction stream may still use that scratch
-  if (rc) return rc;
-  float4* in = h->stage_in + (size_t)stream * h->v.max_points;
-  if (n) HIP_TRY(hipMemcpyAsync(in, xyzi, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-  rc = launch_extract(h, h->stream, 0, stream, 1, in, 0, (int)n, height, width);
-  if (rc) return rc;
-  rc = launch_odometry(h, 0, stream, 1);
-  if (rc) return rc;
-  return wait_pose(h, stream, 1, pose_out, info);
+  SideLocks lk(h, true, true);
+  if ((rc = scan_alone(h))) return rc;
+  if (n) HIP_TRY(hipMemcpyAsync(h->stage_in + (size_t)stream * h->v.max_points, xyzi, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  return scan_tail(h, stream, (int)n, height, width, pose_out, info);
 }
 
 // ---- polar scans: the sensor's counts go up, the projection to XYZI runs on the device (kernels_polar.h) ----
@@ -1280,13 +1279,13 @@ int liodom_set_polar_geometry(liodom_handle_t* h, const liodom_polar_geometry_t*
   }
   if (h->pol_tables) (void)hipFree(h->pol_tables);
   if (h->pol_stage) (void)hipFree(h->pol_stage);
-  if (h->pol_pin) (void)hipHostFree(h->pol_pin);
-  h->pol_tables = tables; h->pol_stage = static_cast<unsigned char*>(stage); h->pol_pin = static_cast<unsigned char*>(pin);
+  if (h->pol_pin.base) (void)hipHostFree(h->pol_pin.base);
+  h->pol_tables = tables; h->pol_stage = static_cast<unsigned char*>(stage);
+  h->pol_pin.bind(pin, (size_t)pv.blob_bytes);      // (a new ring: it starts at slot 0 with no upload to wait for)
   pv.beam = static_cast<const float4*>(tables);
   pv.enc = reinterpret_cast<const float2*>(static_cast<const unsigned char*>(tables) + beam_bytes);
   h->pol = pv;
-  h->pol_stage_next = 0; h->pol_pin_next = 0;
-  for (int b = 0; b < kEdgePipeBufs; b++) h->ev_polpin_valid[b] = false;
+  h->pol_stage_next = 0;
   h->polar = true;
   return LIODOM_OK;
 }
@@ -1341,16 +1340,10 @@ int liodom_process_scan_polar(liodom_handle_t* h, int stream, const void* blob, 
   if (rc) return rc;
   if ((rc = check_usable(h))) return rc;
   if ((rc = polar_ready(h, blob))) return rc;
-  SideLocks lk(h, true, true);        // as liodom_process_scan: the extraction scratch on the odometry stream
-  if ((rc = tickets_idle(h))) return rc;
-  if ((rc = drain_pipeline(h))) return rc;
-  float4* in = h->stage_in + (size_t)stream * h->v.max_points;
-  if ((rc = polar_upload_project(h, h->stream, blob, in))) return rc;
-  rc = launch_extract(h, h->stream, 0, stream, 1, in, 0, h->pol.n, h->pol.H, h->pol.W);
-  if (rc) return rc;
-  rc = launch_odometry(h, 0, stream, 1);
-  if (rc) return rc;
-  return wait_pose(h, stream, 1, pose_out, info);
+  SideLocks lk(h, true, true);
+  if ((rc = scan_alone(h))) return rc;
+  if ((rc = polar_upload_project(h, h->stream, blob, h->stage_in + (size_t)stream * h->v.max_points))) return rc;
+  return scan_tail(h, stream, h->pol.n, h->pol.H, h->pol.W, pose_out, info);
 }
 
 int liodom_scan_buffer_polar(liodom_handle_t* h, int stream, void** blob, int64_t* bytes) {
@@ -1360,10 +1353,7 @@ int liodom_scan_buffer_polar(liodom_handle_t* h, int stream, void** blob, int64_
   if (!h->polar) { g_last_error = "no polar geometry has been set (liodom_set_polar_geometry)"; return LIODOM_ERR_UNSUPPORTED; }
   if (h->S != 1) { g_last_error = "liodom_scan_buffer_polar: one-stream handles only"; return LIODOM_ERR_UNSUPPORTED; }
   SideLocks lk(h, false, true);
-  const int r = h->pol_pin_next;
-  // the upload that last read this slot (three scans ago) must have left it
-  if (h->ev_polpin_valid[r]) { HIP_TRY(hipEventSynchronize(h->ev_polpin[r])); h->ev_polpin_valid[r] = false; }
-  *blob = h->pol_pin + (size_t)r * (size_t)h->pol.blob_bytes;
+  if ((rc = ring_hand_out(h->pol_pin, h->ev_polpin, blob))) return rc;
   if (bytes) *bytes = h->pol.blob_bytes;
   return LIODOM_OK;
 }
@@ -1378,32 +1368,11 @@ int liodom_extract_edges_device_polar(liodom_handle_t* h, int stream, const void
   SideLocks lk(h, false, true);
   if ((rc = ticket_slot_free(h))) return rc;
   hipStream_t q = extract_queue(h);
-  // The source rules of liodom_extract_edges_device: a slot of the handle's own blob ring or a registered buffer is read
-  // asynchronously where it lies (and stays untouched until the ticket's edges or pose have been returned); a pageable blob is
-  // copied through the ring.
-  const size_t bb = (size_t)h->pol.blob_bytes;
-  const unsigned char* lo = h->pol_pin;
-  const unsigned char* src = static_cast<const unsigned char*>(blob);
-  const bool own = src >= lo && src < lo + (size_t)kEdgePipeBufs * bb;
-  bool pinned = own;
-  if (!own) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, blob) == hipSuccess) pinned = attr.type == hipMemoryTypeHost;
-    else (void)hipGetLastError();                    // (unregistered pageable memory: not an error)
-  }
-  const int r = own ? (int)((size_t)(src - lo) / bb) : h->pol_pin_next;
-  if (!pinned) {
-    if (h->ev_polpin_valid[r]) { HIP_TRY(hipEventSynchronize(h->ev_polpin[r])); h->ev_polpin_valid[r] = false; }
-    std::memcpy(h->pol_pin + (size_t)r * bb, blob, bb);
-    blob = h->pol_pin + (size_t)r * bb;
-  }
+  int used = -1;      // (the source rules of liodom_extract_edges_device, over the blob ring)
+  if ((rc = ring_source(h->pol_pin, h->ev_polpin, &blob, (size_t)h->pol.blob_bytes, &used))) return rc;
   float4* in = h->stage_in + (size_t)stream * h->v.max_points;
   if ((rc = polar_upload_project(h, q, blob, in))) return rc;
-  if (own || !pinned) {                              // the ring slot may be refilled once this upload has left it
-    HIP_TRY(hipEventRecord(h->ev_polpin[r], q));
-    h->ev_polpin_valid[r] = true;
-    h->pol_pin_next = (r + 1) % kEdgePipeBufs;
-  }
+  if ((rc = ring_uploaded(h->pol_pin, h->ev_polpin, used, q))) return rc;
   return ticket_extract(h, q, stream, in, h->pol.n, h->pol.H, h->pol.W, ticket);
 }
 
@@ -1676,7 +1645,7 @@ int liodom_alloc_resident(liodom_handle_t* h, int n_slots) {
   SideLocks lk(h, true, true);
   HIP_TRY(hipStreamSynchronize(h->stream_x));       // an extraction issued ahead may still read the old buffer
   HIP_TRY(sync_odometry(h));
-  h->pf_slot = -1; h->pf_subset = false;
+  h->pipe.ahead_clear();
   if (h->resident) { hipFree(h->resident); h->resident = nullptr; h->n_slots = 0; }
   const size_t bytes = sizeof(float4) * (size_t)h->S * (size_t)n_slots * (size_t)h->v.max_points;
   void* raw = nullptr;
@@ -1752,7 +1721,7 @@ static int upload_slot_async(liodom_handle_t* h, int slot, const float* host, in
     }
   }
   hipStream_t q = extract_queue(h);
-  if (h->ev_xdone_valid[r]) HIP_TRY(hipStreamWaitEvent(h->stream_c, h->ev_xdone[r], 0));
+  if (h->pipe.xdone_valid[r]) HIP_TRY(hipStreamWaitEvent(h->stream_c, h->ev_xdone[r], 0));
   for (int s = 0; s < h->S && n > 0; s++) {
     float4* dst = h->resident + ((size_t)slot * h->S + s) * (size_t)h->v.max_points;
     HIP_TRY(hipMemcpyAsync(dst, host + (size_t)s * (size_t)stride, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, h->stream_c));
@@ -1764,7 +1733,7 @@ static int upload_slot_async(liodom_handle_t* h, int slot, const float* host, in
 static int upload_slot_consumed(liodom_handle_t* h, int slot) {      // call right after the slot's extraction has been issued
   const int r = slot % 3;
   HIP_TRY(hipEventRecord(h->ev_xdone[r], extract_queue(h)));
-  h->ev_xdone_valid[r] = true;
+  h->pipe.xdone_valid[r] = true;
   return LIODOM_OK;
 }
 
@@ -1779,26 +1748,24 @@ static int step_resident(liodom_handle_t* h, int slot, const int32_t* streams, i
     g_last_error = "bad resident slot"; return LIODOM_ERR_INVALID_ARG;
   }
   // resident layout: [slot][stream][max_points]: one lock-step launch reads a contiguous block
-  h->replay_live.store(true);
+  EdgePipe& pipe = h->pipe;
+  const int eb = pipe.replay_buffer();
   const bool full = n_active == h->S, next_full = n_next == h->S;
   int rc;
   if (n_active > 0) {
-    const int eb = h->parity;
     // issued ahead for exactly these streams?  Anything else — another slot, another list, nothing — is extracted now
-    const bool ahead = h->pf_slot == slot && (full ? !h->pf_subset
-                                                   : (h->pf_subset && (int)h->pf_list.size() == n_active && std::equal(streams, streams + n_active, h->pf_list.begin())));
-    if (!ahead) { rc = issue_extract_list(h, slot, eb, (int)n, height, width, streams, n_active); if (rc) return rc; }
-    h->pf_slot = -1; h->pf_subset = false;
+    if (!pipe.ahead_matches(slot, streams, n_active, h->S)) { rc = issue_extract_list(h, slot, eb, (int)n, height, width, streams, n_active); if (rc) return rc; }
+    pipe.ahead_clear();
     if (full) {
-      rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb]);
+      rc = enqueue_pipeline_odometry(h, eb, pipe.eb_seq[eb]);
     } else {
       // (list kEdgePipeBufs + eb, uploaded on the odometry stream behind the previous odometry of buffer eb)
       rc = put_stream_list(h, h->stream, kEdgePipeBufs + eb, streams, n_active);
       if (rc) return rc;
-      rc = enqueue_pipeline_odometry(h, eb, h->eb_seq[eb], -(kEdgePipeBufs + eb) - 1, n_active, streams);
+      rc = enqueue_pipeline_odometry(h, eb, pipe.eb_seq[eb], -(kEdgePipeBufs + eb) - 1, n_active, streams);
     }
     if (rc) return rc;
-    h->parity = (eb + 1) % kEdgePipeBufs;
+    pipe.replay_advance();
   }
   if (!(full && (next_slot < 0 || next_full))) h->subset_steps++;      // (liodom_get_modes: steps that were not the plain step)
   if (next_slot >= 0) {                           // overlap the next scan's (upload and) extraction with this odometry
@@ -1806,10 +1773,9 @@ static int step_resident(liodom_handle_t* h, int slot, const int32_t* streams, i
     // (a gate in front of the next scan's extraction — start it when this scan's first solve starts, so that it runs beside the
     //  solves instead of beside the first kNN pass — was measured: -1.6 %; removed)
     // (an extraction issued ahead earlier and not consumed — n_active == 0 — is replaced: same buffer, same HIP stream)
-    if (n_next > 0) { rc = issue_extract_list(h, next_slot, h->parity, (int)n, height, width, next_streams, n_next); if (rc) return rc; }
+    if (n_next > 0) { rc = issue_extract_list(h, next_slot, pipe.parity, (int)n, height, width, next_streams, n_next); if (rc) return rc; }
     if (next_host) { rc = upload_slot_consumed(h, next_slot); if (rc) return rc; }
-    h->pf_slot = next_slot; h->pf_subset = !next_full;
-    if (!next_full) h->pf_list.assign(next_streams, next_streams + n_next);
+    pipe.ahead_set(next_slot, next_streams, n_next, h->S);
   }
   if (wait && n_active > 0) return wait_pose(h, full ? 0 : -1, n_active, poses_out, infos_out, 0, full ? nullptr : streams);
   return LIODOM_OK;
@@ -1918,9 +1884,9 @@ int liodom_replay_host(liodom_handle_t* h, const float* xyzi_base, int64_t scan_
     if (i == 0) {                                 // first scan: upload + extraction now
       int rc1 = upload_slot_async(h, slot, src(0), scan_stride_floats, n);
       if (rc1) return rc1;
-      rc1 = issue_extract(h, slot, h->parity, (int)n, height, width);
+      rc1 = issue_extract(h, slot, h->pipe.parity, (int)n, height, width);
       if (rc1) return rc1;
-      h->pf_slot = slot; h->pf_subset = false;
+      h->pipe.ahead_set(slot, nullptr, h->S, h->S);
       rc1 = upload_slot_consumed(h, slot);
       if (rc1) return rc1;
     }
@@ -1928,7 +1894,7 @@ int liodom_replay_host(liodom_handle_t* h, const float* xyzi_base, int64_t scan_
   });
   if (rc) return rc;
   if (h->stream_c) HIP_TRY(hipStreamSynchronize(h->stream_c));
-  for (int b = 0; b < 3; b++) h->ev_xdone_valid[b] = false;
+  for (int b = 0; b < 3; b++) h->pipe.xdone_valid[b] = false;
   return drain_pipeline(h);                       // the caller's buffer may be reused / unpinned after the return
 }
 
@@ -1952,7 +1918,7 @@ int liodom_sync(liodom_handle_t* h) {
   if (h->stream_k) HIP_TRY(hipStreamSynchronize(h->stream_k));
   // everything has completed: unless an extraction has been issued ahead for the replay's next scan, the pipeline edge buffers
   // are free again (for the ticket API, or for a replay that starts over at buffer 0)
-  if (h->pf_slot < 0) return drain_pipeline(h);
+  if (h->pipe.pf_slot < 0) return drain_pipeline(h);
   return LIODOM_OK;
 }
 
