@@ -17,7 +17,7 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h",
                                                   "kernels_places.h", "liodom_places_host.h", "place_state_format.h",
                                                   "kernels_graph.h", "liodom_graph_host.h", "graph_csr.h",
-                                                  "liodom_sizes.h", "handle_plan.h", "step_plan.h", "edge_pipe.h", "liodom_step_host.h")] + [
+                                                  "liodom_sizes.h", "handle_plan.h", "step_plan.h", "edge_pipe.h", "map_attach.h", "liodom_step_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",

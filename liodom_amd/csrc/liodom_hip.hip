@@ -21,6 +21,7 @@
 #include "handle_plan.h"
 #include "step_plan.h"
 #include "edge_pipe.h"
+#include "map_attach.h"
 
 using namespace liodom_dev;
 
@@ -124,25 +125,18 @@ struct liodom_handle {
   std::vector<void*> allocs;
   // profiling
   std::atomic<bool> profiling{false};   // read without a lock by SideLocks / extract_queue, written under both mutexes
-  std::vector<liodom_map*> mappers;   // per stream: attached device map (mapping replay) or null
-  std::vector<liodom_mapper_options_t> mapper_opts;   // per stream: what its mapper was attached with (liodom_attach_mapper_ex)
-  // lagged mappers (lag = 1; all null / 0 until the first such attach): per stream, the frame the step's append overwrites
+  // which map each stream writes (mapping replay) or reads (localising in a map it never writes; a step enqueues one
+  // k_map_local_rows launch per distinct map over the step's rows), and with hits on or off: map_attach.h.  Below, the device
+  // words that mirror it, each null until first used.
+  StreamMaps<liodom_map, liodom_mapper_options_t> maps;
+  // lagged mappers (lag = 1; from the first such attach on): per stream, the frame the step's append overwrites
   float4* lag_stash = nullptr;        // [S][edge_cap]
   int* lag_stash_n = nullptr;         // [S] its points (0 while the window is not full)
   int* lag_on = nullptr;              // [S] the stream has a lagged mapper (read by k_window_stash)
-  int n_lagged = 0;                   // streams with a lagged mapper
-  // map readers (liodom_attach_map_reader; all empty / null until the first such attach): streams that localise in a map they
-  // never write.  A step enqueues one k_map_local_rows launch per distinct map over the step's rows.
-  std::vector<liodom_map*> readers;   // per stream: the map it reads, or null
-  std::vector<int> reader_xy, reader_z;   // per stream: getLocalMap extents of its reader
-  std::vector<liodom_map*> read_maps; // distinct maps with readers; a map's tag is its index + 1 (freed places are null and taken again)
-  int4* reader_sel = nullptr;         // [S] device: {tag of the map the stream reads (0: none), cells_xy, cells_z, 0}
-  int n_readers = 0;                  // streams with a reader
-  // per-scan map-hit records (liodom_set_map_hits; all null / empty until the first enabling call)
+  int4* reader_sel = nullptr;         // [S] from the first reader on: {tag of the map the stream reads (0: none), cells_xy, cells_z, 0}
+  // per-scan map-hit records (liodom_set_map_hits; from the first enabling call on)
   liodom_map_hit_t* hit_log = nullptr;   // [S][pose_log_cap] device, indexed like pose_log
   int* hit_radius = nullptr;          // [S] device: -1 off, else the radius the stream's scans are counted with
-  std::vector<int> hit_radius_h;      // ... and the host's copy
-  int n_hits = 0;                     // streams with hits on
   std::vector<EventPair> ev_pool;
   size_t ev_used = 0;
   double k_ms[LIODOM_NUM_KERNELS] = {0};
@@ -160,6 +154,14 @@ int dev_alloc(liodom_handle* h, T** p, size_t count, int memset_value = 0) {
   HIP_TRY(hipMemsetAsync(raw, memset_value, bytes, h->stream));
   *p = static_cast<T*>(raw);
   return LIODOM_OK;
+}
+
+// A map whose last attachment has gone gets a stream of its own again (a failure leaves it with none, and "attached" to callers).
+hipError_t map_own_stream(liodom_map* m) {
+  m->stream = nullptr; m->own_stream = false;
+  const hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) m->own_stream = true;
+  return e;
 }
 
 int drain_events(liodom_handle* h) {
@@ -572,7 +574,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     h->scans_enqueued.assign(S, 0);
     h->step.bind(S);
     h->last_eb.assign(S, 0);
-    h->mappers.assign(S, nullptr); h->mapper_opts.assign(S, liodom_mapper_options_t{2, 1, 0, 0, 0, 0, {0, 0}});
+    h->maps.bind(h, S);
   }
   if (p.pose_covariance) {
     // per-scan pose covariance (kernels_cov.h): nothing of it exists on handles created without it
@@ -665,14 +667,7 @@ void liodom_destroy(liodom_handle_t* h) {
   if (h->stream_k) { hipStreamSynchronize(h->stream_k); hipStreamDestroy(h->stream_k); }
   if (h->ev_ov) hipEventDestroy(h->ev_ov);
   if (h->ev_ch) hipEventDestroy(h->ev_ch);
-  for (int kind = 0; kind < 2; kind++) {       // attached maps outlive the handle: give them a stream of their own again
-    for (liodom_map* mp : (kind == 0 ? h->mappers : h->readers)) {
-      if (!mp || mp->n_attached == 0 || mp->attached_to != h) continue;      // (a map several streams held: done already; or one that has moved to another handle)
-      mp->n_attached = 0; mp->n_readers = 0; mp->attached_to = nullptr;
-      mp->stream = nullptr; mp->own_stream = false;
-      if (hipStreamCreateWithFlags(&mp->stream, hipStreamNonBlocking) == hipSuccess) mp->own_stream = true;
-    }
-  }
+  while (liodom_map* mp = h->maps.release_next()) (void)map_own_stream(mp);      // attached maps outlive the handle
   for (void* p : h->allocs) hipFree(p);
   if (h->resident) hipFree(h->resident);
   if (h->host_out) hipHostFree(h->host_out);
@@ -846,9 +841,9 @@ int liodom_import_stream_state(liodom_handle_t* h, int stream, const void* blob,
 
 // The attachment of a stream, whichever kind: its writing mapper's map and extents, or its reader's.
 static liodom_map* stream_map(const liodom_handle* h, int stream, int* cells_xy, int* cells_z) {
-  if (liodom_map* mp = h->mappers[(size_t)stream]) { *cells_xy = h->mapper_opts[(size_t)stream].cells_xy; *cells_z = h->mapper_opts[(size_t)stream].cells_z; return mp; }
-  if (!h->readers.empty() && h->readers[(size_t)stream]) { *cells_xy = h->reader_xy[(size_t)stream]; *cells_z = h->reader_z[(size_t)stream]; return h->readers[(size_t)stream]; }
-  return nullptr;
+  liodom_map* mp = h->maps.map_of(stream);
+  if (mp) { *cells_xy = h->maps.opts(stream).cells_xy; *cells_z = h->maps.opts(stream).cells_z; }
+  return mp;
 }
 
 int liodom_seed_stream(liodom_handle_t* h, int stream, const double* pose) {
@@ -1453,59 +1448,19 @@ void liodom_mapper_options_default(liodom_mapper_options_t* o) {
   o->cells_xy = 2; o->cells_z = 1;      // liodom_mapping_node.cc:130-134
 }
 
-// One attachment of `m` to a stream of `h` comes (+1) or goes (-1).  The first one moves the map onto the handle's HIP stream; the
-// map gets a stream of its own again only when the last one goes.  The odometry stream has drained (the callers synchronise).
-static int map_attachment(liodom_handle* h, liodom_map* m, int delta, bool reader) {
-  if (delta > 0) {
-    if (m->n_attached == 0 || m->attached_to != h) {      // (a map another handle still names moves here, as it always did)
-      HIP_TRY(hipStreamSynchronize(m->stream));
-      if (m->own_stream) { (void)hipStreamDestroy(m->stream); m->own_stream = false; }
-      m->stream = h->stream;
-      m->attached_to = h; m->n_attached = 0; m->n_readers = 0;
-    }
-    m->n_attached++;
-    if (reader) m->n_readers++;
-    return LIODOM_OK;
+// The HIP half of a transition of h->maps (map_attach.h), in the order the record names.  The odometry stream has drained (the
+// callers synchronise).
+static int carry_out(liodom_handle* h, int stream, const AttachEffects<liodom_map>& e) {
+  if (liodom_map* m = e.move_in) {
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (m->own_stream) { (void)hipStreamDestroy(m->stream); m->own_stream = false; }
+    m->stream = h->stream;
   }
-  if (m->attached_to != h) return LIODOM_OK;      // (the map has moved to another handle since)
-  if (reader && m->n_readers > 0) m->n_readers--;
-  if (m->n_attached > 0) m->n_attached--;
-  if (m->n_attached == 0) {
-    m->n_readers = 0; m->attached_to = nullptr;
-    m->stream = nullptr; m->own_stream = false;
-    HIP_TRY(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-    m->own_stream = true;
-  }
-  return LIODOM_OK;
-}
-// Attachments of `m` other than the one stream `stream` of `h` holds now (which an attach call replaces): writers, readers.
-static void other_attachments(const liodom_handle* h, int stream, const liodom_map* m, int* writers, int* readers) {
-  int own_w = (h->mappers[(size_t)stream] == m) ? 1 : 0;
-  int own_r = (!h->readers.empty() && h->readers[(size_t)stream] == m) ? 1 : 0;
-  if (m->attached_to != h) { own_w = 0; own_r = 0; }
-  *readers = m->n_readers - own_r;
-  *writers = (m->n_attached - m->n_readers) - own_w;
-}
-// Takes the stream's attachment away, whichever kind it is.
-static int detach_stream_map(liodom_handle* h, int stream) {
-  if (liodom_map* old = h->mappers[(size_t)stream]) {
-    h->mappers[(size_t)stream] = nullptr;
-    if (h->mapper_opts[(size_t)stream].lag == 1) h->n_lagged--;
-    const int rc = map_attachment(h, old, -1, false);
-    if (rc) return rc;
-  }
-  if (!h->readers.empty() && h->readers[(size_t)stream]) {
-    liodom_map* old = h->readers[(size_t)stream];
-    h->readers[(size_t)stream] = nullptr;
-    h->n_readers--;
-    const int4 none = make_int4(0, 0, 0, 0);
-    HIP_TRY(hipMemcpy(h->reader_sel + stream, &none, sizeof(none), hipMemcpyHostToDevice));
-    bool still = false;
-    for (liodom_map* q : h->readers) still = still || q == old;
-    if (!still) for (liodom_map*& q : h->read_maps) if (q == old) q = nullptr;
-    const int rc = map_attachment(h, old, -1, true);
-    if (rc) return rc;
-  }
+  const int4 none = make_int4(0, 0, 0, 0), sel = make_int4(e.sel[0], e.sel[1], e.sel[2], e.sel[3]);
+  if (e.sel_cleared) HIP_TRY(hipMemcpy(h->reader_sel + stream, &none, sizeof(none), hipMemcpyHostToDevice));
+  if (e.own_again) HIP_TRY(map_own_stream(e.own_again));
+  if (e.sel_written) HIP_TRY(hipMemcpy(h->reader_sel + stream, &sel, sizeof(sel), hipMemcpyHostToDevice));
+  if (e.lag_on >= 0 && h->lag_on) HIP_TRY(hipMemcpy(h->lag_on + stream, &e.lag_on, sizeof(int), hipMemcpyHostToDevice));
   return LIODOM_OK;
 }
 
@@ -1518,31 +1473,20 @@ int liodom_attach_map_reader(liodom_handle_t* h, int stream, liodom_map_t* m, in
   if (m->device != h->config.device) { g_last_error = "liodom_attach_map_reader: map and handle live on different devices"; return LIODOM_ERR_INVALID_ARG; }
   if (cells_xy < 0 || cells_z < 0) { g_last_error = "liodom_attach_map_reader: negative extent"; return LIODOM_ERR_INVALID_ARG; }
   SideLocks lk(h, true, false);
-  int writers = 0, readers = 0;
-  other_attachments(h, stream, m, &writers, &readers);
-  if (writers > 0) { g_last_error = "liodom_attach_map_reader: the map is attached writing (liodom_attach_mapper): a map is read or written, not both"; return LIODOM_ERR_INVALID_ARG; }
-  if (m->n_attached > 0 && m->attached_to != h) { g_last_error = "liodom_attach_map_reader: the map is attached to another handle"; return LIODOM_ERR_INVALID_ARG; }
+  switch (h->maps.reader_check(stream, m)) {
+    case kAttachMapIsWritten: g_last_error = "liodom_attach_map_reader: the map is attached writing (liodom_attach_mapper): a map is read or written, not both"; return LIODOM_ERR_INVALID_ARG;
+    case kAttachOtherHandle: g_last_error = "liodom_attach_map_reader: the map is attached to another handle"; return LIODOM_ERR_INVALID_ARG;
+    default: break;
+  }
   HIP_TRY(sync_odometry(h));
   if (!h->reader_sel) {      // one int4 per stream, from the first reader on
     if ((rc = dev_alloc(h, &h->reader_sel, (size_t)h->S))) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->readers.assign((size_t)h->S, nullptr); h->reader_xy.assign((size_t)h->S, 0); h->reader_z.assign((size_t)h->S, 0);
   }
-  if (h->n_hits > 0 && h->hit_radius_h[(size_t)stream] >= 0 && (rc = map_keep_occ(m))) return rc;      // (hit records: the kept occupancy, sized once)
-  // (attach first, detach second: a stream that re-attaches the map it reads keeps the map on the handle's stream throughout)
-  if ((rc = map_attachment(h, m, +1, true))) return rc;
-  if ((rc = detach_stream_map(h, stream))) return rc;
-  size_t t = 0;
-  for (; t < h->read_maps.size() && h->read_maps[t] != m; t++) {}
-  if (t == h->read_maps.size()) {
-    for (t = 0; t < h->read_maps.size() && h->read_maps[t]; t++) {}
-    if (t == h->read_maps.size()) h->read_maps.push_back(m); else h->read_maps[t] = m;
-  }
-  h->readers[(size_t)stream] = m; h->reader_xy[(size_t)stream] = cells_xy; h->reader_z[(size_t)stream] = cells_z;
-  h->n_readers++;
-  const int4 sel = make_int4((int)t + 1, cells_xy, cells_z, 0);
-  HIP_TRY(hipMemcpy(h->reader_sel + stream, &sel, sizeof(sel), hipMemcpyHostToDevice));
-  return LIODOM_OK;
+  if (h->maps.hits_on(stream) && (rc = map_keep_occ(m))) return rc;      // (hit records: the kept occupancy, sized once)
+  liodom_mapper_options_t o{};
+  o.cells_xy = cells_xy; o.cells_z = cells_z;
+  return carry_out(h, stream, h->maps.attach(stream, m, true, o));
 }
 
 static_assert(sizeof(liodom_map_hit_t) == liodom_dev::kMapHitRecordBytes, "k_map_hit_rows writes the record as eight 16-byte stores");
@@ -1559,13 +1503,10 @@ int liodom_set_map_hits(liodom_handle_t* h, int stream, int radius) {
     if ((rc = dev_alloc(h, &h->hit_log, (size_t)h->S * (size_t)h->v.pose_log_cap))) return rc;
     if ((rc = dev_alloc(h, &h->hit_radius, (size_t)h->S, 0xff))) return rc;      // (all -1)
     HIP_TRY(hipStreamSynchronize(h->stream));
-    h->hit_radius_h.assign((size_t)h->S, -1);
   }
-  liodom_map* rd = h->readers.empty() ? nullptr : h->readers[(size_t)stream];
+  liodom_map* rd = h->maps.reader(stream);
   if (radius >= 0 && rd && (rc = map_keep_occ(rd))) return rc;
-  int& cur = h->hit_radius_h[(size_t)stream];
-  h->n_hits += (radius >= 0 ? 1 : 0) - (cur >= 0 ? 1 : 0);
-  cur = radius;
+  h->maps.set_hits(stream, radius);
   HIP_TRY(hipMemcpy(h->hit_radius + stream, &radius, sizeof(int), hipMemcpyHostToDevice));
   return LIODOM_OK;
 }
@@ -1602,10 +1543,8 @@ int liodom_attach_mapper_ex(liodom_handle_t* h, int stream, liodom_map_t* m, con
     }
   }
   SideLocks lk(h, true, false);
-  if (m) {
-    int writers = 0, readers = 0;
-    other_attachments(h, stream, m, &writers, &readers);
-    if (readers > 0) { g_last_error = "liodom_attach_mapper: the map is attached reading (liodom_attach_map_reader): a map is read or written, not both"; return LIODOM_ERR_INVALID_ARG; }
+  if (m && h->maps.writer_check(stream, m) == kAttachMapIsRead) {
+    g_last_error = "liodom_attach_mapper: the map is attached reading (liodom_attach_map_reader): a map is read or written, not both"; return LIODOM_ERR_INVALID_ARG;
   }
   HIP_TRY(sync_odometry(h));
   if (m && o.lag == 1 && !h->lag_stash) {      // one edge_cap frame per stream, from the first lagged attach on
@@ -1615,20 +1554,7 @@ int liodom_attach_mapper_ex(liodom_handle_t* h, int stream, liodom_map_t* m, con
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
   if (m && o.prune_period > 0 && (rc = map_ensure_prune(m))) return rc;
-  // (attach first, detach second: re-attaching the stream's own map keeps it on the handle's stream; a map whose last attachment
-  //  goes gets a stream of its own again)
-  if (m && (rc = map_attachment(h, m, +1, false))) return rc;
-  if ((rc = detach_stream_map(h, stream))) return rc;
-  if (m) {
-    h->mappers[stream] = m;
-    h->mapper_opts[stream] = o;
-    if (o.lag == 1) h->n_lagged++;
-  }
-  if (h->lag_on) {
-    const int on = (m && o.lag == 1) ? 1 : 0;
-    HIP_TRY(hipMemcpy(h->lag_on + stream, &on, sizeof(int), hipMemcpyHostToDevice));
-  }
-  return LIODOM_OK;
+  return carry_out(h, stream, m ? h->maps.attach(stream, m, false, o) : h->maps.detach(stream));
 }
 
 int liodom_attach_mapper(liodom_handle_t* h, int stream, liodom_map_t* m, int cells_xy, int cells_z) {
@@ -2199,7 +2125,7 @@ int liodom_get_modes(liodom_handle_t* h, char* buf, int cap) {
   (void)hipMemcpy(r.hb_stats, reinterpret_cast<const char*>(v.state) + offsetof(StreamState, hb_stats), sizeof(r.hb_stats), hipMemcpyDeviceToHost);
   r.chain_count = h->step.chain_count; r.done0 = done_cnt[0]; r.done1 = done_cnt[32];
   if (h->replay_timed) { r.replay_enqueue_us = h->replay_enq_ns / (1e3 * (double)h->replay_timed); r.replay_wait_us = h->replay_wait_ns / (1e3 * (double)h->replay_timed); }
-  r.n_lagged = h->n_lagged; r.n_readers = h->n_readers; r.subset_steps = h->subset_steps; r.n_hits = h->n_hits;
+  r.n_lagged = h->maps.n_lagged; r.n_readers = h->maps.n_readers; r.subset_steps = h->subset_steps; r.n_hits = h->maps.n_hits;
   plan_format_modes(h->plan, r, buf, cap);
   return LIODOM_OK;
 }

@@ -4,6 +4,7 @@
 #include <chrono>
 
 #include "liodom_map.h"
+#include "map_attach.h"
 #include "reloc_candidates.h"
 #include "reloc_bnb.h"
 
@@ -35,10 +36,9 @@ struct liodom_map {
   size_t blocks_entries = 0;               // first call allocates them, a call that needs more regrows them)
   unsigned char* h_pin = nullptr;          // liodom_map_search_pose_bnb: pinned host staging of a round's nodes, candidates and counts
   size_t pin_bytes = 0;
-  // attachments to a handle's streams (liodom_attach_mapper* / liodom_attach_map_reader): the map runs on the handle's HIP stream
-  // while n_attached > 0 and gets one of its own again when the last attachment goes
-  int n_attached = 0, n_readers = 0;
-  const void* attached_to = nullptr;
+  // attachments to a handle's streams (liodom_attach_mapper* / liodom_attach_map_reader, map_attach.h): the map runs on the
+  // handle's HIP stream while link.n_attached > 0 and gets one of its own again when the last attachment goes
+  liodom_dev::MapLink link;
 };
 
 namespace {

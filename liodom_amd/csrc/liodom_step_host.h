@@ -76,11 +76,11 @@ int issue_plan(liodom_handle* h, const StepPlan& plan, const StepData& d) {
         // optional prune around pose_k, then the same getLocalMap.
         for (int i = 0; i < count; i++) {
           const int s = d.list ? (int)d.list[i] : s0 + i;
-          liodom_map* mp = h->mappers[s];
+          liodom_map* mp = h->maps.writer(s);
           if (!mp) continue;
           ProfScope ps(h, KID_OTHER);
           StreamState* st = v.state + s;
-          const liodom_mapper_options_t& mo = h->mapper_opts[s];
+          const liodom_mapper_options_t& mo = h->maps.opts(s);
           int rc = mo.lag == 1 ? map_enqueue_update(mp, h->lag_stash + (size_t)s * v.edge_cap, h->lag_stash_n + s, nullptr, h->stream)
                                : map_enqueue_update(mp, v.edges + ((size_t)eb * v.n_streams + s) * v.edge_cap, &st->n_edges_buf[eb], st->final_odom, h->stream);
           if (rc) return rc;
@@ -96,18 +96,20 @@ int issue_plan(liodom_handle* h, const StepPlan& plan, const StepData& d) {
         // map readers: getLocalMap(pose_k) of the step's reader rows, one launch per distinct map (k_map_local_rows plans in LDS and
         // writes nothing of the map, so the rows share it); nothing else — no stash, no update, no prune.  A reader whose extents
         // the LDS plan cannot hold takes the two old launches.
-        if (h->n_readers > 0) {
+        if (h->maps.n_readers > 0) {
           ProfScope ps(h, KID_OTHER);
-          for (size_t t = 0; t < h->read_maps.size(); t++) {
-            liodom_map* mp = h->read_maps[t];
+          const std::vector<liodom_map*>& tags = h->maps.tags;
+          for (size_t t = 0; t < tags.size(); t++) {
+            liodom_map* mp = tags[t];
             if (!mp) continue;
             bool rows = false;
             for (int i = 0; i < count; i++) {
               const int s = d.list ? (int)d.list[i] : s0 + i;
-              if (h->readers[s] != mp) continue;
-              if (h->plan.map_rows && map_rows_fit(mp, h->reader_xy[s], h->reader_z[s])) { rows = true; continue; }
+              if (h->maps.reader(s) != mp) continue;
+              const liodom_mapper_options_t& ro = h->maps.opts(s);
+              if (h->plan.map_rows && map_rows_fit(mp, ro.cells_xy, ro.cells_z)) { rows = true; continue; }
               StreamState* st = v.state + s;
-              const int rc = map_enqueue_local(mp, st->final_odom, h->reader_xy[s], h->reader_z[s], v.recv_pts + (size_t)s * v.recv_cap, v.recv_cap, &st->n_recv, h->stream, 1);
+              const int rc = map_enqueue_local(mp, st->final_odom, ro.cells_xy, ro.cells_z, v.recv_pts + (size_t)s * v.recv_cap, v.recv_cap, &st->n_recv, h->stream, 1);
               if (rc) return rc;
             }
             if (!rows) continue;
@@ -125,7 +127,7 @@ int issue_plan(liodom_handle* h, const StepPlan& plan, const StepData& d) {
         // per-scan hit records (liodom_set_map_hits): the step's rows with hits on, counted at final_odom against the occupancy
         // of the map they read — one k_map_hit_rows launch per distinct map, in front of it the occupancy's two launches only if
         // the map may have changed since it was built — and one launch for the rows without a reader (NO_READER records).
-        if (h->n_hits > 0) {
+        if (h->maps.n_hits > 0) {
           ProfScope ps(h, KID_OTHER);
           MapHitRows r{};
           r.edges = v.edges + (size_t)eb * v.n_streams * v.edge_cap; r.edge_stride = v.edge_cap;
@@ -135,14 +137,14 @@ int issue_plan(liodom_handle* h, const StepPlan& plan, const StepData& d) {
           r.scan_no = &v.state[0].scan_counter; r.raw = &v.state[0].append_raw;
           r.radius_of = h->hit_radius; r.sel = h->reader_sel; r.s0 = s0;
           r.list = s0 < 0 ? reinterpret_cast<const int*>(v.pipe_flags) + kStreamListBase + (size_t)(-s0 - 1) * (size_t)v.n_streams : nullptr;
-          auto reads = [&](int s) { return h->readers.empty() ? nullptr : h->readers[s]; };
-          for (size_t t = 0; t <= h->read_maps.size(); t++) {      // (the last turn: tag 0, the rows without a reader)
-            liodom_map* mp = t < h->read_maps.size() ? h->read_maps[t] : nullptr;
-            if (t < h->read_maps.size() && !mp) continue;
+          const std::vector<liodom_map*>& tags = h->maps.tags;
+          for (size_t t = 0; t <= tags.size(); t++) {      // (the last turn: tag 0, the rows without a reader)
+            liodom_map* mp = t < tags.size() ? tags[t] : nullptr;
+            if (t < tags.size() && !mp) continue;
             bool any = false;
             for (int i = 0; i < count && !any; i++) {
               const int s = d.list ? (int)d.list[i] : s0 + i;
-              any = h->hit_radius_h[s] >= 0 && reads(s) == mp;
+              any = h->maps.hits_on(s) && h->maps.reader(s) == mp;
             }
             if (!any) continue;
             if (mp) { const int rc = map_refresh_occ(mp, h->stream); if (rc) return rc; }
@@ -232,7 +234,7 @@ int enqueue_odometry(liodom_handle* h, int eb, int s0, int count, unsigned int w
   rq.s0 = s0; rq.count = count; rq.list = list; rq.wait_edges = wait_edges; rq.signal_odo = signal_odo;
   rq.profiling = h->profiling; rq.ov_suppress = h->ov_suppress; rq.alone = g_live_handles.load() <= 1;
   rq.scans_enqueued = count > 0 ? h->scans_enqueued[rq.stream_at(0)] : 0;
-  if (h->n_lagged > 0) for (int i = 0; i < count; i++) { const int s = rq.stream_at(i); rq.lagged = rq.lagged || (h->mappers[s] && h->mapper_opts[s].lag == 1); }
+  if (h->maps.any_lagged()) for (int i = 0; i < count; i++) rq.lagged = rq.lagged || h->maps.lagged(rq.stream_at(i));
   StepPlan plan;
   plan_odometry_step(h->plan, &h->step, rq, &plan);
   StepData d;
