@@ -505,6 +505,18 @@ typedef struct liodom_map_config_t {
 #define LIODOM_MAP_LEAF_RANGE 16u
 #define LIODOM_MAP_KEY_RANGE 32u
 #define LIODOM_MAP_RESULT_OVERFLOW 64u
+/* LIODOM_MAP_RESULT_OVERFLOW says that a getLocalMap left the device incomplete.  Sticky like the other bits (liodom_map_reset
+ * clears them; an import takes the blob's).  Raised when
+ *   - a STEP's local map (an attached mapper's or a map reader's, after every scan) is larger than the handle's recv_capacity: the
+ *     stream receives the first recv_capacity points in visit order (the reference's loops, a cell cut where the capacity ends), its
+ *     received map holds exactly recv_capacity points, and the next scan searches window ++ that truncated cloud.  The host getters
+ *     (liodom_map_get_local, liodom_map_get_local_batch, liodom_seed_stream) do NOT raise it for a result larger than the
+ *     caller's buffer: they return LIODOM_ERR_CAPACITY with the full size, copy nothing and leave the status alone;
+ *   - one visit finds more than 4096 cells: the result holds the first 4096 found cells in visit order;
+ *   - a visit is cut by the planners' loop guard, 65536 iterations of the visit's loops (the inner and the outer ones counted
+ *     together): the result holds the cells found up to the cut.  cells_xy * 2 + 1 = 255 keys a side (cells_xy = 127 on 1 m
+ *     cells) is the largest square that stays under it.
+ * The last two are raised by steps and host getters alike, and the call returns what it has. */
 
 void liodom_map_config_default(liodom_map_config_t* c);
 /* Map::Map (src/map.cc:70-81) */

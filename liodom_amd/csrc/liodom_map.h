@@ -454,6 +454,13 @@ __device__ __forceinline__ void map_plan_add(const MapView& m, int kx, int ky, i
   *ne += 1;
   *total += e.count;
 }
+// The loop guard of the planners: a visit is cut after kMapVisitMax loop iterations (inner and outer together), so that no sizes
+// or extents can keep the planning lane busy without end.  A loop that ends on it has left keys out: the planner raises
+// MAP_STATUS_LOCAL_OVERFLOW, whatever `sticky` is (as for more than kMapLocalEntriesMax found cells).  `cut = map_visit_cut(guard)`
+// stands behind the loop's own condition, so it is evaluated — and 1 — only while the loop would still go on.
+constexpr int kMapVisitMax = 65536;
+__device__ __forceinline__ int map_visit_cut(int guard) { return guard >= kMapVisitMax ? 1 : 0; }
+
 __global__ void k_map_local_plan(MapView m, const double* T_ptr, int cells_xy, int cells_z, int out_cap, int* n_out, int sticky) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   MapState& st = *m.st;
@@ -467,17 +474,18 @@ __global__ void k_map_local_plan(MapView m, const double* T_ptr, int cells_xy, i
   const int end_x = (int)(voxel_x + cells_xy * m.xy);
   const int init_y = (int)(voxel_y - cells_xy * m.xy);
   const int end_y = (int)(voxel_y + cells_xy * m.xy);
-  int ne = 0, total = 0, guard = 0;
-  for (int i = init_x; i <= end_x && guard < 65536; i = (int)(i + m.xy), guard++) {          // :162
-    for (int j = init_y; j <= end_y && guard < 65536; j = (int)(j + m.xy), guard++) {        // :163
+  int ne = 0, total = 0, guard = 0, cut = 0;
+  for (int i = init_x; i <= end_x && !(cut = map_visit_cut(guard)); i = (int)(i + m.xy), guard++) {          // :162
+    for (int j = init_y; j <= end_y && !(cut = map_visit_cut(guard)); j = (int)(j + m.xy), guard++) {        // :163
       map_plan_add(m, i, j, voxel_z, &ne, &total);
     }
   }
   const int init_z = (int)(voxel_z - cells_z * m.xy);                                // :175 (xy size)
   const int end_z = (int)(voxel_z + cells_z * m.xy);                                 // :176
-  for (int i = init_z; i <= end_z && guard < 65536; i = (int)(i + m.z), guard++) {   // :178
+  for (int i = init_z; i <= end_z && !(cut = map_visit_cut(guard)); i = (int)(i + m.z), guard++) {   // :178
     map_plan_add(m, voxel_x, voxel_y, i, &ne, &total);
   }
+  if (cut) atomicOr(&st.status, MAP_STATUS_LOCAL_OVERFLOW);                         // keys were left out: whatever `sticky` is
   if (total > out_cap && sticky) atomicOr(&st.status, MAP_STATUS_LOCAL_OVERFLOW);   // host callers get LIODOM_ERR_CAPACITY instead
   st.n_entries = ne;
   st.n_result = total;
@@ -568,18 +576,18 @@ __global__ __launch_bounds__(kMapRowsThreads) void k_map_local_rows(MapView m, M
     const int end_x = (int)(voxel_x + cells_xy * m.xy);
     const int init_y = (int)(voxel_y - cells_xy * m.xy);
     const int end_y = (int)(voxel_y + cells_xy * m.xy);
-    int guard = 0;
-    for (int i = init_x; i <= end_x && guard < 65536 && !over; i = (int)(i + m.xy), guard++) {          // :162
-      for (int j = init_y; j <= end_y && guard < 65536 && !over; j = (int)(j + m.xy), guard++) {        // :163
+    int guard = 0, cut = 0;
+    for (int i = init_x; i <= end_x && !over && !(cut = map_visit_cut(guard)); i = (int)(i + m.xy), guard++) {          // :162
+      for (int j = init_y; j <= end_y && !over && !(cut = map_visit_cut(guard)); j = (int)(j + m.xy), guard++) {        // :163
         add(i, j, voxel_z);
       }
     }
     const int init_z = (int)(voxel_z - cells_z * m.xy);                                // :175 (xy size)
     const int end_z = (int)(voxel_z + cells_z * m.xy);                                 // :176
-    for (int i = init_z; i <= end_z && guard < 65536 && !over; i = (int)(i + m.z), guard++) {   // :178
+    for (int i = init_z; i <= end_z && !over && !(cut = map_visit_cut(guard)); i = (int)(i + m.z), guard++) {   // :178
       add(voxel_x, voxel_y, i);
     }
-    sh_nk = nk; sh_over = over; sh_ne = 0; sh_total = 0;
+    sh_nk = nk; sh_over = over | cut; sh_ne = 0; sh_total = 0;          // either way keys were left out
   }
   __syncthreads();
   const int nk = sh_nk;
