@@ -827,6 +827,69 @@ int liodom_map_search_pose_bnb(liodom_map_t* m, const float* edges_xyzi, int n_e
                                const liodom_pose_search_bnb_t* opt /*NULL: defaults*/, liodom_pose_search_result_t* out,
                                liodom_pose_search_stats_t* stats /*optional*/);
 
+/* ---- registering a scan to the map in 6-DoF (no counterpart in the reference; DESIGN.md §3 "Registering a scan to the map").
+ * The searches above return a grid cell: x, y, yaw as fine as their step, no roll, pitch or z of their own.
+ * liodom_map_register_poses carries the seeded first scan of liodom_seed_stream on, for n start poses at once, without a handle
+ * and without writing anything of the map.  Each row is independent:
+ *   start     the quaternion is normalised in double and T made from it, as liodom_seed_stream does.
+ *   local map getLocalMap(T_start, cells_xy, cells_z), fetched ONCE: content and order of liodom_map_get_local; it is not fetched
+ *             again as the pose moves.
+ *   pass p    from (q, t): the edges transformed by T(q, t) and rounded to float; per edge the exact 5 nearest points of the row's
+ *             local map (float squared distance, ties to the lower index); a correspondence is valid iff there are 5, the fifth is
+ *             closer than 1 m (squared distance < 1.0f) and the line gate passes; the line is through the two nearest.  Then one LM
+ *             solve from (q, t) as a scan's solve (4 iterations, Huber 0.2, min_range / max_range in the range weight).
+ *   ending    an empty local map: LIODOM_REG_NO_MAP; a pass with fewer than min_matches valid correspondences:
+ *             LIODOM_REG_FEW_MATCHES; a solve with termination 5: LIODOM_REG_EVAL_FAILURE — in all three the returned pose is the
+ *             pose before that pass.  A pass that moved the pose by |dt| <= stop_translation and |vec(q_new (x) conj(q_old))| <=
+ *             stop_rotation ends the row as LIODOM_REG_CONVERGED; otherwise LIODOM_REG_MAX_PASSES after the last pass.
+ *   result    pose; passes = solves whose result was taken; matches = valid correspondences of the last pass that searched;
+ *             last_move_t / last_move_r = the two norms of the last taken pass (0 if none); local_points.  When the last pass's
+ *             solve was taken (CONVERGED, MAX_PASSES): information, final_cost, sigma2, cov_flags as liodom_pose_cov_t defines
+ *             them — H at the returned pose over that pass's correspondences —, n_residuals = matches and last_lm the solve's
+ *             trace.  Otherwise information and sigma2 are NaN, n_residuals = 0 and final_cost = 0 with cov_flags
+ *             LIODOM_COV_NO_SOLVE (NO_MAP, FEW_MATCHES; last_lm zero) or LIODOM_COV_EVAL_FAILURE (last_lm = the failed solve's).
+ *   corr      (optional) [n][n_edges][2]: the last searching pass's (a, b) indices into the row's local map, -1 where the edge had
+ *             no valid correspondence (all -1 for NO_MAP).  An edge with a non-finite coordinate has none.
+ * Coordinates beyond +-2^20 m take no part (the map holds no cell there).  Nothing of the map is written: its exported state, its
+ * status and its generation are the same before and after, on a detached map, a map readers are attached to and a map a mapper
+ * writes — between steps, under the threading rule of liodom_map_export_state.  Equal calls return equal bytes; row i of a batch
+ * returns the bytes a one-row call with pose i returns.  The workspace belongs to the map: allocated by the first call, regrown
+ * when n x local_capacity grows, freed with the map.
+ * LIODOM_ERR_INVALID_ARG, nothing written, workspace untouched: a null where one is required; n < 1 or n > 64; n_edges < 0 or above
+ * max_update_points; a non-finite pose or | |q| - 1 | > 1e-6; reserved != 0, max_passes outside 1 .. 16, min_matches < 1, negative
+ * extents, capacity or thresholds, ranges that are not 0 <= min < max.  LIODOM_ERR_CAPACITY: a row's local map is larger than
+ * local_capacity — the full sizes are in out[i].local_points (as liodom_map_get_local_batch reports sizes) and nothing else is
+ * written.  n_edges = 0 is valid: every row ends as FEW_MATCHES (NO_MAP on an empty local map) with its start pose. */
+#define LIODOM_REG_CONVERGED 0
+#define LIODOM_REG_MAX_PASSES 1
+#define LIODOM_REG_FEW_MATCHES 2
+#define LIODOM_REG_NO_MAP 3
+#define LIODOM_REG_EVAL_FAILURE 4
+typedef struct liodom_map_register_t {
+  int32_t cells_xy, cells_z;       /* getLocalMap extents around each start pose (defaults 2, 1) */
+  int32_t max_passes;              /* 1 .. 16 correspondence passes (default 10) */
+  int32_t min_matches;             /* a pass with fewer valid correspondences ends the row (default 6) */
+  int32_t local_capacity;          /* points of one row's local map the workspace holds (0 = 65536) */
+  int32_t reserved;                /* must be 0 */
+  double  stop_translation;        /* [m]   a pass that moved the pose by <= both of these ends the row as converged (default 1e-4) */
+  double  stop_rotation;           /* half-angle, as the solver's tangent (default 1e-5) */
+  double  min_range, max_range;    /* the residual's range weight (defaults 3, 75) */
+} liodom_map_register_t;           /* 56 bytes */
+typedef struct liodom_map_registration_t {
+  double  pose[7];                 /* [qx qy qz qw tx ty tz] */
+  double  information[36];         /* H = sum rho' J^T J at `pose`, the tangent and order of liodom_pose_cov_t */
+  double  final_cost, sigma2;      /* as liodom_pose_cov_t defines them */
+  double  last_move_t, last_move_r;
+  int32_t termination;             /* LIODOM_REG_* */
+  int32_t passes, matches, n_residuals, local_points;
+  uint32_t cov_flags;              /* LIODOM_COV_* of the final evaluation */
+  liodom_lm_trace_t last_lm;
+} liodom_map_registration_t;       /* 432 bytes */
+void liodom_map_register_default(liodom_map_register_t* o);
+int liodom_map_register_poses(liodom_map_t* m, const float* edges_xyzi, int n_edges, const double* poses /*n x 7*/, int n,
+                              const liodom_map_register_t* opt /*NULL: defaults*/, liodom_map_registration_t* out /*[n]*/,
+                              int32_t* corr /*optional, [n][n_edges][2]*/);
+
 /* ---- finding the place: a database of binary polar descriptors (no counterpart in the reference; DESIGN.md §3 "Finding the
  * place", INTEGRATION.md §7 "Relocalising without a guess").  Every search above needs a pose to search around; a liodom_places_t
  * answers "near which key frame was this scan taken?" without one.  It is an object of its own: it touches no handle and no map,

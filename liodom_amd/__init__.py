@@ -9,4 +9,5 @@ from . import api  # noqa: F401
 from .api import (Places, PlaceGeometry, PlaceMatch, PlacePolicy, PLACE_MATCH_DTYPE, Config, MapHit, MAP_HIT_DTYPE, TrackPolicy, TRACKING, LOST, HIT_VALID, HIT_NO_READER, HIT_NO_SOLVE, device_count, device_pci_bus_id, KernelStat, Liodom, Map, MapConfig, MapperOptions, make_mapper_options, LiodomError, LmTrace, Params, PoseCov, StepInfo, build, lib_path,  # noqa: F401
                   load, make_config, make_params, parse_stream_state, parse_map_state, build_map_state, join_map_state, PolarGeometry, PolarLayout, polar_geometry,
                   polar_geometry_from_angles, polar_layout, pack_polar,
+                  RegisterOptions, Registration, make_register_options, registration_dict,
                   PoseGraph, GraphEdge, GraphOptions, GraphReport, GRAPH_EDGE_DTYPE, GRAPH_TERMINATIONS, graph_edges, make_graph_options)

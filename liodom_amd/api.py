@@ -14,7 +14,7 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "kernels_compact.h", "kernels_knn.h", "kernels_knn8.h", "kernels_lm.h", "kernels_rebuild.h",
                                                   "kernels_filter.h", "kernels_cov.h", "kernels_state.h", "stream_state_format.h", "pose7.h", "kernels_polar.h", "kernels_mapper.h", "liodom_math.h", "wave_ops.h",
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
-                                                  "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h",
+                                                  "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h", "kernels_register.h", "map_register.h",
                                                   "kernels_places.h", "liodom_places_host.h", "place_state_format.h",
                                                   "kernels_graph.h", "liodom_graph_host.h", "graph_csr.h",
                                                   "liodom_sizes.h", "handle_plan.h", "step_plan.h", "edge_pipe.h", "map_attach.h", "liodom_step_host.h")] + [
@@ -181,6 +181,35 @@ class PoseSearchStats(C.Structure):
     """liodom_pose_search_stats_t: what a liodom_map_search_pose_bnb call did."""
     _fields_ = [("n_candidates", C.c_int64), ("nodes_bounded", C.c_int64), ("candidates_scored", C.c_int64),
                 ("rounds", C.c_int32), ("levels_built", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class RegisterOptions(C.Structure):
+    """liodom_map_register_t: the options of liodom_map_register_poses (include/liodom_hip.h)."""
+    _fields_ = [("cells_xy", C.c_int32), ("cells_z", C.c_int32), ("max_passes", C.c_int32), ("min_matches", C.c_int32),
+                ("local_capacity", C.c_int32), ("reserved", C.c_int32), ("stop_translation", C.c_double), ("stop_rotation", C.c_double),
+                ("min_range", C.c_double), ("max_range", C.c_double)]
+
+
+class Registration(C.Structure):
+    """liodom_map_registration_t: how one start pose of liodom_map_register_poses ended."""
+    _fields_ = [("pose", C.c_double * 7), ("information", C.c_double * 36), ("final_cost", C.c_double), ("sigma2", C.c_double),
+                ("last_move_t", C.c_double), ("last_move_r", C.c_double), ("termination", C.c_int32), ("passes", C.c_int32),
+                ("matches", C.c_int32), ("n_residuals", C.c_int32), ("local_points", C.c_int32), ("cov_flags", C.c_uint32),
+                ("last_lm", LmTrace)]
+
+
+REG_CONVERGED, REG_MAX_PASSES, REG_FEW_MATCHES, REG_NO_MAP, REG_EVAL_FAILURE = 0, 1, 2, 3, 4
+REGISTER_ROWS_MAX = 64
+
+
+def registration_dict(r):
+    """A Registration record as NumPy arrays and plain numbers: pose (7,), information 6 x 6, the scalars, last_lm as a dict."""
+    return dict(pose=np.array(r.pose[:]), information=np.ctypeslib.as_array(r.information).reshape(6, 6).copy(),
+                final_cost=r.final_cost, sigma2=r.sigma2, last_move_t=r.last_move_t, last_move_r=r.last_move_r,
+                termination=int(r.termination), passes=int(r.passes), matches=int(r.matches), n_residuals=int(r.n_residuals),
+                local_points=int(r.local_points), cov_flags=int(r.cov_flags),
+                last_lm=dict(iterations=int(r.last_lm.iterations), accepted=int(r.last_lm.accepted), termination=int(r.last_lm.termination),
+                             initial_cost=r.last_lm.initial_cost, final_cost=r.last_lm.final_cost))
 
 
 class MapHit(C.Structure):
@@ -878,6 +907,10 @@ def load():
     L.liodom_places_query.argtypes = [vp, fp, C.c_int64, ip, C.c_int, C.c_int, vp, ip]
     L.liodom_places_query_desc.restype = C.c_int
     L.liodom_places_query_desc.argtypes = [vp, u64p, C.c_int, C.c_int, vp]
+    L.liodom_map_register_default.restype = None
+    L.liodom_map_register_default.argtypes = [C.POINTER(RegisterOptions)]
+    L.liodom_map_register_poses.restype = C.c_int
+    L.liodom_map_register_poses.argtypes = [vp, C.POINTER(C.c_float), C.c_int, dp, C.c_int, C.POINTER(RegisterOptions), vp, ip]
     L.liodom_places_state_size.restype = C.c_int
     L.liodom_places_state_size.argtypes = [vp, i64p]
     L.liodom_places_export_state.restype = C.c_int
@@ -971,6 +1004,7 @@ EXPORTED_SYMBOLS = [
     "liodom_map_score_poses", "liodom_pose_search_default", "liodom_map_search_pose",
     "liodom_pose_search_bnb_default", "liodom_map_bound_nodes", "liodom_map_search_pose_bnb",
     "liodom_set_map_hits", "liodom_get_map_hit_log", "liodom_map_hit_rows",
+    "liodom_map_register_default", "liodom_map_register_poses",
     "liodom_place_geometry_default", "liodom_places_create", "liodom_places_destroy", "liodom_places_count", "liodom_places_reset",
     "liodom_places_describe", "liodom_places_add", "liodom_places_query", "liodom_places_query_desc",
     "liodom_places_state_size", "liodom_places_export_state", "liodom_places_import_state",
@@ -1037,6 +1071,20 @@ def make_pose_search(centre, **kw):
             raise KeyError(k)
         setattr(s, k, v)
     return s
+
+
+def make_register_options(**kw):
+    """RegisterOptions with the defaults of liodom_map_register_default (cells 2 / 1, 10 passes, 6 matches, stops 1e-4 m / 1e-5,
+    ranges 3 / 75); keywords set cells_xy, cells_z, max_passes, min_matches, local_capacity, reserved, stop_translation,
+    stop_rotation, min_range, max_range."""
+    o = RegisterOptions()
+    load().liodom_map_register_default(C.byref(o))
+    names = {f[0]: f[1] for f in RegisterOptions._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise KeyError(k)
+        setattr(o, k, float(v) if names[k] is C.c_double else int(v))
+    return o
 
 
 def _fp(a):
@@ -1441,13 +1489,16 @@ class Liodom:
         p = np.ascontiguousarray(pose7, dtype=np.float64).reshape(7)
         self._check(self.L.liodom_seed_stream(self.h, int(stream), _dp(p)))
 
-    def relocalize(self, map, scan, height, width, centre, levels, min_fraction=0.5, stream=0):
+    def relocalize(self, map, scan, height, width, centre, levels, min_fraction=0.5, stream=0, refine=None):
         """Finds the stream's pose in a saved map from a rough guess and seeds the stream with it.  The scan's edges
         (extract_edges) are scored against `map` on one candidate grid per level (Map.search_pose; `levels` is a list of dicts of its
         grid keywords; a level with bnb=True goes to Map.search_pose_bnb instead, with its batch= if given), the first around `centre` = [qx qy qz qw tx ty tz], each later one around the level before's best.  If the last
         level's score / (2 * n_edges) >= min_fraction the stream is seeded with the best pose (seed_stream) and
         dict(pose, hits_r, hits_0, n_edges, fraction, levels=[each level's result]) comes back: process the SAME scan next.  Otherwise
-        None, and the stream is as it was but for the edges extract_edges left in it."""
+        None, and the stream is as it was but for the edges extract_edges left in it.
+        refine = dict(options of Map.register_poses) (opt-in): the verified pose is registered to the map in 6-DoF
+        (Map.register_poses) and, if that row ended CONVERGED or MAX_PASSES, the stream is seeded with the registered pose instead;
+        the result gains searched_pose and registration (the row's dict).  refine = None: exactly as above."""
         edges = self.extract_edges(scan, height, width, stream=stream)["edges"]
         pose, found = self._search_levels(map, edges, centre, levels)
         if not found or edges.shape[0] == 0:
@@ -1456,8 +1507,25 @@ class Liodom:
         fraction = (last["hits_r"] + last["hits_0"]) / (2.0 * edges.shape[0])
         if not fraction >= min_fraction:
             return None
+        extra = {}
+        if refine is not None:
+            best, rows = self._refine_poses(map, edges, [pose], refine)
+            extra = dict(searched_pose=np.array(pose, np.float64), registration=rows[0])
+            if best is not None:
+                pose = rows[best]["pose"].copy()
         self.seed_stream(pose, stream=stream)
-        return dict(pose=pose, hits_r=last["hits_r"], hits_0=last["hits_0"], n_edges=int(edges.shape[0]), fraction=fraction, levels=found)
+        return dict(pose=pose, hits_r=last["hits_r"], hits_0=last["hits_0"], n_edges=int(edges.shape[0]), fraction=fraction, levels=found, **extra)
+
+    @staticmethod
+    def _refine_poses(map, edges, poses, refine):
+        """Map.register_poses of `poses` in one call -> (index of the best row, rows): the best row is the one with the most valid
+        correspondences among those that ended CONVERGED — failing that, MAX_PASSES —; None if no row ended either way."""
+        rows = map.register_poses(edges, np.asarray(poses, np.float64).reshape(-1, 7), **dict(refine))
+        for end in (REG_CONVERGED, REG_MAX_PASSES):
+            ok = [i for i, r in enumerate(rows) if r["termination"] == end]
+            if ok:
+                return max(ok, key=lambda i: (rows[i]["matches"], -i)), rows
+        return None, rows
 
     @staticmethod
     def _search_levels(map, edges, centre, levels):
@@ -1476,19 +1544,24 @@ class Liodom:
         [qx qy qz qw tx ty tz] — the pose that scan ended with — and the tag `id`.  Returns the place's index."""
         return places.add(self.get_edges(stream=stream)["edges"], pose, id)
 
-    def relocalize_global(self, map, places, scan, height, width, k, levels, min_fraction=0.5, pager=None, stream=0):
+    def relocalize_global(self, map, places, scan, height, width, k, levels, min_fraction=0.5, pager=None, stream=0, refine=None):
         """relocalize without a guess: the scan's edges (extract_edges, once) are looked up in `places` (Places.query, the k best),
         and `levels` (as relocalize's) run around the pose of every match in turn; with a `pager` (MapPager of `map`), pager.step at
         the match's pose comes first, so that the map holds the cells around it.  The match whose last level scores highest wins
         (ties go to the better rank).  If its score / (2 * n_edges) >= min_fraction the stream is seeded with the searched pose
         (with a pager: after a pager.step there) and dict(pose, hits_r, hits_0, n_edges, fraction, levels, match, rank, matches)
         comes back: process the SAME scan next.  Otherwise — also for an empty database — None, and the stream is as it was but for
-        the edges extract_edges left in it.  A host loop over existing calls: nothing is scored here."""
+        the edges extract_edges left in it.  A host loop over existing calls: nothing is scored here.
+        refine = dict(options of Map.register_poses) (opt-in): every match whose last level reaches min_fraction is registered to
+        the map in 6-DoF, all in ONE Map.register_poses call (with a pager: the winning match alone, after the pager.step at its
+        pose), and the stream is seeded with the registered pose of the best row — most valid correspondences among the rows that
+        ended CONVERGED, failing that MAX_PASSES; the result then describes that match and gains searched_pose, registration (its
+        row) and registrations (all rows).  If no row ends either way the searched pose is seeded, as without refine."""
         edges = self.extract_edges(scan, height, width, stream=stream)["edges"]
         if edges.shape[0] == 0 or not levels:
             return None
         matches = places.query([edges], k)[0]
-        best = None
+        best, verified = None, []
         for rank, m in enumerate(matches):
             if m["index"] < 0:
                 break
@@ -1498,6 +1571,8 @@ class Liodom:
             score = found[-1]["hits_r"] + found[-1]["hits_0"]
             if best is None or score > best[0]:
                 best = (score, rank, m, pose, found)
+            if score / (2.0 * edges.shape[0]) >= min_fraction:
+                verified.append((score, rank, m, pose, found))
         if best is None:
             return None
         score, rank, m, pose, found = best
@@ -1506,9 +1581,20 @@ class Liodom:
             return None
         if pager is not None:
             pager.step(pose_T34(pose))
+        extra = {}
+        if refine is not None:
+            cands = [best] if pager is not None else verified
+            pick, rows = self._refine_poses(map, edges, [c[3] for c in cands], refine)
+            if pick is not None:
+                score, rank, m, searched, found = cands[pick]
+                fraction = score / (2.0 * edges.shape[0])
+                pose = rows[pick]["pose"].copy()
+                extra = dict(searched_pose=np.array(searched, np.float64), registration=rows[pick], registrations=rows)
+            else:
+                extra = dict(searched_pose=np.array(pose, np.float64), registration=None, registrations=rows)
         self.seed_stream(pose, stream=stream)
         return dict(pose=pose, hits_r=found[-1]["hits_r"], hits_0=found[-1]["hits_0"], n_edges=int(edges.shape[0]), fraction=fraction,
-                    levels=found, match=m, rank=rank, matches=matches)
+                    levels=found, match=m, rank=rank, matches=matches, **extra)
 
     def set_map_hits(self, radius, stream=0):
         """Per-scan map-hit records for `stream` (liodom_set_map_hits): radius 0 or 1 switches them on, -1 off."""
@@ -1747,6 +1833,30 @@ class Map:
                     pose=np.array(r.pose[:]), T=np.array(r.T[:]).reshape(3, 4),
                     stats=dict(n_candidates=int(st.n_candidates), nodes_bounded=int(st.nodes_bounded), candidates_scored=int(st.candidates_scored),
                                rounds=int(st.rounds), levels_built=int(st.levels_built)))
+
+    def register_poses(self, edges, poses, want_corr=False, **options):
+        """Registers the edge cloud `edges` [E, 4] to the map in 6-DoF from every start pose of poses = [n, 7] ([qx qy qz qw tx ty tz])
+        in one call (liodom_map_register_poses; options as make_register_options) -> a list of n dicts (registration_dict), each
+        with corr [E, 2] (int32, -1: no correspondence) when want_corr.  Read-only on the map; works on an attached map between
+        steps.  LiodomError with .code ERR_INVALID_ARG / ERR_CAPACITY; on ERR_CAPACITY .sizes holds the rows' local-map sizes."""
+        e = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        n = p.shape[0]
+        opt = make_register_options(**options)
+        out = (Registration * max(n, 1))()
+        corr = np.full((max(n, 1), max(e.shape[0], 1), 2), -1, np.int32) if want_corr else None
+        try:
+            self._chk(self._L.liodom_map_register_poses(self.h, _fp(e), e.shape[0], _dp(p if n else np.zeros(7)), n, C.byref(opt), out,
+                                                        _ip(corr) if want_corr else None))
+        except LiodomError as err:
+            if err.code == ERR_CAPACITY:
+                err.sizes = np.array([out[i].local_points for i in range(n)], np.int64)
+            raise
+        res = [registration_dict(out[i]) for i in range(n)]
+        if want_corr:
+            for i in range(n):
+                res[i]["corr"] = corr[i, :e.shape[0]].copy()
+        return res
 
     def prune(self, T34=None, keep_xy=2, keep_z=1):
         """Drops every cell outside the box of keep_xy / keep_z cells around the pose's cell (liodom_map_prune); returns the

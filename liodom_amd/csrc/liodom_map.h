@@ -1042,3 +1042,4 @@ __global__ __launch_bounds__(256) void k_map_merge(MapView m, const unsigned cha
 #include "kernels_reloc.h"
 #include "kernels_reloc_bnb.h"
 #include "kernels_map_hits.h"
+#include "kernels_register.h"

@@ -7,6 +7,7 @@
 #include "map_attach.h"
 #include "reloc_candidates.h"
 #include "reloc_bnb.h"
+#include "map_register.h"
 
 struct liodom_map {
   liodom_map_config_t cfg;
@@ -36,6 +37,8 @@ struct liodom_map {
   size_t blocks_entries = 0;               // first call allocates them, a call that needs more regrows them)
   unsigned char* h_pin = nullptr;          // liodom_map_search_pose_bnb: pinned host staging of a round's nodes, candidates and counts
   size_t pin_bytes = 0;
+  unsigned char* d_reg = nullptr;          // liodom_map_register_poses: the workspace map_register.h lays out (the first call allocates
+  size_t reg_bytes = 0;                    // it, a call whose n x local_capacity needs more regrows it)
   // attachments to a handle's streams (liodom_attach_mapper* / liodom_attach_map_reader, map_attach.h): the map runs on the
   // handle's HIP stream while link.n_attached > 0 and gets one of its own again when the last attachment goes
   liodom_dev::MapLink link;
@@ -187,6 +190,7 @@ void map_free(liodom_map* mp) {
   if (mp->d_occ) (void)hipFree(mp->d_occ);
   if (mp->d_blocks) (void)hipFree(mp->d_blocks);
   if (mp->h_pin) (void)hipHostFree(mp->h_pin);
+  if (mp->d_reg) (void)hipFree(mp->d_reg);
   if (mp->own_stream && mp->stream) (void)hipStreamDestroy(mp->stream);
   delete mp;
 }
@@ -1011,6 +1015,99 @@ int liodom_map_search_pose_bnb(liodom_map_t* mp, const float* edges_xyzi, int n_
     std::fprintf(stderr, "liodom_map_search_pose_bnb: build %.3f ms, bound %.3f ms, exact %.3f ms, host %.3f ms, total %.3f ms\n", clk.build, clk.bound,
                  clk.exact, total - clk.build - clk.bound - clk.exact, total);
   }
+  return LIODOM_OK;
+}
+
+// ---- registering a scan to the map (kernels_register.h, map_register.h) ----
+void liodom_map_register_default(liodom_map_register_t* o) {
+  if (o) liodom_dev::map_register_default(o);
+}
+
+int liodom_map_register_poses(liodom_map_t* mp, const float* edges, int n_edges, const double* poses, int n, const liodom_map_register_t* opt,
+                              liodom_map_registration_t* out, int32_t* corr) {
+  using namespace liodom_dev;
+  // every refusal comes before anything is allocated, staged or launched
+  if (!mp || !poses || !out || (n_edges > 0 && !edges)) { g_last_error = "liodom_map_register_poses: null map, poses, out or edges"; return LIODOM_ERR_INVALID_ARG; }
+  if (n < 1 || n > kRegisterRowsMax) { g_last_error = "liodom_map_register_poses: n outside 1 .. 64"; return LIODOM_ERR_INVALID_ARG; }
+  if (n_edges < 0 || n_edges > mp->cfg.max_update_points) { g_last_error = "liodom_map_register_poses: n_edges negative or above the map's max_update_points"; return LIODOM_ERR_INVALID_ARG; }
+  liodom_map_register_t o;
+  if (opt) o = *opt; else map_register_default(&o);
+  if (const char* why = map_register_check(&o)) { g_last_error = std::string("liodom_map_register_poses: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  for (int i = 0; i < n; i++) {
+    if (pose7_check(poses + 7 * (size_t)i) != kPose7Ok) {
+      g_last_error = "liodom_map_register_poses: non-finite pose, or the quaternion is not normalised (" POSE7_RULE ")"; return LIODOM_ERR_INVALID_ARG;
+    }
+  }
+  const int cap = map_register_local_cap(&o);
+  RegisterLayout L;
+  if (!map_register_layout(n, cap, mp->cfg.max_update_points, &L)) { g_last_error = "liodom_map_register_poses: n x local_capacity does not fit a workspace"; return LIODOM_ERR_CAPACITY; }
+  HIP_TRY(hipSetDevice(mp->device));
+  if (mp->reg_bytes < (size_t)L.bytes) {
+    HIP_TRY(hipStreamSynchronize(mp->stream));
+    if (mp->d_reg) { (void)hipFree(mp->d_reg); mp->d_reg = nullptr; mp->reg_bytes = 0; }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&mp->d_reg), (size_t)L.bytes));
+    mp->reg_bytes = (size_t)L.bytes;
+  }
+  unsigned char* ws = mp->d_reg;
+  double* d_pose = reinterpret_cast<double*>(ws + L.pose);
+  double* d_T = reinterpret_cast<double*>(ws + L.T);
+  int* d_cnt = reinterpret_cast<int*>(ws + L.count);
+  float4* d_pts = reinterpret_cast<float4*>(ws + L.pts);
+  // the start poses as liodom_seed_stream makes its own: quaternion normalised in double, the matrix by iso_from_qt
+  std::vector<double> h_pose(8 * (size_t)n, 0.0), h_T(12 * (size_t)n);
+  for (int i = 0; i < n; i++) {
+    pose7_normalised(poses + 7 * (size_t)i, h_pose.data() + 8 * (size_t)i);
+    iso_from_qt(h_pose.data() + 8 * (size_t)i, h_pose.data() + 8 * (size_t)i + 4, h_T.data() + 12 * (size_t)i);
+  }
+  HIP_TRY(hipMemcpyAsync(d_pose, h_pose.data(), sizeof(double) * h_pose.size(), hipMemcpyHostToDevice, mp->stream));
+  HIP_TRY(hipMemcpyAsync(d_T, h_T.data(), sizeof(double) * h_T.size(), hipMemcpyHostToDevice, mp->stream));
+  if (n_edges > 0) HIP_TRY(hipMemcpyAsync(mp->d_in, edges, sizeof(float4) * (size_t)n_edges, hipMemcpyHostToDevice, mp->stream));
+  // 1. the rows' local maps, fetched once (content and order of liodom_map_get_local)
+  if (map_rows_fit(mp, o.cells_xy, o.cells_z)) {
+    MapRows r{};
+    r.T = d_T; r.T_stride = 12; r.out = d_pts; r.out_stride = cap; r.n_out = d_cnt; r.n_stride = 1; r.total = d_cnt + n;
+    r.sel = nullptr; r.list = nullptr; r.tag = 0; r.s0 = 0; r.cap = cap; r.cells_xy = o.cells_xy; r.cells_z = o.cells_z; r.sticky = 0;
+    hipLaunchKernelGGL(k_map_local_rows<false>, dim3(map_rows_grid_x(n, cap), n), dim3(kMapRowsThreads), 0, mp->stream, mp->m, r);
+    HIP_TRY(hipGetLastError());
+  } else {
+    // a visit the LDS plan cannot hold: the two launches of liodom_map_get_local, row after row, as readers do
+    for (int i = 0; i < n; i++) {
+      int rc = map_enqueue_local(mp, d_T + 12 * (size_t)i, o.cells_xy, o.cells_z, d_pts + (size_t)i * cap, cap, d_cnt + i, mp->stream, 0);
+      if (rc) return rc;
+      HIP_TRY(hipMemcpyAsync(d_cnt + n + i, &mp->m.st->n_result, sizeof(int), hipMemcpyDeviceToDevice, mp->stream));
+    }
+  }
+  std::vector<int> cnt(2 * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost, mp->stream));
+  HIP_TRY(hipStreamSynchronize(mp->stream));
+  bool fits = true;
+  for (int i = 0; i < n; i++) fits = fits && cnt[(size_t)n + i] <= cap;
+  if (!fits) {
+    for (int i = 0; i < n; i++) out[i].local_points = cnt[(size_t)n + i];
+    g_last_error = "liodom_map_register_poses: a row's local map is larger than local_capacity"; return LIODOM_ERR_CAPACITY;
+  }
+  // 2. a 1 m grid per row, 3. every pass and every LM iteration of every row in one launch
+  RegisterView v{};
+  v.pose = d_pose; v.count = d_cnt; v.pts = d_pts;
+  v.order = reinterpret_cast<int*>(ws + L.order); v.slot = reinterpret_cast<int*>(ws + L.slot);
+  v.key = reinterpret_cast<unsigned long long*>(ws + L.key); v.first = reinterpret_cast<int*>(ws + L.first); v.fill = reinterpret_cast<int*>(ws + L.fill);
+  v.corr = reinterpret_cast<int2*>(ws + L.corr); v.out = reinterpret_cast<liodom_map_registration_t*>(ws + L.out);
+  v.edges = mp->d_in; v.n_edges = n_edges; v.local_cap = cap; v.edge_cap = std::max(L.edge_cap, 1); v.table = L.table;
+  v.max_passes = o.max_passes; v.min_matches = o.min_matches;
+  v.stop_t = o.stop_translation; v.stop_r = o.stop_rotation; v.min_range = o.min_range; v.max_range = o.max_range;
+  {
+    MapStateTimer tm(mp->stream, "liodom_map_register_poses");
+    hipLaunchKernelGGL(k_map_register_grid, dim3(n), dim3(kRegThreads), 0, mp->stream, v);
+    hipLaunchKernelGGL(k_map_register, dim3(n), dim3(kRegThreads), 0, mp->stream, v);
+    tm.stop();
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, v.out, sizeof(liodom_map_registration_t) * (size_t)n, hipMemcpyDeviceToHost, mp->stream));
+  if (corr && n_edges > 0) {
+    for (int i = 0; i < n; i++)
+      HIP_TRY(hipMemcpyAsync(corr + 2 * (size_t)i * (size_t)n_edges, v.corr + (size_t)i * v.edge_cap, sizeof(int2) * (size_t)n_edges, hipMemcpyDeviceToHost, mp->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(mp->stream));      // (the staged edges and poses are the caller's memory)
   return LIODOM_OK;
 }
 

@@ -1088,6 +1088,25 @@ LD_HD int lm_update(LmState& st, const double* acc) {
 }
 
 // ---------------------------------------------------------------------------------------
+// liodom_map_register_poses (kernels_register.h): how far one pass moved the pose and whether that ends the row as converged.
+// move_t = |t_new - t_old|_2, move_r = |vec(q_new (x) conj(q_old))|_2 — the half-angle size of the solver's tangent, whatever the
+// sign of either quaternion.  Converged iff move_t <= stop_t and move_r <= stop_r (a NaN move never converges).  Strict FP64.
+// tests/register_model.py restates it; tests/test_register_model.py holds this function to it.
+// ---------------------------------------------------------------------------------------
+LD_HD bool register_pass_converged(const double* q_old, const double* t_old, const double* q_new, const double* t_new, double stop_t,
+                                   double stop_r, double* move_t, double* move_r) {
+  const double d0 = t_new[0] - t_old[0], d1 = t_new[1] - t_old[1], d2 = t_new[2] - t_old[2];
+  *move_t = sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+  const double ax = q_new[0], ay = q_new[1], az = q_new[2], aw = q_new[3];
+  const double bx = -q_old[0], by = -q_old[1], bz = -q_old[2], bw = q_old[3];
+  const double vx = ((aw * bx + ax * bw) + ay * bz) - az * by;
+  const double vy = ((aw * by + ay * bw) + az * bx) - ax * bz;
+  const double vz = ((aw * bz + az * bw) + ax * by) - ay * bx;
+  *move_r = sqrt((vx * vx + vy * vy) + vz * vz);
+  return *move_t <= stop_t && *move_r <= stop_r;
+}
+
+// ---------------------------------------------------------------------------------------
 // Pose graph (kernels_graph.h; contract: include/liodom_hip.h "closing loops").  No counterpart in the reference.  Strict FP64,
 // no contraction.  A pose is X = (q, t), world <- frame, [qx qy qz qw tx ty tz], q of unit norm.  An edge (i, j, Z, Omega) says
 // "X_i^-1 o X_j was measured as Z".  D = Z^-1 o X_i^-1 o X_j = (q_d, t_d) with

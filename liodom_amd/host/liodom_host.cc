@@ -796,6 +796,20 @@ liodom_pose_search_result_t Map::searchPoseBnb(const PointCloud& edges, const li
   return out;
 }
 
+std::vector<liodom_map_registration_t> Map::registerPoses(const PointCloud& edges, const std::vector<std::array<double, 7>>& poses,
+                                                          const liodom_map_register_t* opt, std::vector<int32_t>* corr) {
+  const int n = (int)poses.size(), n_edges = (int)edges.points.size();
+  std::vector<double> p(7 * (size_t)std::max(n, 1));
+  for (int i = 0; i < n; i++) std::copy(poses[(size_t)i].begin(), poses[(size_t)i].end(), p.begin() + 7 * (size_t)i);
+  std::vector<liodom_map_registration_t> out((size_t)std::max(n, 1));
+  if (corr) corr->assign(2 * (size_t)n * (size_t)n_edges, -1);
+  check(liodom_map_register_poses(m_, reinterpret_cast<const float*>(edges.points.data()), n_edges, p.data(), n, opt, out.data(),
+                                  corr && !corr->empty() ? corr->data() : nullptr),
+        "liodom_map_register_poses");
+  out.resize((size_t)n);
+  return out;
+}
+
 void LaserOdometer::attachMapper(Map* map, int cells_xy, int cells_z) {
   check(liodom_attach_mapper(eng_->handle(), 0, map ? map->handle() : nullptr, cells_xy, cells_z), "liodom_attach_mapper");
 }

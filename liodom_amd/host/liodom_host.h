@@ -248,6 +248,12 @@ class Map {
   // 2^31 - 1 candidates; batch 0: the library's default; *stats (optional): what the search did.
   liodom_pose_search_result_t searchPoseBnb(const PointCloud& edges, const liodom_pose_search_t& search, int batch = 0,
                                             liodom_pose_search_stats_t* stats = nullptr);
+  // registerPoses (liodom_map_register_poses; no counterpart in the reference): the edge cloud registered to the map in 6-DoF from
+  // every start pose ([qx qy qz qw tx ty tz]) in one call; one record per pose.  opt = nullptr: liodom_map_register_default.
+  // *corr (optional): per pose and edge the last pass's (a, b) indices into the row's local map, -1 without a correspondence.
+  // Only reads the map; works on an attached one between scans.
+  std::vector<liodom_map_registration_t> registerPoses(const PointCloud& edges, const std::vector<std::array<double, 7>>& poses,
+                                                       const liodom_map_register_t* opt = nullptr, std::vector<int32_t>* corr = nullptr);
   int numCells();
   liodom_map_t* handle() const { return m_; }
   double xySize() const { return xy_; }

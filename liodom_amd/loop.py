@@ -10,8 +10,12 @@ the whole graph under the plain quadratic cost.  close(loss=(name, scale), rejec
 with a robust loss on the loop edges (kind 1), the loop edges whose weight collapsed below r switched off, and a second, plain
 quadratic solve over the survivors from the robust result, which takes the robust loss's bias off them.
 
-What close() cannot do: scans that were no key frames are not in the rebuilt map (their clouds are not kept); a loop measurement
-is as fine as the last search level's step.  The robust solve is only as good as its scale, which is in units of sqrt(chi2) of
+A searched pose is a grid cell: x, y, yaw as fine as the last level's step, no roll, pitch or z.  LoopCloser(refine=dict(...))
+registers it to the map in 6-DoF first (Map.register_poses, refine_loop) and measures the loop edge with the registered pose;
+loop_info="solve" then weighs the edge by what that registration's solve knows, instead of a constant.
+
+What close() cannot do: scans that were no key frames are not in the rebuilt map (their clouds are not kept); without refine a
+loop measurement is as fine as the last search level's step.  The robust solve is only as good as its scale, which is in units of sqrt(chi2) of
 a loop edge: it has to exceed what honest drift puts on a TRUE loop edge at the dead-reckoned poses, or the true edges are
 down-weighted with the false one and the solve settles in the wrong minimum (DESIGN.md §3 "Closing loops" has a ring of 8 key
 frames on which Geman-McClure with scale 3 rejects every true loop and scale 5 does not).  And it rejects by consensus: where
@@ -56,6 +60,31 @@ def between(Xi, Xj):
     return compose(inverse(Xi), Xj)
 
 
+def edge_jacobian_j(Xi, Xj, Z):
+    """B = de / d(delta_j) of graph_edge_error (liodom_math.h) at (X_i, X_j, Z): [[Q, 0], [0, W]] with W = R_z^T R_i^T and
+    Q[:, k] = s vec(conj(q_z) (x) conj(q_i) (x) [e_k, 0] (x) q_j), s the sign of the error quaternion's w."""
+    Xi, Xj, Z = _pose(Xi), _pose(Xj), _pose(Z)
+    conj = lambda q: np.array([-q[0], -q[1], -q[2], q[3]])
+    a = _qmul(conj(Z[:4]), conj(Xi[:4]))
+    s = 1.0 if _qmul(a, Xj[:4])[3] >= 0 else -1.0
+    B = np.zeros((6, 6))
+    for k in range(3):
+        e = np.zeros(4)
+        e[k] = 1.0
+        B[:3, k] = s * _qmul(_qmul(a, e), Xj[:4])[:3]
+    B[3:, 3:] = api.pose_T34(Z)[:, :3].T @ api.pose_T34(Xi)[:, :3].T
+    return B
+
+
+def solve_information(place_pose, registered_pose, Z, H, sigma2):
+    """The information of the loop edge "X_place^-1 o X_registered was measured as Z" from the registration's solve: the pose's
+    covariance is sigma2 H^-1 in the solver's tangent, which is the graph's, and the edge's error moves by e = B delta_j, so
+    Omega = B^-T (H / sigma2) B^-1.  Symmetric by construction (the two halves are averaged against rounding)."""
+    Binv = np.linalg.inv(edge_jacobian_j(place_pose, registered_pose, Z))
+    om = Binv.T @ (np.asarray(H, np.float64).reshape(6, 6) / float(sigma2)) @ Binv
+    return 0.5 * (om + om.T)
+
+
 class LoopCloser:
     """LoopCloser(map, places, levels, ...): feed(pose, edges) per scan, close() when loops have been found.
 
@@ -67,6 +96,11 @@ class LoopCloser:
     k             matches asked of the database per key frame
     min_fraction  a match becomes a loop edge if its last level scores (hits_r + hits_0) / (2 n_edges) >= min_fraction
     odometry_info, loop_info   the information matrices (6 x 6, half-angle rotation first) of the two kinds of edge
+    refine        None, or dict(options of Map.register_poses, min_fraction=...): a searched pose is registered to the map in 6-DoF
+                  (refine_loop) and the loop edge measures the registered pose; it is kept only if the registration ended CONVERGED
+                  or MAX_PASSES with matches / n_edges >= refine's min_fraction (default 0.25)
+                  loop_info="solve" (needs refine): the edge's information is solve_information of the registration; where that
+                  is not defined (flags other than COV_VALID) LOOP_INFO stands
     max_update_points          points per Map.update call of the rebuild
 
     `places` must be this LoopCloser's alone: empty when it is handed in, and filled by feed() only — a place's tag is its key
@@ -77,9 +111,16 @@ class LoopCloser:
     key_poses: the key frames' poses as fed (after close(): as corrected); clouds: their edge clouds (sensor frame)."""
 
     def __init__(self, map, places, levels, graph=None, min_dist=4.0, min_yaw=float("inf"), min_gap=10, k=3, min_fraction=0.5,
-                 odometry_info=ODOMETRY_INFO, loop_info=LOOP_INFO, max_update_points=65536, max_nodes=4096, max_edges=16384):
+                 odometry_info=ODOMETRY_INFO, loop_info=LOOP_INFO, max_update_points=65536, max_nodes=4096, max_edges=16384, refine=None):
         if min_gap < 1 or k < 1:
             raise ValueError("LoopCloser: needs min_gap >= 1 and k >= 1")
+        self.info_from_solve = isinstance(loop_info, str)
+        if self.info_from_solve:
+            if loop_info != "solve" or refine is None:
+                raise ValueError("LoopCloser: loop_info is a 6 x 6 matrix, or \"solve\" together with refine")
+            loop_info = LOOP_INFO
+        self.refine = None if refine is None else dict(refine)
+        self.refine_min_fraction = float(self.refine.pop("min_fraction", 0.25)) if self.refine is not None else None
         self.map, self.places, self.levels = map, places, list(levels)
         self.graph = api.PoseGraph(max_nodes, max_edges) if graph is None else graph
         self.policy = api.PlacePolicy(min_dist, min_yaw)
@@ -120,10 +161,37 @@ class LoopCloser:
                 fraction = (results[-1]["hits_r"] + results[-1]["hits_0"]) / (2.0 * edges.shape[0])
                 if not fraction >= self.min_fraction:
                     continue
-                self.graph.add_edges(api.graph_edges([place], [node], [between(m["place_pose"], found)], self.loop_info, kind=1))
+                if self.refine is None:
+                    self.graph.add_edges(api.graph_edges([place], [node], [between(m["place_pose"], found)], self.loop_info, kind=1))
+                    self.loops.append((place, node))
+                    loops.append(dict(place=place, node=node, fraction=fraction, pose=np.array(found, np.float64), match=m))
+                    continue
+                Z, info, record = self.refine_loop(edges, m["place_pose"], found)
+                if Z is None:
+                    continue
+                self.graph.add_edges(api.graph_edges([place], [node], [Z], info, kind=1))
                 self.loops.append((place, node))
-                loops.append(dict(place=place, node=node, fraction=fraction, pose=np.array(found, np.float64), match=m))
+                loops.append(dict(place=place, node=node, fraction=fraction, pose=record["pose"].copy(), match=m,
+                                  searched_pose=np.array(found, np.float64), registration=record))
         return dict(key_frame=True, node=node, loops=loops)
+
+    def refine_loop(self, edges, place_pose, found):
+        """Registers the searched pose `found` of the edge cloud `edges` to the map (Map.register_poses with refine's options) ->
+        (Z, info, record): Z = between(place_pose, registered pose) and its information — loop_info, or with loop_info="solve"
+        solve_information of the registration —, record = the registration's dict.  (None, None, record) if the registration did
+        not end CONVERGED or MAX_PASSES, or with matches / n_edges below refine's min_fraction: no loop edge."""
+        if self.refine is None:
+            raise ValueError("LoopCloser.refine_loop: the LoopCloser was made without refine")
+        edges = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
+        record = self.map.register_poses(edges, np.asarray(found, np.float64).reshape(1, 7), **self.refine)[0]
+        taken = record["termination"] in (api.REG_CONVERGED, api.REG_MAX_PASSES)
+        if not taken or edges.shape[0] == 0 or not record["matches"] / float(edges.shape[0]) >= self.refine_min_fraction:
+            return None, None, record
+        Z = between(place_pose, record["pose"])
+        info = self.loop_info
+        if self.info_from_solve and record["cov_flags"] == api.COV_VALID and record["sigma2"] > 0.0 and np.isfinite(record["information"]).all():
+            info = solve_information(place_pose, record["pose"], Z, record["information"], record["sigma2"])
+        return Z, info, record
 
     def add_loop(self, place, node, Z, info=None):
         """A loop edge from another source — a surveyed tie, a user's hint, a test —: "X_place^-1 o X_node was measured as Z", the
