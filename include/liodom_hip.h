@@ -1083,6 +1083,57 @@ int liodom_graph_set_edge_active(liodom_graph_t* g, int first, int n, const int3
 int liodom_graph_get_edge_active(liodom_graph_t* g, int first, int n, int32_t* active);
 int liodom_graph_edge_weights(liodom_graph_t* g, double* rho /*optional, [n_edges]*/, double* weight /*optional, [n_edges]*/);
 
+/* ---- covariances of the graph and the loop gate (DESIGN.md §3 "Covariances of the graph and the loop gate").
+ * All opt-in: a graph on which none of these calls is made computes what it did before they existed.  None of them changes poses,
+ * edges or settings.
+ *
+ * H is the matrix liodom_graph_multiply(g, 0, ...) applies at the current poses: over the active edges, weighted where a robust
+ * loss is set, rows and columns of fixed nodes dropped.  Sigma = H^-1 in the coordinates of delta — half-angle rotation first,
+ * then translation, world frame: those of liodom_pose_cov_t.  Sigma[r, c] is the 6 x 6 block of nodes r and c, row-major.  A
+ * column of Sigma is solved by preconditioned conjugate gradients, one workgroup per column, until |e_c - H x| <= pcg_tolerance
+ * (by the solver's own recurrence) or max_pcg_iterations.
+ *   liodom_graph_cov_options_default   max_pcg_iterations 0 (= 6 x free nodes, at most 65 536), batch_columns 0 (columns per
+ *       launch; 0: as many as fit 256 MiB of workspace, at least 6), pcg_tolerance 1e-8.  opt NULL in a call: these.
+ *   liodom_graph_solve_columns   x[k] (6 columns of 6 n_nodes doubles each, column b of node nodes[k] at x + (6 k + b) 6 n_nodes)
+ *       and status[6 k + b] with the iterations, the LIODOM_GRAPH_COV_* status and the recurrence's |r| of that column.
+ *   liodom_graph_covariance      blocks[k] = Sigma[rows[k], cols[k]] (36 doubles) and status[k].
+ *   liodom_graph_gate_edges      for each candidate edge (i, j, Z, Omega; validated exactly as liodom_graph_add_edges validates,
+ *       kind ignored): d2 = e^T S^-1 e, S = [A B] [[Sigma ii, Sigma ij], [Sigma ij^T, Sigma jj]] [A B]^T + Omega^-1 with e, A, B
+ *       the edge's error and Jacobians at the current poses — the squared Mahalanobis distance between the measured Z and the
+ *       relative pose the graph predicts; chi-square with 6 degrees of freedom if the graph's information matrices are honest.
+ *   liodom_graph_cov_counters    how many column launches these calls have made on g and how many columns those solved, since
+ *       liodom_graph_create (either optional).
+ * Statuses — a block takes the worst of its six columns, a gate the worst of its two nodes' columns; the numbers ascend:
+ *     LIODOM_GRAPH_COV_OK 0              solved                                             the block or d2
+ *     LIODOM_GRAPH_COV_NOT_CONVERGED 1   the iterations ran out                             the last iterate
+ *     LIODOM_GRAPH_COV_BREAKDOWN 2       the solve broke down (H not positive definite)     NaN
+ *     LIODOM_GRAPH_COV_UNANCHORED 3      the node's connected component over the active edges holds no fixed node: it has no
+ *                                        finite covariance; no solve is launched for it    NaN
+ *     LIODOM_GRAPH_COV_NOT_PD 4          Omega of the candidate or S is not positive definite (gate only)   NaN
+ * A fixed node gives zero columns and zero blocks, status OK, whatever the other node is.  Equal graphs, settings and queries give equal bytes,
+ * whatever batch_columns is.  LIODOM_ERR_INVALID_ARG, graph untouched, as above; also an option that is negative or a NaN. */
+typedef struct liodom_graph_cov_options_t {
+  int32_t max_pcg_iterations, batch_columns;
+  double pcg_tolerance;
+} liodom_graph_cov_options_t;  /* 16 bytes */
+#define LIODOM_GRAPH_COV_OK 0
+#define LIODOM_GRAPH_COV_NOT_CONVERGED 1
+#define LIODOM_GRAPH_COV_BREAKDOWN 2
+#define LIODOM_GRAPH_COV_UNANCHORED 3
+#define LIODOM_GRAPH_COV_NOT_PD 4
+typedef struct liodom_graph_cov_status_t {
+  int32_t iterations, status;
+  double residual;
+} liodom_graph_cov_status_t;   /* 16 bytes */
+void liodom_graph_cov_options_default(liodom_graph_cov_options_t* opt);
+int liodom_graph_solve_columns(liodom_graph_t* g, const int32_t* nodes, int n, const liodom_graph_cov_options_t* opt,
+                               double* x /*n x 6 x 6 n_nodes*/, liodom_graph_cov_status_t* status /*n x 6*/);
+int liodom_graph_covariance(liodom_graph_t* g, const int32_t* rows, const int32_t* cols, int n, const liodom_graph_cov_options_t* opt,
+                            double* blocks /*n x 36*/, int32_t* status /*n*/);
+int liodom_graph_gate_edges(liodom_graph_t* g, const liodom_graph_edge_t* candidates, int n, const liodom_graph_cov_options_t* opt,
+                            double* d2 /*n*/, int32_t* status /*n*/);
+int liodom_graph_cov_counters(liodom_graph_t* g, int64_t* launches /*optional*/, int64_t* columns /*optional*/);
+
 #ifdef __cplusplus
 }
 #endif

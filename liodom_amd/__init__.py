@@ -10,4 +10,5 @@ from .api import (Places, PlaceGeometry, PlaceMatch, PlacePolicy, PLACE_MATCH_DT
                   load, make_config, make_params, parse_stream_state, parse_map_state, build_map_state, join_map_state, PolarGeometry, PolarLayout, polar_geometry,
                   polar_geometry_from_angles, polar_layout, pack_polar,
                   RegisterOptions, Registration, make_register_options, registration_dict,
-                  PoseGraph, GraphEdge, GraphOptions, GraphReport, GRAPH_EDGE_DTYPE, GRAPH_TERMINATIONS, graph_edges, make_graph_options)
+                  PoseGraph, GraphEdge, GraphOptions, GraphReport, GRAPH_EDGE_DTYPE, GRAPH_TERMINATIONS, graph_edges, make_graph_options,
+                  GraphCovOptions, GRAPH_COV_STATUSES, GRAPH_COV_STATUS_DTYPE, make_graph_cov_options)

@@ -16,7 +16,7 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
                                                   "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h", "kernels_register.h", "map_register.h",
                                                   "kernels_places.h", "liodom_places_host.h", "place_state_format.h",
-                                                  "kernels_graph.h", "liodom_graph_host.h", "graph_csr.h",
+                                                  "kernels_graph.h", "liodom_graph_host.h", "graph_csr.h", "graph_marginals.h",
                                                   "liodom_sizes.h", "handle_plan.h", "step_plan.h", "edge_pipe.h", "map_attach.h", "liodom_step_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
@@ -285,6 +285,16 @@ class GraphReport(C.Structure):
     """liodom_graph_report_t."""
     _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("max_gradient", C.c_double), ("final_lambda", C.c_double),
                 ("iterations", C.c_int32), ("accepted_steps", C.c_int32), ("pcg_iterations", C.c_int32), ("termination", C.c_int32)]
+
+
+class GraphCovOptions(C.Structure):
+    """liodom_graph_cov_options_t."""
+    _fields_ = [("max_pcg_iterations", C.c_int32), ("batch_columns", C.c_int32), ("pcg_tolerance", C.c_double)]
+
+
+GRAPH_COV_STATUSES = ("ok", "not_converged", "breakdown", "unanchored", "not_pd")      # LIODOM_GRAPH_COV_*
+GRAPH_COV_OK, GRAPH_COV_NOT_CONVERGED, GRAPH_COV_BREAKDOWN, GRAPH_COV_UNANCHORED, GRAPH_COV_NOT_PD = range(5)
+GRAPH_COV_STATUS_DTYPE = np.dtype([("iterations", "<i4"), ("status", "<i4"), ("residual", "<f8")])      # liodom_graph_cov_status_t
 
 
 class PlacePolicy:
@@ -955,6 +965,16 @@ def load():
     L.liodom_graph_get_edge_active.argtypes = [vp, C.c_int, C.c_int, ip]
     L.liodom_graph_edge_weights.restype = C.c_int
     L.liodom_graph_edge_weights.argtypes = [vp, dp, dp]
+    L.liodom_graph_cov_options_default.restype = None
+    L.liodom_graph_cov_options_default.argtypes = [C.POINTER(GraphCovOptions)]
+    L.liodom_graph_solve_columns.restype = C.c_int
+    L.liodom_graph_solve_columns.argtypes = [vp, ip, C.c_int, C.POINTER(GraphCovOptions), dp, vp]
+    L.liodom_graph_covariance.restype = C.c_int
+    L.liodom_graph_covariance.argtypes = [vp, ip, ip, C.c_int, C.POINTER(GraphCovOptions), dp, ip]
+    L.liodom_graph_gate_edges.restype = C.c_int
+    L.liodom_graph_gate_edges.argtypes = [vp, vp, C.c_int, C.POINTER(GraphCovOptions), dp, ip]
+    L.liodom_graph_cov_counters.restype = C.c_int
+    L.liodom_graph_cov_counters.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -1013,6 +1033,8 @@ EXPORTED_SYMBOLS = [
     "liodom_graph_linearize", "liodom_graph_multiply", "liodom_graph_options_default", "liodom_graph_optimize",
     "liodom_graph_set_loss", "liodom_graph_get_loss", "liodom_graph_set_edge_active", "liodom_graph_get_edge_active",
     "liodom_graph_edge_weights",
+    "liodom_graph_cov_options_default", "liodom_graph_solve_columns", "liodom_graph_covariance", "liodom_graph_gate_edges",
+    "liodom_graph_cov_counters",
 ]
 
 
@@ -2069,6 +2091,18 @@ def make_graph_options(**kw):
     return o
 
 
+def make_graph_cov_options(**kw):
+    """GraphCovOptions with the defaults of liodom_graph_cov_options_default (PCG to 1e-8 in at most 6 x free nodes iterations,
+    columns per launch chosen by the library)."""
+    o = GraphCovOptions()
+    load().liodom_graph_cov_options_default(C.byref(o))
+    for k, v in kw.items():
+        if k not in ("max_pcg_iterations", "batch_columns", "pcg_tolerance"):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
+
+
 def graph_edges(i, j, z, info, kind=0):
     """n edge records (GRAPH_EDGE_DTYPE) from i (n,), j (n,), z [n, 7] and info [n, 6, 6] or one [6, 6] for all."""
     i = np.asarray(i, np.int32).reshape(-1)
@@ -2212,3 +2246,46 @@ class PoseGraph:
         rho, w = np.zeros(max(E, 1)), np.zeros(max(E, 1))
         self._chk(self._L.liodom_graph_edge_weights(self.h, _dp(rho), _dp(w)))
         return rho[:E], w[:E]
+
+    # ---- covariances and the loop gate (include/liodom_hip.h "covariances of the graph"; keywords: make_graph_cov_options) ----
+    def solve_columns(self, nodes, **opt):
+        """Columns of Sigma = H^-1 at the current poses (liodom_graph_solve_columns) -> (x [n, 6, N, 6], status (n, 6) of
+        GRAPH_COV_STATUS_DTYPE): x[k, b] is the column of component b of node nodes[k], laid out as delta is; status[k, b] its
+        iterations, status (GRAPH_COV_*) and the recurrence's |r|."""
+        v = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
+        n, N = v.shape[0], self.count()[0]
+        x = np.zeros((max(n, 1), 6, max(N, 1), 6))
+        st = np.zeros((max(n, 1), 6), GRAPH_COV_STATUS_DTYPE)
+        o = make_graph_cov_options(**opt)
+        self._chk(self._L.liodom_graph_solve_columns(self.h, _ip(v) if n else None, n, C.byref(o), _dp(x), st.ctypes.data_as(C.c_void_p)))
+        return x[:n], st[:n]
+
+    def covariance(self, rows, cols=None, **opt):
+        """Blocks of Sigma = H^-1 at the current poses (liodom_graph_covariance) -> (blocks [n, 6, 6], status (n,) of GRAPH_COV_*):
+        blocks[k] = Sigma[rows[k], cols[k]], half-angle rotation first, world frame; cols None: the marginals Sigma[n, n]."""
+        r = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int32)
+        c = r.copy() if cols is None else np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int32)
+        if c.shape[0] != r.shape[0]:
+            raise ValueError("one column node per row node")
+        n = r.shape[0]
+        blocks, st = np.zeros((max(n, 1), 6, 6)), np.zeros(max(n, 1), np.int32)
+        o = make_graph_cov_options(**opt)
+        self._chk(self._L.liodom_graph_covariance(self.h, _ip(r) if n else None, _ip(c) if n else None, n, C.byref(o), _dp(blocks), _ip(st)))
+        return blocks[:n], st[:n]
+
+    def gate_edges(self, edges, **opt):
+        """The chi-square gate of candidate edges (GRAPH_EDGE_DTYPE, not added) -> (d2 (n,), status (n,) of GRAPH_COV_*): the
+        squared Mahalanobis distance between each edge's z and the relative pose the graph predicts, under the graph's own
+        covariance plus the edge's (liodom_graph_gate_edges); NaN unless the status is ok or not_converged."""
+        e = np.ascontiguousarray(edges, dtype=GRAPH_EDGE_DTYPE).reshape(-1)
+        n = e.shape[0]
+        d2, st = np.zeros(max(n, 1)), np.zeros(max(n, 1), np.int32)
+        o = make_graph_cov_options(**opt)
+        self._chk(self._L.liodom_graph_gate_edges(self.h, e.ctypes.data_as(C.c_void_p) if n else None, n, C.byref(o), _dp(d2), _ip(st)))
+        return d2[:n], st[:n]
+
+    def cov_counters(self):
+        """(column launches, columns solved) by the three calls above since the graph was made."""
+        a, b = C.c_int64(), C.c_int64()
+        self._chk(self._L.liodom_graph_cov_counters(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value

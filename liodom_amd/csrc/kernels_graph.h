@@ -13,6 +13,9 @@
 //   k_graph_retract / k_graph_cost / k_graph_sum   the candidate poses, their chi2 per edge, and a sum in a fixed order
 //   k_graph_linearize_robust / k_graph_cost_robust   the same two with a robust loss per edge and edges that are switched off (at
 //                       the end of this file); launched only where a graph asks for either
+//   k_graph_pcg_columns / k_graph_cov_gather / k_graph_gate   columns of H^-1, one workgroup of k_graph_pcg's kind per column; the
+//                       6 x 6 blocks of H^-1 picked out of them; and the chi-square gate of a candidate edge (after the robust
+//                       instances, at the very end); launched only by the covariance calls
 //
 // Fixed nodes: delta = 0; their rows and columns drop out (gradient 0, inverse block 0, skipped as a neighbour).  A free node
 // without edges: its block counts as the identity, its gradient is 0, it stays where it is.
@@ -556,6 +559,150 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_cost_robust(int n_edges
   double r = 0.0, wt = 0.0;
   if (ce != kGraphLossInactive) graph_loss(ce, scale[e], s, &r, &wt);
   chi2[e] = s; rho[e] = r; w[e] = wt;
+}
+
+
+// ---- covariances of the graph and the loop gate (liodom_graph_solve_columns / _covariance / _gate_edges; graph_marginals.h plans
+// the launches; tests/graph_cov_model.py restates them).  They stand after every other kernel, as the robust instances do. ----
+//
+// k_graph_pcg_columns: columns of H^-1.  Workgroup b solves H x = e_c, c = first_column + b = 6 slot + k: the unit vector at
+// component k of node col_node[slot] (a free node whose component holds a fixed one: the host leaves every other node out), at
+// lambda = 0.  The loop is k_graph_pcg's — the same ownership of nodes, the same sums in the same order, the same breakdown tests —
+// as a second copy, so that k_graph_pcg's code does not move; what differs: the right-hand side, no gradient exit, and the
+// stopping rule |r| <= tolerance (|e_c| = 1).  Workgroup b owns the five vectors x, r, p, z, Ap (6 node_cap doubles each) at
+// ws + b * 30 * node_cap; it reads nothing another workgroup writes: no polling, no atomic, no flag.  status[b]: iterations,
+// flag (GRAPH_PCG_*), residual |r| when the loop ended; gmax is 0.
+__global__ __launch_bounds__(kGraphPcgThreads) void k_graph_pcg_columns(int n_nodes, long long node_cap, long long edge_cap, int first_column,
+                                                                        int max_iterations, double tolerance, const int* __restrict__ col_node,
+                                                                        const int* __restrict__ fixed, const int* __restrict__ parent,
+                                                                        const double* __restrict__ poses, const int* __restrict__ offsets,
+                                                                        const int* __restrict__ entries, const int* __restrict__ ei,
+                                                                        const int* __restrict__ ej, const double* __restrict__ D,
+                                                                        const double* __restrict__ Minv, const double* __restrict__ Hij,
+                                                                        const int* __restrict__ bad, double* ws,
+                                                                        GraphPcgStatus* __restrict__ status) {
+  __shared__ double sh_a[kGraphPcgWaves], sh_b[kGraphPcgWaves * 2];
+  __shared__ double sh_v1[kGraphPcgWaves * 9], sh_v2[kGraphPcgWaves * 9];
+  __shared__ int sh_f1[kGraphPcgWaves], sh_f2[kGraphPcgWaves];
+  const int tid = (int)threadIdx.x;
+  const int column = first_column + (int)blockIdx.x;
+  const int rhs_node = col_node[column / 6], rhs_k = column % 6;
+  double* x = ws + (long long)blockIdx.x * 30ll * node_cap;
+  double* r = x + 6ll * node_cap;
+  double* p = r + 6ll * node_cap;
+  double* zv = p + 6ll * node_cap;
+  double* Ap = zv + 6ll * node_cap;
+  const double lambda = 0.0;
+  for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) { x[6ll * n + k] = 0.0; r[6ll * n + k] = (n == rhs_node && k == rhs_k) ? 1.0 : 0.0; }
+  }
+  graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, sh_v1, sh_f1, sh_v2, sh_f2);
+  double s2[2] = {0.0, 0.0};
+  for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const double rk = r[6ll * n + k], zk = zv[6ll * n + k];
+      p[6ll * n + k] = zk;
+      s2[0] += rk * rk; s2[1] += rk * zk;
+    }
+  }
+  graph_block_sum<2>(s2, sh_b);
+  const double g2 = s2[0];
+  double rz = s2[1], rr = s2[0];
+  int iterations = 0, flag = GRAPH_PCG_MAX_ITER;
+  if (*bad != 0 || !(g2 > 0.0) || !ld_isfinite(g2) || !(rz > 0.0)) flag = GRAPH_PCG_BREAKDOWN;
+  else {
+    for (int it = 0; it < max_iterations; it++) {
+      __syncthreads();                               // p of every node is written
+      double s1[1] = {0.0};
+      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+        double y[6];
+        graph_row_multiply(n, node_cap, edge_cap, lambda, fixed, offsets, entries, ei, ej, D, Hij, p, y);
+#pragma unroll
+        for (int k = 0; k < 6; k++) { Ap[6ll * n + k] = y[k]; s1[0] += p[6ll * n + k] * y[k]; }
+      }
+      graph_block_sum<1>(s1, sh_a);
+      const double pAp = s1[0];
+      if (!(pAp > 0.0) || !ld_isfinite(pAp)) { flag = GRAPH_PCG_BREAKDOWN; break; }
+      const double alpha = rz / pAp;
+      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+          x[6ll * n + k] += alpha * p[6ll * n + k];
+          r[6ll * n + k] -= alpha * Ap[6ll * n + k];
+        }
+      }
+      graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, sh_v1, sh_f1, sh_v2, sh_f2);
+      s2[0] = 0.0; s2[1] = 0.0;
+      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) { const double rk = r[6ll * n + k]; s2[0] += rk * rk; s2[1] += rk * zv[6ll * n + k]; }
+      }
+      graph_block_sum<2>(s2, sh_b);
+      rr = s2[0];
+      iterations = it + 1;
+      if (rr <= tolerance * tolerance * g2) { flag = GRAPH_PCG_CONVERGED; break; }
+      if (!ld_isfinite(rr) || !(s2[1] > 0.0)) { flag = GRAPH_PCG_BREAKDOWN; break; }
+      const double beta = s2[1] / rz;
+      rz = s2[1];
+      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) p[6ll * n + k] = zv[6ll * n + k] + beta * p[6ll * n + k];
+      }
+    }
+  }
+  if (tid == 0) {
+    GraphPcgStatus* st = status + blockIdx.x;
+    st->iterations = iterations; st->flag = flag; st->gmax = 0.0;
+    st->residual = g2 > 0.0 ? sqrt(rr / g2) : 0.0;
+  }
+}
+
+// One thread per requested block k = Sigma[row[k], col[k]] (36 doubles, row-major): entry (a, b) is x of column 6 slot[col[k]] + b
+// at [6 row[k] + a], copied if that column is one of the n_columns this launch's workspace holds (first_column on); the other
+// entries are left as they are — the host clears the blocks once and launches this after every batch of columns.  slot[n] < 0 (a
+// fixed node, or one the solve leaves out) and fixed rows: nothing is written, the entries stay 0.
+__global__ __launch_bounds__(kGraphThreads) void k_graph_cov_gather(int n_blocks, long long node_cap, int first_column, int n_columns,
+                                                                    const int* __restrict__ row, const int* __restrict__ col,
+                                                                    const int* __restrict__ slot, const int* __restrict__ fixed,
+                                                                    const double* __restrict__ ws, double* __restrict__ blocks) {
+  const int k = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
+  if (k >= n_blocks) return;
+  const int rn = row[k], s = slot[col[k]];
+  if (s < 0 || fixed[rn] != 0) return;
+  for (int b = 0; b < 6; b++) {
+    const int c = 6 * s + b - first_column;
+    if (c < 0 || c >= n_columns) continue;
+    const double* x = ws + (long long)c * 30ll * node_cap + 6ll * rn;
+#pragma unroll
+    for (int a = 0; a < 6; a++) blocks[36ll * k + a * 6 + b] = x[a];
+  }
+}
+
+// One thread per candidate edge c = (ci[c], cj[c], z, info): graph_gate (liodom_math.h) at the current poses with the blocks
+// Sigma[i, i], Sigma[i, j], Sigma[j, j] at blocks[3 c], [3 c + 1], [3 c + 2].  flag[c] = 1 where Omega or S is not positive
+// definite (d2[c] is then NaN), else 0.
+__global__ __launch_bounds__(kGraphThreads) void k_graph_gate(int n, const double* __restrict__ poses, const int* __restrict__ ci,
+                                                              const int* __restrict__ cj, const double* __restrict__ z,
+                                                              const double* __restrict__ info, const double* __restrict__ blocks,
+                                                              double* __restrict__ d2, int* __restrict__ flag) {
+  const int c = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
+  if (c >= n) return;
+  double Xi[7], Xj[7], Z[7], Om[36], Sii[36], Sij[36], Sjj[36];
+  const double* pi = poses + 7ll * ci[c];
+  const double* pj = poses + 7ll * cj[c];
+#pragma unroll
+  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * c + k]; }
+#pragma unroll
+  for (int k = 0; k < 36; k++) {
+    Om[k] = info[36ll * c + k];
+    Sii[k] = blocks[108ll * c + k]; Sij[k] = blocks[108ll * c + 36 + k]; Sjj[k] = blocks[108ll * c + 72 + k];
+  }
+  double d;
+  const bool ok = graph_gate(Xi, Xj, Z, Om, Sii, Sij, Sjj, &d);
+  d2[c] = d;
+  flag[c] = ok ? 0 : 1;
 }
 
 }  // namespace liodom_dev

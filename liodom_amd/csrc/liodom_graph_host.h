@@ -11,11 +11,18 @@
 // every edge gets a code (its kind's loss, or "inactive") and a scale, and the CSR and the chain are made of the active edges.
 // If every code is 0 the quadratic kernels run, as they did before a loss existed; otherwise their robust twins, which also
 // write rho and w per edge, and the cost that is summed is rho.
+//
+// Covariances and the loop gate (liodom_graph_solve_columns / _covariance / _gate_edges): graph_marginals.h decides which nodes
+// have a covariance, which columns of H^-1 are solved and in how many launches; here graph_cov_solve launches
+// k_graph_pcg_columns on the linearisation graph_prepare keeps (lambda 0), k_graph_cov_gather picks the requested blocks out of
+// each launch's columns, k_graph_gate turns three blocks and a candidate edge into d2.  The host copy of the graph is only read.
 #pragma once
+#include <cmath>
 #include <mutex>
 #include <vector>
 
 #include "graph_csr.h"
+#include "graph_marginals.h"
 #include "kernels_graph.h"
 
 struct liodom_graph {
@@ -43,6 +50,11 @@ struct liodom_graph {
   double *d_scale = nullptr, *d_rho = nullptr, *d_w = nullptr;
   double *d_x = nullptr, *d_r = nullptr, *d_p = nullptr, *d_zv = nullptr, *d_Ap = nullptr, *d_in = nullptr, *d_sum = nullptr;
   liodom_dev::GraphPcgStatus* d_status = nullptr;
+  // the covariance calls (graph_marginals.h): buffers made at the first call that needs them, grown when a call needs more, freed
+  // with the graph
+  struct Grown { void* p = nullptr; size_t bytes = 0; };
+  Grown cov_ws, cov_status, cov_col_node, cov_slot, cov_rows, cov_cols, cov_blocks, cov_z, cov_info, cov_d2, cov_flag;
+  int64_t cov_launches = 0, cov_columns = 0;
 };
 
 namespace {
@@ -165,6 +177,126 @@ int graph_check_range(const liodom_graph* g, int first, int n, size_t have, cons
   }
   return LIODOM_OK;
 }
+
+// ---- the covariance calls ----
+int graph_grow(liodom_graph* g, liodom_graph::Grown* b, size_t bytes) {
+  if (bytes <= b->bytes && b->p) return LIODOM_OK;
+  void* raw = nullptr;
+  HIP_TRY(hipMalloc(&raw, std::max<size_t>(bytes, 16)));
+  if (b->p) {
+    for (void*& q : g->allocs) if (q == b->p) { q = raw; break; }
+    hipFree(b->p);
+  } else {
+    g->allocs.push_back(raw);
+  }
+  b->p = raw; b->bytes = std::max<size_t>(bytes, 16);
+  return LIODOM_OK;
+}
+
+int graph_cov_options(const liodom_graph_cov_options_t* in, liodom_graph_cov_options_t* opt, const char* who) {
+  liodom_dev::graph_cov_options_default(opt);
+  if (in) *opt = *in;
+  if (const char* why = liodom_dev::graph_cov_options_refusal(opt)) { g_last_error = std::string(who) + ": " + why; return LIODOM_ERR_INVALID_ARG; }
+  return LIODOM_OK;
+}
+
+// What a solve of the columns of some nodes leaves: which nodes have a covariance, the column nodes and, per column, its status.
+struct GraphCovSolve {
+  std::vector<int32_t> anchored, col_node, slot;
+  std::vector<liodom_graph_cov_status_t> column;      // [6 x column nodes]
+  // the status of node n's six columns: fixed OK, not anchored UNANCHORED, else the worst of the six
+  int32_t node_status(const liodom_graph* g, int32_t n) const {
+    if (g->fixed[(size_t)n]) return LIODOM_GRAPH_COV_OK;
+    if (!anchored[(size_t)n]) return LIODOM_GRAPH_COV_UNANCHORED;
+    int32_t s = LIODOM_GRAPH_COV_OK;
+    for (int b = 0; b < 6; b++) s = liodom_dev::graph_cov_worst(s, column[6 * (size_t)slot[(size_t)n] + (size_t)b].status);
+    return s;
+  }
+};
+
+// Solves the columns of the distinct free, anchored nodes among nodes[0 .. n) in launches of the plan's size; after each launch,
+// with its columns in g->cov_ws and before the next one overwrites them, after_launch(first column, columns) enqueues what reads
+// them.  The caller has validated the query and holds the mutex.
+template <typename F>
+int graph_cov_solve(liodom_graph* g, const liodom_graph_cov_options_t& opt, const int32_t* nodes, int n, GraphCovSolve* out, F after_launch) {
+  using namespace liodom_dev;
+  const int N = (int)g->fixed.size(), E = (int)g->edges.size();
+  int rc;
+  if ((rc = graph_prepare(g))) return rc;
+  std::vector<int32_t> ei((size_t)E), ej((size_t)E);
+  for (int e = 0; e < E; e++) { ei[(size_t)e] = g->edges[(size_t)e].i; ej[(size_t)e] = g->edges[(size_t)e].j; }
+  if (!graph_anchored(ei.data(), ej.data(), E, g->active.data(), g->fixed.data(), N, &out->anchored)) {
+    g_last_error = "liodom_graph: an edge names a node that does not exist"; return LIODOM_ERR_INVALID_ARG;      // (checked when it was added)
+  }
+  graph_column_nodes(nodes, n, g->fixed.data(), out->anchored.data(), N, &out->col_node, &out->slot);
+  GraphCovPlan plan;
+  if (!graph_cov_plan((int)out->col_node.size(), g->max_nodes, opt.batch_columns, kGraphCovWorkspaceBudget, &plan)) {
+    g_last_error = "liodom_graph: the workspace of the covariance solve does not fit"; return LIODOM_ERR_INVALID_ARG;
+  }
+  out->column.assign((size_t)plan.columns, liodom_graph_cov_status_t{0, LIODOM_GRAPH_COV_OK, 0.0});
+  if ((rc = graph_grow(g, &g->cov_slot, sizeof(int32_t) * (size_t)std::max(N, 1)))) return rc;
+  if (N) HIP_TRY(hipMemcpyAsync(g->cov_slot.p, out->slot.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, g->stream));
+  if (plan.columns == 0) { HIP_TRY(hipStreamSynchronize(g->stream)); return LIODOM_OK; }
+  if ((rc = graph_grow(g, &g->cov_ws, plan.workspace_bytes)) || (rc = graph_grow(g, &g->cov_status, sizeof(GraphPcgStatus) * (size_t)plan.columns)) ||
+      (rc = graph_grow(g, &g->cov_col_node, sizeof(int32_t) * out->col_node.size())))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(g->cov_col_node.p, out->col_node.data(), sizeof(int32_t) * out->col_node.size(), hipMemcpyHostToDevice, g->stream));
+  int n_free = 0;
+  for (int k = 0; k < N; k++) n_free += g->fixed[(size_t)k] ? 0 : 1;
+  const int max_pcg = graph_cov_iterations(&opt, n_free);
+  GraphPcgStatus* d_st = static_cast<GraphPcgStatus*>(g->cov_status.p);
+  for (int l = 0; l < plan.launches; l++) {
+    int first = 0, count = 0;
+    graph_cov_launch(&plan, l, &first, &count);
+    hipLaunchKernelGGL(k_graph_pcg_columns, dim3((unsigned)count), dim3(kGraphPcgThreads), 0, g->stream, N, (long long)g->max_nodes, (long long)g->max_edges,
+                       first, max_pcg, opt.pcg_tolerance, static_cast<const int*>(g->cov_col_node.p), g->d_fixed, g->d_parent, g->d_poses, g->d_offsets,
+                       g->d_entries, g->d_ei, g->d_ej, g->d_D, g->d_Minv, g->d_Hij, g->d_bad, static_cast<double*>(g->cov_ws.p), d_st + first);
+    HIP_TRY(hipGetLastError());
+    g->cov_launches++; g->cov_columns += count;
+    if ((rc = after_launch(first, count))) return rc;
+  }
+  std::vector<GraphPcgStatus> st((size_t)plan.columns);
+  HIP_TRY(hipMemcpyAsync(st.data(), d_st, sizeof(GraphPcgStatus) * st.size(), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  for (size_t c = 0; c < st.size(); c++) {
+    out->column[c].iterations = st[c].iterations;
+    out->column[c].residual = st[c].residual;
+    out->column[c].status = st[c].flag == GRAPH_PCG_CONVERGED ? LIODOM_GRAPH_COV_OK
+                          : st[c].flag == GRAPH_PCG_MAX_ITER ? LIODOM_GRAPH_COV_NOT_CONVERGED : LIODOM_GRAPH_COV_BREAKDOWN;
+  }
+  return LIODOM_OK;
+}
+
+// blocks[k] = Sigma[rows[k], cols[k]] into g->cov_blocks (left on the device, entries of fixed nodes 0; enqueued and waited for)
+// and status[k] by the rules of include/liodom_hip.h.  A status of BREAKDOWN or UNANCHORED means the caller writes NaN.
+int graph_cov_blocks(liodom_graph* g, const liodom_graph_cov_options_t& opt, const int32_t* rows, const int32_t* cols, int n, int32_t* status) {
+  using namespace liodom_dev;
+  int rc;
+  if ((rc = graph_grow(g, &g->cov_rows, sizeof(int32_t) * (size_t)n)) || (rc = graph_grow(g, &g->cov_cols, sizeof(int32_t) * (size_t)n)) ||
+      (rc = graph_grow(g, &g->cov_blocks, sizeof(double) * 36 * (size_t)n)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(g->cov_rows.p, rows, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(g->cov_cols.p, cols, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemsetAsync(g->cov_blocks.p, 0, sizeof(double) * 36 * (size_t)n, g->stream));
+  GraphCovSolve sol;
+  rc = graph_cov_solve(g, opt, cols, n, &sol, [&](int first, int count) -> int {
+    hipLaunchKernelGGL(k_graph_cov_gather, dim3(graph_blocks(n)), dim3(kGraphThreads), 0, g->stream, n, (long long)g->max_nodes, first, count,
+                       static_cast<const int*>(g->cov_rows.p), static_cast<const int*>(g->cov_cols.p), static_cast<const int*>(g->cov_slot.p), g->d_fixed,
+                       static_cast<const double*>(g->cov_ws.p), static_cast<double*>(g->cov_blocks.p));
+    HIP_TRY(hipGetLastError());
+    return LIODOM_OK;
+  });
+  if (rc) return rc;
+  for (int k = 0; k < n; k++) {
+    const int32_t r = rows[k], c = cols[k];
+    if (g->fixed[(size_t)r] || g->fixed[(size_t)c]) status[k] = LIODOM_GRAPH_COV_OK;
+    else if (!sol.anchored[(size_t)r] || !sol.anchored[(size_t)c]) status[k] = LIODOM_GRAPH_COV_UNANCHORED;
+    else status[k] = sol.node_status(g, c);
+  }
+  return LIODOM_OK;
+}
+
+inline bool graph_cov_is_nan(int32_t status) { return status == LIODOM_GRAPH_COV_BREAKDOWN || status == LIODOM_GRAPH_COV_UNANCHORED || status == LIODOM_GRAPH_COV_NOT_PD; }
 
 }  // namespace
 
@@ -502,6 +634,146 @@ int liodom_graph_optimize(liodom_graph_t* g, const liodom_graph_options_t* opt_i
   if (rc != LIODOM_OK) { g->uploaded = false; g->linearized = false; return rc; }
   if (moved) g->poses.swap(out);
   if (report) *report = rep;
+  return LIODOM_OK;
+}
+
+void liodom_graph_cov_options_default(liodom_graph_cov_options_t* opt) {
+  if (opt) liodom_dev::graph_cov_options_default(opt);
+}
+
+int liodom_graph_cov_counters(liodom_graph_t* g, int64_t* launches, int64_t* columns) {
+  if (!g) { g_last_error = "liodom_graph_cov_counters: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  std::lock_guard<std::mutex> lk(g->mx);
+  if (launches) *launches = g->cov_launches;
+  if (columns) *columns = g->cov_columns;
+  return LIODOM_OK;
+}
+
+int liodom_graph_solve_columns(liodom_graph_t* g, const int32_t* nodes, int n, const liodom_graph_cov_options_t* opt_in, double* x,
+                               liodom_graph_cov_status_t* status) {
+  using namespace liodom_dev;
+  if (!g) { g_last_error = "liodom_graph_solve_columns: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  liodom_graph_cov_options_t opt;
+  if (int rc = graph_cov_options(opt_in, &opt, "liodom_graph_solve_columns")) return rc;
+  std::lock_guard<std::mutex> lk(g->mx);
+  const int N = (int)g->fixed.size();
+  if (const char* why = graph_query_refusal(nodes, n, N)) { g_last_error = std::string("liodom_graph_solve_columns: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  if (n > 0 && (!x || !status)) { g_last_error = "liodom_graph_solve_columns: null x or status"; return LIODOM_ERR_INVALID_ARG; }
+  if (n == 0) return LIODOM_OK;
+  HIP_TRY(hipSetDevice(g->device));
+  const size_t len = 6 * (size_t)N;
+  std::vector<double> solved;                         // [column][6 N]: every solved column, copied out launch by launch
+  GraphCovSolve sol;
+  bool sized = false;
+  int rc = graph_cov_solve(g, opt, nodes, n, &sol, [&](int first, int count) -> int {
+    if (!sized) { solved.resize(6 * sol.col_node.size() * len); sized = true; }
+    HIP_TRY(hipMemcpy2DAsync(&solved[(size_t)first * len], sizeof(double) * len, g->cov_ws.p, sizeof(double) * kGraphCovColumnDoubles * (size_t)g->max_nodes,
+                             sizeof(double) * len, (size_t)count, hipMemcpyDeviceToHost, g->stream));
+    return LIODOM_OK;
+  });
+  if (rc) return rc;
+  const double nan = std::nan("");
+  for (int k = 0; k < n; k++) {
+    const int32_t v = nodes[k];
+    for (int b = 0; b < 6; b++) {
+      double* out = x + (6 * (size_t)k + (size_t)b) * len;
+      liodom_graph_cov_status_t* st = status + 6 * (size_t)k + (size_t)b;
+      if (g->fixed[(size_t)v]) {
+        std::fill(out, out + len, 0.0);
+        *st = liodom_graph_cov_status_t{0, LIODOM_GRAPH_COV_OK, 0.0};
+      } else if (!sol.anchored[(size_t)v]) {
+        std::fill(out, out + len, nan);
+        *st = liodom_graph_cov_status_t{0, LIODOM_GRAPH_COV_UNANCHORED, nan};
+      } else {
+        const size_t c = 6 * (size_t)sol.slot[(size_t)v] + (size_t)b;
+        *st = sol.column[c];
+        if (st->status == LIODOM_GRAPH_COV_BREAKDOWN) std::fill(out, out + len, nan);
+        else std::memcpy(out, &solved[c * len], sizeof(double) * len);
+      }
+    }
+  }
+  return LIODOM_OK;
+}
+
+int liodom_graph_covariance(liodom_graph_t* g, const int32_t* rows, const int32_t* cols, int n, const liodom_graph_cov_options_t* opt_in,
+                            double* blocks, int32_t* status) {
+  using namespace liodom_dev;
+  if (!g) { g_last_error = "liodom_graph_covariance: null graph"; return LIODOM_ERR_INVALID_ARG; }
+  liodom_graph_cov_options_t opt;
+  if (int rc = graph_cov_options(opt_in, &opt, "liodom_graph_covariance")) return rc;
+  std::lock_guard<std::mutex> lk(g->mx);
+  const int N = (int)g->fixed.size();
+  const char* why = graph_query_refusal(rows, n, N);
+  if (!why) why = graph_query_refusal(cols, n, N);
+  if (why) { g_last_error = std::string("liodom_graph_covariance: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  if (n > 0 && (!blocks || !status)) { g_last_error = "liodom_graph_covariance: null blocks or status"; return LIODOM_ERR_INVALID_ARG; }
+  if (n == 0) return LIODOM_OK;
+  HIP_TRY(hipSetDevice(g->device));
+  std::vector<int32_t> st((size_t)n);
+  if (int rc = graph_cov_blocks(g, opt, rows, cols, n, st.data())) return rc;
+  std::vector<double> out(36 * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(out.data(), g->cov_blocks.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  for (int k = 0; k < n; k++) {
+    if (graph_cov_is_nan(st[(size_t)k])) std::fill(out.begin() + 36 * (size_t)k, out.begin() + 36 * ((size_t)k + 1), std::nan(""));
+  }
+  std::memcpy(blocks, out.data(), sizeof(double) * out.size());
+  std::memcpy(status, st.data(), sizeof(int32_t) * st.size());
+  return LIODOM_OK;
+}
+
+int liodom_graph_gate_edges(liodom_graph_t* g, const liodom_graph_edge_t* candidates, int n, const liodom_graph_cov_options_t* opt_in, double* d2,
+                            int32_t* status) {
+  using namespace liodom_dev;
+  if (!g || n < 0 || (n > 0 && !candidates)) { g_last_error = "liodom_graph_gate_edges: null graph or candidates, or a negative count"; return LIODOM_ERR_INVALID_ARG; }
+  liodom_graph_cov_options_t opt;
+  if (int rc = graph_cov_options(opt_in, &opt, "liodom_graph_gate_edges")) return rc;
+  std::lock_guard<std::mutex> lk(g->mx);
+  const int N = (int)g->fixed.size();
+  for (int k = 0; k < n; k++) {
+    const char* why = candidates[k].reserved != 0 ? "an edge's reserved field is not 0"
+                                                  : graph_edge_refusal(candidates[k].i, candidates[k].j, candidates[k].z, candidates[k].info, N);
+    if (why) { g_last_error = std::string("liodom_graph_gate_edges: ") + why; return LIODOM_ERR_INVALID_ARG; }
+  }
+  if (n > 0 && (!d2 || !status)) { g_last_error = "liodom_graph_gate_edges: null d2 or status"; return LIODOM_ERR_INVALID_ARG; }
+  if (n == 0) return LIODOM_OK;
+  if ((size_t)n > (size_t)0x7fffffff / 3) { g_last_error = "liodom_graph_gate_edges: too many candidates"; return LIODOM_ERR_INVALID_ARG; }
+  HIP_TRY(hipSetDevice(g->device));
+  // three blocks per candidate: Sigma[i, i], Sigma[i, j], Sigma[j, j]
+  std::vector<int32_t> rows(3 * (size_t)n), cols(3 * (size_t)n), st(3 * (size_t)n), ci((size_t)n), cj((size_t)n), flag((size_t)n);
+  std::vector<double> z(7 * (size_t)n), info(36 * (size_t)n), out((size_t)n);
+  for (int k = 0; k < n; k++) {
+    const liodom_graph_edge_t& c = candidates[k];
+    rows[3 * (size_t)k] = c.i; cols[3 * (size_t)k] = c.i;
+    rows[3 * (size_t)k + 1] = c.i; cols[3 * (size_t)k + 1] = c.j;
+    rows[3 * (size_t)k + 2] = c.j; cols[3 * (size_t)k + 2] = c.j;
+    ci[(size_t)k] = c.i; cj[(size_t)k] = c.j;
+    graph_pose_normalised(c.z, &z[7 * (size_t)k]);          // (as liodom_graph_add_edges stores it)
+    std::memcpy(&info[36 * (size_t)k], c.info, sizeof(c.info));
+  }
+  int rc;
+  if ((rc = graph_cov_blocks(g, opt, rows.data(), cols.data(), 3 * n, st.data()))) return rc;
+  // (the candidates' i and j reuse the buffers of the rows and columns: the gather that read those has been waited for)
+  if ((rc = graph_grow(g, &g->cov_z, sizeof(double) * z.size())) || (rc = graph_grow(g, &g->cov_info, sizeof(double) * info.size())) ||
+      (rc = graph_grow(g, &g->cov_d2, sizeof(double) * (size_t)n)) || (rc = graph_grow(g, &g->cov_flag, sizeof(int32_t) * (size_t)n)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(g->cov_rows.p, ci.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(g->cov_cols.p, cj.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(g->cov_z.p, z.data(), sizeof(double) * z.size(), hipMemcpyHostToDevice, g->stream));
+  HIP_TRY(hipMemcpyAsync(g->cov_info.p, info.data(), sizeof(double) * info.size(), hipMemcpyHostToDevice, g->stream));
+  hipLaunchKernelGGL(k_graph_gate, dim3(graph_blocks(n)), dim3(kGraphThreads), 0, g->stream, n, g->d_poses, static_cast<const int*>(g->cov_rows.p),
+                     static_cast<const int*>(g->cov_cols.p), static_cast<const double*>(g->cov_z.p), static_cast<const double*>(g->cov_info.p),
+                     static_cast<const double*>(g->cov_blocks.p), static_cast<double*>(g->cov_d2.p), static_cast<int*>(g->cov_flag.p));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out.data(), g->cov_d2.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipMemcpyAsync(flag.data(), g->cov_flag.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, g->stream));
+  HIP_TRY(hipStreamSynchronize(g->stream));
+  for (int k = 0; k < n; k++) {
+    int32_t s = graph_cov_worst(st[3 * (size_t)k], st[3 * (size_t)k + 2]);
+    if (s != LIODOM_GRAPH_COV_BREAKDOWN && s != LIODOM_GRAPH_COV_UNANCHORED && flag[(size_t)k]) s = LIODOM_GRAPH_COV_NOT_PD;
+    status[k] = s;
+    d2[k] = graph_cov_is_nan(s) ? std::nan("") : out[(size_t)k];
+  }
   return LIODOM_OK;
 }
 

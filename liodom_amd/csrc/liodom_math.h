@@ -1310,5 +1310,58 @@ LD_HD bool graph_damped_inverse(const double* D36, double lambda, double* inv36)
   }
   return spd_inverse6(H21, inv36);
 }
+// The chi-square gate of a candidate edge (i, j, Z, Omega) (k_graph_gate; include/liodom_hip.h "covariances of the graph"): the
+// squared Mahalanobis distance of the edge's error at the current poses under the graph's own uncertainty,
+//   S = [A B] [[Sii, Sij], [Sij^T, Sjj]] [A B]^T + Omega^-1,      d2 = e^T S^-1 e,
+// Sii, Sij, Sjj the 6 x 6 row-major blocks of H^-1 in the coordinates of delta (Sij = Sigma[i, j]; a fixed node's blocks are 0).
+// The cross term M = A Sij B^T enters as M + M^T and the two halves of S are averaged, so S is symmetric whatever rounding left
+// of the blocks' symmetry; d2 by the packed Cholesky solve.  false, *d2 = NaN: Omega or S is not positive definite.
+LD_HD bool graph_gate(const double* Xi, const double* Xj, const double* Z, const double* Om, const double* Sii, const double* Sij,
+                      const double* Sjj, double* d2) {
+  double e[6], A[36], B[36], S[36], T1[36], T2[36], T3[36];
+  *d2 = __builtin_nan("");
+  double H21[21];
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) {
+    LD_UNROLL
+    for (int j = i; j < 6; j++) H21[h_idx(i, j)] = Om[i * 6 + j];
+  }
+  if (!spd_inverse6(H21, S)) return false;                       // S = Omega^-1
+  graph_edge_error(Xi, Xj, Z, e, A, B);
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {                                  // T1 = A Sii, T2 = A Sij, T3 = B Sjj
+    LD_UNROLL
+    for (int c = 0; c < 6; c++) {
+      double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 6; k++) { s1 += A[r * 6 + k] * Sii[k * 6 + c]; s2 += A[r * 6 + k] * Sij[k * 6 + c]; s3 += B[r * 6 + k] * Sjj[k * 6 + c]; }
+      T1[r * 6 + c] = s1; T2[r * 6 + c] = s2; T3[r * 6 + c] = s3;
+    }
+  }
+  double M[36];
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {
+    LD_UNROLL
+    for (int c = 0; c < 6; c++) {
+      double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 6; k++) { s1 += T1[r * 6 + k] * A[c * 6 + k]; s2 += T2[r * 6 + k] * B[c * 6 + k]; s3 += T3[r * 6 + k] * B[c * 6 + k]; }
+      S[r * 6 + c] += s1 + s3;
+      M[r * 6 + c] = s2;
+    }
+  }
+  double L[21], y[6];
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {
+    LD_UNROLL
+    for (int c = 0; c <= r; c++) L[lt_idx(r, c)] = 0.5 * (S[r * 6 + c] + S[c * 6 + r]) + (M[r * 6 + c] + M[c * 6 + r]);
+  }
+  if (!chol_solve6_packed(L, e, y)) return false;
+  double s = 0.0;
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) s += e[r] * y[r];
+  *d2 = s;
+  return true;
+}
 
 }  // namespace liodom_dev

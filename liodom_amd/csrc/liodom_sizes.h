@@ -116,4 +116,9 @@ constexpr int kHbSlackMin = 32;
 // ---- liodom_map.h: k_map_local_rows ----
 constexpr int kMapRowsThreads = 256;
 
+// ---- kernels_graph.h: k_graph_pcg_columns ----
+// Bytes of workspace an automatic plan of the covariance calls gives one launch (graph_marginals.h): 30 node_cap doubles per
+// column, so 1092 columns of a 1024-node graph, 17 at the full 65 536 nodes — and never fewer than 6.
+constexpr size_t kGraphCovWorkspaceBudget = (size_t)256 << 20;
+
 }  // namespace liodom_dev

@@ -626,6 +626,21 @@ void PoseGraph::edgeWeights(std::vector<double>* rho, std::vector<double>* weigh
   if (weight) weight->assign(e, 0.0);
   check(liodom_graph_edge_weights(g_, rho ? rho->data() : nullptr, weight ? weight->data() : nullptr), "liodom_graph_edge_weights");
 }
+void PoseGraph::covariance(const std::vector<int32_t>& rows, const std::vector<int32_t>& cols, std::vector<double>* blocks, std::vector<int32_t>* status,
+                           const liodom_graph_cov_options_t* options) {
+  const std::vector<int32_t>& c = cols.empty() ? rows : cols;
+  if (c.size() != rows.size() || !blocks || !status) throw std::invalid_argument("PoseGraph::covariance: one column node per row node, and both outputs");
+  blocks->assign(36 * rows.size(), 0.0);
+  status->assign(rows.size(), 0);
+  check(liodom_graph_covariance(g_, rows.data(), c.data(), (int)rows.size(), options, blocks->data(), status->data()), "liodom_graph_covariance");
+}
+void PoseGraph::gateEdges(const std::vector<liodom_graph_edge_t>& candidates, std::vector<double>* d2, std::vector<int32_t>* status,
+                          const liodom_graph_cov_options_t* options) {
+  if (!d2 || !status) throw std::invalid_argument("PoseGraph::gateEdges: both outputs are needed");
+  d2->assign(candidates.size(), 0.0);
+  status->assign(candidates.size(), 0);
+  check(liodom_graph_gate_edges(g_, candidates.data(), (int)candidates.size(), options, d2->data(), status->data()), "liodom_graph_gate_edges");
+}
 
 MapPager::MapPager(Map* map, int keep_xy, int keep_z, int load_xy, int load_z)
     : map_(map), keep_xy_(keep_xy), keep_z_(keep_z), load_xy_(load_xy), load_z_(load_z) {

@@ -343,6 +343,13 @@ class PoseGraph {
   void setEdgeActive(int first, const std::vector<bool>& active);                               // edges first .. first + size - 1
   std::vector<bool> edgeActive();
   void edgeWeights(std::vector<double>* rho, std::vector<double>* weight);                      // per edge; null: not wanted
+  // covariances and the loop gate (include/liodom_hip.h "covariances of the graph"); options null: the defaults.
+  // covariance: blocks [n x 36] = Sigma[rows[k], cols[k]] of H^-1 at the current poses (cols empty: the marginals Sigma[n, n]) and
+  // their LIODOM_GRAPH_COV_* statuses.  gateEdges: d2 per candidate edge (not added) and its status.
+  void covariance(const std::vector<int32_t>& rows, const std::vector<int32_t>& cols, std::vector<double>* blocks, std::vector<int32_t>* status,
+                  const liodom_graph_cov_options_t* options = nullptr);
+  void gateEdges(const std::vector<liodom_graph_edge_t>& candidates, std::vector<double>* d2, std::vector<int32_t>* status,
+                 const liodom_graph_cov_options_t* options = nullptr);
   liodom_graph_t* handle() const { return g_; }
  private:
   liodom_graph_t* g_ = nullptr;

@@ -19,7 +19,9 @@ loop measurement is as fine as the last search level's step.  The robust solve i
 a loop edge: it has to exceed what honest drift puts on a TRUE loop edge at the dead-reckoned poses, or the true edges are
 down-weighted with the false one and the solve settles in the wrong minimum (DESIGN.md §3 "Closing loops" has a ring of 8 key
 frames on which Geman-McClure with scale 3 rejects every true loop and scale 5 does not).  And it rejects by consensus: where
-false loop edges agree with each other and outnumber the true ones, they win.
+false loop edges agree with each other and outnumber the true ones, they win.  LoopCloser(gate=16.81) asks the graph first: a
+loop candidate whose squared Mahalanobis distance from the relative pose the graph predicts — under the graph's own covariance,
+PoseGraph.gate_edges — exceeds the gate is never added.  That needs no consensus, and is only as calibrated as odometry_info.
 """
 import math
 
@@ -102,16 +104,26 @@ class LoopCloser:
                   loop_info="solve" (needs refine): the edge's information is solve_information of the registration; where that
                   is not defined (flags other than COV_VALID) LOOP_INFO stands
     max_update_points          points per Map.update call of the rebuild
+    gate          None, or a threshold on d2 (PoseGraph.gate_edges): before feed() or add_loop() adds a loop edge, its squared
+                  Mahalanobis distance d2 from the relative pose the graph predicts — under the graph's own covariance at the
+                  current poses plus the edge's — is computed on the device, and the edge is added only if the status is "ok" and
+                  d2 <= gate.  16.81 is the 0.99 quantile of chi-square with 6 degrees of freedom: a true loop is then refused one
+                  time in a hundred — IF the information matrices are honest.  d2 is only as calibrated as odometry_info is: a
+                  constant that understates the drift makes true loops look like outliers, one that overstates it lets false ones
+                  pass.  gate_options: keywords of api.make_graph_cov_options for that call.  None: nothing is computed, every
+                  candidate is added, as before the gate existed.
 
     `places` must be this LoopCloser's alone: empty when it is handed in, and filled by feed() only — a place's tag is its key
     frame's node index, and close() rewrites the poses by it (it raises ValueError, before anything is changed, if the database
     holds anything else).
 
-    feed returns dict(key_frame, node, loops): loops = [dict(place, node, fraction, pose, match)] of the edges added.
+    feed returns dict(key_frame, node, loops): loops = [dict(place, node, fraction, pose, match)] of the edges added; with a gate
+    each carries d2.  gated: [(place, node, d2, status)] of the loop edges the gate refused (status one of api.GRAPH_COV_STATUSES).
     key_poses: the key frames' poses as fed (after close(): as corrected); clouds: their edge clouds (sensor frame)."""
 
     def __init__(self, map, places, levels, graph=None, min_dist=4.0, min_yaw=float("inf"), min_gap=10, k=3, min_fraction=0.5,
-                 odometry_info=ODOMETRY_INFO, loop_info=LOOP_INFO, max_update_points=65536, max_nodes=4096, max_edges=16384, refine=None):
+                 odometry_info=ODOMETRY_INFO, loop_info=LOOP_INFO, max_update_points=65536, max_nodes=4096, max_edges=16384, refine=None,
+                 gate=None, gate_options=None):
         if min_gap < 1 or k < 1:
             raise ValueError("LoopCloser: needs min_gap >= 1 and k >= 1")
         self.info_from_solve = isinstance(loop_info, str)
@@ -133,6 +145,9 @@ class LoopCloser:
         self.loops = []                  # (place node, node) of every active loop edge, in the graph's edge order
         self.rejected = []               # (place node, node, weight) of the loop edges close() has switched off
         self.last_pose = None            # the last pose fed, key frame or not
+        self.gate = None if gate is None else float(gate)
+        self.gate_options = dict(gate_options or {})
+        self.gated = []                  # (place node, node, d2, status) of the loop edges the gate refused
 
     def feed(self, pose, edges):
         pose = _pose(pose)
@@ -162,17 +177,17 @@ class LoopCloser:
                 if not fraction >= self.min_fraction:
                     continue
                 if self.refine is None:
-                    self.graph.add_edges(api.graph_edges([place], [node], [between(m["place_pose"], found)], self.loop_info, kind=1))
-                    self.loops.append((place, node))
-                    loops.append(dict(place=place, node=node, fraction=fraction, pose=np.array(found, np.float64), match=m))
+                    added, extra = self._add_gated(place, node, between(m["place_pose"], found), self.loop_info)
+                    if added:
+                        loops.append(dict(place=place, node=node, fraction=fraction, pose=np.array(found, np.float64), match=m, **extra))
                     continue
                 Z, info, record = self.refine_loop(edges, m["place_pose"], found)
                 if Z is None:
                     continue
-                self.graph.add_edges(api.graph_edges([place], [node], [Z], info, kind=1))
-                self.loops.append((place, node))
-                loops.append(dict(place=place, node=node, fraction=fraction, pose=record["pose"].copy(), match=m,
-                                  searched_pose=np.array(found, np.float64), registration=record))
+                added, extra = self._add_gated(place, node, Z, info)
+                if added:
+                    loops.append(dict(place=place, node=node, fraction=fraction, pose=record["pose"].copy(), match=m,
+                                      searched_pose=np.array(found, np.float64), registration=record, **extra))
         return dict(key_frame=True, node=node, loops=loops)
 
     def refine_loop(self, edges, place_pose, found):
@@ -193,15 +208,30 @@ class LoopCloser:
             info = solve_information(place_pose, record["pose"], Z, record["information"], record["sigma2"])
         return Z, info, record
 
+    def _add_gated(self, place, node, Z, info):
+        """Adds the loop edge (place, node, Z, info) unless the gate refuses it -> (added, dict(d2=...) with a gate, else {})."""
+        edge = api.graph_edges([place], [node], [Z], info, kind=1)
+        extra = {}
+        if self.gate is not None:
+            d2, status = self.graph.gate_edges(edge, **self.gate_options)
+            if int(status[0]) != api.GRAPH_COV_OK or not float(d2[0]) <= self.gate:
+                self.gated.append((place, node, float(d2[0]), api.GRAPH_COV_STATUSES[int(status[0])]))
+                return False, extra
+            extra = dict(d2=float(d2[0]))
+        self.graph.add_edges(edge)
+        self.loops.append((place, node))
+        return True, extra
+
     def add_loop(self, place, node, Z, info=None):
         """A loop edge from another source — a surveyed tie, a user's hint, a test —: "X_place^-1 o X_node was measured as Z", the
-        edge feed() would add (kind 1, info None: loop_info).  place and node are key frames' node indices, place < node."""
+        edge feed() would add (kind 1, info None: loop_info).  place and node are key frames' node indices, place < node.
+        -> whether the edge was added: always True without a gate; with one, False where the gate refused it (it is then the
+        last entry of self.gated)."""
         place, node = int(place), int(node)
         if not (0 <= place < node < len(self.key_poses)):
             raise ValueError("LoopCloser.add_loop: place and node must be key frames with place < node")
         info = self.loop_info if info is None else np.array(info, np.float64).reshape(6, 6)
-        self.graph.add_edges(api.graph_edges([place], [node], [_pose(Z)], info, kind=1))
-        self.loops.append((place, node))
+        return self._add_gated(place, node, _pose(Z), info)[0]
 
     def _loop_edges(self):
         """Edge indices of the active loop edges: one per entry of self.loops, in its order."""
