@@ -16,7 +16,7 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "liodom_map.h", "liodom_map_host.h", "map_state_format.h", "kernels_reloc.h", "reloc_candidates.h",
                                                   "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h", "kernels_register.h", "map_register.h",
                                                   "kernels_places.h", "liodom_places_host.h", "place_state_format.h",
-                                                  "kernels_graph.h", "liodom_graph_host.h", "graph_csr.h", "graph_marginals.h",
+                                                  "kernels_graph.h", "liodom_graph_host.h", "graph_csr.h", "graph_marginals.h", "graph_lm.h",
                                                   "liodom_sizes.h", "handle_plan.h", "step_plan.h", "edge_pipe.h", "map_attach.h", "liodom_step_host.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 

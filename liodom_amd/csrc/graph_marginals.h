@@ -1,5 +1,5 @@
 // graph_marginals.h — the plain-C++ half of the graph's covariance calls (liodom_graph_solve_columns / _covariance / _gate_edges;
-// kernels at the end of kernels_graph.h, host entry points in liodom_graph_host.h; DESIGN.md §3 "Covariances of the graph and the
+// kernels in kernels_graph.h, host entry points in liodom_graph_host.h; DESIGN.md §3 "Covariances of the graph and the
 // loop gate"): the options' defaults and validation, the validation of a query, which nodes have a finite covariance at all, the
 // distinct nodes whose columns of H^-1 are solved, and how those columns are cut into launches that fit a workspace —
 // overflow-checked.  No HIP include: tests/graph_marginals_main.cc compiles it for the host alone, plain and under sanitizers
@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/liodom_hip.h"
+#include "graph_lm.h"
 #include "liodom_sizes.h"
 
 namespace liodom_dev {
@@ -39,11 +40,7 @@ inline const char* graph_cov_options_refusal(const liodom_graph_cov_options_t* o
   if (!(o->pcg_tolerance >= 0.0)) return "pcg_tolerance is negative or not a number";
   return nullptr;
 }
-inline int graph_cov_iterations(const liodom_graph_cov_options_t* o, int n_free) {
-  if (o->max_pcg_iterations > 0) return o->max_pcg_iterations;
-  const long long six = 6ll * n_free;
-  return (int)(six < 65536 ? six : 65536);
-}
+inline int graph_cov_iterations(const liodom_graph_cov_options_t* o, int n_free) { return graph_pcg_cap(o->max_pcg_iterations, n_free); }
 
 // A query names nodes: n >= 0, a list where n > 0, every index a node of the graph.
 inline const char* graph_query_refusal(const int32_t* nodes, int n, int n_nodes) {

@@ -1,76 +1,128 @@
 // Closing loops (liodom_graph_*; no counterpart in the reference): a pose graph over key frames, linearised and solved on the
 // device.  Included by liodom_hip.hip.  The arithmetic of one edge is liodom_math.h "Pose graph"; tests/graph_model.py restates
-// everything here in NumPy.
+// everything here in NumPy (graph_robust_model.py the losses, graph_cov_model.py the covariances).  By subject:
 //
-//   k_graph_linearize   one thread per edge: e, chi2, A^T Omega e, B^T Omega e, A^T Omega A, A^T Omega B, B^T Omega B.  Outputs are
+//   edges     graph_load_edge     Xi, Xj, Z, Omega of one edge, for every kernel with a thread per edge
+//             k_graph_linearize<ROBUST>   e, chi2, A^T Omega e, B^T Omega e, A^T Omega A, A^T Omega B, B^T Omega B.  Outputs are
 //                       component-major (entry k of edge e at [k * edge_cap + e]): consecutive lanes store consecutive addresses.
-//   k_graph_gather      one thread per node over the CSR of its (edge, side) pairs, in CSR order: gradient, diagonal block, inverse of
-//                       the damped block.  No atomics: a sum depends on the graph alone.
-//   k_graph_pcg         the whole preconditioned conjugate-gradient loop for (H + lambda diag H) x = -g in ONE workgroup of 1024
-//                       threads: no workgroup waits for another, the host is not asked anything inside the loop.  The
-//                       preconditioner is block-Jacobi in the coordinates of the odometry chain ("the preconditioner" below).
-//   k_graph_multiply    y = (H + lambda diag H) x by node rows, the row code of k_graph_pcg as a launch of its own
-//   k_graph_retract / k_graph_cost / k_graph_sum   the candidate poses, their chi2 per edge, and a sum in a fixed order
-//   k_graph_linearize_robust / k_graph_cost_robust   the same two with a robust loss per edge and edges that are switched off (at
-//                       the end of this file); launched only where a graph asks for either
-//   k_graph_pcg_columns / k_graph_cov_gather / k_graph_gate   columns of H^-1, one workgroup of k_graph_pcg's kind per column; the
-//                       6 x 6 blocks of H^-1 picked out of them; and the chi-square gate of a candidate edge (after the robust
-//                       instances, at the very end); launched only by the covariance calls
+//             k_graph_cost<ROBUST>        chi2 per edge at the candidate poses
+//                       ROBUST = true where a graph has a loss on some edge's kind or an edge switched off: rho and w per edge as
+//                       well.  ROBUST = false reads no code and no scale and writes no rho and no w.
+//             k_graph_gate        the chi-square gate of a candidate edge (launched only by the covariance calls)
+//   nodes     k_graph_gather      one thread per node over the CSR of its (edge, side) pairs, in CSR order: gradient, diagonal block,
+//                       inverse of the damped block.  No atomics: a sum depends on the graph alone.
+//             k_graph_multiply    y = (H + lambda diag H) x by node rows (graph_row_multiply: the row code of the PCG loop)
+//             k_graph_retract / k_graph_sum   the candidate poses, and a sum in a fixed order
+//   solving   graph_pcg_run       the whole preconditioned conjugate-gradient loop in ONE workgroup of 1024 threads: no workgroup
+//                       waits for another, the host is not asked anything inside the loop.  The preconditioner is block-Jacobi in
+//                       the coordinates of the odometry chain ("the preconditioner" below).  Its two callers:
+//             k_graph_pcg         (H + lambda diag H) x = -g, the Levenberg-Marquardt step, with the exit on max |g|
+//             k_graph_pcg_columns columns of H^-1, one workgroup per column (the covariance calls), and
+//             k_graph_cov_gather  the 6 x 6 blocks of H^-1 picked out of them
 //
 // Fixed nodes: delta = 0; their rows and columns drop out (gradient 0, inverse block 0, skipped as a neighbour).  A free node
 // without edges: its block counts as the identity, its gradient is 0, it stays where it is.
 #pragma once
 
+#include "graph_lm.h"
 #include "liodom_math.h"
 #include "wave_ops.h"
 
 namespace liodom_dev {
 
 constexpr int kGraphThreads = 256;          // the edge- and node-parallel kernels
-constexpr int kGraphPcgThreads = 1024;      // the one workgroup of k_graph_pcg and k_graph_sum
+constexpr int kGraphPcgThreads = 1024;      // the one workgroup of graph_pcg_run and k_graph_sum
 constexpr int kGraphPcgWaves = kGraphPcgThreads / 64;
 
-enum { GRAPH_PCG_CONVERGED = 0, GRAPH_PCG_MAX_ITER = 1, GRAPH_PCG_BREAKDOWN = 2, GRAPH_PCG_GRADIENT = 3 };
 struct GraphPcgStatus {
-  int iterations, flag;
-  double gmax;              // max |g| over the free nodes
-  double residual;          // |r| / |g| when the loop ended
+  int iterations, flag;     // GRAPH_PCG_* (graph_lm.h)
+  double gmax;              // max |g| over the free nodes (k_graph_pcg_columns: 0)
+  double residual;          // |r| / |b| when the loop ended
 };
 
+// ---- edges ---------------------------------------------------------------------------------------------------------------------
+// Edge e = (ei[e], ej[e], z, info): the poses of its two nodes, its measurement and its information matrix
+__device__ __forceinline__ void graph_load_edge(long long e, const double* __restrict__ poses, const int* __restrict__ ei,
+                                                const int* __restrict__ ej, const double* __restrict__ z, const double* __restrict__ info,
+                                                double* Xi, double* Xj, double* Z, double* Om) {
+  const double* pi = poses + 7ll * ei[e];
+  const double* pj = poses + 7ll * ej[e];
+#pragma unroll
+  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * e + k]; }
+#pragma unroll
+  for (int k = 0; k < 36; k++) Om[k] = info[36ll * e + k];
+}
+
+// ROBUST: code[e] is the edge's loss (kGraphLoss*) or kGraphLossInactive, scale[e] its c; the host derives both from the graph's
+// table and flags.  Per edge: the raw s = e^T Omega e in chi2, rho(s) and w = rho'(s); w multiplies the finished entries of the
+// five blocks at the store (graph_edge_blocks_t), so code 0 — or w = 1 — gives the quadratic instance's bytes.  An inactive
+// edge: s, rho = w = 0, and nothing else — no node's list names it, its blocks are never read.
+template <bool ROBUST>
 __global__ __launch_bounds__(kGraphThreads) void k_graph_linearize(int n_edges, long long edge_cap, const double* __restrict__ poses,
                                                                    const int* __restrict__ ei, const int* __restrict__ ej,
                                                                    const double* __restrict__ z, const double* __restrict__ info,
-                                                                   double* __restrict__ chi2, double* __restrict__ gi, double* __restrict__ gj,
-                                                                   double* __restrict__ Hii, double* __restrict__ Hij, double* __restrict__ Hjj) {
+                                                                   const int* __restrict__ code, const double* __restrict__ scale,
+                                                                   double* __restrict__ chi2, double* __restrict__ rho,
+                                                                   double* __restrict__ w, double* __restrict__ gi,
+                                                                   double* __restrict__ gj, double* __restrict__ Hii,
+                                                                   double* __restrict__ Hij, double* __restrict__ Hjj) {
   const int e = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
   if (e >= n_edges) return;
   double Xi[7], Xj[7], Z[7], Om[36], err[6], A[36], B[36];
-  const double* pi = poses + 7ll * ei[e];
-  const double* pj = poses + 7ll * ej[e];
-#pragma unroll
-  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * e + k]; }
-#pragma unroll
-  for (int k = 0; k < 36; k++) Om[k] = info[36ll * e + k];
+  graph_load_edge(e, poses, ei, ej, z, info, Xi, Xj, Z, Om);
+  const int ce = ROBUST ? code[e] : kGraphLossNone;
+  if (ROBUST && ce == kGraphLossInactive) {
+    graph_edge_error(Xi, Xj, Z, err, nullptr, nullptr);
+    chi2[e] = graph_edge_chi2(err, Om);
+    rho[e] = 0.0; w[e] = 0.0;
+    return;
+  }
   graph_edge_error(Xi, Xj, Z, err, A, B);
-  graph_edge_blocks(err, A, B, Om, edge_cap, chi2 + e, gi + e, gj + e, Hii + e, Hij + e, Hjj + e);
+  graph_edge_blocks_t<ROBUST>(err, A, B, Om, edge_cap, ce, ROBUST ? scale[e] : 0.0, chi2 + e, ROBUST ? rho + e : nullptr,
+                              ROBUST ? w + e : nullptr, gi + e, gj + e, Hii + e, Hij + e, Hjj + e);
 }
 
+template <bool ROBUST>
 __global__ __launch_bounds__(kGraphThreads) void k_graph_cost(int n_edges, const double* __restrict__ poses, const int* __restrict__ ei,
                                                               const int* __restrict__ ej, const double* __restrict__ z,
-                                                              const double* __restrict__ info, double* __restrict__ chi2) {
+                                                              const double* __restrict__ info, const int* __restrict__ code,
+                                                              const double* __restrict__ scale, double* __restrict__ chi2,
+                                                              double* __restrict__ rho, double* __restrict__ w) {
   const int e = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
   if (e >= n_edges) return;
   double Xi[7], Xj[7], Z[7], Om[36], err[6];
-  const double* pi = poses + 7ll * ei[e];
-  const double* pj = poses + 7ll * ej[e];
-#pragma unroll
-  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * e + k]; }
-#pragma unroll
-  for (int k = 0; k < 36; k++) Om[k] = info[36ll * e + k];
+  graph_load_edge(e, poses, ei, ej, z, info, Xi, Xj, Z, Om);
   graph_edge_error(Xi, Xj, Z, err, nullptr, nullptr);
-  chi2[e] = graph_edge_chi2(err, Om);
+  const double s = graph_edge_chi2(err, Om);
+  chi2[e] = s;
+  if (ROBUST) {
+    const int ce = code[e];
+    double r = 0.0, wt = 0.0;
+    if (ce != kGraphLossInactive) graph_loss(ce, scale[e], s, &r, &wt);
+    rho[e] = r; w[e] = wt;
+  }
 }
 
+// One thread per candidate edge c = (ci[c], cj[c], z, info): graph_gate (liodom_math.h) at the current poses with the blocks
+// Sigma[i, i], Sigma[i, j], Sigma[j, j] at blocks[3 c], [3 c + 1], [3 c + 2].  flag[c] = 1 where Omega or S is not positive
+// definite (d2[c] is then NaN), else 0.
+__global__ __launch_bounds__(kGraphThreads) void k_graph_gate(int n, const double* __restrict__ poses, const int* __restrict__ ci,
+                                                              const int* __restrict__ cj, const double* __restrict__ z,
+                                                              const double* __restrict__ info, const double* __restrict__ blocks,
+                                                              double* __restrict__ d2, int* __restrict__ flag) {
+  const int c = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
+  if (c >= n) return;
+  double Xi[7], Xj[7], Z[7], Om[36], Sii[36], Sij[36], Sjj[36];
+  graph_load_edge(c, poses, ci, cj, z, info, Xi, Xj, Z, Om);
+#pragma unroll
+  for (int k = 0; k < 36; k++) { Sii[k] = blocks[108ll * c + k]; Sij[k] = blocks[108ll * c + 36 + k]; Sjj[k] = blocks[108ll * c + 72 + k]; }
+  double d;
+  const bool ok = graph_gate(Xi, Xj, Z, Om, Sii, Sij, Sjj, &d);
+  d2[c] = d;
+  flag[c] = ok ? 0 : 1;
+}
+
+// ---- nodes ---------------------------------------------------------------------------------------------------------------------
 // g [n * 6 + k]; D and Minv component-major ([k * node_cap + n]).  Minv is the inverse of the node's damped preconditioner block:
 // for a node on the chain (parent[n] >= 0: the edge (n - 1, n) it hangs on; graph_precondition below) the B^T Omega B of that
 // edge, otherwise its diagonal block D.  *bad = 1 where a free node's damped block is not positive definite (every writer
@@ -189,6 +241,26 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_multiply(int n_nodes, l
   for (int r = 0; r < 6; r++) y[6ll * n + r] = yr[r];
 }
 
+// cand = poses (+) delta for the free nodes, poses for the fixed ones
+__global__ __launch_bounds__(kGraphThreads) void k_graph_retract(int n_nodes, const double* __restrict__ poses, const int* __restrict__ fixed,
+                                                                 const double* __restrict__ delta, double* __restrict__ cand) {
+  const int n = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
+  if (n >= n_nodes) return;
+  double X[7], d[6], out[7];
+#pragma unroll
+  for (int k = 0; k < 7; k++) X[k] = poses[7ll * n + k];
+#pragma unroll
+  for (int k = 0; k < 6; k++) d[k] = delta[6ll * n + k];
+  if (fixed[n] != 0) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) out[k] = X[k];
+  } else {
+    graph_retract(X, d, out);
+  }
+#pragma unroll
+  for (int k = 0; k < 7; k++) cand[7ll * n + k] = out[k];
+}
+
 // Sum over the wave in a fixed order (DPP within a row of 16 lanes, v_permlane16_swap and v_permlane32_swap across); every lane
 // active, every lane gets the result.
 __device__ __forceinline__ double graph_wave_sum(double x) {
@@ -215,6 +287,15 @@ __device__ __forceinline__ void graph_block_sum(double (&v)[K], double* lds) {
     for (int w = 0; w < kGraphPcgWaves; w++) s += lds[w * K + k];
     v[k] = s;
   }
+}
+
+// *out = in[0] + ... + in[n - 1], one workgroup: thread t adds entries t, t + 1024, ... in ascending order, then graph_block_sum
+__global__ __launch_bounds__(kGraphPcgThreads) void k_graph_sum(int n, const double* __restrict__ in, double* __restrict__ out) {
+  __shared__ double sh[kGraphPcgWaves];
+  double s[1] = {0.0};
+  for (int i = (int)threadIdx.x; i < n; i += kGraphPcgThreads) s[0] += in[i];
+  graph_block_sum<1>(s, sh);
+  if (threadIdx.x == 0) *out = s[0];
 }
 
 // ---- the preconditioner -------------------------------------------------------------------------------------------------------
@@ -283,11 +364,17 @@ __device__ __forceinline__ void graph_block_segscan(double (&v)[9], bool f, doub
   for (int k = 0; k < 9; k++) v[k] = ll == 0 ? cv[k] : (ef ? ev[k] : cv[k] + ev[k]);
 }
 
+// The LDS of one PCG workgroup: the sums of graph_block_sum<1> and <2> and of the two scans of the preconditioner
+struct GraphPcgLds {
+  double a[kGraphPcgWaves], b[kGraphPcgWaves * 2], v1[kGraphPcgWaves * 9], v2[kGraphPcgWaves * 9];
+  int f1[kGraphPcgWaves], f2[kGraphPcgWaves];
+};
+
 // z = M^-1 r (above).  Every thread of the workgroup calls it; it begins and ends with a barrier, so r may have been written by
 // any thread before and z may be read by any thread after.  z doubles as the store of Binv S^T r between the two scans.
 __device__ __forceinline__ void graph_precondition(int n_nodes, long long node_cap, const int* __restrict__ parent,
                                                    const double* __restrict__ poses, const double* __restrict__ Minv, const double* r,
-                                                   double* z, double* lds_v1, int* lds_f1, double* lds_v2, int* lds_f2) {
+                                                   double* z, GraphPcgLds* lds) {
   __syncthreads();
   const int c = (n_nodes + kGraphPcgThreads - 1) / kGraphPcgThreads;
   const int lo = min(n_nodes, (int)threadIdx.x * c), hi = min(n_nodes, lo + c);
@@ -329,7 +416,7 @@ __device__ __forceinline__ void graph_precondition(int n_nodes, long long node_c
         for (int k = 0; k < 6; k++) z[6ll * n + k] = y[k];
       }
     }
-    if (pass == 0) graph_block_segscan<true>(q, f, lds_v1, lds_f1);
+    if (pass == 0) graph_block_segscan<true>(q, f, lds->v1, lds->f1);
   }
   // S: prefix sums.  A root begins its segment.
   for (int pass = 0; pass < 2; pass++) {
@@ -358,17 +445,88 @@ __device__ __forceinline__ void graph_precondition(int n_nodes, long long node_c
         for (int k = 0; k < 3; k++) { z[6ll * n + k] = q[k]; z[6ll * n + 3 + k] = q[3 + k] + 2.0 * x3[k] - 2.0 * q[6 + k]; }
       }
     }
-    if (pass == 0) graph_block_segscan<false>(q, f, lds_v2, lds_f2);
+    if (pass == 0) graph_block_segscan<false>(q, f, lds->v2, lds->f2);
   }
   __syncthreads();
 }
 
-// Preconditioned conjugate gradients for (H + lambda diag H) x = -g, one workgroup.  Thread t owns nodes t, t + 1024, ...: it
+// ---- solving --------------------------------------------------------------------------------------------------------------------
+// Preconditioned conjugate gradients for (H + lambda diag H) x = b, one workgroup; every thread calls it with x = 0, r = b and
+// z = M^-1 r in place (the caller's graph_precondition has ended with its barrier).  Thread t owns nodes t, t + 1024, ...: it
 // alone reads and writes their entries of x, r and Ap; p — read across nodes by the row product — and r and z around the
 // preconditioner need barriers.  Per iteration: p visible; p^T A p; the preconditioner's four; (r^T r, r^T z).  The vectors live
-// in global memory ([n * 6 + k]).  Ends with |r| <= tolerance |g| (converged), after max_iterations, or at p^T A p <= 0 or a
-// block that is not positive definite (breakdown; x is then what the iterations before had).  max |g| <= gradient_tolerance:
-// nothing is solved.
+// in global memory ([n * 6 + k]).  Ends with |r| <= tolerance |b| (converged), after max_iterations, or at p^T A p <= 0 or a
+// block that is not positive definite (breakdown; x is then what the iterations before had).  gradient_exit: nothing is solved.
+// Returns the status with gmax = 0.
+__device__ __forceinline__ GraphPcgStatus graph_pcg_run(int n_nodes, long long node_cap, long long edge_cap, double lambda, int max_iterations,
+                                                        double tolerance, bool gradient_exit, const int* __restrict__ fixed,
+                                                        const int* __restrict__ parent, const double* __restrict__ poses,
+                                                        const int* __restrict__ offsets, const int* __restrict__ entries,
+                                                        const int* __restrict__ ei, const int* __restrict__ ej, const double* __restrict__ D,
+                                                        const double* __restrict__ Minv, const double* __restrict__ Hij,
+                                                        const int* __restrict__ bad, double* x, double* r, double* p, double* zv, double* Ap,
+                                                        GraphPcgLds* lds) {
+  const int tid = (int)threadIdx.x;
+  double s2[2] = {0.0, 0.0};
+  for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const double rk = r[6ll * n + k], zk = zv[6ll * n + k];
+      p[6ll * n + k] = zk;
+      s2[0] += rk * rk; s2[1] += rk * zk;
+    }
+  }
+  graph_block_sum<2>(s2, lds->b);
+  const double g2 = s2[0];
+  double rz = s2[1], rr = s2[0];
+  int iterations = 0, flag = GRAPH_PCG_MAX_ITER;
+  if (gradient_exit) flag = GRAPH_PCG_GRADIENT;
+  else if (*bad != 0 || !(g2 > 0.0) || !ld_isfinite(g2) || !(rz > 0.0)) flag = GRAPH_PCG_BREAKDOWN;
+  else {
+    for (int it = 0; it < max_iterations; it++) {
+      __syncthreads();                               // p of every node is written
+      double s1[1] = {0.0};
+      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+        double y[6];
+        graph_row_multiply(n, node_cap, edge_cap, lambda, fixed, offsets, entries, ei, ej, D, Hij, p, y);
+#pragma unroll
+        for (int k = 0; k < 6; k++) { Ap[6ll * n + k] = y[k]; s1[0] += p[6ll * n + k] * y[k]; }
+      }
+      graph_block_sum<1>(s1, lds->a);
+      const double pAp = s1[0];
+      if (!(pAp > 0.0) || !ld_isfinite(pAp)) { flag = GRAPH_PCG_BREAKDOWN; break; }
+      const double alpha = rz / pAp;
+      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+          x[6ll * n + k] += alpha * p[6ll * n + k];
+          r[6ll * n + k] -= alpha * Ap[6ll * n + k];
+        }
+      }
+      graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, lds);
+      s2[0] = 0.0; s2[1] = 0.0;
+      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) { const double rk = r[6ll * n + k]; s2[0] += rk * rk; s2[1] += rk * zv[6ll * n + k]; }
+      }
+      graph_block_sum<2>(s2, lds->b);
+      rr = s2[0];
+      iterations = it + 1;
+      if (rr <= tolerance * tolerance * g2) { flag = GRAPH_PCG_CONVERGED; break; }
+      if (!ld_isfinite(rr) || !(s2[1] > 0.0)) { flag = GRAPH_PCG_BREAKDOWN; break; }
+      const double beta = s2[1] / rz;
+      rz = s2[1];
+      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) p[6ll * n + k] = zv[6ll * n + k] + beta * p[6ll * n + k];
+      }
+    }
+  }
+  return GraphPcgStatus{iterations, flag, 0.0, g2 > 0.0 ? sqrt(rr / g2) : 0.0};
+}
+
+// The Levenberg-Marquardt step: b = -g.  max |g| <= gradient_tolerance: nothing is solved (GRAPH_PCG_GRADIENT); status->gmax is
+// max |g| either way, a NaN where g holds one.
 __global__ __launch_bounds__(kGraphPcgThreads) void k_graph_pcg(int n_nodes, long long node_cap, long long edge_cap, double lambda,
                                                                 int max_iterations, double tolerance, double gradient_tolerance,
                                                                 const int* __restrict__ fixed, const int* __restrict__ parent,
@@ -379,9 +537,8 @@ __global__ __launch_bounds__(kGraphPcgThreads) void k_graph_pcg(int n_nodes, lon
                                                                 const double* __restrict__ Hij, const int* __restrict__ bad,
                                                                 double* x, double* r, double* p, double* zv, double* Ap,
                                                                 GraphPcgStatus* __restrict__ status) {
-  __shared__ double sh_a[kGraphPcgWaves], sh_b[kGraphPcgWaves * 2], sh_m[kGraphPcgWaves];
-  __shared__ double sh_v1[kGraphPcgWaves * 9], sh_v2[kGraphPcgWaves * 9];
-  __shared__ int sh_f1[kGraphPcgWaves], sh_f2[kGraphPcgWaves];
+  __shared__ GraphPcgLds lds;
+  __shared__ double sh_m[kGraphPcgWaves];
   const int tid = (int)threadIdx.x;
   double gmax = 0.0;
   bool g_nan = false;
@@ -406,17 +563,7 @@ __global__ __launch_bounds__(kGraphPcgThreads) void k_graph_pcg(int n_nodes, lon
     }
     if (lane == 0) sh_m[wave] = m;
   }
-  graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, sh_v1, sh_f1, sh_v2, sh_f2);      // (its barriers also publish sh_m)
-  double s2[2] = {0.0, 0.0};
-  for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-      const double rk = r[6ll * n + k], zk = zv[6ll * n + k];
-      p[6ll * n + k] = zk;
-      s2[0] += rk * rk; s2[1] += rk * zk;
-    }
-  }
-  graph_block_sum<2>(s2, sh_b);
+  graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, &lds);      // (its barriers also publish sh_m)
   gmax = 0.0;
   {
     bool nan = false;
@@ -424,154 +571,18 @@ __global__ __launch_bounds__(kGraphPcgThreads) void k_graph_pcg(int n_nodes, lon
     for (int w = 0; w < kGraphPcgWaves; w++) { const double o = sh_m[w]; nan = nan || o != o; gmax = fmax(gmax, o); }
     if (nan) gmax = __builtin_nan("");
   }
-  const double g2 = s2[0];
-  double rz = s2[1], rr = s2[0];
-  int iterations = 0, flag = GRAPH_PCG_MAX_ITER;
-  if (gmax <= gradient_tolerance) flag = GRAPH_PCG_GRADIENT;
-  else if (*bad != 0 || !(g2 > 0.0) || !ld_isfinite(g2) || !(rz > 0.0)) flag = GRAPH_PCG_BREAKDOWN;
-  else {
-    for (int it = 0; it < max_iterations; it++) {
-      __syncthreads();                               // p of every node is written
-      double s1[1] = {0.0};
-      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-        double y[6];
-        graph_row_multiply(n, node_cap, edge_cap, lambda, fixed, offsets, entries, ei, ej, D, Hij, p, y);
-#pragma unroll
-        for (int k = 0; k < 6; k++) { Ap[6ll * n + k] = y[k]; s1[0] += p[6ll * n + k] * y[k]; }
-      }
-      graph_block_sum<1>(s1, sh_a);
-      const double pAp = s1[0];
-      if (!(pAp > 0.0) || !ld_isfinite(pAp)) { flag = GRAPH_PCG_BREAKDOWN; break; }
-      const double alpha = rz / pAp;
-      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-          x[6ll * n + k] += alpha * p[6ll * n + k];
-          r[6ll * n + k] -= alpha * Ap[6ll * n + k];
-        }
-      }
-      graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, sh_v1, sh_f1, sh_v2, sh_f2);
-      s2[0] = 0.0; s2[1] = 0.0;
-      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) { const double rk = r[6ll * n + k]; s2[0] += rk * rk; s2[1] += rk * zv[6ll * n + k]; }
-      }
-      graph_block_sum<2>(s2, sh_b);
-      rr = s2[0];
-      iterations = it + 1;
-      if (rr <= tolerance * tolerance * g2) { flag = GRAPH_PCG_CONVERGED; break; }
-      if (!ld_isfinite(rr) || !(s2[1] > 0.0)) { flag = GRAPH_PCG_BREAKDOWN; break; }
-      const double beta = s2[1] / rz;
-      rz = s2[1];
-      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) p[6ll * n + k] = zv[6ll * n + k] + beta * p[6ll * n + k];
-      }
-    }
-  }
-  if (tid == 0) {
-    status->iterations = iterations; status->flag = flag; status->gmax = gmax;
-    status->residual = g2 > 0.0 ? sqrt(rr / g2) : 0.0;
-  }
+  GraphPcgStatus st = graph_pcg_run(n_nodes, node_cap, edge_cap, lambda, max_iterations, tolerance, gmax <= gradient_tolerance, fixed, parent, poses,
+                                    offsets, entries, ei, ej, D, Minv, Hij, bad, x, r, p, zv, Ap, &lds);
+  st.gmax = gmax;
+  if (tid == 0) *status = st;
 }
 
-// cand = poses (+) delta for the free nodes, poses for the fixed ones
-__global__ __launch_bounds__(kGraphThreads) void k_graph_retract(int n_nodes, const double* __restrict__ poses, const int* __restrict__ fixed,
-                                                                 const double* __restrict__ delta, double* __restrict__ cand) {
-  const int n = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
-  if (n >= n_nodes) return;
-  double X[7], d[6], out[7];
-#pragma unroll
-  for (int k = 0; k < 7; k++) X[k] = poses[7ll * n + k];
-#pragma unroll
-  for (int k = 0; k < 6; k++) d[k] = delta[6ll * n + k];
-  if (fixed[n] != 0) {
-#pragma unroll
-    for (int k = 0; k < 7; k++) out[k] = X[k];
-  } else {
-    graph_retract(X, d, out);
-  }
-#pragma unroll
-  for (int k = 0; k < 7; k++) cand[7ll * n + k] = out[k];
-}
-
-// *out = in[0] + ... + in[n - 1], one workgroup: thread t adds entries t, t + 1024, ... in ascending order, then graph_block_sum
-__global__ __launch_bounds__(kGraphPcgThreads) void k_graph_sum(int n, const double* __restrict__ in, double* __restrict__ out) {
-  __shared__ double sh[kGraphPcgWaves];
-  double s[1] = {0.0};
-  for (int i = (int)threadIdx.x; i < n; i += kGraphPcgThreads) s[0] += in[i];
-  graph_block_sum<1>(s, sh);
-  if (threadIdx.x == 0) *out = s[0];
-}
-
-
-// The robust instances (a loss on some edge's kind, or an edge switched off; the host launches k_graph_linearize and k_graph_cost
-// otherwise: they are what they were before a loss existed, and these two stand after every other kernel so that nothing before
-// them moves in the code object).  code[e] is the edge's loss (kGraphLoss*) or kGraphLossInactive, scale[e] its
-// c; the host derives both from the graph's table and flags.  Per edge: the raw s = e^T Omega e in chi2, rho(s) and w = rho'(s);
-// w multiplies the finished entries of the five blocks at the store (graph_edge_blocks_t), so code 0 — or w = 1 — gives the
-// quadratic kernel's bytes.  An inactive edge: s, rho = w = 0, and nothing else — no node's list names it, its blocks are never read.
-__global__ __launch_bounds__(kGraphThreads) void k_graph_linearize_robust(int n_edges, long long edge_cap, const double* __restrict__ poses,
-                                                                          const int* __restrict__ ei, const int* __restrict__ ej,
-                                                                          const double* __restrict__ z, const double* __restrict__ info,
-                                                                          const int* __restrict__ code, const double* __restrict__ scale,
-                                                                          double* __restrict__ chi2, double* __restrict__ rho,
-                                                                          double* __restrict__ w, double* __restrict__ gi,
-                                                                          double* __restrict__ gj, double* __restrict__ Hii,
-                                                                          double* __restrict__ Hij, double* __restrict__ Hjj) {
-  const int e = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
-  if (e >= n_edges) return;
-  double Xi[7], Xj[7], Z[7], Om[36], err[6], A[36], B[36];
-  const double* pi = poses + 7ll * ei[e];
-  const double* pj = poses + 7ll * ej[e];
-#pragma unroll
-  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * e + k]; }
-#pragma unroll
-  for (int k = 0; k < 36; k++) Om[k] = info[36ll * e + k];
-  const int ce = code[e];
-  if (ce == kGraphLossInactive) {
-    graph_edge_error(Xi, Xj, Z, err, nullptr, nullptr);
-    chi2[e] = graph_edge_chi2(err, Om);
-    rho[e] = 0.0; w[e] = 0.0;
-    return;
-  }
-  graph_edge_error(Xi, Xj, Z, err, A, B);
-  graph_edge_blocks_t<true>(err, A, B, Om, edge_cap, ce, scale[e], chi2 + e, rho + e, w + e, gi + e, gj + e, Hii + e, Hij + e, Hjj + e);
-}
-
-__global__ __launch_bounds__(kGraphThreads) void k_graph_cost_robust(int n_edges, const double* __restrict__ poses, const int* __restrict__ ei,
-                                                                     const int* __restrict__ ej, const double* __restrict__ z,
-                                                                     const double* __restrict__ info, const int* __restrict__ code,
-                                                                     const double* __restrict__ scale, double* __restrict__ chi2,
-                                                                     double* __restrict__ rho, double* __restrict__ w) {
-  const int e = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
-  if (e >= n_edges) return;
-  double Xi[7], Xj[7], Z[7], Om[36], err[6];
-  const double* pi = poses + 7ll * ei[e];
-  const double* pj = poses + 7ll * ej[e];
-#pragma unroll
-  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * e + k]; }
-#pragma unroll
-  for (int k = 0; k < 36; k++) Om[k] = info[36ll * e + k];
-  graph_edge_error(Xi, Xj, Z, err, nullptr, nullptr);
-  const double s = graph_edge_chi2(err, Om);
-  const int ce = code[e];
-  double r = 0.0, wt = 0.0;
-  if (ce != kGraphLossInactive) graph_loss(ce, scale[e], s, &r, &wt);
-  chi2[e] = s; rho[e] = r; w[e] = wt;
-}
-
-
-// ---- covariances of the graph and the loop gate (liodom_graph_solve_columns / _covariance / _gate_edges; graph_marginals.h plans
-// the launches; tests/graph_cov_model.py restates them).  They stand after every other kernel, as the robust instances do. ----
-//
-// k_graph_pcg_columns: columns of H^-1.  Workgroup b solves H x = e_c, c = first_column + b = 6 slot + k: the unit vector at
+// Columns of H^-1 (liodom_graph_solve_columns / _covariance / _gate_edges; graph_marginals.h plans the launches;
+// tests/graph_cov_model.py restates them).  Workgroup b solves H x = e_c, c = first_column + b = 6 slot + k: the unit vector at
 // component k of node col_node[slot] (a free node whose component holds a fixed one: the host leaves every other node out), at
-// lambda = 0.  The loop is k_graph_pcg's — the same ownership of nodes, the same sums in the same order, the same breakdown tests —
-// as a second copy, so that k_graph_pcg's code does not move; what differs: the right-hand side, no gradient exit, and the
-// stopping rule |r| <= tolerance (|e_c| = 1).  Workgroup b owns the five vectors x, r, p, z, Ap (6 node_cap doubles each) at
-// ws + b * 30 * node_cap; it reads nothing another workgroup writes: no polling, no atomic, no flag.  status[b]: iterations,
-// flag (GRAPH_PCG_*), residual |r| when the loop ended; gmax is 0.
+// lambda = 0 and without a gradient exit; |e_c| = 1, so the stopping rule is |r| <= tolerance.  Workgroup b owns the five vectors
+// x, r, p, z, Ap (6 node_cap doubles each) at ws + b * 30 * node_cap; it reads nothing another workgroup writes: no polling, no
+// atomic, no flag.  status[b]: iterations, flag (GRAPH_PCG_*), residual |r| when the loop ended; gmax is 0.
 __global__ __launch_bounds__(kGraphPcgThreads) void k_graph_pcg_columns(int n_nodes, long long node_cap, long long edge_cap, int first_column,
                                                                         int max_iterations, double tolerance, const int* __restrict__ col_node,
                                                                         const int* __restrict__ fixed, const int* __restrict__ parent,
@@ -581,9 +592,7 @@ __global__ __launch_bounds__(kGraphPcgThreads) void k_graph_pcg_columns(int n_no
                                                                         const double* __restrict__ Minv, const double* __restrict__ Hij,
                                                                         const int* __restrict__ bad, double* ws,
                                                                         GraphPcgStatus* __restrict__ status) {
-  __shared__ double sh_a[kGraphPcgWaves], sh_b[kGraphPcgWaves * 2];
-  __shared__ double sh_v1[kGraphPcgWaves * 9], sh_v2[kGraphPcgWaves * 9];
-  __shared__ int sh_f1[kGraphPcgWaves], sh_f2[kGraphPcgWaves];
+  __shared__ GraphPcgLds lds;
   const int tid = (int)threadIdx.x;
   const int column = first_column + (int)blockIdx.x;
   const int rhs_node = col_node[column / 6], rhs_k = column % 6;
@@ -592,71 +601,14 @@ __global__ __launch_bounds__(kGraphPcgThreads) void k_graph_pcg_columns(int n_no
   double* p = r + 6ll * node_cap;
   double* zv = p + 6ll * node_cap;
   double* Ap = zv + 6ll * node_cap;
-  const double lambda = 0.0;
   for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
 #pragma unroll
     for (int k = 0; k < 6; k++) { x[6ll * n + k] = 0.0; r[6ll * n + k] = (n == rhs_node && k == rhs_k) ? 1.0 : 0.0; }
   }
-  graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, sh_v1, sh_f1, sh_v2, sh_f2);
-  double s2[2] = {0.0, 0.0};
-  for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-      const double rk = r[6ll * n + k], zk = zv[6ll * n + k];
-      p[6ll * n + k] = zk;
-      s2[0] += rk * rk; s2[1] += rk * zk;
-    }
-  }
-  graph_block_sum<2>(s2, sh_b);
-  const double g2 = s2[0];
-  double rz = s2[1], rr = s2[0];
-  int iterations = 0, flag = GRAPH_PCG_MAX_ITER;
-  if (*bad != 0 || !(g2 > 0.0) || !ld_isfinite(g2) || !(rz > 0.0)) flag = GRAPH_PCG_BREAKDOWN;
-  else {
-    for (int it = 0; it < max_iterations; it++) {
-      __syncthreads();                               // p of every node is written
-      double s1[1] = {0.0};
-      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-        double y[6];
-        graph_row_multiply(n, node_cap, edge_cap, lambda, fixed, offsets, entries, ei, ej, D, Hij, p, y);
-#pragma unroll
-        for (int k = 0; k < 6; k++) { Ap[6ll * n + k] = y[k]; s1[0] += p[6ll * n + k] * y[k]; }
-      }
-      graph_block_sum<1>(s1, sh_a);
-      const double pAp = s1[0];
-      if (!(pAp > 0.0) || !ld_isfinite(pAp)) { flag = GRAPH_PCG_BREAKDOWN; break; }
-      const double alpha = rz / pAp;
-      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-          x[6ll * n + k] += alpha * p[6ll * n + k];
-          r[6ll * n + k] -= alpha * Ap[6ll * n + k];
-        }
-      }
-      graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, sh_v1, sh_f1, sh_v2, sh_f2);
-      s2[0] = 0.0; s2[1] = 0.0;
-      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) { const double rk = r[6ll * n + k]; s2[0] += rk * rk; s2[1] += rk * zv[6ll * n + k]; }
-      }
-      graph_block_sum<2>(s2, sh_b);
-      rr = s2[0];
-      iterations = it + 1;
-      if (rr <= tolerance * tolerance * g2) { flag = GRAPH_PCG_CONVERGED; break; }
-      if (!ld_isfinite(rr) || !(s2[1] > 0.0)) { flag = GRAPH_PCG_BREAKDOWN; break; }
-      const double beta = s2[1] / rz;
-      rz = s2[1];
-      for (int n = tid; n < n_nodes; n += kGraphPcgThreads) {
-#pragma unroll
-        for (int k = 0; k < 6; k++) p[6ll * n + k] = zv[6ll * n + k] + beta * p[6ll * n + k];
-      }
-    }
-  }
-  if (tid == 0) {
-    GraphPcgStatus* st = status + blockIdx.x;
-    st->iterations = iterations; st->flag = flag; st->gmax = 0.0;
-    st->residual = g2 > 0.0 ? sqrt(rr / g2) : 0.0;
-  }
+  graph_precondition(n_nodes, node_cap, parent, poses, Minv, r, zv, &lds);
+  const GraphPcgStatus st = graph_pcg_run(n_nodes, node_cap, edge_cap, 0.0, max_iterations, tolerance, false, fixed, parent, poses, offsets,
+                                          entries, ei, ej, D, Minv, Hij, bad, x, r, p, zv, Ap, &lds);
+  if (tid == 0) status[blockIdx.x] = st;
 }
 
 // One thread per requested block k = Sigma[row[k], col[k]] (36 doubles, row-major): entry (a, b) is x of column 6 slot[col[k]] + b
@@ -678,31 +630,6 @@ __global__ __launch_bounds__(kGraphThreads) void k_graph_cov_gather(int n_blocks
 #pragma unroll
     for (int a = 0; a < 6; a++) blocks[36ll * k + a * 6 + b] = x[a];
   }
-}
-
-// One thread per candidate edge c = (ci[c], cj[c], z, info): graph_gate (liodom_math.h) at the current poses with the blocks
-// Sigma[i, i], Sigma[i, j], Sigma[j, j] at blocks[3 c], [3 c + 1], [3 c + 2].  flag[c] = 1 where Omega or S is not positive
-// definite (d2[c] is then NaN), else 0.
-__global__ __launch_bounds__(kGraphThreads) void k_graph_gate(int n, const double* __restrict__ poses, const int* __restrict__ ci,
-                                                              const int* __restrict__ cj, const double* __restrict__ z,
-                                                              const double* __restrict__ info, const double* __restrict__ blocks,
-                                                              double* __restrict__ d2, int* __restrict__ flag) {
-  const int c = (int)(blockIdx.x * kGraphThreads + threadIdx.x);
-  if (c >= n) return;
-  double Xi[7], Xj[7], Z[7], Om[36], Sii[36], Sij[36], Sjj[36];
-  const double* pi = poses + 7ll * ci[c];
-  const double* pj = poses + 7ll * cj[c];
-#pragma unroll
-  for (int k = 0; k < 7; k++) { Xi[k] = pi[k]; Xj[k] = pj[k]; Z[k] = z[7ll * c + k]; }
-#pragma unroll
-  for (int k = 0; k < 36; k++) {
-    Om[k] = info[36ll * c + k];
-    Sii[k] = blocks[108ll * c + k]; Sij[k] = blocks[108ll * c + 36 + k]; Sjj[k] = blocks[108ll * c + 72 + k];
-  }
-  double d;
-  const bool ok = graph_gate(Xi, Xj, Z, Om, Sii, Sij, Sjj, &d);
-  d2[c] = d;
-  flag[c] = ok ? 0 : 1;
 }
 
 }  // namespace liodom_dev

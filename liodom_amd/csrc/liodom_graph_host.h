@@ -4,12 +4,13 @@
 //
 // The graph lives on the host (poses, fixed flags, edge records): that copy is what the calls read and write, and what an error
 // leaves untouched.  The device copy and the CSR are made again, before the next launch, whenever the host copy has changed.
-// The Levenberg-Marquardt loop runs here around the launches; per step tried: k_graph_gather, k_graph_pcg, k_graph_retract,
-// k_graph_cost, k_graph_sum, and after an accepted one k_graph_linearize, k_graph_sum — whatever the number of PCG iterations.
+// The Levenberg-Marquardt loop runs here around the launches and graph_lm.h decides; per step tried: k_graph_gather, k_graph_pcg,
+// k_graph_retract, k_graph_cost, k_graph_sum, and after an accepted one k_graph_linearize, k_graph_sum — whatever the number of
+// PCG iterations.
 //
 // Robust losses and switched-off edges: the table of losses per kind and the active flags are part of the host copy.  At upload
 // every edge gets a code (its kind's loss, or "inactive") and a scale, and the CSR and the chain are made of the active edges.
-// If every code is 0 the quadratic kernels run, as they did before a loss existed; otherwise their robust twins, which also
+// If every code is 0 the quadratic instances of k_graph_linearize and k_graph_cost run; otherwise the robust ones, which also
 // write rho and w per edge, and the cost that is summed is rho.
 //
 // Covariances and the loop gate (liodom_graph_solve_columns / _covariance / _gate_edges): graph_marginals.h decides which nodes
@@ -22,6 +23,7 @@
 #include <vector>
 
 #include "graph_csr.h"
+#include "graph_lm.h"
 #include "graph_marginals.h"
 #include "kernels_graph.h"
 
@@ -37,6 +39,7 @@ struct liodom_graph {
   std::vector<int32_t> active;                // [n_edges]
   int32_t loss[liodom_dev::kGraphLossKinds] = {};        // per edge kind 0 .. 15; kept by reset
   double loss_scale[liodom_dev::kGraphLossKinds] = {};
+  std::vector<int32_t> ei, ej;                // (made at upload) the edges' nodes, as the device holds them
   bool robust = false;                        // (made at upload) some edge's code is not 0: the robust kernels run
   int n_active = 0;                           // (made at upload)
   bool uploaded = false;                      // the device holds this graph (poses in d_poses) and its CSR
@@ -76,13 +79,25 @@ int graph_alloc(liodom_graph* g, T** ptr, size_t count) {
   return LIODOM_OK;
 }
 
+inline int graph_n_free(const liodom_graph* g) {
+  int n_free = 0;
+  for (int32_t f : g->fixed) n_free += f ? 0 : 1;
+  return n_free;
+}
+
+// why an edge (one to add, or a candidate for the gate) is refused; nullptr: it is not
+inline const char* graph_edge_refusal(const liodom_graph_edge_t& ed, int n_nodes) {
+  return ed.reserved != 0 ? "an edge's reserved field is not 0" : liodom_dev::graph_edge_refusal(ed.i, ed.j, ed.z, ed.info, n_nodes);
+}
+
 inline unsigned graph_blocks(int n) { return (unsigned)std::max(1, (n + liodom_dev::kGraphThreads - 1) / liodom_dev::kGraphThreads); }
 
 // the device copy of the graph and its CSR
 int graph_upload(liodom_graph* g) {
   if (g->uploaded) return LIODOM_OK;
   const int N = (int)g->fixed.size(), E = (int)g->edges.size();
-  std::vector<int32_t> ei((size_t)E), ej((size_t)E), offsets, entries, parent, code((size_t)E);
+  std::vector<int32_t>&ei = g->ei, &ej = g->ej, offsets, entries, parent, code((size_t)E);
+  ei.resize((size_t)E); ej.resize((size_t)E);
   std::vector<double> z(7 * (size_t)E), info(36 * (size_t)E), scale((size_t)E);
   bool robust = false;
   int n_active = 0;
@@ -126,19 +141,19 @@ int graph_upload(liodom_graph* g) {
   return LIODOM_OK;
 }
 
-// per-edge quantities at d_poses, and *cost = their chi2 — with a loss or an edge switched off: their rho — summed (enqueued and
-// waited for)
-int graph_linearize(liodom_graph* g, double* cost) {
+// *cost = the edges' chi2 — with a loss or an edge switched off: their rho — summed, at `poses`: the candidate's, or d_poses, and
+// then the per-edge blocks are made as well (the linearisation).  Enqueued and waited for.
+int graph_enqueue_cost(liodom_graph* g, const double* poses, double* cost) {
   using namespace liodom_dev;
   const int E = (int)g->edges.size();
-  if (E && g->robust) {
-    hipLaunchKernelGGL(k_graph_linearize_robust, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, (long long)g->max_edges, g->d_poses,
-                       g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_code, g->d_scale, g->d_chi2, g->d_rho, g->d_w, g->d_gi, g->d_gj, g->d_Hii,
-                       g->d_Hij, g->d_Hjj);
+  if (E && poses == g->d_poses) {
+    hipLaunchKernelGGL(g->robust ? k_graph_linearize<true> : k_graph_linearize<false>, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E,
+                       (long long)g->max_edges, poses, g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_code, g->d_scale, g->d_chi2, g->d_rho, g->d_w, g->d_gi,
+                       g->d_gj, g->d_Hii, g->d_Hij, g->d_Hjj);
     HIP_TRY(hipGetLastError());
   } else if (E) {
-    hipLaunchKernelGGL(k_graph_linearize, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, (long long)g->max_edges, g->d_poses,
-                       g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_chi2, g->d_gi, g->d_gj, g->d_Hii, g->d_Hij, g->d_Hjj);
+    hipLaunchKernelGGL(g->robust ? k_graph_cost<true> : k_graph_cost<false>, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, poses, g->d_ei,
+                       g->d_ej, g->d_z, g->d_info, g->d_code, g->d_scale, g->d_chi2, g->d_rho, g->d_w);
     HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(k_graph_sum, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, E, g->robust ? g->d_rho : g->d_chi2, g->d_sum);
@@ -164,7 +179,7 @@ int graph_prepare(liodom_graph* g) {
   if ((rc = graph_upload(g))) return rc;
   if (g->linearized) return LIODOM_OK;
   double cost = 0.0;
-  if ((rc = graph_linearize(g, &cost))) return rc;
+  if ((rc = graph_enqueue_cost(g, g->d_poses, &cost))) return rc;
   if ((rc = graph_gather(g, 0.0))) return rc;
   HIP_TRY(hipStreamSynchronize(g->stream));
   g->linearized = true;
@@ -222,10 +237,8 @@ int graph_cov_solve(liodom_graph* g, const liodom_graph_cov_options_t& opt, cons
   using namespace liodom_dev;
   const int N = (int)g->fixed.size(), E = (int)g->edges.size();
   int rc;
-  if ((rc = graph_prepare(g))) return rc;
-  std::vector<int32_t> ei((size_t)E), ej((size_t)E);
-  for (int e = 0; e < E; e++) { ei[(size_t)e] = g->edges[(size_t)e].i; ej[(size_t)e] = g->edges[(size_t)e].j; }
-  if (!graph_anchored(ei.data(), ej.data(), E, g->active.data(), g->fixed.data(), N, &out->anchored)) {
+  if ((rc = graph_prepare(g))) return rc;          // (the upload keeps ei, ej)
+  if (!graph_anchored(g->ei.data(), g->ej.data(), E, g->active.data(), g->fixed.data(), N, &out->anchored)) {
     g_last_error = "liodom_graph: an edge names a node that does not exist"; return LIODOM_ERR_INVALID_ARG;      // (checked when it was added)
   }
   graph_column_nodes(nodes, n, g->fixed.data(), out->anchored.data(), N, &out->col_node, &out->slot);
@@ -241,9 +254,7 @@ int graph_cov_solve(liodom_graph* g, const liodom_graph_cov_options_t& opt, cons
       (rc = graph_grow(g, &g->cov_col_node, sizeof(int32_t) * out->col_node.size())))
     return rc;
   HIP_TRY(hipMemcpyAsync(g->cov_col_node.p, out->col_node.data(), sizeof(int32_t) * out->col_node.size(), hipMemcpyHostToDevice, g->stream));
-  int n_free = 0;
-  for (int k = 0; k < N; k++) n_free += g->fixed[(size_t)k] ? 0 : 1;
-  const int max_pcg = graph_cov_iterations(&opt, n_free);
+  const int max_pcg = graph_cov_iterations(&opt, graph_n_free(g));
   GraphPcgStatus* d_st = static_cast<GraphPcgStatus*>(g->cov_status.p);
   for (int l = 0; l < plan.launches; l++) {
     int first = 0, count = 0;
@@ -385,8 +396,7 @@ int liodom_graph_add_edges(liodom_graph_t* g, const liodom_graph_edge_t* edges, 
   std::lock_guard<std::mutex> lk(g->mx);
   const int N = (int)g->fixed.size();
   for (int k = 0; k < n; k++) {
-    const char* why = edges[k].reserved != 0 ? "an edge's reserved field is not 0" : liodom_dev::graph_edge_refusal(edges[k].i, edges[k].j, edges[k].z, edges[k].info, N);
-    if (why) { g_last_error = std::string("liodom_graph_add_edges: ") + why; return LIODOM_ERR_INVALID_ARG; }
+    if (const char* why = graph_edge_refusal(edges[k], N)) { g_last_error = std::string("liodom_graph_add_edges: ") + why; return LIODOM_ERR_INVALID_ARG; }
   }
   if (g->edges.size() + (size_t)n > (size_t)g->max_edges) { g_last_error = "liodom_graph_add_edges: more edges than max_edges"; return LIODOM_ERR_CAPACITY; }
   if (n == 0) return LIODOM_OK;
@@ -538,88 +548,51 @@ int liodom_graph_edge_weights(liodom_graph_t* g, double* rho, double* weight) {
 }
 
 void liodom_graph_options_default(liodom_graph_options_t* opt) {
-  if (!opt) return;
-  opt->max_iterations = 20; opt->max_pcg_iterations = 0;
-  opt->pcg_tolerance = 1e-8; opt->gradient_tolerance = 1e-9; opt->cost_tolerance = 1e-10;
+  if (opt) liodom_dev::graph_lm_options_default(opt);
 }
 
 int liodom_graph_optimize(liodom_graph_t* g, const liodom_graph_options_t* opt_in, liodom_graph_report_t* report) {
   using namespace liodom_dev;
   if (!g) { g_last_error = "liodom_graph_optimize: null graph"; return LIODOM_ERR_INVALID_ARG; }
   liodom_graph_options_t opt;
-  liodom_graph_options_default(&opt);
+  graph_lm_options_default(&opt);
   if (opt_in) opt = *opt_in;
-  if (opt.max_iterations < 0 || opt.max_pcg_iterations < 0 || !(opt.pcg_tolerance >= 0.0) || !(opt.gradient_tolerance >= 0.0) || !(opt.cost_tolerance >= 0.0)) {
-    g_last_error = "liodom_graph_optimize: an option is negative or not a number"; return LIODOM_ERR_INVALID_ARG;
-  }
+  if (const char* why = graph_lm_options_refusal(&opt)) { g_last_error = std::string("liodom_graph_optimize: ") + why; return LIODOM_ERR_INVALID_ARG; }
   std::lock_guard<std::mutex> lk(g->mx);
-  const int N = (int)g->fixed.size(), E = (int)g->edges.size();
-  int n_free = 0;
-  for (int n = 0; n < N; n++) n_free += g->fixed[(size_t)n] ? 0 : 1;
+  const int N = (int)g->fixed.size(), n_free = graph_n_free(g);
   if (n_free == N) { g_last_error = "liodom_graph_optimize: the graph has no fixed node"; return LIODOM_ERR_INVALID_ARG; }
-  liodom_graph_report_t rep;
-  std::memset(&rep, 0, sizeof(rep));
-  rep.final_lambda = 1e-4;
-  rep.termination = LIODOM_GRAPH_TERM_GRADIENT;
   HIP_TRY(hipSetDevice(g->device));
   int rc;
   if ((rc = graph_upload(g))) return rc;
   double cost = 0.0;
-  if ((rc = graph_linearize(g, &cost))) return rc;
+  if ((rc = graph_enqueue_cost(g, g->d_poses, &cost))) return rc;
   g->linearized = false;                              // (Minv is about to be made for another lambda)
-  rep.initial_cost = rep.final_cost = cost;
-  if (n_free == 0 || g->n_active == 0) { if (report) *report = rep; return LIODOM_OK; }
-  const int max_pcg = opt.max_pcg_iterations > 0 ? opt.max_pcg_iterations : std::min(6 * n_free, 65536);
-  double lambda = 1e-4;
+  GraphLm lm;
+  if (!lm.begin(opt, cost, n_free, g->n_active)) { if (report) *report = lm.rep; return LIODOM_OK; }
   bool moved = false;                                 // d_poses differs from the host's poses
   // from here on an error must leave the host copy as it is and the device copy marked stale
   auto run = [&]() -> int {
-    int pending = -1;                                 // the termination found; one more launch reports max |g| at the poses left
     while (true) {
-      const int pcg_its = (pending >= 0 || rep.iterations >= opt.max_iterations) ? 0 : max_pcg;
-      if ((rc = graph_gather(g, lambda))) return rc;
-      hipLaunchKernelGGL(k_graph_pcg, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, N, (long long)g->max_nodes, (long long)g->max_edges, lambda,
-                         pcg_its, opt.pcg_tolerance, opt.gradient_tolerance, g->d_fixed, g->d_parent, g->d_poses, g->d_offsets, g->d_entries, g->d_ei, g->d_ej,
-                         g->d_g, g->d_D, g->d_Minv, g->d_Hij, g->d_bad, g->d_x, g->d_r, g->d_p, g->d_zv, g->d_Ap, g->d_status);
+      if ((rc = graph_gather(g, lm.lambda))) return rc;
+      hipLaunchKernelGGL(k_graph_pcg, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, N, (long long)g->max_nodes, (long long)g->max_edges, lm.lambda,
+                         lm.pcg_iterations(), opt.pcg_tolerance, opt.gradient_tolerance, g->d_fixed, g->d_parent, g->d_poses, g->d_offsets, g->d_entries,
+                         g->d_ei, g->d_ej, g->d_g, g->d_D, g->d_Minv, g->d_Hij, g->d_bad, g->d_x, g->d_r, g->d_p, g->d_zv, g->d_Ap, g->d_status);
       HIP_TRY(hipGetLastError());
       GraphPcgStatus st;
       HIP_TRY(hipMemcpyAsync(&st, g->d_status, sizeof(st), hipMemcpyDeviceToHost, g->stream));
       HIP_TRY(hipStreamSynchronize(g->stream));
-      rep.max_gradient = st.gmax;
-      if (pending >= 0) { rep.termination = pending; return LIODOM_OK; }
-      if (st.flag == GRAPH_PCG_GRADIENT) { rep.termination = LIODOM_GRAPH_TERM_GRADIENT; return LIODOM_OK; }
-      if (rep.iterations >= opt.max_iterations) { rep.termination = LIODOM_GRAPH_TERM_MAX_ITERATIONS; return LIODOM_OK; }      // (that launch solved nothing)
-      if (st.flag == GRAPH_PCG_BREAKDOWN) { rep.pcg_iterations += st.iterations; rep.termination = LIODOM_GRAPH_TERM_BREAKDOWN; return LIODOM_OK; }
-      rep.pcg_iterations += st.iterations;
-      rep.iterations++;
+      if (!lm.after_pcg(st.flag, st.iterations, st.gmax)) return LIODOM_OK;
       hipLaunchKernelGGL(k_graph_retract, dim3(graph_blocks(N)), dim3(kGraphThreads), 0, g->stream, N, g->d_poses, g->d_fixed, g->d_x, g->d_cand);
       HIP_TRY(hipGetLastError());
-      if (g->robust) {
-        hipLaunchKernelGGL(k_graph_cost_robust, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, g->d_cand, g->d_ei, g->d_ej, g->d_z, g->d_info,
-                           g->d_code, g->d_scale, g->d_chi2, g->d_rho, g->d_w);
-      } else {
-        hipLaunchKernelGGL(k_graph_cost, dim3(graph_blocks(E)), dim3(kGraphThreads), 0, g->stream, E, g->d_cand, g->d_ei, g->d_ej, g->d_z, g->d_info, g->d_chi2);
-      }
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_graph_sum, dim3(1), dim3(kGraphPcgThreads), 0, g->stream, E, g->robust ? g->d_rho : g->d_chi2, g->d_sum);
-      HIP_TRY(hipGetLastError());
       double cand = 0.0;
-      HIP_TRY(hipMemcpyAsync(&cand, g->d_sum, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-      HIP_TRY(hipStreamSynchronize(g->stream));
-      if (cand < cost) {                              // (false for a NaN)
+      if ((rc = graph_enqueue_cost(g, g->d_cand, &cand))) return rc;
+      const GraphLmStep step = lm.after_cost(cand);
+      if (step == GRAPH_LM_DONE) return LIODOM_OK;
+      if (step == GRAPH_LM_ACCEPTED) {
         std::swap(g->d_poses, g->d_cand);
         moved = true;
-        rep.accepted_steps++;
-        const double decrease = cost != 0.0 ? (cost - cand) / std::fabs(cost) : 0.0;      // (an indefinite Omega can make chi2 negative)
-        lambda = std::max(lambda / 10.0, 1e-12);
-        rep.final_lambda = lambda;
-        if ((rc = graph_linearize(g, &cost))) return rc;          // (the same edges summed in the same order: equal to cand)
-        rep.final_cost = cost;
-        if (decrease <= opt.cost_tolerance) pending = LIODOM_GRAPH_TERM_COST;
-      } else {
-        lambda *= 10.0;
-        rep.final_lambda = lambda;
-        if (lambda > 1e12) { rep.termination = LIODOM_GRAPH_TERM_LAMBDA; return LIODOM_OK; }
+        if ((rc = graph_enqueue_cost(g, g->d_poses, &cost))) return rc;
+        lm.relinearized(cost);
       }
     }
   };
@@ -633,7 +606,7 @@ int liodom_graph_optimize(liodom_graph_t* g, const liodom_graph_options_t* opt_i
   }
   if (rc != LIODOM_OK) { g->uploaded = false; g->linearized = false; return rc; }
   if (moved) g->poses.swap(out);
-  if (report) *report = rep;
+  if (report) *report = lm.rep;
   return LIODOM_OK;
 }
 
@@ -731,9 +704,7 @@ int liodom_graph_gate_edges(liodom_graph_t* g, const liodom_graph_edge_t* candid
   std::lock_guard<std::mutex> lk(g->mx);
   const int N = (int)g->fixed.size();
   for (int k = 0; k < n; k++) {
-    const char* why = candidates[k].reserved != 0 ? "an edge's reserved field is not 0"
-                                                  : graph_edge_refusal(candidates[k].i, candidates[k].j, candidates[k].z, candidates[k].info, N);
-    if (why) { g_last_error = std::string("liodom_graph_gate_edges: ") + why; return LIODOM_ERR_INVALID_ARG; }
+    if (const char* why = ::graph_edge_refusal(candidates[k], N)) { g_last_error = std::string("liodom_graph_gate_edges: ") + why; return LIODOM_ERR_INVALID_ARG; }
   }
   if (n > 0 && (!d2 || !status)) { g_last_error = "liodom_graph_gate_edges: null d2 or status"; return LIODOM_ERR_INVALID_ARG; }
   if (n == 0) return LIODOM_OK;

@@ -1,5 +1,5 @@
-"""Covariances of the pose graph and the loop gate (include/liodom_hip.h "covariances of the graph"; graph_marginals.h; the kernels at
-the end of kernels_graph.h) restated in float64 NumPy on top of graph_model.linearize / graph_model.dense (or their robust twins in
+"""Covariances of the pose graph and the loop gate (include/liodom_hip.h "covariances of the graph"; graph_marginals.h; the kernels
+in kernels_graph.h) restated in float64 NumPy on top of graph_model.linearize / graph_model.dense (or their robust twins in
 graph_robust_model): which nodes are anchored, the dense H over the free anchored nodes and its inverse, the statuses, the gate's
 d2 — and the error bounds the GPU tests hold the library to, with the designed graphs they run on.  No GPU, no library call."""
 import math

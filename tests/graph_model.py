@@ -228,10 +228,12 @@ def chi2(poses, edges):
     return float(total)
 
 
-def lm(poses, fixed, edges, max_iterations=20, gradient_tolerance=1e-9, cost_tolerance=1e-10):
+def lm(poses, fixed, edges, max_iterations=20, gradient_tolerance=1e-9, cost_tolerance=1e-10, trace=None):
     """The library's Levenberg-Marquardt with a dense solve in place of the conjugate gradients -> (poses, report dict with
     initial_cost, final_cost, max_gradient, final_lambda, iterations, accepted_steps, termination, costs = chi2 after each
-    accepted step)."""
+    accepted step).  trace (a list): gets ("gradient", max |g|) wherever the library would launch a solve and ("cost", chi2 of the
+    candidate) after every step tried, in order."""
+    trace = [] if trace is None else trace
     poses = normalised(poses)
     fx = np.asarray(fixed).reshape(-1) != 0
     N = poses.shape[0]
@@ -245,6 +247,7 @@ def lm(poses, fixed, edges, max_iterations=20, gradient_tolerance=1e-9, cost_tol
     while True:
         Hm, g = dense(lin, edges)
         rep["max_gradient"] = float(np.max(np.abs(g[free])))
+        trace.append(("gradient", rep["max_gradient"]))
         if rep["max_gradient"] <= gradient_tolerance:
             rep["termination"] = "gradient"
             break
@@ -264,6 +267,7 @@ def lm(poses, fixed, edges, max_iterations=20, gradient_tolerance=1e-9, cost_tol
         rep["iterations"] += 1
         cand = np.stack([retract(poses[n], delta[6 * n:6 * n + 6]) if not fx[n] else poses[n] for n in range(N)])
         c = chi2(cand, edges)
+        trace.append(("cost", c))
         if c < cost:
             decrease = (cost - c) / cost
             poses, cost = cand, c
@@ -275,6 +279,7 @@ def lm(poses, fixed, edges, max_iterations=20, gradient_tolerance=1e-9, cost_tol
             if decrease <= cost_tolerance:
                 Hm, g = dense(lin, edges)
                 rep["max_gradient"] = float(np.max(np.abs(g[free])))
+                trace.append(("gradient", rep["max_gradient"]))
                 rep["termination"] = "cost"
                 break
         else:

@@ -1,5 +1,5 @@
 """Robust losses and switched-off edges of the pose graph (include/liodom_hip.h "closing loops", "robust losses"; liodom_math.h
-graph_loss; kernels_graph.h k_graph_linearize_robust) restated in float64 NumPy on top of graph_model: the losses, the weighted
+graph_loss; kernels_graph.h k_graph_linearize<true>) restated in float64 NumPy on top of graph_model: the losses, the weighted
 linearisation — every FINISHED per-edge entry times w, inactive edges left out —, H x, the cost, and a dense Levenberg-Marquardt
 with the library's rules.  Also the designed graphs of the tests.  No GPU, no library call."""
 import math

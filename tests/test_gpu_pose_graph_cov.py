@@ -1,5 +1,5 @@
-"""Covariances of the pose graph and the loop gate on the GPU (liodom_graph_solve_columns / _covariance / _gate_edges; the kernels at
-the end of kernels_graph.h) against tests/graph_cov_model.py, on its designed graphs: chains of 2, 5, 64, 65 nodes, rings of 1024,
+"""Covariances of the pose graph and the loop gate on the GPU (liodom_graph_solve_columns / _covariance / _gate_edges; the kernels
+in kernels_graph.h) against tests/graph_cov_model.py, on its designed graphs: chains of 2, 5, 64, 65 nodes, rings of 1024,
 1025 and 1030 (a thread of the solving workgroup first owns two nodes at 1025), a ring of 12 with two loops, a hub of degree 40,
 two components of which one has no fixed node, and a ring with Geman-McClure weights and a switched-off edge.  The bounds are the
 model's (drift_allowance, block_bound, gate_bound) — none is taken from what the library returns.  The model of a graph is made
