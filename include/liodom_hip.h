@@ -1134,6 +1134,68 @@ int liodom_graph_gate_edges(liodom_graph_t* g, const liodom_graph_edge_t* candid
                             double* d2 /*n*/, int32_t* status /*n*/);
 int liodom_graph_cov_counters(liodom_graph_t* g, int64_t* launches /*optional*/, int64_t* columns /*optional*/);
 
+/* ---- odometry edges from the scans' own covariances (DESIGN.md §3 "Odometry edges from the scans' covariances", INTEGRATION.md
+ * §7).  Opt-in: a handle that never makes these calls allocates and launches what it did before they existed.
+ *
+ * For an interval (a, b), a < b, of a stream's scans — X_k = (q_k, t_k) the pose of scan k, its quaternion divided by its norm
+ * when taken in, C_k the `covariance` of scan k's liodom_pose_cov_t in its tangent (d, dt) — the calls give the edge
+ * "X_a^-1 o X_b was measured as Z with information Omega" in the form liodom_graph_add_edges takes:
+ *   Z        q_z = conj(q_a) (x) q_b, t_z = R_a^T (t_b - t_a).
+ *   usable   scan k is usable iff its record has scan_index == k, flags == LIODOM_COV_VALID exactly and 36 finite covariance
+ *            entries (the lower triangle of C_k is what is read; sigma2 H^-1 is symmetric bit for bit).
+ *   Sigma    the sum over the usable k = a + 1 .. b of M_k = T_k (inflation C_k + F) T_k^T, T_k = [[I, 0], [-2 [u_k]x, I]],
+ *            u_k = t_b - t_k, F = diag(fr^2 x 3, ft^2 x 3): the error of scan k's solve is a world-frame tangent perturbation of X_k
+ *            that every later pose rides on rigidly (d_b = d, dt_b = dt - 2 [u_k]x d), and the scans' errors are taken as
+ *            independent — an approximation: a solve registers against a window of earlier scans; `inflation` is where a
+ *            calibration puts what that costs.  Summation order, a function of (a, b) alone: lane l of 64 sums
+ *            its scans k = l (mod 64) in ascending order from 0; the 64 partials v are combined as P1[r] = v[r] + v[r + 32]
+ *            (r < 32), P2[r] = P1[r] + P1[r + 16], P3[r] = P2[r] + P2[15 - r], P4[r] = P3[r] + P3[7 - r], P5[r] = P4[r] + P4[r + 2],
+ *            Sigma = P5[0] + P5[1].  Equal inputs give equal bytes.
+ *   Omega    B = de/d(delta_j) of the edge's error at (X_a, X_b, Z); Sigma_e = B Sigma B^T (`covariance`), Omega = Sigma_e^-1 by
+ *            Cholesky (`information`), both symmetric bit for bit.  Omega does not depend on the frame the poses are given in.
+ * All arithmetic is double, no contraction.
+ *
+ *   liodom_odom_edge_options_default   inflation 1, floor_rotation 0 (fr, half-angle radians), floor_translation 0 (ft, metres):
+ *       the raw records.  opt NULL in a call: these.  A non-finite or negative value, inflation 0 or reserved != 0:
+ *       LIODOM_ERR_INVALID_ARG.
+ *   liodom_chain_odometry_edges   the public form: host arrays poses[m x 7] and records[m], entry k is scan k; n intervals
+ *       0 <= from[i] < to[i] < m, n <= 2^20 (else LIODOM_ERR_INVALID_ARG, nothing written; n = 0: LIODOM_OK).  Needs no handle: it runs on the
+ *       calling thread's current device, with buffers of its own for the duration of the call.
+ *   liodom_get_odometry_edges     the same kernel on the stream's own pose log and covariance log, in place on the device.
+ *       It takes the locks and synchronises as liodom_get_pose_covariance_log does.  pose_covariance = 0: LIODOM_ERR_UNSUPPORTED.
+ *       An interval must satisfy first <= from < to < min(scans enqueued, pose_log_capacity), first = the stream's scan count at
+ *       its last liodom_reset, liodom_reset_stream, liodom_seed_stream or liodom_import_stream_state (0 after liodom_create): the
+ *       log below it belongs to an earlier life of the stream.  Else LIODOM_ERR_INVALID_ARG, nothing written.
+ * Flags of a record:
+ *     LIODOM_ODOM_EDGE_VALID 1     Z and Omega are defined
+ *     LIODOM_ODOM_EDGE_GAPS 2      n_missing > 0: unusable scans contributed nothing — the caller decides what to do
+ *     LIODOM_ODOM_EDGE_NOT_PD 4    n_used == 0, Cholesky failed or Omega is not finite: covariance and information NaN, Z valid
+ *     LIODOM_ODOM_EDGE_NO_POSE 8   a non-finite pose at a, at b or in between (or a zero quaternion at a or b): z, covariance and
+ *                                  information NaN; no other flag is set */
+typedef struct liodom_odom_edge_t {
+  int32_t scan_from, scan_to;
+  uint32_t flags;              /* LIODOM_ODOM_EDGE_* */
+  int32_t n_used, n_missing;   /* usable / unusable scans among from + 1 .. to */
+  int32_t reserved;            /* 0 */
+  double z[7];
+  double covariance[36];       /* Sigma_e, row-major */
+  double information[36];      /* Omega, row-major */
+} liodom_odom_edge_t;          /* 656 bytes */
+#define LIODOM_ODOM_EDGE_VALID 1u
+#define LIODOM_ODOM_EDGE_GAPS 2u
+#define LIODOM_ODOM_EDGE_NOT_PD 4u
+#define LIODOM_ODOM_EDGE_NO_POSE 8u
+#define LIODOM_ODOM_EDGES_MAX (1 << 20)
+typedef struct liodom_odom_edge_options_t {
+  double inflation, floor_rotation, floor_translation;
+  int32_t reserved[4];         /* 0 */
+} liodom_odom_edge_options_t;  /* 40 bytes */
+void liodom_odom_edge_options_default(liodom_odom_edge_options_t* opt);
+int liodom_chain_odometry_edges(const double* poses /*m x 7*/, const liodom_pose_cov_t* records /*m*/, int m, const int32_t* from,
+                                const int32_t* to, int n, const liodom_odom_edge_options_t* opt, liodom_odom_edge_t* out /*n*/);
+int liodom_get_odometry_edges(liodom_handle_t* h, int stream, const int32_t* from, const int32_t* to, int n,
+                              const liodom_odom_edge_options_t* opt, liodom_odom_edge_t* out /*n*/);
+
 #ifdef __cplusplus
 }
 #endif

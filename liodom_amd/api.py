@@ -17,7 +17,8 @@ _SRC = [os.path.join(_HERE, "csrc", f) for f in ("liodom_hip.hip", "liodom_kerne
                                                   "kernels_reloc_bnb.h", "reloc_bnb.h", "kernels_map_hits.h", "kernels_register.h", "map_register.h",
                                                   "kernels_places.h", "liodom_places_host.h", "place_state_format.h",
                                                   "kernels_graph.h", "liodom_graph_host.h", "graph_csr.h", "graph_marginals.h", "graph_lm.h",
-                                                  "liodom_sizes.h", "handle_plan.h", "step_plan.h", "edge_pipe.h", "map_attach.h", "liodom_step_host.h")] + [
+                                                  "liodom_sizes.h", "handle_plan.h", "step_plan.h", "edge_pipe.h", "map_attach.h", "liodom_step_host.h",
+                                                  "odom_edges.h", "kernels_odom_edges.h")] + [
     os.path.join(_ROOT, "include", "liodom_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
@@ -294,6 +295,20 @@ class GraphCovOptions(C.Structure):
 
 GRAPH_COV_STATUSES = ("ok", "not_converged", "breakdown", "unanchored", "not_pd")      # LIODOM_GRAPH_COV_*
 GRAPH_COV_OK, GRAPH_COV_NOT_CONVERGED, GRAPH_COV_BREAKDOWN, GRAPH_COV_UNANCHORED, GRAPH_COV_NOT_PD = range(5)
+# liodom_odom_edge_t / liodom_odom_edge_options_t: odometry edges chained from the scans' covariances
+ODOM_EDGE_DTYPE = np.dtype([("scan_from", "<i4"), ("scan_to", "<i4"), ("flags", "<u4"), ("n_used", "<i4"), ("n_missing", "<i4"), ("reserved", "<i4"),
+                            ("z", "<f8", (7,)), ("covariance", "<f8", (6, 6)), ("information", "<f8", (6, 6))])
+ODOM_EDGE_VALID, ODOM_EDGE_GAPS, ODOM_EDGE_NOT_PD, ODOM_EDGE_NO_POSE = 1, 2, 4, 8
+ODOM_EDGES_MAX = 1 << 20
+POSE_COV_DTYPE = np.dtype([("scan_index", "<i4"), ("flags", "<u4"), ("n_residuals", "<i4"), ("termination", "<i4"), ("final_cost", "<f8"),
+                           ("sigma2", "<f8"), ("information", "<f8", (6, 6)), ("covariance", "<f8", (6, 6)), ("eigenvalues", "<f8", (6,)),
+                           ("eigenvectors", "<f8", (6, 6))])      # liodom_pose_cov_t as a structured array (944 bytes)
+
+
+class OdomEdgeOptions(C.Structure):
+    _fields_ = [("inflation", C.c_double), ("floor_rotation", C.c_double), ("floor_translation", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
 GRAPH_COV_STATUS_DTYPE = np.dtype([("iterations", "<i4"), ("status", "<i4"), ("residual", "<f8")])      # liodom_graph_cov_status_t
 
 
@@ -975,6 +990,12 @@ def load():
     L.liodom_graph_gate_edges.argtypes = [vp, vp, C.c_int, C.POINTER(GraphCovOptions), dp, ip]
     L.liodom_graph_cov_counters.restype = C.c_int
     L.liodom_graph_cov_counters.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.liodom_odom_edge_options_default.restype = None
+    L.liodom_odom_edge_options_default.argtypes = [C.POINTER(OdomEdgeOptions)]
+    L.liodom_chain_odometry_edges.restype = C.c_int
+    L.liodom_chain_odometry_edges.argtypes = [dp, vp, C.c_int, ip, ip, C.c_int, C.POINTER(OdomEdgeOptions), vp]
+    L.liodom_get_odometry_edges.restype = C.c_int
+    L.liodom_get_odometry_edges.argtypes = [vp, C.c_int, ip, ip, C.c_int, C.POINTER(OdomEdgeOptions), vp]
     _lib = L
     return L
 
@@ -1035,6 +1056,7 @@ EXPORTED_SYMBOLS = [
     "liodom_graph_edge_weights",
     "liodom_graph_cov_options_default", "liodom_graph_solve_columns", "liodom_graph_covariance", "liodom_graph_gate_edges",
     "liodom_graph_cov_counters",
+    "liodom_odom_edge_options_default", "liodom_chain_odometry_edges", "liodom_get_odometry_edges",
 ]
 
 
@@ -1449,6 +1471,21 @@ class Liodom:
         recs = (PoseCov * max(count, 1))()
         self._check(self.L.liodom_get_pose_covariance_log(self.h, stream, first, count, recs))
         return [pose_cov_dict(recs[i]) for i in range(count)]
+
+    def odometry_edges(self, stream, scan_from, scan_to, **options):
+        """The odometry edges of the intervals (scan_from[i], scan_to[i]) of `stream`, chained on the device from the stream's own
+        pose log and covariance log (liodom_get_odometry_edges; handles created with pose_covariance = 1): a structured array
+        (ODOM_EDGE_DTYPE) with z, covariance (Sigma_e), information (Omega) and flags (ODOM_EDGE_*) per interval.  **options:
+        inflation, floor_rotation, floor_translation (make_odom_edge_options).  A refused call raises LiodomError with .code."""
+        f, t = _intervals(scan_from, scan_to)
+        out = np.zeros(f.shape[0], ODOM_EDGE_DTYPE)
+        rc = self.L.liodom_get_odometry_edges(self.h, int(stream), _ip(f), _ip(t), f.shape[0], C.byref(make_odom_edge_options(**options)),
+                                              out.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            e = LiodomError("liodom_get_odometry_edges failed (%d): %s" % (rc, (self.L.liodom_last_error() or b"").decode()))
+            e.code = rc
+            raise e
+        return out
 
     def wait_pose_covariance(self, stream, scan_index):
         """The covariance record of scan `scan_index` (one of the two latest of the stream), as a dict of NumPy arrays."""
@@ -2101,6 +2138,61 @@ def make_graph_cov_options(**kw):
             raise KeyError(k)
         setattr(o, k, v)
     return o
+
+
+def make_odom_edge_options(**kw):
+    """OdomEdgeOptions with the defaults of liodom_odom_edge_options_default (inflation 1, no floors: the raw records)."""
+    o = OdomEdgeOptions()
+    load().liodom_odom_edge_options_default(C.byref(o))
+    for k, v in kw.items():
+        if k == "reserved":
+            o.reserved[:] = [int(x) for x in v]
+        elif k in ("inflation", "floor_rotation", "floor_translation"):
+            setattr(o, k, float(v))
+        else:
+            raise KeyError(k)
+    return o
+
+
+def _intervals(scan_from, scan_to):
+    f = np.ascontiguousarray(np.asarray(scan_from, np.int32).reshape(-1))
+    t = np.ascontiguousarray(np.asarray(scan_to, np.int32).reshape(-1))
+    if f.shape != t.shape:
+        raise ValueError("one scan_to per scan_from")
+    return f, t
+
+
+def pose_cov_records(dicts):
+    """A list of pose_cov_dict dicts (Liodom.pose_covariance_log) as a POSE_COV_DTYPE array, what chain_odometry_edges takes."""
+    out = np.zeros(len(dicts), POSE_COV_DTYPE)
+    for k, d in enumerate(dicts):
+        for name in POSE_COV_DTYPE.names:
+            out[name][k] = d[name]
+    return out
+
+
+def chain_odometry_edges(poses, records, scan_from, scan_to, out=None, **options):
+    """liodom_chain_odometry_edges: the odometry edges of the intervals (scan_from[i], scan_to[i]) of a stream given as host
+    arrays — poses [m, 7] and records (POSE_COV_DTYPE, m), entry k is scan k — on the current device; needs no handle.
+    -> a structured array (ODOM_EDGE_DTYPE); `out` (optional): the array the records are written into.  **options as
+    make_odom_edge_options.  A refused call raises LiodomError with .code and leaves `out` untouched."""
+    L = load()
+    p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+    r = np.ascontiguousarray(records, dtype=POSE_COV_DTYPE).reshape(-1)
+    if r.shape[0] != p.shape[0]:
+        raise ValueError("one record per pose")
+    f, t = _intervals(scan_from, scan_to)
+    if out is None:
+        out = np.zeros(f.shape[0], ODOM_EDGE_DTYPE)
+    if out.dtype != ODOM_EDGE_DTYPE or out.shape != (f.shape[0],) or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous ODOM_EDGE_DTYPE array with one record per interval")
+    rc = L.liodom_chain_odometry_edges(_dp(p), r.ctypes.data_as(C.c_void_p), p.shape[0], _ip(f), _ip(t), f.shape[0],
+                                       C.byref(make_odom_edge_options(**options)), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        e = LiodomError("liodom_chain_odometry_edges failed (%d): %s" % (rc, (L.liodom_last_error() or b"").decode()))
+        e.code = rc
+        raise e
+    return out
 
 
 def graph_edges(i, j, z, info, kind=0):

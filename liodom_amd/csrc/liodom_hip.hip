@@ -22,6 +22,8 @@
 #include "step_plan.h"
 #include "edge_pipe.h"
 #include "map_attach.h"
+#include "odom_edges.h"
+#include "kernels_odom_edges.h"
 
 using namespace liodom_dev;
 
@@ -120,6 +122,9 @@ struct liodom_handle {
   HostOut* host_out = nullptr;       // host-mapped pinned result records, one per stream
   HostCov* cov_host = nullptr;       // pose_covariance = 1: host-mapped covariance records, two per stream (DevView::cov_host)
   std::vector<int> scans_enqueued;   // per stream: scans launched so far (expected HostOut.seq)
+  std::vector<int> log_first;        // per stream: scans_enqueued as the last reset, seed or import left it — the first scan this life of the stream logs (liodom_get_odometry_edges)
+  void* odom_ws = nullptr;           // liodom_get_odometry_edges: intervals and records of one call on the device; null until the first call
+  size_t odom_ws_bytes = 0;
   unsigned char* state_stage = nullptr;       // stream-state blob staging (liodom_export_stream_state / liodom_import_stream_state): device side,
   unsigned char* state_stage_host = nullptr;  // page-locked host side; both allocated by the first export or import
   std::vector<void*> allocs;
@@ -363,6 +368,7 @@ int reset_state(liodom_handle* h) {
     HIP_TRY(hipMemsetAsync(h->v.cov_raw, 0, sizeof(PoseCovRaw) * (size_t)h->S, h->stream));
   }
   std::fill(h->scans_enqueued.begin(), h->scans_enqueued.end(), 0);
+  std::fill(h->log_first.begin(), h->log_first.end(), 0);
   HIP_TRY(hipMemsetAsync(h->v.win_n, 0, sizeof(int) * (size_t)h->S * h->P, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return LIODOM_OK;
@@ -572,6 +578,7 @@ int liodom_create(const liodom_params_t* params, const liodom_config_t* config, 
     if (hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) { g_last_error = "hipHostGetDevicePointer failed"; return fail(LIODOM_ERR_HIP); }
     v.host_out = static_cast<HostOut*>(dp);
     h->scans_enqueued.assign(S, 0);
+    h->log_first.assign(S, 0);
     h->step.bind(S);
     h->last_eb.assign(S, 0);
     h->maps.bind(h, S);
@@ -676,6 +683,7 @@ void liodom_destroy(liodom_handle_t* h) {
   if (h->host_edges_meta) hipHostFree(h->host_edges_meta);
   if (h->host_edges_hdr) hipHostFree(h->host_edges_hdr);
   if (h->pin.base) hipHostFree(h->pin.base);
+  if (h->odom_ws) hipFree(h->odom_ws);
   if (h->pol_tables) hipFree(h->pol_tables);
   if (h->pol_stage) hipFree(h->pol_stage);
   if (h->pol_pin.base) hipHostFree(h->pol_pin.base);
@@ -766,6 +774,7 @@ static int install_stream_state(liodom_handle* h, int stream, const unsigned cha
   std::memset(h->host_out + 2 * s, 0, sizeof(HostOut) * 2);
   if (h->cov_host) std::memset(h->cov_host + 2 * s, 0, sizeof(HostCov) * 2);
   h->scans_enqueued[s] = scan_counter;
+  h->log_first[s] = scan_counter;
   h->step.hb_since[s] = -1;      // (hash_incr: the stream's next step rebuilds from the whole window)
   return LIODOM_OK;
 }
@@ -1872,6 +1881,78 @@ int liodom_get_pose_covariance_log(liodom_handle_t* h, int stream, int first, in
   if (out && count)
     HIP_TRY(hipMemcpy(out, h->v.cov_log + (size_t)stream * h->v.pose_log_cap + first, sizeof(liodom_pose_cov_t) * (size_t)count, hipMemcpyDeviceToHost));
   return LIODOM_OK;
+}
+
+// ---- odometry edges from the scans' covariances (odom_edges.h decides, kernels_odom_edges.h computes) ----
+// One launch of k_odom_edges on q over device-resident poses and records; ws: odom_ws_bytes(n) of device memory (the records
+// first: they are stored as 8-byte words).  Returns after the records have arrived in `out`.
+static size_t odom_ws_bytes(int n) { return (size_t)n * (sizeof(liodom_odom_edge_t) + 2 * sizeof(int32_t)); }
+static int odom_edges_launch(const double* d_poses, const liodom_pose_cov_t* d_recs, const int32_t* from, const int32_t* to, int n,
+                             const liodom_odom_edge_options_t& o, unsigned char* ws, hipStream_t q, liodom_odom_edge_t* out) {
+  liodom_odom_edge_t* d_out = reinterpret_cast<liodom_odom_edge_t*>(ws);
+  int32_t* d_from = reinterpret_cast<int32_t*>(ws + (size_t)n * sizeof(liodom_odom_edge_t));
+  int32_t* d_to = d_from + n;
+  HIP_TRY(hipMemcpyAsync(d_from, from, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, q));
+  HIP_TRY(hipMemcpyAsync(d_to, to, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, q));
+  hipLaunchKernelGGL(k_odom_edges, dim3((unsigned int)n), dim3(64), 0, q, d_poses, d_recs, d_from, d_to, n, o.inflation,
+                     o.floor_rotation * o.floor_rotation, o.floor_translation * o.floor_translation, d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(liodom_odom_edge_t) * (size_t)n, hipMemcpyDeviceToHost, q));
+  HIP_TRY(hipStreamSynchronize(q));
+  return LIODOM_OK;
+}
+// the options of a call (null: the defaults) into *o, or why not
+static int odom_edge_options_in(const liodom_odom_edge_options_t* opt, liodom_odom_edge_options_t* o, const char* who) {
+  if (opt) *o = *opt; else odom_edge_options_default(o);
+  if (const char* why = odom_edge_options_refusal(o)) { g_last_error = std::string(who) + ": " + why; return LIODOM_ERR_INVALID_ARG; }
+  return LIODOM_OK;
+}
+
+void liodom_odom_edge_options_default(liodom_odom_edge_options_t* opt) {
+  if (opt) odom_edge_options_default(opt);
+}
+
+int liodom_chain_odometry_edges(const double* poses, const liodom_pose_cov_t* records, int m, const int32_t* from, const int32_t* to,
+                                int n, const liodom_odom_edge_options_t* opt, liodom_odom_edge_t* out) {
+  static const char* who = "liodom_chain_odometry_edges";
+  liodom_odom_edge_options_t o;
+  if (const int rc = odom_edge_options_in(opt, &o, who)) return rc;
+  if (m < 0 || (m > 0 && (!poses || !records))) { g_last_error = std::string(who) + ": m < 0, or null poses or records"; return LIODOM_ERR_INVALID_ARG; }
+  if (const char* why = odom_edge_ranges_refusal(from, to, n, 0, m, nullptr)) { g_last_error = std::string(who) + ": " + why; return LIODOM_ERR_INVALID_ARG; }
+  if (n == 0) return LIODOM_OK;
+  if (!out) { g_last_error = std::string(who) + ": null out"; return LIODOM_ERR_INVALID_ARG; }
+  // one block of device memory for the call: records (8-byte aligned sizes first), poses, then the launch's workspace
+  const size_t rec_bytes = sizeof(liodom_pose_cov_t) * (size_t)m, pose_bytes = sizeof(double) * 7 * (size_t)m;
+  struct Block { void* p = nullptr; ~Block() { if (p) hipFree(p); } } blk;
+  HIP_TRY(hipMalloc(&blk.p, rec_bytes + pose_bytes + odom_ws_bytes(n)));
+  unsigned char* base = static_cast<unsigned char*>(blk.p);
+  HIP_TRY(hipMemcpyAsync(base, records, rec_bytes, hipMemcpyHostToDevice, nullptr));
+  HIP_TRY(hipMemcpyAsync(base + rec_bytes, poses, pose_bytes, hipMemcpyHostToDevice, nullptr));
+  return odom_edges_launch(reinterpret_cast<const double*>(base + rec_bytes), reinterpret_cast<const liodom_pose_cov_t*>(base), from, to, n, o,
+                           base + rec_bytes + pose_bytes, nullptr, out);
+}
+
+int liodom_get_odometry_edges(liodom_handle_t* h, int stream, const int32_t* from, const int32_t* to, int n,
+                              const liodom_odom_edge_options_t* opt, liodom_odom_edge_t* out) {
+  static const char* who = "liodom_get_odometry_edges";
+  int rc = check_stream(h, stream);
+  if (rc) return rc;
+  if (!h->v.cov_log) { g_last_error = std::string(who) + ": the handle was created with pose_covariance = 0"; return LIODOM_ERR_UNSUPPORTED; }
+  liodom_odom_edge_options_t o;
+  if ((rc = odom_edge_options_in(opt, &o, who))) return rc;
+  SideLocks lk(h, true, false);      // (no scan can be enqueued meanwhile: the limit below holds until the records are out)
+  const int limit = odom_edge_log_limit(h->scans_enqueued[stream], h->v.pose_log_cap);
+  if (const char* why = odom_edge_ranges_refusal(from, to, n, h->log_first[stream], limit, nullptr)) { g_last_error = std::string(who) + ": " + why; return LIODOM_ERR_INVALID_ARG; }
+  if (n == 0) return LIODOM_OK;
+  if (!out) { g_last_error = std::string(who) + ": null out"; return LIODOM_ERR_INVALID_ARG; }
+  HIP_TRY(sync_odometry(h));
+  if (h->odom_ws_bytes < odom_ws_bytes(n)) {      // the call's workspace: made by the first call, grown when one needs more
+    if (h->odom_ws) { HIP_TRY(hipFree(h->odom_ws)); h->odom_ws = nullptr; h->odom_ws_bytes = 0; }
+    HIP_TRY(hipMalloc(&h->odom_ws, odom_ws_bytes(n)));
+    h->odom_ws_bytes = odom_ws_bytes(n);
+  }
+  return odom_edges_launch(h->v.pose_log + (size_t)stream * h->v.pose_log_cap * 7, h->v.cov_log + (size_t)stream * h->v.pose_log_cap, from, to, n,
+                           o, static_cast<unsigned char*>(h->odom_ws), h->stream, out);
 }
 
 int liodom_wait_pose_covariance(liodom_handle_t* h, int stream, int scan_index, liodom_pose_cov_t* out) {

@@ -1364,4 +1364,206 @@ LD_HD bool graph_gate(const double* Xi, const double* Xj, const double* Z, const
   return true;
 }
 
+// Odometry edges from the scans' covariances (k_odom_edges, kernels_odom_edges.h; contract: include/liodom_hip.h "odometry edges
+// from the scans' own covariances").  The covariance of the relative pose of scans a < b is chained from the per-scan records:
+// Sigma = sum over the usable k = a + 1 .. b of M_k = T_k (inflation C_k + F) T_k^T, T_k = [[I, 0], [G_k, I]], G_k = -2 [u_k]x,
+// u_k = t_b - t_k; then Sigma_e = B Sigma B^T with B of graph_edge_error and Omega = Sigma_e^-1.  Symmetric matrices travel as
+// their 21 lower-triangle entries (lt_idx).  Sums run over k and over the zeros of G too, from 0.0, in the order written:
+// tests/odom_edge_model.py restates every one, and tests/test_odom_edge_math_host.py compares bits.
+constexpr unsigned int kOdomEdgeValid = 1u, kOdomEdgeGaps = 2u, kOdomEdgeNotPd = 4u, kOdomEdgeNoPose = 8u;
+constexpr int kOdomAccN = 24;        // a lane's accumulator: 21 sums, then the usable, unusable and non-finite-pose scans it met
+constexpr int kOdomEdgeWords = 82;   // liodom_odom_edge_t as 8-byte words: 3 of header, 7 of z, 36 + 36
+
+// The usable-scan test: the record is scan k's, its flags are exactly kCovValid, its 36 covariance entries are finite.
+LD_HD bool odom_scan_usable(int scan_index, unsigned int flags, const double* cov36, int k) {
+  bool finite = true;
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) finite = finite && ld_isfinite(cov36[i]);
+  return scan_index == k && flags == kCovValid && finite;
+}
+// The transport term M_k (21) of a scan with covariance C (36, its lower triangle read) at lever arm u = t_b - t_k, with
+// P = inflation C + diag(fr2 x 3, ft2 x 3):  M_rr = P_rr,  N = M_tr = G P_rr + P_tr,  M_tt = (N G^T + G P_rt) + P_tt.
+LD_HD void odom_transport_term(const double* C36, const double* u, double inflation, double fr2, double ft2, double* M21) {
+  double P[21];
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {
+    LD_UNROLL
+    for (int c = 0; c <= r; c++) P[lt_idx(r, c)] = r == c ? inflation * C36[r * 6 + c] + (r < 3 ? fr2 : ft2) : inflation * C36[r * 6 + c];
+  }
+  const double g0 = 2.0 * u[0], g1 = 2.0 * u[1], g2 = 2.0 * u[2];
+  const double G[9] = {0.0, g2, -g1, -g2, 0.0, g0, g1, -g0, 0.0};
+  double N[9];
+  LD_UNROLL
+  for (int i = 0; i < 3; i++) {
+    LD_UNROLL
+    for (int j = 0; j < 3; j++) {
+      double s = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 3; k++) s += G[i * 3 + k] * P[k >= j ? lt_idx(k, j) : lt_idx(j, k)];
+      N[i * 3 + j] = s + P[lt_idx(3 + i, j)];
+      M21[lt_idx(3 + i, j)] = N[i * 3 + j];
+      if (j <= i) M21[lt_idx(i, j)] = P[lt_idx(i, j)];
+    }
+  }
+  LD_UNROLL
+  for (int i = 0; i < 3; i++) {
+    LD_UNROLL
+    for (int j = 0; j <= i; j++) {
+      double s1 = 0.0, s2 = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 3; k++) { s1 += N[i * 3 + k] * G[j * 3 + k]; s2 += G[i * 3 + k] * P[lt_idx(3 + j, k)]; }
+      M21[lt_idx(3 + i, 3 + j)] = (s1 + s2) + P[lt_idx(3 + i, 3 + j)];
+    }
+  }
+}
+// What lane `lane` of 64 gives to interval (a, b): acc[0 .. 20] += M_k over its scans k = lane (mod 64), a < k <= b, ascending,
+// that are usable and have a finite pose; acc[21], [22], [23] count its usable, unusable and non-finite-pose scans.  acc is
+// zeroed here.  poses: 7 doubles per scan; Rec: liodom_pose_cov_t (scan_index, flags, covariance).  The one loop: at most
+// ceil((b - a) / 64) rounds.
+template <class Rec>
+LD_HD void odom_lane_partial(const double* poses, const Rec* recs, int a, int b, int lane, double inflation, double fr2, double ft2,
+                             double* acc /*kOdomAccN*/) {
+  LD_UNROLL
+  for (int i = 0; i < kOdomAccN; i++) acc[i] = 0.0;
+  const double tb[3] = {poses[(size_t)b * 7 + 4], poses[(size_t)b * 7 + 5], poses[(size_t)b * 7 + 6]};
+  int k = a + 1 + ((lane - (a + 1)) & 63);      // the first k > a with k = lane (mod 64)
+  for (; k <= b; k += 64) {
+    const double* X = poses + (size_t)k * 7;
+    bool pose_ok = true;
+    LD_UNROLL
+    for (int i = 0; i < 7; i++) pose_ok = pose_ok && ld_isfinite(X[i]);
+    const Rec* r = recs + k;
+    const bool usable = odom_scan_usable(r->scan_index, r->flags, r->covariance, k);
+    acc[usable ? 21 : 22] += 1.0;
+    if (!pose_ok) acc[23] += 1.0;
+    if (usable && pose_ok) {
+      const double u[3] = {tb[0] - X[4], tb[1] - X[5], tb[2] - X[6]};
+      double M[21];
+      odom_transport_term(r->covariance, u, inflation, fr2, ft2, M);
+      LD_UNROLL
+      for (int i = 0; i < 21; i++) acc[i] += M[i];
+    }
+  }
+}
+// The fixed order in which the 64 lanes' partials of one accumulator entry are combined — what wave_reduce_scatter32_f64
+// (wave_ops.h) computes on the device, restated for the host (a + b == b + a bit for bit, so which lane of a pair adds is free).
+inline double odom_combine64(const double* v /*64*/) {
+  double p[32];
+  for (int r = 0; r < 32; r++) p[r] = v[r] + v[r + 32];
+  for (int r = 0; r < 16; r++) p[r] = p[r] + p[r + 16];
+  for (int r = 0; r < 8; r++) p[r] = p[r] + p[15 - r];
+  for (int r = 0; r < 4; r++) p[r] = p[r] + p[7 - r];
+  for (int r = 0; r < 2; r++) p[r] = p[r] + p[r + 2];
+  return p[0] + p[1];
+}
+// Sigma_e = B Sigma B^T (36, the upper triangle computed and mirrored) from B (36, row-major) and Sigma (21)
+LD_HD void odom_edge_covariance(const double* B36, const double* S21, double* Se36) {
+  double T[36];
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {
+    LD_UNROLL
+    for (int c = 0; c < 6; c++) {
+      double s = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 6; k++) s += B36[r * 6 + k] * S21[k >= c ? lt_idx(k, c) : lt_idx(c, k)];
+      T[r * 6 + c] = s;
+    }
+  }
+  LD_UNROLL
+  for (int r = 0; r < 6; r++) {
+    LD_UNROLL
+    for (int c = r; c < 6; c++) {
+      double s = 0.0;
+      LD_UNROLL
+      for (int k = 0; k < 6; k++) s += T[r * 6 + k] * B36[c * 6 + k];
+      Se36[r * 6 + c] = s;
+      Se36[c * 6 + r] = s;
+    }
+  }
+}
+// Omega = Sigma_e^-1 by Cholesky of its upper triangle, the result mirrored (spd_inverse6); false, Om36 untouched: Sigma_e is not
+// positive definite, or an entry of the inverse is not finite.
+LD_HD bool odom_edge_information(const double* Se36, double* Om36) {
+  double H21[21], inv[36];
+  LD_UNROLL
+  for (int i = 0; i < 6; i++) {
+    LD_UNROLL
+    for (int j = i; j < 6; j++) H21[h_idx(i, j)] = Se36[i * 6 + j];
+  }
+  if (!spd_inverse6(H21, inv)) return false;
+  bool finite = true;
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) finite = finite && ld_isfinite(inv[i]);
+  if (!finite) return false;
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) Om36[i] = inv[i];
+  return true;
+}
+// The pose as the chain takes it in: the quaternion divided by sqrt(((q0^2 + q1^2) + q2^2) + q3^2) (pose7.h's rule); false where
+// an entry of the result is not finite.
+LD_HD bool odom_pose_in(const double* X, double* out) {
+  const double n = sqrt(((X[0] * X[0] + X[1] * X[1]) + X[2] * X[2]) + X[3] * X[3]);
+  bool finite = true;
+  LD_UNROLL
+  for (int i = 0; i < 7; i++) { out[i] = i < 4 ? X[i] / n : X[i]; finite = finite && ld_isfinite(out[i]); }
+  return finite;
+}
+// The record of interval (a, b) from the combined accumulator tot (kOdomAccN) and the raw poses of a and b, as 8-byte words w
+// (kOdomEdgeWords: liodom_odom_edge_t's layout — scan_from | scan_to << 32, flags | n_used << 32, n_missing, z, Sigma_e, Omega).
+LD_HD void odom_edge_finish(const double* Xa_raw, const double* Xb_raw, int a, int b, const double* tot, unsigned long long* w) {
+  union { double d; unsigned long long u; } cv;
+  const int n_used = (int)tot[21], n_missing = (int)tot[22];
+  double Xa[7], Xb[7];
+  const bool oka = odom_pose_in(Xa_raw, Xa), okb = odom_pose_in(Xb_raw, Xb);
+  const bool pose_ok = oka && okb && tot[23] == 0.0;
+  const double qnan = __builtin_nan("");
+  double z[7], Se[36], Om[36];
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) { Se[i] = qnan; Om[i] = qnan; }
+  LD_UNROLL
+  for (int i = 0; i < 7; i++) z[i] = qnan;
+  unsigned int flags = kOdomEdgeNoPose;
+  if (pose_ok) {
+    const double ca[4] = {-Xa[0], -Xa[1], -Xa[2], Xa[3]};
+    double Ra[9];
+    pg_quat_mul(ca, Xb, z);
+    pg_rot3(Xa, Ra);
+    const double d[3] = {Xb[4] - Xa[4], Xb[5] - Xa[5], Xb[6] - Xa[6]};
+    LD_UNROLL
+    for (int r = 0; r < 3; r++) z[4 + r] = Ra[r] * d[0] + Ra[3 + r] * d[1] + Ra[6 + r] * d[2];      // R_a^T (t_b - t_a)
+    flags = n_missing > 0 ? kOdomEdgeGaps : 0u;
+    bool pd = false;
+    if (n_used > 0) {
+      double e[6], A[36], B[36], S[36];
+      graph_edge_error(Xa, Xb, z, e, A, B);
+      odom_edge_covariance(B, tot, S);
+      pd = odom_edge_information(S, Om);
+      if (pd) {
+        LD_UNROLL
+        for (int i = 0; i < 36; i++) Se[i] = S[i];
+      }
+    }
+    flags |= pd ? kOdomEdgeValid : kOdomEdgeNotPd;
+  }
+  w[0] = (unsigned long long)(unsigned int)a | ((unsigned long long)(unsigned int)b << 32);
+  w[1] = (unsigned long long)flags | ((unsigned long long)(unsigned int)n_used << 32);
+  w[2] = (unsigned long long)(unsigned int)n_missing;
+  LD_UNROLL
+  for (int i = 0; i < 7; i++) { cv.d = z[i]; w[3 + i] = cv.u; }
+  LD_UNROLL
+  for (int i = 0; i < 36; i++) { cv.d = Se[i]; w[10 + i] = cv.u; cv.d = Om[i]; w[46 + i] = cv.u; }
+}
+// One interval on the host, lane by lane in the kernel's order: the reference the device's bytes are held to.
+template <class Rec>
+inline void odom_edge_host(const double* poses, const Rec* recs, int a, int b, double inflation, double fr, double ft,
+                           unsigned long long* w /*kOdomEdgeWords*/) {
+  double part[64][kOdomAccN], col[64], tot[kOdomAccN];
+  for (int lane = 0; lane < 64; lane++) odom_lane_partial(poses, recs, a, b, lane, inflation, fr * fr, ft * ft, part[lane]);
+  for (int e = 0; e < kOdomAccN; e++) {
+    for (int lane = 0; lane < 64; lane++) col[lane] = part[lane][e];
+    tot[e] = odom_combine64(col);
+  }
+  odom_edge_finish(poses + (size_t)a * 7, poses + (size_t)b * 7, a, b, tot, w);
+}
+
 }  // namespace liodom_dev

@@ -220,6 +220,14 @@ std::vector<uint8_t> Engine::saveState(int stream) {
   blob.resize((size_t)n);
   return blob;
 }
+std::vector<liodom_odom_edge_t> Engine::odometryEdges(const std::vector<int32_t>& scan_from, const std::vector<int32_t>& scan_to,
+                                                      const liodom_odom_edge_options_t* opt, int stream) {
+  if (scan_from.size() != scan_to.size()) throw std::invalid_argument("Engine::odometryEdges: one scan_to per scan_from");
+  std::vector<liodom_odom_edge_t> out(scan_from.size());
+  check(liodom_get_odometry_edges(h_, stream, scan_from.data(), scan_to.data(), (int)scan_from.size(), opt, out.data()),
+        "liodom_get_odometry_edges");
+  return out;
+}
 void Engine::loadState(const std::vector<uint8_t>& blob, int stream) {
   check(liodom_import_stream_state(h_, stream, blob.data(), (int64_t)blob.size()), "liodom_import_stream_state");
 }

@@ -167,6 +167,11 @@ class Engine {
   // in list order.  next_slot >= 0 issues that slot's extraction ahead for next_streams (null: the same list).
   std::vector<std::array<double, 7>> stepSubset(int slot, const std::vector<int32_t>& streams, int64_t n, int height, int width,
                                                 int next_slot = -1, const std::vector<int32_t>* next_streams = nullptr);
+  // The odometry edges of the intervals (scan_from[i], scan_to[i]) of a stream, Z and Omega chained on the device from the
+  // stream's own pose log and covariance log (liodom_get_odometry_edges; pose_covariance = 1; no counterpart in the reference):
+  // records in the form PoseGraph / liodom_graph_add_edges take z and information.  opt null: inflation 1, no floors.
+  std::vector<liodom_odom_edge_t> odometryEdges(const std::vector<int32_t>& scan_from, const std::vector<int32_t>& scan_to,
+                                                const liodom_odom_edge_options_t* opt = nullptr, int stream = 0);
  private:
   liodom_handle_t* h_ = nullptr;
   bool covariance_ = false;

@@ -88,7 +88,7 @@ def solve_information(place_pose, registered_pose, Z, H, sigma2):
 
 
 class LoopCloser:
-    """LoopCloser(map, places, levels, ...): feed(pose, edges) per scan, close() when loops have been found.
+    """LoopCloser(map, places, levels, ...): feed(pose, edges, scan=None) per scan, close() when loops have been found.
 
     map, places   the Map the loop measurements are searched in and the Places database of the key frames
     levels        the grids of Map.search_pose, coarse to fine, run around a match's pose (as Liodom.relocalize's)
@@ -98,6 +98,15 @@ class LoopCloser:
     k             matches asked of the database per key frame
     min_fraction  a match becomes a loop edge if its last level scores (hits_r + hits_0) / (2 n_edges) >= min_fraction
     odometry_info, loop_info   the information matrices (6 x 6, half-angle rotation first) of the two kinds of edge
+                  odometry_info="solve" (needs odometry_source=(handle, stream), a handle created with pose_covariance = 1): the
+                  information of an odometry edge is chained on the device from the covariance records of the scans between the
+                  two key frames (Liodom.odometry_edges for the interval (the previous key frame's scan, this key frame's scan);
+                  feed's `scan` is the scan index the handle gave the pose, info.scan_index), with odometry_options — inflation,
+                  floor_rotation, floor_translation; tools/odometry_info_calibration.py measures the inflation a sensor and scene call
+                  for.  Z stays between(the fed poses): Omega does not depend on the frame the log's poses are in.
+                  ODOMETRY_INFO stands, and odometry_fallbacks counts it, where feed got no scan, the scan index did not
+                  increase (the first key frame after close() has seeded the stream again), the call was refused, or the record's
+                  flags are not exactly ODOM_EDGE_VALID (scans without a usable record: GAPS).
     refine        None, or dict(options of Map.register_poses, min_fraction=...): a searched pose is registered to the map in 6-DoF
                   (refine_loop) and the loop edge measures the registered pose; it is kept only if the registration ended CONVERGED
                   or MAX_PASSES with matches / n_edges >= refine's min_fraction (default 0.25)
@@ -123,7 +132,7 @@ class LoopCloser:
 
     def __init__(self, map, places, levels, graph=None, min_dist=4.0, min_yaw=float("inf"), min_gap=10, k=3, min_fraction=0.5,
                  odometry_info=ODOMETRY_INFO, loop_info=LOOP_INFO, max_update_points=65536, max_nodes=4096, max_edges=16384, refine=None,
-                 gate=None, gate_options=None):
+                 gate=None, gate_options=None, odometry_source=None, odometry_options=None):
         if min_gap < 1 or k < 1:
             raise ValueError("LoopCloser: needs min_gap >= 1 and k >= 1")
         self.info_from_solve = isinstance(loop_info, str)
@@ -131,6 +140,17 @@ class LoopCloser:
             if loop_info != "solve" or refine is None:
                 raise ValueError("LoopCloser: loop_info is a 6 x 6 matrix, or \"solve\" together with refine")
             loop_info = LOOP_INFO
+        self.odometry_from_solve = isinstance(odometry_info, str)
+        if self.odometry_from_solve:
+            if odometry_info != "solve" or odometry_source is None:
+                raise ValueError("LoopCloser: odometry_info is a 6 x 6 matrix, or \"solve\" together with odometry_source=(handle, stream)")
+            odometry_info = ODOMETRY_INFO
+        elif odometry_source is not None or odometry_options:
+            raise ValueError("LoopCloser: odometry_source and odometry_options go with odometry_info=\"solve\"")
+        self.odometry_source = None if odometry_source is None else (odometry_source[0], int(odometry_source[1]))
+        self.odometry_options = dict(odometry_options or {})
+        self.odometry_fallbacks = 0      # odometry edges that got the constant although odometry_info="solve"
+        self.last_key_scan = None        # the scan index fed with the last key frame (None: none was)
         self.refine = None if refine is None else dict(refine)
         self.refine_min_fraction = float(self.refine.pop("min_fraction", 0.25)) if self.refine is not None else None
         self.map, self.places, self.levels = map, places, list(levels)
@@ -149,7 +169,24 @@ class LoopCloser:
         self.gate_options = dict(gate_options or {})
         self.gated = []                  # (place node, node, d2, status) of the loop edges the gate refused
 
-    def feed(self, pose, edges):
+    def odometry_information(self, scan):
+        """The information of the odometry edge from the last key frame to a key frame taken at scan index `scan`: with
+        odometry_info="solve" the chained one (see the class), else — and wherever that is not to be had, counted in
+        odometry_fallbacks — the constant."""
+        if not self.odometry_from_solve:
+            return self.odometry_info
+        if scan is not None and self.last_key_scan is not None and int(scan) > self.last_key_scan:
+            handle, stream = self.odometry_source
+            try:
+                rec = handle.odometry_edges(stream, [self.last_key_scan], [int(scan)], **self.odometry_options)[0]
+            except api.LiodomError:
+                rec = None
+            if rec is not None and int(rec["flags"]) == api.ODOM_EDGE_VALID:
+                return np.array(rec["information"], np.float64).reshape(6, 6)
+        self.odometry_fallbacks += 1
+        return self.odometry_info
+
+    def feed(self, pose, edges, scan=None):
         pose = _pose(pose)
         self.last_pose = pose
         if not self.policy.feed(pose):
@@ -157,7 +194,8 @@ class LoopCloser:
         edges = np.ascontiguousarray(edges, dtype=np.float32).reshape(-1, 4)
         node = self.graph.add_nodes(pose[None], [1 if not self.key_poses else 0])
         if self.key_poses:
-            self.graph.add_edges(api.graph_edges([node - 1], [node], [between(self.key_poses[-1], pose)], self.odometry_info, kind=0))
+            self.graph.add_edges(api.graph_edges([node - 1], [node], [between(self.key_poses[-1], pose)], self.odometry_information(scan), kind=0))
+        self.last_key_scan = None if scan is None else int(scan)
         self.key_poses.append(pose)
         self.clouds.append(edges.copy())
         # lagged insertion: only key frames with min_gap newer ones behind them are places
@@ -313,6 +351,7 @@ class LoopCloser:
             self.places.import_state(api.build_place_state(st["geometry"], st["desc"], st["ids"], poses, st["bits"]))
         if handle is not None:
             handle.seed_stream(current, stream=stream)
+            self.last_key_scan = None      # the stream's scan indices start over: the next key frame's interval would span two lives
         self.key_poses = [p.copy() for p in after]
         self.last_pose = current
         self.policy.last = [float(v) for v in after[-1]]
